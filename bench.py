@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- BASELINE.json metric: GFLOP/s + wall time of the full eigen_sx solve (reference flop model).
 
-    python bench.py --gpus 1 --steps K --warmup W
+    python bench.py --gpus 1 --steps K --warmup W [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
 
 A "step" is one full eigen_sx solve (scaling -> pentadiagonal reduction -> band D&C -> back-transform, all
@@ -9,7 +9,14 @@ eigenpairs) with the input matrix already resident in HBM when the timed region 
 beforehand because the solver destroys `a`, exactly like the reference).  value = flops credited by the reference's
 own model (4/3 N^3 + counted D&C GEMM flops + 2 nvec N^2, src/eigen_sx.F:165,:248,:285-296) / wall time.
 
-  --gpus 1 : BASELINE.json configs[1], N=8192 random symmetric fp64 on one MI355X.  The line also carries an
+A plain run sets up, warms up, times the K steps and prints the line (with the stage times and the roofline figures
+sampled inside those steps).  --full adds everything else: the accuracy checks of the last solve, the extra blocks and
+the cpu_baseline (--gpus 1).  --dump-outputs DIR writes what the last timed solve returned: DIR/eigenvalues.npy (all
+N, float64) and DIR/eigenvectors.npy (float64, N rows; every column when they fit in 48 MiB, else as many columns as
+fit, picked by numpy.random.default_rng(20240807), in increasing order: dump_columns).  The input matrix is generated
+from a fixed seed.
+
+  --gpus 1 : BASELINE.json configs[1], N=8192 random symmetric fp64 on one MI355X.  With --full the line also carries an
              `extra` block with configs[2]'s matrix (N=32768) on the same GPU (the faster of two timed solves, both
              listed), so that north_star's "trailing update >= 70 % of the fp64 MFMA roofline at N=32768 on 1 GPU" is
              timed by the driver's run, and `extra_s` / `extra_n65536` with configs[3] / [4] (one timed solve each).
@@ -45,8 +52,12 @@ def parse_args():
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--size", dest="n", type=int, default=0, help="matrix size (default 8192 on one GPU, 32768 on several)")
     ap.add_argument("--route", default="sx", choices=["sx", "s"])
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extra", action="store_true", help="--gpus 1: skip the extra N=32768 / N=65536 solves")
+    ap.add_argument("--full", action="store_true", help="also the accuracy checks, the extra solves and the cpu_baseline "
+                    "(a plain run only times the steps)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the last timed solve's eigenvalues and "
+                    "eigenvectors (a seeded sample of columns when large) to DIR/*.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the cpu_baseline")
+    ap.add_argument("--no-extra", action="store_true", help="--full, --gpus 1: skip the extra N=32768 / N=65536 solves")
     ap.add_argument("--cpu-n", type=int, default=0, help="size of the cpu_baseline solve (OpenMP oracle on the host cores); "
                     "0 = the GPU line's N (the headline configuration)")
     ap.add_argument("--mf", type=int, default=0, help="m_forward (panel width) of the main line; default 64 on one GPU (reference default 48; N=8192 reduction on one box: 132.8 / 132.0 / 132.6 / 133.7 ms for 48 / 64 / 96 / 128), 128 on several (N=32768: what the per-rank rehearsal was tuned with)")
@@ -115,6 +126,18 @@ if ARGS is not None and ARGS.gpus > 1 and "WORLD_SIZE" not in os.environ:
 
 import numpy as np  # noqa: E402
 import torch  # noqa: E402
+
+
+DUMP_EIGENVECTOR_BYTES = 48 << 20   # --dump-outputs: 64 MiB in all, the eigenvalues (8 N bytes) included
+
+
+def dump_columns(n):
+    """indices of the eigenvectors that --dump-outputs writes: all n when they fit in DUMP_EIGENVECTOR_BYTES, else as many
+    as fit (at least one), chosen by a fixed seed and sorted"""
+    ncol = min(n, max(1, DUMP_EIGENVECTOR_BYTES // (8 * n)))
+    if ncol == n:
+        return np.arange(n)
+    return np.sort(np.random.default_rng(20240807).choice(n, ncol, replace=False))
 
 
 def main():
@@ -348,10 +371,33 @@ def main():
     else:
         comm_max = 0.0
 
-    # accuracy of the last solve (outside the timed region): the reference's gates
+    if args.dump_outputs:
+        # what the last timed solve returned: w, and the columns `sel` of Z (z[j, i] = Z(i, j); on the distributed path
+        # every rank holds the entries of its cyclic block, the owners' entries are summed into rank 0's copy)
+        sel = dump_columns(n)
+        ncol = len(sel)
+        if replicas:
+            z_out = z[torch.from_numpy(sel).to(dev), :n].T.cpu().numpy()
+        else:
+            pos = np.full(n, -1)
+            pos[sel] = np.arange(ncol)
+            mine = np.nonzero(pos[cols] >= 0)[0]
+            part = torch.zeros(n, ncol, dtype=torch.float64, device=dev)
+            part[torch.from_numpy(rows).to(dev)[:, None], torch.from_numpy(pos[cols[mine]]).to(dev)[None, :]] = \
+                z[torch.from_numpy(mine).to(dev), : len(rows)].T
+            part = part.cpu() if dist.get_backend() != "nccl" else part
+            dist.all_reduce(part)
+            z_out = part.cpu().numpy()
+        if rank == 0:
+            os.makedirs(args.dump_outputs, exist_ok=True)
+            np.save(os.path.join(args.dump_outputs, "eigenvalues.npy"), w.cpu().numpy())
+            np.save(os.path.join(args.dump_outputs, "eigenvectors.npy"), np.ascontiguousarray(z_out))
+        del z_out
+
+    # --full: accuracy of the last solve (outside the timed region): the reference's gates
     eps = np.finfo(np.float64).eps
     acc = {}
-    if replicas:
+    if args.full and replicas:
         Z = z[:n, :n].T
         Afull = A_loc_T.T
         anorm = torch.linalg.norm(Afull).item()
@@ -361,7 +407,7 @@ def main():
                "orthogonality_metric_lt_8": round(
                    torch.linalg.norm(Z.T @ Z - torch.eye(n, dtype=torch.float64, device=dev)).item() / (n * eps), 5)}
         del Z, Afull
-    else:
+    elif args.full:
         # distributed checks on the cyclic blocks: trace and Frobenius norm of A against the eigenvalues, and the
         # residual ||A Z - Z W||_F through a 2-D SUMMA-free formulation: every rank multiplies ITS block of A with
         # the matching rows of Z gathered along its grid row ... kept simple: rank-local pieces of the invariants
@@ -406,19 +452,20 @@ def main():
         acc = {"probe_residual_over_anorm": probe,
                "trace_error_over_anorm": abs(float(w.sum().item()) - float(trc[0].item())) / anorm,
                "frobenius_error_over_anorm": abs(float(torch.linalg.norm(w).item()) - anorm) / anorm,
-               "max_abs_znorm2_minus_1": float((zc - 1.0).abs().max().item()),
-               "comm_seconds_per_solve_max_over_ranks": round(comm_max, 4),
-               "sanity": mg_note,
-               # what carried the per-step exchange and the bulk collectives, and the init-time self-test of both transports
-               "transport": ee.eigen_comm_info(),
-               # rank 0's sampled reduction steps (every 32nd), HIP events on the compute stream, averages in microseconds.
-               # One rank per GPU: ONE launch per step ("symv" is then the whole step launch: kl of the previous step | ka over
-               # the rank's own rows | local mat-vec; the other entries are None).  Ranks sharing a card (wait kernels) or the
-               # collective exchanges: role by role -- local mat-vec | sums of the tile partial sums to the row owners |
-               # wait for the Y messages | ka over the rank's own rows | wait for the X messages
-               "per_step_us": {name: (round(kinds[3 * k_ + 2] / kinds[3 * k_] * 1e6, 2) if kinds[3 * k_] > 0 else None)
-                               for k_, name in ((0, "symv"), (2, "exchange_reduce_and_push"), (3, "wait"), (4, "ka"), (5, "wait_x"))},
-               "per_step_samples": int(kinds[0])}
+               "max_abs_znorm2_minus_1": float((zc - 1.0).abs().max().item())}
+    if not replicas:
+        acc.update({"comm_seconds_per_solve_max_over_ranks": round(comm_max, 4),
+                    "sanity": mg_note,
+                    # what carried the per-step exchange and the bulk collectives, and the init-time self-test of both transports
+                    "transport": ee.eigen_comm_info(),
+                    # rank 0's sampled reduction steps (every 32nd), HIP events on the compute stream, averages in microseconds.
+                    # One rank per GPU: ONE launch per step ("symv" is then the whole step launch: kl of the previous step | ka over
+                    # the rank's own rows | local mat-vec; the other entries are None).  Ranks sharing a card (wait kernels) or the
+                    # collective exchanges: role by role -- local mat-vec | sums of the tile partial sums to the row owners |
+                    # wait for the Y messages | ka over the rank's own rows | wait for the X messages
+                    "per_step_us": {name: (round(kinds[3 * k_ + 2] / kinds[3 * k_] * 1e6, 2) if kinds[3 * k_] > 0 else None)
+                                    for k_, name in ((0, "symv"), (2, "exchange_reduce_and_push"), (3, "wait"), (4, "ka"), (5, "wait_x"))},
+                    "per_step_samples": int(kinds[0])})
     total_flops_all = flops_one * args.steps * (world if replicas else 1)
 
     out = None
@@ -461,7 +508,7 @@ def main():
         }
         out.update(roofline_blocks(prof, n))
 
-    # ---- extra blocks (one GPU): driver-timed solves of the other BASELINE configs on this GPU -----------------
+    # ---- extra blocks (--full, one GPU): driver-timed solves of the other BASELINE configs on this GPU ----------
     #   extra          configs[2]'s matrix, N=32768 eigen_sx all eigenpairs (north_star's 70 % trailing-update target)
     #   extra_s        configs[3]'s, N=32768 eigen_s (tridiagonal route) all eigenpairs
     #   extra_n65536   configs[4]'s, N=65536 eigenvalues only (mode 'N': reduction + bisection)
@@ -537,7 +584,7 @@ def main():
         torch.cuda.empty_cache()
         return ex
 
-    if world == 1 and not args.no_extra and n != 32768 and args.route == "sx":
+    if args.full and world == 1 and not args.no_extra and n != 32768 and args.route == "sx":
         del a_bufs, z, w, A_loc_T
         torch.cuda.empty_cache()
         for key, (n2, route2, mode2, mf2, warm2, timed2) in {"extra": (32768, "sx", "A", args.extra_mf, True, 2),
@@ -549,7 +596,7 @@ def main():
                 out[key] = {"error": str(exc_x)}
 
     if rank == 0:
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             # cpu_baseline: the OpenMP oracle on the headline configuration itself (N = the GPU line's N), after all GPU work,
             # alone on the host cores (beside the GPU's extra blocks its busy-waiting OpenMP barriers and the HIP runtime's
             # threads starved each other under the box's CPU quota: the run was killed after 7 silent minutes)

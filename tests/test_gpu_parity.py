@@ -708,13 +708,31 @@ def _run_bench(args, env_extra):
     return json.loads(lines[0]), r.stderr
 
 
-def test_bench_launches_ranks_and_walks_the_ladder():
+def _check_bench_dump(d, n):
+    """the files of bench.py --dump-outputs against numpy on the same seeded matrix: every eigenvalue, and the eigenvector
+    columns bench.dump_columns(n) in that order (paired with their eigenvalues by the residual), 64 MiB in all"""
+    from bench import dump_columns
+    from eigenexa_amd import layout
+
+    sel = dump_columns(n)
+    assert os.path.getsize(d / "eigenvalues.npy") + os.path.getsize(d / "eigenvectors.npy") <= 64 << 20
+    w, Z = np.load(d / "eigenvalues.npy"), np.load(d / "eigenvectors.npy")
+    assert w.dtype == np.float64 and Z.dtype == np.float64 and w.shape == (n,) and Z.shape == (n, len(sel))
+    A = layout.random_symmetric(n)
+    assert np.abs(w - np.linalg.eigvalsh(A)).max() < 1e-12 * np.abs(w).max()
+    res, orth = layout.accuracy_metrics(A, w[sel], Z)
+    assert res < GATE_RES and orth < GATE_ORTH
+
+
+def test_bench_launches_ranks_and_walks_the_ladder(tmp_path):
     """`python bench.py --gpus 3` (no launcher; gloo rehearsal with the ranks sharing this card): an n_gpus = 3 strong-scaling
-    line that names its transport and carries the per-step breakdown; with the peer windows' self-test forced to fail
-    the same command reports independent replicas instead"""
-    common = ["--gpus", "3", "--steps", "1", "--warmup", "1", "--size", "1536", "--no-cpu-baseline"]
-    out, _ = _run_bench(common, {"EIGX_BENCH_BACKEND": "gloo"})
+    line that names its transport and carries the per-step breakdown; --dump-outputs gathers a seeded sample of the sharded
+    eigenvectors (N = 2560: 2457 of the columns fit the cap); with the peer windows' self-test forced to fail the same
+    command reports independent replicas instead"""
+    common = ["--gpus", "3", "--steps", "1", "--warmup", "1", "--size", "2560", "--full", "--no-cpu-baseline"]
+    out, _ = _run_bench(common + ["--dump-outputs", str(tmp_path)], {"EIGX_BENCH_BACKEND": "gloo"})
     assert out["n_gpus"] == 3 and out["scaling"] == "strong" and out["value"] > 0
+    _check_bench_dump(tmp_path, 2560)
     assert out["config"]["transport"]["step_exchange"].startswith("peer writes")
     assert out["config"]["transport"]["selftest"]["ipc_errors"] == 0
     assert out["config"]["probe_residual_over_anorm"] < 1e-13
@@ -723,6 +741,20 @@ def test_bench_launches_ranks_and_walks_the_ladder():
     out, err = _run_bench(common, {"EIGX_BENCH_BACKEND": "gloo", "EIGX_SELFTEST_FAIL": "ipc"})
     assert out["n_gpus"] == 3 and out["scaling"] == "weak" and "replicas" in out["config"]["parallelism"]
     assert "falls back to independent replicas" in err
+
+
+def test_bench_plain_line_full_line_and_dumped_outputs(tmp_path):
+    """`python bench.py --gpus 1`: a plain run times the steps and prints the headline line only; --dump-outputs writes what
+    the last timed solve returned (N = 2560: a seeded sample of the eigenvectors, as at the headline N); --full adds the
+    accuracy gates and the cpu_baseline"""
+    common = ["--gpus", "1", "--steps", "2", "--warmup", "1", "--size", "2560"]
+    out, _ = _run_bench(common + ["--dump-outputs", str(tmp_path)], {})
+    assert out["n_gpus"] == 1 and out["steps"] == 2 and out["ms_per_step"] > 0 and out["value"] > 0
+    assert "residual_metric_lt_768" not in out["config"] and "cpu_baseline" not in out and "extra" not in out
+    _check_bench_dump(tmp_path, 2560)
+    out, _ = _run_bench(common + ["--full", "--no-extra", "--cpu-n", "640"], {"EIGX_CPU_CORES": "4"})
+    assert out["config"]["residual_metric_lt_768"] < GATE_RES and out["config"]["orthogonality_metric_lt_8"] < GATE_ORTH
+    assert out["cpu_baseline"]["n"] == 640 and out["cpu_baseline"]["value"] > 0
 
 
 def test_gemm_gather_vs_torch(gpu_lib):

@@ -583,6 +583,23 @@ def test_matrix_market_reader(tmp_path):
         layout.read_matrix_market(str(p), 5)
 
 
+def test_bench_dump_columns_fit_the_size_cap():
+    """bench.py --dump-outputs: eigenvalues plus the chosen eigenvector columns stay within 64 MiB at every N (the .npy
+    headers included); every column while they fit, else a seeded, sorted, duplicate-free sample, the same every time"""
+    from bench import dump_columns
+
+    for n in (1, 2, 640, 2508, 2509, 2560, 8192, 16384, 32768, 65536, 131072):
+        sel = dump_columns(n)
+        assert 8 * n + 8 * n * len(sel) + 2 * 128 <= 64 << 20, n
+        assert len(sel) >= 1 and sel.min() >= 0 and sel.max() < n and (np.diff(sel) > 0).all(), n
+        assert np.array_equal(sel, dump_columns(n)), n
+        if 8 * n * n <= 48 << 20:
+            assert len(sel) == n, n
+        else:
+            assert len(sel) < n and 8 * n * (len(sel) + 1) > 48 << 20, n   # as many columns as fit
+    assert len(dump_columns(8192)) == 768 and len(dump_columns(32768)) == 192
+
+
 def test_bench_spawns_its_own_ranks():
     """`python bench.py --gpus N` without a launcher starts N ranks itself (before anything touches a GPU) and relays
     rank 0's line and the worst exit code; `--gpus N` under a different WORLD_SIZE is refused."""
@@ -607,15 +624,15 @@ def test_bench_spawns_its_own_ranks():
 
 
 def test_reference_benchmark_sources_find_their_symbols_in_the_module():
-    """Build-container-only boundary check (skipped where /root/reference is absent): every entity of eigen_libs_mod /
-    eigen_blacs_mod that the reference's OWN benchmark sources (benchmark/main2.f, mat_set.f, w_test.f, ev_test.f) call,
-    and every keyword argument they pass, exists in eigenexa_amd/fortran/eigen_libs_mod.F90 with that dummy-argument
-    name.  The sources are read as TEXT: a `flang -fsyntax-only` pass over them is not possible here, because they also
-    `use mpi` and the image's mpi.mod is in gfortran's format (unreadable by flang) -- writing a replacement module would
-    be a stand-in for something the image lacks, which this project's rules exclude."""
-    ref = "/root/reference/benchmark"
-    if not os.path.isdir(ref):
-        pytest.skip("reference tree not present")
+    """Boundary check: every entity of eigen_libs_mod / eigen_blacs_mod that the reference's OWN benchmark sources
+    (benchmark/main2.f, mat_set.f, w_test.f, ev_test.f) call, and every keyword argument they pass, exists in
+    eigenexa_amd/fortran/eigen_libs_mod.F90 with that dummy-argument name.  The calls and keywords were read from those
+    sources as TEXT into tests/golden/reference_calls.json (tools/make_reference_calls.py): a `flang -fsyntax-only`
+    pass over them is not possible, because they also `use mpi` and the image's mpi.mod is in gfortran's format (unreadable
+    by flang) -- writing a replacement module would be a stand-in for something the image lacks, which this project's
+    rules exclude."""
+    import json
+
     mod = open(os.path.join(ROOT, "eigenexa_amd", "fortran", "eigen_libs_mod.F90")).read().lower()
     public = set()
     for m in re.finditer(r"^\s*public\s*::\s*(.+)$", mod, re.M):
@@ -631,30 +648,12 @@ def test_reference_benchmark_sources_find_their_symbols_in_the_module():
             for nm in line.split(","):
                 args |= dummies.get(nm.strip(), set())
         dummies[m.group(1)] = args
-    used, kw = set(), {}
-    for fn in ("main2.f", "mat_set.f", "w_test.f", "ev_test.f"):
-        text = open(os.path.join(ref, fn), errors="replace").read()
-        lines = []
-        for ln in text.splitlines():
-            if not ln or ln[0] in "cC*!":          # fixed-form comment lines
-                continue
-            ln = ln.split("!")[0]
-            if len(ln) > 5 and ln[5] not in " 0" and lines:   # continuation line (column 6)
-                lines[-1] += ln[6:]
-            else:
-                lines.append(ln)
-        for ln in lines:
-            low = ln.lower()
-            for m in re.finditer(r"\b(eigen_[a-z0-9_]+|get_constant_[a-z0-9_]+)\s*\(([^)]*)\)", low):
-                name = m.group(1)
-                used.add(name)
-                for k in re.findall(r"\b([a-z_][a-z0-9_]*)\s*=", m.group(2)):
-                    kw.setdefault(name, set()).add(k)
-            for m in re.finditer(r"call\s+(eigen_[a-z0-9_]+)\b", low):
-                used.add(m.group(1))
-    used -= {"eigen_libs_mod", "eigen_blacs_mod"}
+    with open(os.path.join(ROOT, "tests", "golden", "reference_calls.json")) as f:
+        calls = json.load(f)
+    used = set(calls["used"])
+    kw = {k: set(v) for k, v in calls["keywords"].items()}
     assert {"eigen_init", "eigen_sx", "eigen_s", "eigen_free", "eigen_get_matdims", "eigen_get_comm",
-            "eigen_get_blacs_context", "eigen_memory_internal", "eigen_loop_start", "eigen_owner_node"} <= used   # the scan sees the calls
+            "eigen_get_blacs_context", "eigen_memory_internal", "eigen_loop_start", "eigen_owner_node"} <= used   # the stored list holds the calls
     missing = sorted(n for n in used if n not in public)
     assert not missing, f"the reference's benchmark sources use {missing}, which eigen_libs_mod.F90 does not export"
     for name, keys in kw.items():

@@ -12,5 +12,5 @@ for t in "7=100000" "7=256" "7=512" "7=128"; do
 done
 for t in "7=100000" "7=256"; do
   echo "== EIGX_TUNE=$t (with the N=32768 extra solve)"
-  EIGX_TUNE=$t python bench.py --steps 2 --warmup 1 --no-cpu-baseline 2>&1 | tail -1 | show
+  EIGX_TUNE=$t python bench.py --steps 2 --warmup 1 --full --no-cpu-baseline 2>&1 | tail -1 | show
 done

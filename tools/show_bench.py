@@ -1,4 +1,5 @@
-"""Lab: the fields of a bench.py JSON line that matter at a glance.  usage: show_bench.py file"""
+"""Lab: the fields of a bench.py JSON line that matter at a glance.  usage: show_bench.py file
+(the extra* and cpu rows are filled only by a `bench.py --full` line; a plain line prints None there)"""
 import json
 import sys
 
