@@ -1848,11 +1848,6 @@ __global__ __launch_bounds__(256) void mg_step_kernel(RedArgs R, KLArgs KL, KAAr
   symv_body<NV, RB, NTL, true, UNC>(R, B, bid, (int)gridDim.x - M.nkl - M.nka);
 }
 
-// zero-fill helper
-__global__ void fill_kernel(double* p, size_t n, double v) {
-  for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) p[i] = v;
-}
-
 // ---- multi-GPU helpers ---------------------------------------------------------------------------------------
 // compact copies of the panel for the local trailing update: UWr(li, :) = [U | W](global row of li, :),
 // UWc(lj, :) = [W | U](global row = global column of lj, :)   (the reference keeps the same four arrays: ur, vr

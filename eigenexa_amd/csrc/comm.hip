@@ -25,7 +25,6 @@
 #include <sys/stat.h>
 #include <unistd.h>
 #include <atomic>
-#include <chrono>
 #include <cstring>
 #include <vector>
 
@@ -92,8 +91,6 @@ bool load_rccl() {
 
 constexpr int kNcclFloat64 = 8;  // ncclDouble
 constexpr int kNcclSum = 0, kNcclMax = 2;
-
-double now_s() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 
 // ---- bootstrap board: a few hundred bytes of POSIX shared memory, one slot per rank ------------------------
 struct Board {

@@ -30,7 +30,6 @@
 #include "eigx_comm.h"
 #include "../../include/eigenexa_amd.h"
 #include <algorithm>
-#include <chrono>
 #include <cfloat>
 #include <cstring>
 
@@ -785,7 +784,7 @@ void band_dc_prepare(Context& ctx, int n) {
 }
 
 void band_dc_dev(Context& ctx, int n, int nvec, const double* d_dev, const double* e_dev, int lde, int band,
-                 double* w_dev, double* z_dev, int ldz) {
+                 double* w_dev, double* z_dev, int ldz, const std::function<void()>& side_work) {
   hipStream_t st = ctx.stream;
   const double eps = DBL_EPSILON / 2.0;
   // Several GPUs (replaces the process tree / ring GEMM of dc2_FS, src/FS_PDLAED0.F90:62-323, src/FS_PDLAED3.F90:526-860):
@@ -937,11 +936,11 @@ void band_dc_dev(Context& ctx, int n, int nvec, const double* d_dev, const doubl
   // enqueued when the LAST pass's product starts: beside the leaves or the low heights it made their small dependent
   // kernels wait behind its long workgroups (leaf kernel 0.45 -> 1.4 ms, or a secular launch 0.03 -> 0.7 ms); beside a
   // chip-filling product it costs its own CU time and nothing else.
+  bool side_done = false;
   auto run_side_work = [&] {
-    if (!ctx.dc_side_work) return;
-    std::function<void()> f = std::move(ctx.dc_side_work);
-    ctx.dc_side_work = nullptr;
-    f();
+    if (side_done || !side_work) return;
+    side_done = true;
+    side_work();
   };
 
   // ---- merges: the passes (height, k) in order --------------------------------------------------------
@@ -961,7 +960,6 @@ void band_dc_dev(Context& ctx, int n, int nvec, const double* d_dev, const doubl
   std::vector<int> ordi, ordt, ordb;
   double gemm_flops = 0.0;
   const bool trace = getenv("EIGX_TRACE_DC") != nullptr;
-  auto now_s = [] { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
   // stream of a pass's secular / eigenvector-row kernels: the high-priority side stream where there is a product to run
   // under (big merges); the low heights are one dependent chain either way, and a second stream only adds event hand-offs
   bool z_ready = false;                         // [Dcur | z] of this pass are already on their way to the host

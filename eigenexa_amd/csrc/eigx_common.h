@@ -8,6 +8,7 @@
 #include <cmath>
 #include <vector>
 #include <ctime>
+#include <chrono>
 
 #define EIGX_HIP_CHECK(expr)                                                        \
   do {                                                                              \
@@ -73,7 +74,31 @@ static inline int numroc(int n, int nb, int p, int P) {
   return cnt;
 }
 
+inline double now_s() {
+  return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count();
+}
+
+// Request of a solver entry point (src/eigen_sx.F:104-110, src/eigen_h.F:104-106): mode upper-cased, nvec == 0 means
+// mode 'N', |nvec| clamped to n
+struct SolveRequest {
+  char mode;
+  int nvec;
+  bool want_vec;
+};
+inline SolveRequest normalize_request(int n, int nvec, char mode) {
+  if (mode >= 'a' && mode <= 'z') mode = (char)(mode - 'a' + 'A');
+  if (nvec == 0) mode = 'N';
+  if (nvec < 0) nvec = -nvec;
+  if (nvec > n) nvec = n;
+  return SolveRequest{mode, nvec, mode != 'N'};
+}
+
 // ---- kernels / launchers (device pointers, column-major, all on `stream`) -------------------
+
+// trivial kernels (solver.hip): p[0:n) = v (grid-stride); w[0:n) = v and w[0:n) *= s (one thread per element)
+__global__ void fill_kernel(double* p, size_t n, double v);
+__global__ void fill_vec_kernel(double* __restrict__ w, int n, double v);
+__global__ void scale_vec_kernel(double* __restrict__ w, int n, double s);
 
 // C = alpha*op(A)*op(B) + beta*C ; opA/opB in {'N','T'}.
 // tri_mode: 0 = full, 1 = only tiles that intersect the upper triangle (global row <= global col)

@@ -80,10 +80,8 @@ struct Context {
   // D&C pipeline (one GPU): the secular / Loewner / eigenvector-row kernels of the NEXT pass run on dc_stream under the
   // big product of the current one; dc_b_ev = their completion, dc_z_ev = [new eigenvalues | next z] are on the host
   hipStream_t dc_stream = nullptr;
-  // work the solver wants enqueued on the side stream when the D&C's last product starts (the T factors of the
-  // back-transformation; see band_dc_dev for why not earlier)
-  std::function<void()> dc_side_work;
-  // stream of that work (== side_stream; a CU-masked stream of its own changed nothing: profiles/r04_bt_mask_ab.log)
+  // stream of the side work band_dc_dev runs for its caller (== side_stream; a CU-masked stream of its own changed
+  // nothing: profiles/r04_bt_mask_ab.log)
   hipStream_t bt_stream = nullptr;
   hipEvent_t dc_b_ev = nullptr, dc_z_ev = nullptr;
   int dc_zero_n = 0; const double* dc_zero_qa = nullptr; const double* dc_zero_qb = nullptr;
@@ -117,19 +115,6 @@ struct Context {
 
 extern Context g_ctx;
 
-// A nested one-GPU solve inside a multi-rank entry point (gathered, replicated problems: KMATH_EIGEN_GEV, eigen_h) runs with
-// the one-rank grid; the guard puts the caller's grid back on EVERY way out -- a workspace allocation that fails inside
-// the nested solve unwinds through here (DeviceAllocError), and a rank left on the one-rank grid would believe
-// nranks == 1 while its communicator is still multi-rank.
-struct GridSwap {
-  Context& c;
-  Grid saved;
-  explicit GridSwap(Context& ctx) : c(ctx), saved(ctx.grid) { c.grid = Grid(); }
-  ~GridSwap() { c.grid = saved; }
-  GridSwap(const GridSwap&) = delete;
-  GridSwap& operator=(const GridSwap&) = delete;
-};
-
 void comm_report_failure(Context& ctx, const char* what);   // comm.hip: sets this rank's and every peer's sticky failure word (P > 1)
 
 // C-ABI boundary guard of the solver entry points: a failed workspace allocation becomes an error code
@@ -155,9 +140,10 @@ void band_reduce_dev(Context& ctx, int n, double* A, int lda, double* d, double*
 
 // dc.hip: zero-fill of the D&C's Q buffers on the side stream, ahead of band_dc_dev (optional)
 void band_dc_prepare(Context& ctx, int n);
-// dc.hip: eigen-decomposition of the band matrix (d, e(:,1..band)); w ascending, z(ldz, nvec)
+// dc.hip: eigen-decomposition of the band matrix (d, e(:,1..band)); w ascending, z(ldz, nvec).  side_work (the
+// caller's T factors of the back-transformation) runs exactly once, when the last merge's product starts.
 void band_dc_dev(Context& ctx, int n, int nvec, const double* d, const double* e, int lde, int band, double* w,
-                 double* z, int ldz);
+                 double* z, int ldz, const std::function<void()>& side_work = {});
 
 // bisect.hip: eigenvalues only of the band matrix by Sturm counts (multi-section); w ascending
 void band_bisect_dev(Context& ctx, int n, const double* d, const double* e, int lde, int band, double* w);
@@ -167,5 +153,15 @@ void band_bisect_dev(Context& ctx, int n, const double* d, const double* e, int 
 void cols_to_cyclic_dev(Context& ctx, int n, int nvec, int nb, int zc, int zc0, int zcnt, const double* zcols, int ldz,
                         double* z_user, int ldz_user, hipStream_t st);
 int64_t solver_workspace_bytes(const Context& ctx, int n, int lda, int ldz, int mf, int mb);
+// eigen_scaling of every solver (src/eigen_scaling.F:86-150): max |a| and a non-finite flag over the upper triangle of
+// this rank's 2-D cyclic block of an n x n matrix (real, or interleaved complex with lda in complex elements: max of
+// |Re|, |Im|, Im of the diagonal not read), combined over the ranks.  NaN / Inf anywhere: w(:) = NaN, errinfo = -1,
+// EIGX_ERR_NONFINITE.  Otherwise *sigma = the factor to scale the matrix by (1 = none).
+int eigen_scaling(Context& ctx, const double* a, int lda, bool cplx, int n, double* w, double* sigma);
+// Host staging of a local block of nr x nc elements of esz (8 or 16) bytes: a pooled device buffer with the leading
+// dimension host_ld(nr) (h == nullptr: allocated only), and the copy of a device block back to the host
+inline int host_ld(int nr) { return pad_ld(nr + 2); }
+void* host_to_dev(Context& ctx, const char* name, const void* h, int ld, int nr, int nc, int esz);
+void dev_to_host(void* h, int ld, const void* d, int ldd, int nr, int nc, int esz);
 
 }  // namespace eigx

@@ -1,5 +1,5 @@
-// herm.hip -- eigen_h: complex Hermitian eigensolver.  One GPU; with more ranks the cyclic blocks are
-// gathered, every rank reduces the replicated problem, and the back-transformation is shared by eigenvector columns.
+// herm.hip -- eigen_h: complex Hermitian eigensolver.  One GPU (herm_solve_full); with more ranks the
+// reduction, the D&C and the back-transformation are sharded over the ranks (herm_solve_sharded).
 //
 // Replaces eigen_h (src/eigen_h.F:30-322): eigen_scaling_h -> eigen_hrd (Hermitian -> REAL symmetric tridiagonal,
 // src/eigen_hrd.F:1-448) -> dc2 (the real tridiagonal D&C of dc.hip, unchanged) -> eigen_hrbakwyx (complex WY
@@ -22,8 +22,7 @@
 #include "eigx_comm.h"
 #include "../../include/eigenexa_amd.h"
 #include <cfloat>
-#include <chrono>
-#include <limits>
+#include <algorithm>
 #include <type_traits>
 #include <vector>
 
@@ -39,6 +38,14 @@ constexpr int HTL = 128;     // tile edge of the Hermitian mat-vec
 constexpr int HTH = 256;     // threads of a mat-vec workgroup (4 waves x 32 tile columns, in units of 4 columns)
 constexpr int PDR = 1024;    // rows per panel-dot chunk
 constexpr int HMB = 128;     // reflectors per back-transformation block (the packed triangle S^H of a block lives in LDS)
+// mat-vec launches with at most this many tile rows run 8 waves per tile, one workgroup per CU (253 tiles for nt = 22):
+// reduction at N = 8192 416 - 422 ms with none, 418 up to 16, 414 up to 22, 421 up to 32 (profiles/r03_eigen_h_hemv8_ab.log)
+constexpr int H_HEMV8_NT = 22;
+// Offset (doubles) of the imaginary plane from the real one, for A and for Z.  The two planes are streamed together at
+// equal offsets; with plane sizes that are multiples of 16 KiB every pair of requests met on the same memory channel.
+// Half a period (+128 B) between them: reduction 488 -> 459 ms at N = 8192 (offset 0 -> 488, 272 -> 486, 784 -> 471,
+// 1040 -> 459, 1552 -> 498, 4112 -> 492 ms, reproducible: profiles/r03_eigen_h_plane_skew.log).
+constexpr int H_PLANE_SKEW = 1040;
 
 struct HArgs {
   double *Ar, *Ai; int ld; int n;
@@ -109,36 +116,12 @@ __global__ void h_split_kernel(const double* __restrict__ a, int lda, int n, dou
   }
 }
 
-// max |re|, |im| over the upper triangle and a non-finite flag (eigen_scaling_h, src/eigen_scaling_h.F)
-__global__ __launch_bounds__(HT) void h_absmax_kernel(const double* __restrict__ a, int lda, int n, double* __restrict__ out) {
-  __shared__ double red[8];
-  double v[2] = {0.0, 0.0};
-  for (int j = blockIdx.x; j < n; j += gridDim.x)
-    for (int i = threadIdx.x; i <= j; i += HT) {
-      const double re = fabs(a[2 * ((size_t)i + (size_t)j * lda)]);
-      const double im = (i == j) ? 0.0 : fabs(a[2 * ((size_t)i + (size_t)j * lda) + 1]);
-      if (!(re <= DBL_MAX) || !(im <= DBL_MAX)) v[1] = 1.0;
-      else v[0] = fmax(v[0], fmax(re, im));
-    }
-  for (int o = 32; o > 0; o >>= 1) { v[0] = fmax(v[0], __shfl_xor(v[0], o, 64)); v[1] = fmax(v[1], __shfl_xor(v[1], o, 64)); }
-  if ((threadIdx.x & 63) == 0) { red[(threadIdx.x >> 6) * 2] = v[0]; red[(threadIdx.x >> 6) * 2 + 1] = v[1]; }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    out[2 * blockIdx.x] = fmax(fmax(red[0], red[2]), fmax(red[4], red[6]));
-    out[2 * blockIdx.x + 1] = fmax(fmax(red[1], red[3]), fmax(red[5], red[7]));
-  }
-}
-
 __global__ void h_scale_kernel(double* __restrict__ a, int lda, int n, double s) {   // interleaved, upper triangle
   const int j = blockIdx.y;
   for (int i = blockIdx.x * blockDim.x + threadIdx.x; i <= j; i += gridDim.x * blockDim.x) {
     a[2 * ((size_t)i + (size_t)j * lda)] *= s;
     a[2 * ((size_t)i + (size_t)j * lda) + 1] *= s;
   }
-}
-
-__global__ void h_fill_kernel(double* p, size_t n, double v) {
-  for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) p[i] = v;
 }
 
 // Reflector scalars of column i (L = i rows) from ||x||^2 (the norm partials of K1, added in one fixed order by every
@@ -685,6 +668,38 @@ __global__ void h_xstack_kernel(const double* __restrict__ Xr, const double* __r
   }
 }
 
+// workspace of h_bt_block for up to nv eigenvector columns: Y = V^H Z stacked (YA | YB), its planes, X = T Y
+struct HBtWork { double *YA, *YB, *Yr, *Yi, *Xr, *Xi; };
+HBtWork h_bt_work(Context& ctx, int nv) {
+  HBtWork W;
+  W.YA = ctx.pool.get_t<double>("h.YAB", (size_t)2 * 2 * HMB * nv);
+  W.YB = W.YA + (size_t)2 * HMB * nv;
+  W.Yr = ctx.pool.get_t<double>("h.Yr", (size_t)HMB * nv);
+  W.Yi = ctx.pool.get_t<double>("h.Yi", (size_t)HMB * nv);
+  W.Xr = ctx.pool.get_t<double>("h.Xr", (size_t)HMB * nv);
+  W.Xi = ctx.pool.get_t<double>("h.Xi", (size_t)HMB * nv);
+  return W;
+}
+// one block of eigen_hrbakwyx on nvec columns of the planes Zr, Zi (ld ldzp, one buffer: V^H Z is batched over them):
+// Z -= V (T (V^H Z)) with the block's nb reflectors stacked as Vs = [Vr | Vi] (rows x 2nb, ld lds), T = Tr + i Ti (ld HMB)
+void h_bt_block(hipStream_t st, const HBtWork& W, const double* Vs, int lds, const double* Tr, const double* Ti, int nb,
+                int rows, int nvec, double* Zr, double* Zi, int ldzp) {
+  // Y = V^H Z from YA = Vs^T Zr, YB = Vs^T Zi: one batched launch (256 tiles: the LDS-ring kernel; two launches of
+  // 128 tiles each went to the 64 x 64 kernel)
+  dgemm_dev(st, 'T', 'N', 2 * nb, nvec, rows, 1.0, Vs, lds, Zr, ldzp, 0.0, W.YA, 2 * HMB, 0, nullptr, nullptr, nullptr, 2, 0,
+            (long)(Zi - Zr), (long)(W.YB - W.YA));
+  hipLaunchKernelGGL(h_ycombine_kernel, dim3(1, nvec), dim3(128), 0, st, W.YA, W.YB, nb, nvec, W.Yr, W.Yi);
+  // X = T Y : Xr = Tr Yr - Ti Yi ; Xi = Tr Yi + Ti Yr
+  dgemm_dev(st, 'N', 'N', nb, nvec, nb, 1.0, Tr, HMB, W.Yr, HMB, 0.0, W.Xr, HMB);
+  dgemm_dev(st, 'N', 'N', nb, nvec, nb, -1.0, Ti, HMB, W.Yi, HMB, 1.0, W.Xr, HMB);
+  dgemm_dev(st, 'N', 'N', nb, nvec, nb, 1.0, Tr, HMB, W.Yi, HMB, 0.0, W.Xi, HMB);
+  dgemm_dev(st, 'N', 'N', nb, nvec, nb, 1.0, Ti, HMB, W.Yr, HMB, 1.0, W.Xi, HMB);
+  // Z -= V X : Zr -= Vs [Xr; -Xi] ; Zi -= Vs [Xi; Xr]   (K = 2nb)
+  hipLaunchKernelGGL(h_xstack_kernel, dim3(1, nvec), dim3(128), 0, st, W.Xr, W.Xi, nb, nvec, W.YA, W.YB);
+  dgemm_dev(st, 'N', 'N', rows, nvec, 2 * nb, -1.0, Vs, lds, W.YA, 2 * HMB, 1.0, Zr, ldzp);
+  dgemm_dev(st, 'N', 'N', rows, nvec, 2 * nb, -1.0, Vs, lds, W.YB, 2 * HMB, 1.0, Zi, ldzp);
+}
+
 __global__ void h_join_kernel(const double* __restrict__ Zr, const double* __restrict__ Zi, int ldzp, int n, int nvec,
                               double* __restrict__ z, int ldz) {
   const int c = blockIdx.y;
@@ -694,43 +709,27 @@ __global__ void h_join_kernel(const double* __restrict__ Zr, const double* __res
   }
 }
 
-__global__ void h_identity_kernel(double* __restrict__ z, int ldz, int nvec) {
+// z(c0 + j, j) = 1 for j < cn: the identity on the eigenvector columns [c0, c0 + cn) (mode 'S')
+__global__ void h_identity_kernel(double* __restrict__ z, int ldz, int c0, int cn) {
   const int j = blockIdx.x * blockDim.x + threadIdx.x;
-  if (j < nvec) z[(size_t)j * ldz + j] = 1.0;
+  if (j < cn) z[(size_t)j * ldz + c0 + j] = 1.0;
 }
-__global__ void h_scale_vec_kernel(double* __restrict__ w, int n, double s) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < n) w[i] *= s;
-}
-__global__ void h_fill_vec_kernel(double* __restrict__ w, int n, double v) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < n) w[i] = v;
-}
-
-double hnow() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
-
 }  // namespace
 
-// a, z: device, interleaved complex(8), leading dimensions in complex elements
-// full (global) matrix on this rank's GPU.  With more than one rank every rank runs this on the same replicated input:
-// the reduction and the real tridiagonal D&C are redundant, the back-transformation (19 % of a solve at N = 8192) is
-// split by eigenvector columns and allgathered.  Correct; the reduction is what a sharded form still has to distribute.
-// bt_P, bt_p: several ranks that hold the same replicated problem share the back-transformation by eigenvector columns
-// (rank bt_p of bt_P takes the columns [bt_p * zc, (bt_p + 1) * zc), zc = ceil(nvec / bt_P)) and allgather the result
+// One GPU.  a, z: device, interleaved complex(8), leading dimensions in complex elements
 static int herm_solve_full(Context& ctx, int n, int nvec, double* a, int lda, double* w, double* z, int ldz, int mf, int mb,
-                           char mode, int bt_P = 1, int bt_p = 0) {
+                           char mode) {
   if (!ctx.initialized) return EIGX_ERR_NOT_INITIALIZED;
   if (n <= 0) {
     fprintf(stderr, "[eigx] warning: non-positive dimension is invalid\n");   // src/eigen_h.F:91-94
     return EIGX_ERR_BAD_ARG;
   }
   if (!a || !w || lda < n) return EIGX_ERR_BAD_ARG;
-  if (mode >= 'a' && mode <= 'z') mode = (char)(mode - 'a' + 'A');
-  if (nvec == 0) mode = 'N';                      // src/eigen_h.F:104-106
-  if (nvec < 0) nvec = -nvec;
-  if (nvec > n) nvec = n;
+  const SolveRequest rq = normalize_request(n, nvec, mode);   // src/eigen_h.F:104-106
+  nvec = rq.nvec;
+  mode = rq.mode;
   if (mode != 'N' && mode != 'A' && mode != 'X' && mode != 'S') mode = 'A';   // 'S': identity + bisection + back-transformation (src/eigen_h.F:207-210)
-  const bool want_vec = mode != 'N';
+  const bool want_vec = rq.want_vec;
   if (want_vec && (!z || ldz < n)) return EIGX_ERR_BAD_ARG;
   int m = mf <= 0 ? 48 : mf;
   if (m > HM) m = HM;
@@ -740,29 +739,13 @@ static int herm_solve_full(Context& ctx, int n, int nvec, double* a, int lda, do
   hipStream_t st = ctx.stream;
   ctx.errinfo = 0;
   for (int q = 0; q < 16; ++q) ctx.timers[q] = 0.0;
-  const double t0 = hnow();
+  const double t0 = now_s();
 
   // ---- eigen_scaling_h -------------------------------------------------------------------------------------------
   double sigma = 1.0;
-  {
-    const int nbk = 256;
-    double* part = ctx.pool.get_t<double>("h.absmax", (size_t)2 * nbk);
-    hipLaunchKernelGGL(h_absmax_kernel, dim3(nbk), dim3(HT), 0, st, a, lda, n, part);
-    std::vector<double> hp(2 * nbk);
-    EIGX_HIP_CHECK(hipMemcpyAsync(hp.data(), part, hp.size() * 8, hipMemcpyDeviceToHost, st));
-    EIGX_HIP_CHECK(hipStreamSynchronize(st));
-    double anrm = 0.0, bad = 0.0;
-    for (int q = 0; q < nbk; ++q) { anrm = std::max(anrm, hp[2 * q]); bad = std::max(bad, hp[2 * q + 1]); }
-    if (bad != 0.0) {   // NaN / Inf in the input: w(:) = NaN (src/eigen_h.F:147-150)
-      hipLaunchKernelGGL(h_fill_vec_kernel, dim3((n + 255) / 256), dim3(256), 0, st, w, n,
-                         std::numeric_limits<double>::quiet_NaN());
-      EIGX_HIP_CHECK(hipStreamSynchronize(st));
-      ctx.errinfo = -1;
-      return EIGX_ERR_NONFINITE;
-    }
-    if (anrm > 0.0 && (anrm < 1e-90 || anrm > 1e90)) { int ex = 0; (void)frexp(anrm, &ex); sigma = ldexp(1.0, -ex); }
-    if (sigma != 1.0) hipLaunchKernelGGL(h_scale_kernel, dim3(8, n), dim3(256), 0, st, a, lda, n, sigma);
-  }
+  const int rc_sc = eigen_scaling(ctx, a, lda, true, n, w, &sigma);
+  if (rc_sc != EIGX_OK) return rc_sc;
+  if (sigma != 1.0) hipLaunchKernelGGL(h_scale_kernel, dim3(8, n), dim3(256), 0, st, a, lda, n, sigma);
 
   // ---- workspace -----------------------------------------------------------------------------------------------------
   const int ld = pad_ld(n + 2);
@@ -770,11 +753,7 @@ static int herm_solve_full(Context& ctx, int n, int nvec, double* a, int lda, do
   HArgs H;
   H.n = n; H.ld = ld; H.ldp = ldp; H.P = 1; H.p = 0;
   H.Ar = ctx.pool.get_t<double>("h.Ar", (size_t)ld * (n + HMB));   // HMB columns of slack: the batched Gram products of phase A
-  // The two planes are streamed together at equal offsets; with plane sizes that are multiples of 16 KiB every pair of
-  // requests met on the same memory channel.  Half a period (+128 B) between them: reduction 488 -> 459 ms at N = 8192
-  // (tools/ab_herm_skew.sh: 0 -> 488, 272 -> 486, 784 -> 471, 1040 -> 459, 1552 -> 498, 4112 -> 492 ms, reproducible).
-  static const int plane_skew = [] { const char* e = getenv("EIGX_H_SKEW"); return e ? atoi(e) : 1040; }();   // doubles
-  H.Ai = ctx.pool.get_t<double>("h.Ai", (size_t)ld * (n + HMB) + plane_skew) + plane_skew;
+  H.Ai = ctx.pool.get_t<double>("h.Ai", (size_t)ld * (n + HMB) + H_PLANE_SKEW) + H_PLANE_SKEW;
   H.Ur = ctx.pool.get_t<double>("h.UW", (size_t)4 * ldp * m);   // the four panel planes in one buffer (one fill per panel)
   H.Ui = H.Ur + (size_t)ldp * m;
   H.Wr = H.Ui + (size_t)ldp * m;
@@ -799,16 +778,15 @@ static int herm_solve_full(Context& ctx, int n, int nvec, double* a, int lda, do
   H.yci = ctx.pool.get_t<double>("h.yci", (size_t)nt_max * ldp);
 
   hipLaunchKernelGGL(h_split_kernel, dim3(8, n), dim3(256), 0, st, a, lda, n, H.Ar, H.Ai, ld);
-  hipLaunchKernelGGL(h_fill_kernel, dim3(64), dim3(256), 0, st, H.e, (size_t)lde, 0.0);
-  hipLaunchKernelGGL(h_fill_kernel, dim3(64), dim3(256), 0, st, H.beta, (size_t)2 * n + 2, 0.0);
-  auto zero_panel = [&]() { hipLaunchKernelGGL(h_fill_kernel, dim3(512), dim3(256), 0, st, H.Ur, (size_t)4 * ldp * m, 0.0); };
+  hipLaunchKernelGGL(fill_kernel, dim3(64), dim3(256), 0, st, H.e, (size_t)lde, 0.0);
+  hipLaunchKernelGGL(fill_kernel, dim3(64), dim3(256), 0, st, H.beta, (size_t)2 * n + 2, 0.0);
+  auto zero_panel = [&]() { hipLaunchKernelGGL(fill_kernel, dim3(512), dim3(256), 0, st, H.Ur, (size_t)4 * ldp * m, 0.0); };
   zero_panel();
 
   // ---- eigen_hrd: Hermitian -> real tridiagonal ---------------------------------------------------------------------
-  const double t1 = hnow();
+  const double t1 = now_s();
   // two launches per column: K1 (finish the previous column, form this one) and K3 (mat-vec + panel dots); the norm
   // partials alternate between two buffers (K1 reads the previous column's while it writes this column's)
-  static const int hemv8_nt = [] { const char* e = getenv("EIGX_H_HEMV8_NT"); return e ? atoi(e) : 22; }();   // lab switch
   int k = 0, par = 0;
   int Lp = 0, ntp = 0, npdcp = 0, npartsp = 0;     // the column that is waiting to be finished (Lp = 0: none)
   double* pnb[2] = {H.pn, H.pn + nwg};
@@ -825,7 +803,7 @@ static int herm_solve_full(Context& ctx, int n, int nvec, double* a, int lda, do
     const int npdc = ceil_div(L, PDR);
     const int nt = ceil_div(L, HTL);
     H.pn = pnb[par];
-    if (nt <= hemv8_nt)   // few tiles (253 for nt = 22): 8 waves per tile, one workgroup per CU
+    if (nt <= H_HEMV8_NT)
       hipLaunchKernelGGL(h_hemv_kernel<8>, dim3(k * npdc + nt * (nt + 1) / 2), dim3(512), 0, st, H, L, k, nt, npdc, 2, nparts,
                          nt * (nt + 1) / 2);
     else
@@ -882,7 +860,7 @@ static int herm_solve_full(Context& ctx, int n, int nvec, double* a, int lda, do
     hipLaunchKernelGGL(h_tinv_kernel, dim3(nblk), dim3(HMB), shm, st, Gall, H.beta, 1, bw, n, Tall);
   }
   EIGX_HIP_CHECK(hipStreamSynchronize(st));
-  const double t2 = hnow();
+  const double t2 = now_s();
 
   // ---- real tridiagonal eigenproblem (dc2 / bisect) --------------------------------------------------------------------
   double* Zr = nullptr;
@@ -891,47 +869,30 @@ static int herm_solve_full(Context& ctx, int n, int nvec, double* a, int lda, do
   if (!want_vec) {
     band_bisect_dev(ctx, n, H.d, H.e, lde, 1, w);
   } else {
-    // both planes in one buffer (V^H Z is one batched product over them), room for bt_P column blocks of
-    // ceil(nvec / bt_P) each, the imaginary plane half a 16 KiB period off the real one's grid (as for A above)
-    const size_t zplane = (size_t)ldzp * (n + bt_P) + 1040;
+    // both planes in one buffer (V^H Z is one batched product over them), the imaginary plane H_PLANE_SKEW off
+    const size_t zplane = (size_t)ldzp * (n + 1) + H_PLANE_SKEW;
     Zr = ctx.pool.get_t<double>("h.Zri", 2 * zplane);
     Zi = Zr + zplane;
     if (mode == 'S') {
       // Z = I (the first nvec columns), eigenvalues by bisection: the back-transformation then delivers the unitary
       // matrix of the reduction itself, Z^H A Z = T (src/eigen_h.F:207-210, eigen_identity src/eigen_identity.F)
-      hipLaunchKernelGGL(h_fill_kernel, dim3(1024), dim3(256), 0, st, Zr, (size_t)ldzp * nvec, 0.0);
-      hipLaunchKernelGGL(h_identity_kernel, dim3(ceil_div(nvec, 256)), dim3(256), 0, st, Zr, ldzp, nvec);
+      hipLaunchKernelGGL(fill_kernel, dim3(1024), dim3(256), 0, st, Zr, (size_t)ldzp * nvec, 0.0);
+      hipLaunchKernelGGL(h_identity_kernel, dim3(ceil_div(nvec, 256)), dim3(256), 0, st, Zr, ldzp, 0, nvec);
       band_bisect_dev(ctx, n, H.d, H.e, lde, 1, w);
     } else {
-      // multi-rank callers reach this point with the gathered (replicated) problem: the real tridiagonal D&C runs
-      // replicated too (its distributed form delivers column blocks, which only the real solvers consume)
-      GridSwap one_rank(ctx);
       band_dc_dev(ctx, n, nvec, H.d, H.e, lde, 1, w, Zr, ldzp);
     }
     if (mode == 'X') band_bisect_dev(ctx, n, H.d, H.e, lde, 1, w);
-    hipLaunchKernelGGL(h_fill_kernel, dim3(1024), dim3(256), 0, st, Zi, (size_t)ldzp * nvec, 0.0);
+    hipLaunchKernelGGL(fill_kernel, dim3(1024), dim3(256), 0, st, Zi, (size_t)ldzp * nvec, 0.0);
   }
-  const double t3 = hnow();
+  const double t3 = now_s();
 
   // ---- eigen_hrbakwyx: z = H_{n-1}^H ... H_1^H y in blocks of HMB reflectors -------------------------------------------
   if (want_vec && n > 1) {
-    double* YA = ctx.pool.get_t<double>("h.YAB", (size_t)2 * 2 * HMB * nvec);
-    double* YB = YA + (size_t)2 * HMB * nvec;
-    double* Yr = ctx.pool.get_t<double>("h.Yr", (size_t)HMB * nvec);
-    double* Yi = ctx.pool.get_t<double>("h.Yi", (size_t)HMB * nvec);
-    double* Xr = ctx.pool.get_t<double>("h.Xr", (size_t)HMB * nvec);
-    double* Xi = ctx.pool.get_t<double>("h.Xi", (size_t)HMB * nvec);
+    const HBtWork W = h_bt_work(ctx, nvec);
     double* Vs = ctx.pool.get_t<double>("h.Vs", (size_t)lds * 2 * HMB);
-    // phase B: apply the blocks in ascending order -- to this rank's eigenvector columns
-    const int zc = ceil_div(nvec, bt_P);
-    const int c0 = (bt_p * zc < nvec) ? bt_p * zc : nvec;
-    const int cn = (c0 + zc <= nvec) ? zc : nvec - c0;
-    double* const Zr_all = Zr;
-    double* const Zi_all = Zi;
-    const int nvec_all = nvec;
-    Zr += (size_t)c0 * ldzp; Zi += (size_t)c0 * ldzp;
-    nvec = cn;
-    for (int b = 0; b < nblk && nvec > 0; ++b) {
+    // phase B: apply the blocks in ascending order
+    for (int b = 0; b < nblk; ++b) {
       const int j0 = 1 + b * bw;
       const int nb = (j0 + bw <= n) ? bw : n - j0;
       const int rows = j0 + nb - 1;
@@ -939,37 +900,15 @@ static int herm_solve_full(Context& ctx, int n, int nvec, double* a, int lda, do
       const double* Ti = Tr + (size_t)HMB * HMB;
       hipLaunchKernelGGL(h_stack_v_kernel, dim3(8, 2 * nb), dim3(256), 0, st, H.Ar + (size_t)j0 * ld, H.Ai + (size_t)j0 * ld,
                          ld, rows, nb, Vs, lds);
-      // Y = V^H Z from YA = Vs^T Zr, YB = Vs^T Zi: one batched launch (256 tiles: the LDS-ring kernel; two launches of
-      // 128 tiles each went to the 64 x 64 kernel)
-      dgemm_dev(st, 'T', 'N', 2 * nb, nvec, rows, 1.0, Vs, lds, Zr, ldzp, 0.0, YA, 2 * HMB, 0, nullptr, nullptr, nullptr, 2, 0,
-                (long)(Zi - Zr), (long)(YB - YA));
-      hipLaunchKernelGGL(h_ycombine_kernel, dim3(1, nvec), dim3(128), 0, st, YA, YB, nb, nvec, Yr, Yi);
-      // X = T Y : Xr = Tr Yr - Ti Yi ; Xi = Tr Yi + Ti Yr
-      dgemm_dev(st, 'N', 'N', nb, nvec, nb, 1.0, Tr, HMB, Yr, HMB, 0.0, Xr, HMB);
-      dgemm_dev(st, 'N', 'N', nb, nvec, nb, -1.0, Ti, HMB, Yi, HMB, 1.0, Xr, HMB);
-      dgemm_dev(st, 'N', 'N', nb, nvec, nb, 1.0, Tr, HMB, Yi, HMB, 0.0, Xi, HMB);
-      dgemm_dev(st, 'N', 'N', nb, nvec, nb, 1.0, Ti, HMB, Yr, HMB, 1.0, Xi, HMB);
-      // Z -= V X : Zr -= Vs [Xr; -Xi] ; Zi -= Vs [Xi; Xr]   (K = 2nb)
-      hipLaunchKernelGGL(h_xstack_kernel, dim3(1, nvec), dim3(128), 0, st, Xr, Xi, nb, nvec, YA, YB);
-      dgemm_dev(st, 'N', 'N', rows, nvec, 2 * nb, -1.0, Vs, lds, YA, 2 * HMB, 1.0, Zr, ldzp);
-      dgemm_dev(st, 'N', 'N', rows, nvec, 2 * nb, -1.0, Vs, lds, YB, 2 * HMB, 1.0, Zi, ldzp);
-    }
-    nvec = nvec_all;
-    Zr = Zr_all; Zi = Zi_all;
-    if (bt_P > 1) {   // every rank gets every column block (the caller cuts its cyclic block out of the full matrix)
-      double* Gr = ctx.pool.get_t<double>("h.ZrG", (size_t)ldzp * zc * bt_P);
-      double* Gi = ctx.pool.get_t<double>("h.ZiG", (size_t)ldzp * zc * bt_P);
-      comm_allgather(ctx, COMM_WORLD, Zr + (size_t)bt_p * zc * ldzp, Gr, (size_t)zc * ldzp, st);
-      comm_allgather(ctx, COMM_WORLD, Zi + (size_t)bt_p * zc * ldzp, Gi, (size_t)zc * ldzp, st);
-      Zr = Gr; Zi = Gi;
+      h_bt_block(st, W, Vs, lds, Tr, Ti, nb, rows, nvec, Zr, Zi, ldzp);
     }
   }
   if (want_vec) hipLaunchKernelGGL(h_join_kernel, dim3(8, nvec), dim3(256), 0, st, Zr, Zi, ldzp, n, nvec, z, ldz);
   if (sigma != 1.0 && sigma != 0.0)
-    hipLaunchKernelGGL(h_scale_vec_kernel, dim3((n + 255) / 256), dim3(256), 0, st, w, n, 1.0 / sigma);
+    hipLaunchKernelGGL(scale_vec_kernel, dim3((n + 255) / 256), dim3(256), 0, st, w, n, 1.0 / sigma);
   EIGX_HIP_CHECK(hipStreamSynchronize(st));
   EIGX_HIP_CHECK(hipGetLastError());
-  const double t4 = hnow();
+  const double t4 = now_s();
 
   // ---- statistics (src/eigen_h.F:284-288): a(1,1) = flops, a(2,1) = seconds (real parts) ------------------------------
   const double f_red = 4.0 / 3.0 * (double)n * n * n;
@@ -999,27 +938,6 @@ static int herm_solve_full(Context& ctx, int n, int nvec, double* a, int lda, do
 //     (each rank contributes the one it owns to an allgather); exit through the real solvers' all-to-all, plane by plane.
 // Nothing of size n^2 is gathered anywhere.
 namespace {
-__global__ __launch_bounds__(HT) void hs_absmax_kernel(const double* __restrict__ a, int lda, int nr, int nc, int Px, int px, int Py,
-                                                       int py, double* __restrict__ out) {
-  __shared__ double red[2 * (HT / 64)];
-  double mx = 0.0, bad = 0.0;
-  for (int lj = blockIdx.x; lj < nc; lj += gridDim.x) {
-    const int gj = lj * Py + py;
-    for (int li = threadIdx.x; li < nr; li += HT) {
-      if (li * Px + px > gj) break;                       // upper triangle only (rows ascend with li)
-      const double re = a[2 * ((size_t)lj * lda + li)], im = a[2 * ((size_t)lj * lda + li) + 1];
-      if (!(fabs(re) <= DBL_MAX) || !(fabs(im) <= DBL_MAX)) bad = 1.0;
-      else mx = fmax(mx, fmax(fabs(re), fabs(im)));
-    }
-  }
-  for (int o = 32; o > 0; o >>= 1) { mx = fmax(mx, __shfl_xor(mx, o, 64)); bad = fmax(bad, __shfl_xor(bad, o, 64)); }
-  if ((threadIdx.x & 63) == 0) { red[2 * (threadIdx.x >> 6)] = mx; red[2 * (threadIdx.x >> 6) + 1] = bad; }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    for (int w = 1; w < HT / 64; ++w) { mx = fmax(mx, red[2 * w]); bad = fmax(bad, red[2 * w + 1]); }
-    out[2 * blockIdx.x] = mx; out[2 * blockIdx.x + 1] = bad;
-  }
-}
 // entry all-to-all, sender: piece for rank d = [plane][k][lr], k-th of my local columns whose tile column d owns
 __global__ void hs_pack_kernel(const double* __restrict__ a, int lda, int nr, const int* __restrict__ cols, int ncmax, int nrmax,
                                double sigma, double* __restrict__ send) {
@@ -1089,10 +1007,6 @@ __global__ void hs_zero_below_kernel(HArgs H, int n, int nlc) {
     H.Ar[(size_t)lc * H.ld + r] = 0.0; H.Ai[(size_t)lc * H.ld + r] = 0.0;
   }
 }
-__global__ void hs_identity_block_kernel(double* __restrict__ z, int ldz, int c0, int cn) {
-  const int j = blockIdx.x * blockDim.x + threadIdx.x;
-  if (j < cn) z[(size_t)j * ldz + c0 + j] = 1.0;
-}
 __global__ void hs_join_cyclic_kernel(const double* __restrict__ zr, const double* __restrict__ zi, int ldt, int nr, int nzc,
                                       double* __restrict__ z, int ldz) {
   const int lj = blockIdx.y;
@@ -1110,12 +1024,11 @@ static int herm_solve_sharded(Context& ctx, int n, int nvec, double* a, int lda,
   const Grid G = ctx.grid;
   const int P = G.nranks, me = G.rank;
   const int nloc_r = local_count(n, G.Px, G.px), nloc_c = local_count(n, G.Py, G.py);
-  if (mode >= 'a' && mode <= 'z') mode = (char)(mode - 'a' + 'A');
-  if (nvec == 0) mode = 'N';                      // src/eigen_h.F:104-106
-  if (nvec < 0) nvec = -nvec;
-  if (nvec > n) nvec = n;
+  const SolveRequest rq = normalize_request(n, nvec, mode);   // src/eigen_h.F:104-106
+  nvec = rq.nvec;
+  mode = rq.mode;
   if (mode != 'N' && mode != 'A' && mode != 'X' && mode != 'S') mode = 'A';
-  const bool want_vec = mode != 'N';
+  const bool want_vec = rq.want_vec;
   int m = mf <= 0 ? 48 : mf;
   if (m > HM) m = HM;
   if (m > n) m = n;
@@ -1124,34 +1037,12 @@ static int herm_solve_sharded(Context& ctx, int n, int nvec, double* a, int lda,
   ctx.errinfo = 0;
   for (int q = 0; q < 16; ++q) ctx.timers[q] = 0.0;
   (void)comm_seconds(ctx, true);
-  const double t0 = hnow();
+  const double t0 = now_s();
 
-  // ---- eigen_scaling_h on the local blocks, maxima combined over the ranks ------------------------------------------
+  // ---- eigen_scaling_h on the local blocks, maxima combined over the ranks (sigma is applied by hs_pack_kernel) --------
   double sigma = 1.0;
-  {
-    const int nbk = 64;
-    double* part = ctx.pool.get_t<double>("hs.absmax", (size_t)2 * nbk + 2);
-    hipLaunchKernelGGL(hs_absmax_kernel, dim3(nbk), dim3(HT), 0, st, a, lda, nloc_r, nloc_c, G.Px, G.px, G.Py, G.py, part);
-    std::vector<double> hp(2 * nbk);
-    EIGX_HIP_CHECK(hipMemcpyAsync(hp.data(), part, hp.size() * 8, hipMemcpyDeviceToHost, st));
-    EIGX_HIP_CHECK(hipStreamSynchronize(st));
-    double two[2] = {0.0, 0.0};
-    for (int q = 0; q < nbk; ++q) { two[0] = std::max(two[0], hp[2 * q]); two[1] = std::max(two[1], hp[2 * q + 1]); }
-    EIGX_HIP_CHECK(hipMemcpyAsync(part, two, 16, hipMemcpyHostToDevice, st));
-    comm_allreduce_max(ctx, COMM_WORLD, part, 2, st);
-    EIGX_HIP_CHECK(hipMemcpyAsync(two, part, 16, hipMemcpyDeviceToHost, st));
-    EIGX_HIP_CHECK(hipStreamSynchronize(st));
-    if (comm_failed(ctx)) return EIGX_ERR_INTERNAL;
-    if (two[1] != 0.0) {   // NaN / Inf in the input (on any rank): w(:) = NaN on every rank (src/eigen_h.F:147-150)
-      hipLaunchKernelGGL(h_fill_vec_kernel, dim3((n + 255) / 256), dim3(256), 0, st, w, n,
-                         std::numeric_limits<double>::quiet_NaN());
-      EIGX_HIP_CHECK(hipStreamSynchronize(st));
-      ctx.errinfo = -1;
-      return EIGX_ERR_NONFINITE;
-    }
-    const double anrm = two[0];
-    if (anrm > 0.0 && (anrm < 1e-90 || anrm > 1e90)) { int ex = 0; (void)frexp(anrm, &ex); sigma = ldexp(1.0, -ex); }
-  }
+  const int rc_sc = eigen_scaling(ctx, a, lda, true, n, w, &sigma);
+  if (rc_sc != EIGX_OK) return rc_sc;
 
   // ---- workspace: the rank's tile columns of the two planes ------------------------------------------------------------
   const int ld = pad_ld(n + 2);
@@ -1161,9 +1052,8 @@ static int herm_solve_sharded(Context& ctx, int n, int nvec, double* a, int lda,
   const int nlc = ntc * HTL;                           // local columns
   HArgs H;
   H.n = n; H.ld = ld; H.ldp = ldp; H.P = P; H.p = me;
-  static const int plane_skew = [] { const char* e = getenv("EIGX_H_SKEW"); return e ? atoi(e) : 1040; }();   // doubles
   H.Ar = ctx.pool.get_t<double>("hs.Ar", (size_t)ld * (nlc + HMB));
-  H.Ai = ctx.pool.get_t<double>("hs.Ai", (size_t)ld * (nlc + HMB) + plane_skew) + plane_skew;
+  H.Ai = ctx.pool.get_t<double>("hs.Ai", (size_t)ld * (nlc + HMB) + H_PLANE_SKEW) + H_PLANE_SKEW;
   H.Ur = ctx.pool.get_t<double>("h.UW", (size_t)4 * ldp * m);
   H.Ui = H.Ur + (size_t)ldp * m;
   H.Wr = H.Ui + (size_t)ldp * m;
@@ -1188,8 +1078,8 @@ static int herm_solve_sharded(Context& ctx, int n, int nvec, double* a, int lda,
   H.yci = ctx.pool.get_t<double>("h.yci", (size_t)nt_max * ldp);
   double* ybuf = ctx.pool.get_t<double>("hs.ybuf", (size_t)4 * ldp + 8);
   const size_t ycount = (size_t)4 * ldp + 2;
-  hipLaunchKernelGGL(h_fill_kernel, dim3(1024), dim3(256), 0, st, H.Ar, (size_t)ld * (nlc + HMB), 0.0);
-  hipLaunchKernelGGL(h_fill_kernel, dim3(1024), dim3(256), 0, st, H.Ai, (size_t)ld * (nlc + HMB), 0.0);
+  hipLaunchKernelGGL(fill_kernel, dim3(1024), dim3(256), 0, st, H.Ar, (size_t)ld * (nlc + HMB), 0.0);
+  hipLaunchKernelGGL(fill_kernel, dim3(1024), dim3(256), 0, st, H.Ai, (size_t)ld * (nlc + HMB), 0.0);
 
   // ---- entry: 2-D cyclic blocks -> tile columns, one all-to-all --------------------------------------------------------
   {
@@ -1227,13 +1117,13 @@ static int herm_solve_sharded(Context& ctx, int n, int nvec, double* a, int lda,
     hipLaunchKernelGGL(hs_unpack_kernel, dim3(ceil_div(nrmax, 256), ncmax, P), dim3(256), 0, st, (const double*)recvb,
                        (const int*)(tab + (size_t)P * ncmax), ncmax, nrmax, n, G.Px, G.Py, G.row_major, H);
   }
-  hipLaunchKernelGGL(h_fill_kernel, dim3(64), dim3(256), 0, st, H.e, (size_t)lde, 0.0);
-  hipLaunchKernelGGL(h_fill_kernel, dim3(64), dim3(256), 0, st, H.beta, (size_t)2 * n + 2, 0.0);
-  auto zero_panel = [&]() { hipLaunchKernelGGL(h_fill_kernel, dim3(512), dim3(256), 0, st, H.Ur, (size_t)4 * ldp * m, 0.0); };
+  hipLaunchKernelGGL(fill_kernel, dim3(64), dim3(256), 0, st, H.e, (size_t)lde, 0.0);
+  hipLaunchKernelGGL(fill_kernel, dim3(64), dim3(256), 0, st, H.beta, (size_t)2 * n + 2, 0.0);
+  auto zero_panel = [&]() { hipLaunchKernelGGL(fill_kernel, dim3(512), dim3(256), 0, st, H.Ur, (size_t)4 * ldp * m, 0.0); };
   zero_panel();
 
   // ---- eigen_hrd, sharded -------------------------------------------------------------------------------------------------
-  const double t1 = hnow();
+  const double t1 = now_s();
   auto ntl_of = [&](int nt) { long c = 0; for (int tx = me; tx < nt; tx += P) c += tx + 1; return (int)c; };   // my tiles of an nt x nt triangle
   int k = 0, par = 0;
   int Lp = 0, ntp = 0, npdcp = 0, npartsp = 0;
@@ -1261,7 +1151,7 @@ static int herm_solve_sharded(Context& ctx, int n, int nvec, double* a, int lda,
     const int ntl = ntl_of(nt);
     H.pn = pnb[par];
     const int grid = std::max(1, k * npdc + ntl);
-    if (nt <= 22)
+    if (nt <= H_HEMV8_NT)
       hipLaunchKernelGGL(h_hemv_kernel<8>, dim3(grid), dim3(512), 0, st, H, L, k, nt, npdc, 2, nparts, ntl);
     else
       hipLaunchKernelGGL(h_hemv_kernel<4>, dim3(grid), dim3(HTH), 0, st, H, L, k, nt, npdc, 4, nparts, ntl);
@@ -1323,7 +1213,7 @@ static int herm_solve_sharded(Context& ctx, int n, int nvec, double* a, int lda,
   }
   EIGX_HIP_CHECK(hipStreamSynchronize(st));
   if (comm_failed(ctx)) return EIGX_ERR_INTERNAL;
-  const double t2 = hnow();
+  const double t2 = now_s();
 
   // ---- real tridiagonal eigenproblem: distributed D&C (my eigenvector columns, all rows) / bisection --------------------
   const int zc = ceil_div(nvec > 0 ? nvec : 1, P);
@@ -1335,31 +1225,25 @@ static int herm_solve_sharded(Context& ctx, int n, int nvec, double* a, int lda,
   if (!want_vec) {
     band_bisect_dev(ctx, n, H.d, H.e, lde, 1, w);
   } else {
-    const size_t zplane = (size_t)ldzp * (zc + 1) + 1040;
+    const size_t zplane = (size_t)ldzp * (zc + 1) + H_PLANE_SKEW;
     Zr = ctx.pool.get_t<double>("hs.Zri", 2 * zplane);
     Zi = Zr + zplane;
     if (mode == 'S') {
-      hipLaunchKernelGGL(h_fill_kernel, dim3(1024), dim3(256), 0, st, Zr, (size_t)ldzp * zc, 0.0);
-      if (cn > 0) hipLaunchKernelGGL(hs_identity_block_kernel, dim3(ceil_div(cn, 256)), dim3(256), 0, st, Zr, ldzp, c0, cn);
+      hipLaunchKernelGGL(fill_kernel, dim3(1024), dim3(256), 0, st, Zr, (size_t)ldzp * zc, 0.0);
+      if (cn > 0) hipLaunchKernelGGL(h_identity_kernel, dim3(ceil_div(cn, 256)), dim3(256), 0, st, Zr, ldzp, c0, cn);
       band_bisect_dev(ctx, n, H.d, H.e, lde, 1, w);
     } else {
       band_dc_dev(ctx, n, nvec, H.d, H.e, lde, 1, w, Zr, ldzp);
     }
     if (mode == 'X') band_bisect_dev(ctx, n, H.d, H.e, lde, 1, w);
-    hipLaunchKernelGGL(h_fill_kernel, dim3(1024), dim3(256), 0, st, Zi, (size_t)ldzp * zc, 0.0);
+    hipLaunchKernelGGL(fill_kernel, dim3(1024), dim3(256), 0, st, Zi, (size_t)ldzp * zc, 0.0);
   }
   if (comm_failed(ctx)) return EIGX_ERR_INTERNAL;
-  const double t3 = hnow();
+  const double t3 = now_s();
 
   // ---- eigen_hrbakwyx on my column block; the reflector blocks stream past in groups of P ---------------------------------
   if (want_vec && n > 1) {
-    const int nv = cn > 0 ? cn : 1;
-    double* YA = ctx.pool.get_t<double>("h.YAB", (size_t)2 * 2 * HMB * nv);
-    double* YB = YA + (size_t)2 * HMB * nv;
-    double* Yr = ctx.pool.get_t<double>("h.Yr", (size_t)HMB * nv);
-    double* Yi = ctx.pool.get_t<double>("h.Yi", (size_t)HMB * nv);
-    double* Xr = ctx.pool.get_t<double>("h.Xr", (size_t)HMB * nv);
-    double* Xi = ctx.pool.get_t<double>("h.Xi", (size_t)HMB * nv);
+    const HBtWork W = h_bt_work(ctx, cn > 0 ? cn : 1);
     const int lds = ld;
     const size_t SB = (size_t)lds * 2 * HMB + (size_t)2 * HMB * HMB;      // [Vs | Tr | Ti] of one block
     double* bsend = ctx.pool.get_t<double>("hs.bsend", SB);
@@ -1385,16 +1269,7 @@ static int herm_solve_sharded(Context& ctx, int n, int nvec, double* a, int lda,
         const double* Vs = brecv + (size_t)q * SB;
         const double* Tr = Vs + (size_t)lds * 2 * HMB;
         const double* Ti = Tr + (size_t)HMB * HMB;
-        dgemm_dev(st, 'T', 'N', 2 * nb, cn, rows, 1.0, Vs, lds, Zr, ldzp, 0.0, YA, 2 * HMB, 0, nullptr, nullptr, nullptr, 2, 0,
-                  (long)(Zi - Zr), (long)(YB - YA));
-        hipLaunchKernelGGL(h_ycombine_kernel, dim3(1, cn), dim3(128), 0, st, YA, YB, nb, cn, Yr, Yi);
-        dgemm_dev(st, 'N', 'N', nb, cn, nb, 1.0, Tr, HMB, Yr, HMB, 0.0, Xr, HMB);
-        dgemm_dev(st, 'N', 'N', nb, cn, nb, -1.0, Ti, HMB, Yi, HMB, 1.0, Xr, HMB);
-        dgemm_dev(st, 'N', 'N', nb, cn, nb, 1.0, Tr, HMB, Yi, HMB, 0.0, Xi, HMB);
-        dgemm_dev(st, 'N', 'N', nb, cn, nb, 1.0, Ti, HMB, Yr, HMB, 1.0, Xi, HMB);
-        hipLaunchKernelGGL(h_xstack_kernel, dim3(1, cn), dim3(128), 0, st, Xr, Xi, nb, cn, YA, YB);
-        dgemm_dev(st, 'N', 'N', rows, cn, 2 * nb, -1.0, Vs, lds, YA, 2 * HMB, 1.0, Zr, ldzp);
-        dgemm_dev(st, 'N', 'N', rows, cn, 2 * nb, -1.0, Vs, lds, YB, 2 * HMB, 1.0, Zi, ldzp);
+        h_bt_block(st, W, Vs, lds, Tr, Ti, nb, rows, cn, Zr, Zi, ldzp);
       }
     }
   }
@@ -1411,11 +1286,11 @@ static int herm_solve_sharded(Context& ctx, int n, int nvec, double* a, int lda,
                          (const double*)ti_, ldt, nloc_r, nzc, z, ldz);
   }
   if (sigma != 1.0 && sigma != 0.0)
-    hipLaunchKernelGGL(h_scale_vec_kernel, dim3((n + 255) / 256), dim3(256), 0, st, w, n, 1.0 / sigma);
+    hipLaunchKernelGGL(scale_vec_kernel, dim3((n + 255) / 256), dim3(256), 0, st, w, n, 1.0 / sigma);
   EIGX_HIP_CHECK(hipStreamSynchronize(st));
   EIGX_HIP_CHECK(hipGetLastError());
   if (comm_failed(ctx)) return EIGX_ERR_INTERNAL;
-  const double t4 = hnow();
+  const double t4 = now_s();
   const double f_red = 4.0 / 3.0 * (double)n * n * n;
   const double f_dc = ctx.timers[11];
   const double f_bt = want_vec ? 2.0 * (double)nvec * n * n : 0.0;
@@ -1429,41 +1304,6 @@ static int herm_solve_sharded(Context& ctx, int n, int nvec, double* a, int lda,
   return EIGX_OK;
 }
 
-namespace {
-// complex (interleaved) versions of the 2-D cyclic layout kernels of solver.hip
-__global__ void hz_pack_kernel(const double* __restrict__ a, int lda, int nr, int nc, double* __restrict__ out, int bx) {
-  const int lj = blockIdx.y;
-  for (int li = blockIdx.x * blockDim.x + threadIdx.x; li < bx; li += gridDim.x * blockDim.x) {
-    const bool ok = li < nr && lj < nc;
-    out[2 * ((size_t)lj * bx + li)] = ok ? a[2 * ((size_t)lj * lda + li)] : 0.0;
-    out[2 * ((size_t)lj * bx + li) + 1] = ok ? a[2 * ((size_t)lj * lda + li) + 1] : 0.0;
-  }
-}
-__global__ void hz_cyclic_to_full_kernel(const double* __restrict__ recv, int bx, int by, int Px, int Py, int order_r, int n,
-                                         double* __restrict__ F, int ldf) {
-  const int q = blockIdx.z;
-  const int qx = order_r ? q / Py : q % Px, qy = order_r ? q % Py : q / Px;
-  const int lj = blockIdx.y;
-  const int gj = lj * Py + qy;
-  if (gj >= n) return;
-  const double* src = recv + 2 * ((size_t)q * bx * by + (size_t)lj * bx);
-  for (int li = blockIdx.x * blockDim.x + threadIdx.x; li < bx; li += gridDim.x * blockDim.x) {
-    const int gi = li * Px + qx;
-    if (gi < n) { F[2 * ((size_t)gj * ldf + gi)] = src[2 * li]; F[2 * ((size_t)gj * ldf + gi) + 1] = src[2 * li + 1]; }
-  }
-}
-__global__ void hz_full_to_cyclic_kernel(const double* __restrict__ F, int ldf, int nloc_r, int ncols, int Px, int px, int Py,
-                                         int py, double* __restrict__ dst, int ldd) {
-  const int lj = blockIdx.y;
-  const int gj = lj * Py + py;
-  if (gj >= ncols) return;
-  for (int li = blockIdx.x * blockDim.x + threadIdx.x; li < nloc_r; li += gridDim.x * blockDim.x) {
-    dst[2 * ((size_t)lj * ldd + li)] = F[2 * ((size_t)gj * ldf + (size_t)li * Px + px)];
-    dst[2 * ((size_t)lj * ldd + li) + 1] = F[2 * ((size_t)gj * ldf + (size_t)li * Px + px) + 1];
-  }
-}
-}  // namespace
-
 // a, z: this rank's 2-D cyclic blocks (device, interleaved complex), as for eigen_sx / eigen_s
 int herm_solve_dev(Context& ctx, int n, int nvec, double* a, int lda, double* w, double* z, int ldz, int mf, int mb,
                    char mode) {
@@ -1471,44 +1311,11 @@ int herm_solve_dev(Context& ctx, int n, int nvec, double* a, int lda, double* w,
   const Grid& G = ctx.grid;
   if (G.nranks == 1) return herm_solve_full(ctx, n, nvec, a, lda, w, z, ldz, mf, mb, mode);
   if (n <= 0) return EIGX_ERR_BAD_ARG;
-  const int nloc_r = local_count(n, G.Px, G.px), nloc_c = local_count(n, G.Py, G.py);
+  const int nloc_r = local_count(n, G.Px, G.px);
   if (!a || !w || lda < nloc_r) return EIGX_ERR_BAD_ARG;
-  char md = mode;
-  if (md >= 'a' && md <= 'z') md = (char)(md - 'a' + 'A');
-  int nv = nvec < 0 ? -nvec : nvec;
-  if (nv > n) nv = n;
-  const bool want_vec = !(md == 'N' || nv == 0);
-  if (want_vec && (!z || ldz < nloc_r)) return EIGX_ERR_BAD_ARG;
+  if (normalize_request(n, nvec, mode).want_vec && (!z || ldz < nloc_r)) return EIGX_ERR_BAD_ARG;
   EIGX_HIP_CHECK(hipSetDevice(ctx.device));
-  // the sharded form (nothing gathered) is the default; EIGX_H_GATHER=1 keeps the first version -- gather the matrix,
-  // reduce it on every rank -- for comparisons
-  static const bool gather = [] { const char* e = getenv("EIGX_H_GATHER"); return e && atoi(e) != 0; }();
-  if (!gather) return herm_solve_sharded(ctx, n, nvec, a, lda, w, z, ldz, mf, mb, mode);
-  hipStream_t st = ctx.stream;
-  const int bx = ceil_div(n, G.Px), by = ceil_div(n, G.Py);
-  const int ldf = n + 2;
-  double* sendb = ctx.pool.get_t<double>("hm.send", (size_t)2 * bx * by);
-  double* recvb = ctx.pool.get_t<double>("hm.recv", (size_t)2 * bx * by * G.nranks);
-  double* Af = ctx.pool.get_t<double>("hm.A", (size_t)2 * ldf * n);
-  double* Zf = ctx.pool.get_t<double>("hm.Z", (size_t)2 * ldf * n);
-  hipLaunchKernelGGL(hz_pack_kernel, dim3(8, by), dim3(256), 0, st, a, lda, nloc_r, nloc_c, sendb, bx);
-  comm_allgather(ctx, COMM_WORLD, sendb, recvb, (size_t)2 * bx * by, st);
-  hipLaunchKernelGGL(hz_cyclic_to_full_kernel, dim3(8, by, G.nranks), dim3(256), 0, st, recvb, bx, by, G.Px, G.Py,
-                     G.row_major, n, Af, ldf);
-  int members[EIGX_MAXP], mine = 0;
-  const int np = comm_group(ctx, COMM_WORLD, members, &mine);
-  const int rc = herm_solve_full(ctx, n, nvec, Af, ldf, w, Zf, ldf, mf, mb, mode, np, mine);
-  if (rc != EIGX_OK) return rc;
-  if (want_vec) {
-    const int nzc = local_count(nv, G.Py, G.py);
-    if (nzc > 0 && nloc_r > 0)
-      hipLaunchKernelGGL(hz_full_to_cyclic_kernel, dim3(8, nzc), dim3(256), 0, st, Zf, ldf, nloc_r, nv, G.Px, G.px, G.Py,
-                         G.py, z, ldz);
-  }
-  if (G.px == 0 && G.py == 0 && nloc_r > 0 && nloc_c > 0)   // statistics a(1,1), a(2,1) on the owner of the first column
-    EIGX_HIP_CHECK(hipMemcpyAsync(a, Af, (size_t)(nloc_r >= 2 ? 4 : 2) * 8, hipMemcpyDeviceToDevice, st));
-  EIGX_HIP_CHECK(hipStreamSynchronize(st));
-  return EIGX_OK;
+  return herm_solve_sharded(ctx, n, nvec, a, lda, w, z, ldz, mf, mb, mode);
 }
 
 int herm_solve_host(Context& ctx, int n, int nvec, double* a, int lda, double* w, double* z, int ldz, int mf, int mb,
@@ -1517,25 +1324,16 @@ int herm_solve_host(Context& ctx, int n, int nvec, double* a, int lda, double* w
   const int nr = local_count(n, ctx.grid.Px, ctx.grid.px), nc = local_count(n, ctx.grid.Py, ctx.grid.py);
   if (n <= 0 || !a || !w || lda < nr) return EIGX_ERR_BAD_ARG;
   EIGX_HIP_CHECK(hipSetDevice(ctx.device));
-  const int ldd = nr + 2;
-  const int ncd = nc > 0 ? nc : 1;
-  double* ad = ctx.pool.get_t<double>("hh.a", (size_t)2 * ldd * ncd);
-  double* zd = ctx.pool.get_t<double>("hh.z", (size_t)2 * ldd * ncd);
+  const int ldd = host_ld(nr);
+  double* ad = (double*)host_to_dev(ctx, "hh.a", a, lda, nr, nc, 16);
+  double* zd = (double*)host_to_dev(ctx, "hh.z", nullptr, 0, nr, nc, 16);
   double* wd = ctx.pool.get_t<double>("hh.w", (size_t)n);
-  if (nr > 0 && nc > 0)
-    EIGX_HIP_CHECK(hipMemcpy2D(ad, (size_t)ldd * 16, a, (size_t)lda * 16, (size_t)nr * 16, (size_t)nc, hipMemcpyHostToDevice));
   const int rc = herm_solve_dev(ctx, n, nvec, ad, ldd, wd, zd, ldd, mf, mb, mode);
   EIGX_HIP_CHECK(hipMemcpy(w, wd, (size_t)n * 8, hipMemcpyDeviceToHost));
   if (rc != EIGX_OK) return rc;
-  char md = mode;
-  if (md >= 'a' && md <= 'z') md = (char)(md - 'a' + 'A');
-  int nv = nvec < 0 ? -nvec : nvec;
-  if (nv > n) nv = n;
-  const int nzc = local_count(nv, ctx.grid.Py, ctx.grid.py);
-  if (z && nzc > 0 && nr > 0 && md != 'N')
-    EIGX_HIP_CHECK(hipMemcpy2D(z, (size_t)ldz * 16, zd, (size_t)ldd * 16, (size_t)nr * 16, (size_t)nzc, hipMemcpyDeviceToHost));
-  if (nr > 0 && nc > 0)
-    EIGX_HIP_CHECK(hipMemcpy(a, ad, (size_t)(nr >= 2 ? 4 : 2) * 8, hipMemcpyDeviceToHost));   // statistics only: a is destroyed
+  const SolveRequest rq = normalize_request(n, nvec, mode);
+  if (z && rq.want_vec) dev_to_host(z, ldz, zd, ldd, nr, local_count(rq.nvec, ctx.grid.Py, ctx.grid.py), 16);
+  dev_to_host(a, lda, ad, ldd, nc > 0 ? std::min(nr, 2) : 0, 1, 16);   // statistics only: a is destroyed
   return EIGX_OK;
 }
 

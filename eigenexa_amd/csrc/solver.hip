@@ -7,7 +7,7 @@
 #include "eigx_context.h"
 #include "eigx_comm.h"
 #include "../../include/eigenexa_amd.h"
-#include <chrono>
+#include <algorithm>
 #include <cfloat>
 #include <limits>
 #include <vector>
@@ -24,20 +24,24 @@ void trbak_mg_dev(Context& ctx, int n, int nvec, const double* Aloc, int lda, do
 
 namespace {
 
-// max |a_ij| over the upper triangle and a non-finite flag (eigen_scaling, src/eigen_scaling.F:86-150)
-// A is the local block of a 2-D cyclic distribution: local (i, j) = global (i*Px + px, j*Py + py); ncl local columns
+// max |a_ij| over the upper triangle and a non-finite flag (eigen_scaling, src/eigen_scaling.F:86-150; complex:
+// src/eigen_scaling_h.F, max of |Re|, |Im|).  A is the local block of a 2-D cyclic distribution: local (i, j) = global
+// (i*Px + px, j*Py + py); ncl local columns.  Im of a diagonal entry is never read (the solver ignores it throughout).
+template <bool CPLX>
 __global__ __launch_bounds__(256) void absmax_kernel(const double* __restrict__ A, int lda, int ncl, int Px, int px, int Py,
                                                      int py, double* __restrict__ out /* [gridDim.x][2] */) {
+  constexpr int E = CPLX ? 2 : 1;   // doubles per element
   __shared__ double smax[4], sbad[4];
   double mx = 0.0, bad = 0.0;
   for (int j = blockIdx.x; j < ncl; j += gridDim.x) {
-    const double* col = A + (size_t)j * lda;
+    const double* col = A + (size_t)j * lda * E;
     const int gj = j * Py + py;
     const int iend = gj >= px ? (gj - px) / Px : -1;   // last local row with global row <= gj
     for (int i = threadIdx.x; i <= iend; i += 256) {
-      const double v = fabs(col[i]);
-      if (!(v <= DBL_MAX)) bad = 1.0;
-      else mx = fmax(mx, v);
+      const double re = fabs(col[(size_t)i * E]);
+      const double im = (CPLX && i * Px + px != gj) ? fabs(col[(size_t)i * E + 1]) : 0.0;
+      if (!(re <= DBL_MAX) || !(im <= DBL_MAX)) bad = 1.0;
+      else mx = fmax(mx, fmax(re, im));
     }
   }
   for (int o = 32; o > 0; o >>= 1) { mx = fmax(mx, __shfl_xor(mx, o, 64)); bad = fmax(bad, __shfl_xor(bad, o, 64)); }
@@ -72,22 +76,8 @@ __global__ void absmax_final_kernel(const double* __restrict__ part, int nb, dou
   }
 }
 
-__global__ void scale_vec_kernel(double* __restrict__ w, int n, double s) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < n) w[i] *= s;
-}
-
-__global__ void fill_vec_kernel(double* __restrict__ w, int n, double v) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < n) w[i] = v;
-}
-
 // local index l of process p (of P) -> global index, blocks of nb (nb = 1: cyclic, l*P + p)
 __device__ __forceinline__ int bc_l2g(int l, int nb, int P, int p) { return ((l / nb) * P + p) * nb + l % nb; }
-
-double now_s() {
-  return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count();
-}
 
 // z(:, j) = e_j for the first gridDim.y columns (modes 'S', 'C': eigen_identity, src/eigen_sx.F:214)
 __global__ void identity_kernel(double* __restrict__ z, int ldz, int n, int c0) {
@@ -263,6 +253,65 @@ void cols_to_cyclic_dev(Context& ctx, int n, int nvec, int nb, int zc, int zc0, 
                        nvec, zc, nb, G.py, G.Py, nloc_r, z_user, ldz_user);
 }
 
+__global__ void fill_kernel(double* p, size_t n, double v) {
+  for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) p[i] = v;
+}
+__global__ void fill_vec_kernel(double* __restrict__ w, int n, double v) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) w[i] = v;
+}
+__global__ void scale_vec_kernel(double* __restrict__ w, int n, double s) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) w[i] *= s;
+}
+
+int eigen_scaling(Context& ctx, const double* a, int lda, bool cplx, int n, double* w, double* sigma) {
+  const Grid& G = ctx.grid;
+  hipStream_t st = ctx.stream;
+  const int nbk = 512;
+  double* part = ctx.pool.get_t<double>("sol.absmax", (size_t)2 * nbk + 8);
+  const int clc = local_count(n, G.Py, G.py);
+  hipLaunchKernelGGL(cplx ? absmax_kernel<true> : absmax_kernel<false>, dim3(nbk), dim3(256), 0, st, a, lda, clc, G.Px, G.px,
+                     G.Py, G.py, part);
+  hipLaunchKernelGGL(absmax_final_kernel, dim3(1), dim3(256), 0, st, part, nbk, part + 2 * nbk);
+  if (G.nranks > 1) comm_allreduce_max(ctx, COMM_WORLD, part + 2 * nbk, 2, st);       // src/eigen_scaling.F:118-123
+  double hp[2] = {0.0, 0.0};
+  EIGX_HIP_CHECK(hipMemcpyAsync(hp, part + 2 * nbk, sizeof(hp), hipMemcpyDeviceToHost, st));
+  EIGX_HIP_CHECK(hipStreamSynchronize(st));
+  if (G.nranks > 1 && comm_failed(ctx)) return EIGX_ERR_INTERNAL;
+  const double anrm = hp[0], bad = hp[1];
+  if (bad != 0.0) {  // NaN/Inf in the input (on any rank): w(:) = NaN on every rank (src/eigen_sx.F:151-155, src/eigen_h.F:147-150)
+    hipLaunchKernelGGL(fill_vec_kernel, dim3((n + 255) / 256), dim3(256), 0, st, w, n, std::numeric_limits<double>::quiet_NaN());
+    EIGX_HIP_CHECK(hipStreamSynchronize(st));
+    ctx.errinfo = -1;
+    return EIGX_ERR_NONFINITE;
+  }
+  // eigen_scaling (src/eigen_scaling.F:76-81,:127-147) rescales only when max|a| leaves the safe range,
+  // to RMIN/RMAX ~ 1e-146/1e+146.  This implementation forms reflector quantities that are cubic in the
+  // matrix scale (u^T A u with un-normalised u), so its safe range is narrower and the target is O(1):
+  // outside [1e-90, 1e90] the matrix is scaled by the exact power of two nearest to 1/max|a|.
+  *sigma = 1.0;
+  if (anrm > 0.0 && (anrm < 1e-90 || anrm > 1e90)) {
+    int ex = 0;
+    (void)frexp(anrm, &ex);
+    *sigma = ldexp(1.0, -ex);
+  }
+  return EIGX_OK;
+}
+
+void* host_to_dev(Context& ctx, const char* name, const void* h, int ld, int nr, int nc, int esz) {
+  const int ldd = host_ld(nr);
+  void* d = ctx.pool.get(name, (size_t)esz * ldd * (nc > 0 ? nc : 1));
+  if (h && nr > 0 && nc > 0)
+    EIGX_HIP_CHECK(hipMemcpy2D(d, (size_t)ldd * esz, h, (size_t)ld * esz, (size_t)nr * esz, (size_t)nc, hipMemcpyHostToDevice));
+  return d;
+}
+
+void dev_to_host(void* h, int ld, const void* d, int ldd, int nr, int nc, int esz) {
+  if (nr > 0 && nc > 0)
+    EIGX_HIP_CHECK(hipMemcpy2D(h, (size_t)ld * esz, d, (size_t)ldd * esz, (size_t)nr * esz, (size_t)nc, hipMemcpyDeviceToHost));
+}
+
 namespace {
 
 // nb = block size of the 2-D block-cyclic layout of a and z over the process grid (1 = the cyclic layout of the
@@ -279,11 +328,10 @@ int solve_dev(Context& ctx, int n, int nvec, double* a, int lda, double* w, doub
   if (nb < 1) return EIGX_ERR_BAD_ARG;
   const int nloc_r = numroc(n, nb, G.px, G.Px), nloc_c = numroc(n, nb, G.py, G.Py);
   if (lda < (nloc_r > 1 ? nloc_r : 1) || !a || !w) return EIGX_ERR_BAD_ARG;
-  if (mode >= 'a' && mode <= 'z') mode = (char)(mode - 'a' + 'A');
-  if (nvec == 0) mode = 'N';                      // src/eigen_sx.F:108-110
-  if (nvec < 0) nvec = -nvec;
-  if (nvec > n) nvec = n;
-  const bool want_vec = (mode != 'N');
+  const SolveRequest rq = normalize_request(n, nvec, mode);   // src/eigen_sx.F:108-110
+  mode = rq.mode;
+  nvec = rq.nvec;
+  const bool want_vec = rq.want_vec;
   if (want_vec && (!z || ldz < (nloc_r > 1 ? nloc_r : 1))) return EIGX_ERR_BAD_ARG;
   if (mf <= 0) mf = 128;
   if (mb <= 0) mb = 128;
@@ -336,35 +384,10 @@ int solve_dev(Context& ctx, int n, int nvec, double* a, int lda, double* w, doub
 
   // ---- eigen_scaling ---------------------------------------------------------------------------
   double sigma = 1.0;
-  {
-    const int nbk = 512;
-    double* part = ctx.pool.get_t<double>("sol.absmax", (size_t)2 * nbk + 8);
-    hipLaunchKernelGGL(absmax_kernel, dim3(nbk), dim3(256), 0, st, a, lda, clc, G.Px, G.px, G.Py, G.py, part);
-    hipLaunchKernelGGL(absmax_final_kernel, dim3(1), dim3(256), 0, st, part, nbk, part + 2 * nbk);
-    if (P > 1) comm_allreduce_max(ctx, COMM_WORLD, part + 2 * nbk, 2, st);       // src/eigen_scaling.F:118-123
-    double hp[2] = {0.0, 0.0};
-    EIGX_HIP_CHECK(hipMemcpyAsync(hp, part + 2 * nbk, sizeof(hp), hipMemcpyDeviceToHost, st));
-    EIGX_HIP_CHECK(hipStreamSynchronize(st));
-    const double anrm = hp[0], bad = hp[1];
-    if (bad != 0.0) {  // NaN/Inf in the input: w(:) = NaN and return (src/eigen_sx.F:151-155)
-      hipLaunchKernelGGL(fill_vec_kernel, dim3((n + 255) / 256), dim3(256), 0, st, w, n,
-                         std::numeric_limits<double>::quiet_NaN());
-      EIGX_HIP_CHECK(hipStreamSynchronize(st));
-      ctx.errinfo = -1;
-      return EIGX_ERR_NONFINITE;
-    }
-    // eigen_scaling (src/eigen_scaling.F:76-81,:127-147) rescales only when max|a| leaves the safe range,
-    // to RMIN/RMAX ~ 1e-146/1e+146.  This implementation forms reflector quantities that are cubic in the
-    // matrix scale (u^T A u with un-normalised u), so its safe range is narrower and the target is O(1):
-    // outside [1e-90, 1e90] the matrix is scaled by the exact power of two nearest to 1/max|a|.
-    if (anrm > 0.0 && (anrm < 1e-90 || anrm > 1e90)) {
-      int ex = 0;
-      (void)frexp(anrm, &ex);
-      sigma = ldexp(1.0, -ex);
-    }
-    if (sigma != 1.0)
-      hipLaunchKernelGGL(scale_upper_kernel, dim3(1024), dim3(256), 0, st, a, lda, clc, G.Px, G.px, G.Py, G.py, sigma);
-  }
+  const int rc_sc = eigen_scaling(ctx, a, lda, false, n, w, &sigma);
+  if (rc_sc != EIGX_OK) return rc_sc;
+  if (sigma != 1.0)
+    hipLaunchKernelGGL(scale_upper_kernel, dim3(1024), dim3(256), 0, st, a, lda, clc, G.Px, G.px, G.Py, G.py, sigma);
 
   // ---- forward reduction --------------------------------------------------------------------------
   const int lde = (n + 3) / 4 * 4;  // nme of src/eigen_sx.F:139
@@ -387,9 +410,9 @@ int solve_dev(Context& ctx, int n, int nvec, double* a, int lda, double* w, doub
   // divide and conquer (launch-bound at its low levels) has the compute stream.  The reduction is complete here
   // (the host synchronised the compute stream above).
   const bool runs_dc = !(mode == 'N' || mode == 'S' || mode == 'C');
-  ctx.dc_side_work = nullptr;   // (a solve that failed before its D&C ran may have left one behind)
+  std::function<void()> side_work;
   if (do_bt && nvec > 0 && P == 1) {
-    if (runs_dc) ctx.dc_side_work = [&ctx, n, a, lda, e, lde, mb, band] { trbak_prepare_dev(ctx, n, a, lda, e, lde, mb, band, ctx.bt_stream); };
+    if (runs_dc) side_work = [&ctx, n, a, lda, e, lde, mb, band] { trbak_prepare_dev(ctx, n, a, lda, e, lde, mb, band, ctx.bt_stream); };
     else trbak_prepare_dev(ctx, n, a, lda, e, lde, mb, band, ctx.side_stream);
   }
   // several GPUs: this rank's eigenvector columns [zc0, zc0 + zcnt) (the D&C delivers them, all n rows each)
@@ -399,8 +422,7 @@ int solve_dev(Context& ctx, int n, int nvec, double* a, int lda, double* w, doub
     if (want_vec && zcnt > 0) hipLaunchKernelGGL(identity_kernel, dim3(8, zcnt), dim3(256), 0, st, z, ldz, n, zc0);
     band_bisect_dev(ctx, n, d, e, lde, band, w);
   } else {
-    band_dc_dev(ctx, n, nvec, d, e, lde, band, w, z, ldz);
-    if (ctx.dc_side_work) { std::function<void()> f = std::move(ctx.dc_side_work); ctx.dc_side_work = nullptr; f(); }   // not consumed (cannot happen today)
+    band_dc_dev(ctx, n, nvec, d, e, lde, band, w, z, ldz, side_work);
     if (mode == 'X') band_bisect_dev(ctx, n, d, e, lde, band, w);
   }
   const double t3 = now_s();
@@ -457,28 +479,16 @@ int solve_host(Context& ctx, int n, int nvec, double* a, int lda, double* w, dou
   const int nr = numroc(n, nb, ctx.grid.px, ctx.grid.Px), nc = numroc(n, nb, ctx.grid.py, ctx.grid.Py);
   if (n <= 0 || !a || !w || lda < nr) return EIGX_ERR_BAD_ARG;
   EIGX_HIP_CHECK(hipSetDevice(ctx.device));
-  const int ldd = pad_ld(nr + 2);  // device leading dimension: even (16-byte column loads), odd multiple of 32
-  const int ncd = nc > 0 ? nc : 1;
-  double* ad = ctx.pool.get_t<double>("host.a", (size_t)ldd * ncd);
-  double* zd = ctx.pool.get_t<double>("host.z", (size_t)ldd * ncd);
+  const int ldd = host_ld(nr);
+  double* ad = (double*)host_to_dev(ctx, "host.a", a, lda, nr, nc, 8);
+  double* zd = (double*)host_to_dev(ctx, "host.z", nullptr, 0, nr, nc, 8);
   double* wd = ctx.pool.get_t<double>("host.w", (size_t)n);
-  if (nr > 0 && nc > 0)
-    EIGX_HIP_CHECK(hipMemcpy2D(ad, (size_t)ldd * 8, a, (size_t)lda * 8, (size_t)nr * 8, (size_t)nc,
-                               hipMemcpyHostToDevice));
   const int rc = solve_dev(ctx, n, nvec, ad, ldd, wd, zd, ldd, mf, mb, mode, band, nb);
   EIGX_HIP_CHECK(hipMemcpy(w, wd, (size_t)n * 8, hipMemcpyDeviceToHost));
   if (rc != EIGX_OK) return rc;
-  char md = mode;
-  if (md >= 'a' && md <= 'z') md = (char)(md - 'a' + 'A');
-  int nv = nvec < 0 ? -nvec : nvec;
-  if (nv > n) nv = n;
-  const int nzc = numroc(nv, nb, ctx.grid.py, ctx.grid.Py);
-  if (z && nzc > 0 && nr > 0 && md != 'N')
-    EIGX_HIP_CHECK(hipMemcpy2D(z, (size_t)ldz * 8, zd, (size_t)ldd * 8, (size_t)nr * 8, (size_t)nzc,
-                               hipMemcpyDeviceToHost));
-  // `a` is destroyed by contract; only the statistics come back
-  const int nst = (nc > 0) ? (nr >= 3 ? 3 : nr) : 0;
-  if (nst > 0) EIGX_HIP_CHECK(hipMemcpy(a, ad, (size_t)nst * 8, hipMemcpyDeviceToHost));
+  const SolveRequest rq = normalize_request(n, nvec, mode);
+  if (z && rq.want_vec) dev_to_host(z, ldz, zd, ldd, nr, numroc(rq.nvec, nb, ctx.grid.py, ctx.grid.Py), 8);
+  dev_to_host(a, lda, ad, ldd, nc > 0 ? std::min(nr, 3) : 0, 1, 8);   // `a` is destroyed by contract: only the statistics
   return EIGX_OK;
 }
 
@@ -759,24 +769,17 @@ int gev_host(Context& ctx, int n, double* a, int lda, double* b, int ldb, double
   const int nr = local_count(n, ctx.grid.Px, ctx.grid.px), nc = local_count(n, ctx.grid.Py, ctx.grid.py);
   if (n <= 0 || !a || !b || !w || !z || lda < nr || ldb < nr || ldz < nr) return EIGX_ERR_BAD_ARG;
   EIGX_HIP_CHECK(hipSetDevice(ctx.device));
-  const int ldd = pad_ld(nr + 2);
-  const int ncd = nc > 0 ? nc : 1;
-  double* ad = ctx.pool.get_t<double>("host.a", (size_t)ldd * ncd);
-  double* zd = ctx.pool.get_t<double>("host.z", (size_t)ldd * ncd);
-  double* bd = ctx.pool.get_t<double>("host.b", (size_t)ldd * ncd);
+  const int ldd = host_ld(nr);
+  double* ad = (double*)host_to_dev(ctx, "host.a", a, lda, nr, nc, 8);
+  double* bd = (double*)host_to_dev(ctx, "host.b", b, ldb, nr, nc, 8);
+  double* zd = (double*)host_to_dev(ctx, "host.z", nullptr, 0, nr, nc, 8);
   double* wd = ctx.pool.get_t<double>("host.w", (size_t)n);
-  if (nr > 0 && nc > 0) {
-    EIGX_HIP_CHECK(hipMemcpy2D(ad, (size_t)ldd * 8, a, (size_t)lda * 8, (size_t)nr * 8, (size_t)nc, hipMemcpyHostToDevice));
-    EIGX_HIP_CHECK(hipMemcpy2D(bd, (size_t)ldd * 8, b, (size_t)ldb * 8, (size_t)nr * 8, (size_t)nc, hipMemcpyHostToDevice));
-  }
   const int rc = gev_dev(ctx, n, ad, ldd, bd, ldd, wd, zd, ldd);
   if (rc != EIGX_OK) return rc;
   EIGX_HIP_CHECK(hipMemcpy(w, wd, (size_t)n * 8, hipMemcpyDeviceToHost));
-  if (nr > 0 && nc > 0) {
-    EIGX_HIP_CHECK(hipMemcpy2D(z, (size_t)ldz * 8, zd, (size_t)ldd * 8, (size_t)nr * 8, (size_t)nc, hipMemcpyDeviceToHost));
-    EIGX_HIP_CHECK(hipMemcpy2D(a, (size_t)lda * 8, ad, (size_t)ldd * 8, (size_t)nr * 8, (size_t)nc, hipMemcpyDeviceToHost));
-    EIGX_HIP_CHECK(hipMemcpy2D(b, (size_t)ldb * 8, bd, (size_t)ldd * 8, (size_t)nr * 8, (size_t)nc, hipMemcpyDeviceToHost));
-  }
+  dev_to_host(z, ldz, zd, ldd, nr, nc, 8);
+  dev_to_host(a, lda, ad, ldd, nr, nc, 8);
+  dev_to_host(b, ldb, bd, ldd, nr, nc, 8);
   return EIGX_OK;
 }
 

@@ -188,41 +188,51 @@ if route.startswith("modes-"):
 if route.startswith("edge-"):
     # error behaviour and scaling on the process grid: NaN / Inf anywhere in the upper triangle -> w = NaN on every rank
     # (src/eigen_sx.F:151-155, the flag travels through the MAX allreduce of eigen_scaling); matrices scaled by 1e+-200
-    # are solved as accurately as the unscaled one (src/eigen_scaling.F:127-147)
+    # are solved as accurately as the unscaled one (src/eigen_scaling.F:127-147); eigen_h: the same on a complex Hermitian
+    # matrix (src/eigen_scaling_h.F), where Im of a diagonal entry is never read either
     rt = route.split("-")[1]
-    fn = ee.eigen_sx if rt == "sx" else ee.eigen_s
-    A = layout.random_symmetric(n, seed=5)
+    fn = {"sx": ee.eigen_sx, "s": ee.eigen_s, "h": ee.eigen_h}[rt]
+    if rt == "h":
+        rng = np.random.default_rng(5)
+        B = rng.standard_normal((n, n)) + 1j * rng.standard_normal((n, n))
+        A = (B + B.conj().T) / 2
+    else:
+        A = layout.random_symmetric(n, seed=5)
     wr = np.linalg.eigvalsh(A)
     rows = np.arange(px, n, xp)
     cols = np.arange(py, n, yp)
     nx, ny = ee.eigen_get_matdims(n)
-    for scale in (1e200, 1e-200, 1.0):
-        a = np.zeros((nx, ny), order="F")
-        a[: len(rows), : len(cols)] = A[np.ix_(rows, cols)] * scale
-        z = np.zeros((nx, ny), order="F")
+
+    def solve(blk):
+        a = np.zeros((nx, ny), dtype=A.dtype, order="F")
+        a[: len(rows), : len(cols)] = blk
+        z = np.zeros((nx, ny), dtype=A.dtype, order="F")
         w = np.zeros(n)
         fn(n, n, a, nx, w, z, nx, m_forward=32, mode="A")
+        return w
+
+    for scale in (1e200, 1e-200, 1.0):
+        w = solve(A[np.ix_(rows, cols)] * scale)
         assert api.last_status() == 0
         assert np.abs(w / scale - wr).max() < 1e-12 * np.abs(wr).max(), scale
     for bad in (np.nan, np.inf):
-        a = np.zeros((nx, ny), order="F")
-        a[: len(rows), : len(cols)] = A[np.ix_(rows, cols)]
+        blk = A[np.ix_(rows, cols)].copy()
         gi, gj = n // 3, n // 2          # one entry of the upper triangle, on whichever rank owns it
         if gi % xp == px and gj % yp == py:
-            a[gi // xp, gj // yp] = bad
-        z = np.zeros((nx, ny), order="F")
-        w = np.zeros(n)
-        fn(n, n, a, nx, w, z, nx, m_forward=32, mode="A")
+            blk[gi // xp, gj // yp] = complex(1.0, bad) if rt == "h" else bad   # eigen_h: in the imaginary part
+        w = solve(blk)
         assert api.last_status() == -5 and np.isnan(w).all(), (api.last_status(), w[:3])
     # the strict lower triangle is never read: poison it on every rank
-    a = np.zeros((nx, ny), order="F")
     blk = A[np.ix_(rows, cols)].copy()
     blk[rows[:, None] > cols[None, :]] = np.nan
-    a[: len(rows), : len(cols)] = blk
-    z = np.zeros((nx, ny), order="F")
-    w = np.zeros(n)
-    fn(n, n, a, nx, w, z, nx, m_forward=32, mode="A")
+    w = solve(blk)
     assert api.last_status() == 0 and np.abs(w - wr).max() < 1e-12 * np.abs(wr).max()
+    if rt == "h":
+        # nor is Im(a_jj): NaN there on every rank's diagonal entries solves normally, as on one GPU
+        blk = A[np.ix_(rows, cols)].copy()
+        blk.imag[rows[:, None] == cols[None, :]] = np.nan
+        w = solve(blk)
+        assert api.last_status() == 0 and np.abs(w - wr).max() < 1e-12 * np.abs(wr).max(), api.last_status()
     ee.eigen_free()
     dist.barrier()
     dist.destroy_process_group()

@@ -376,12 +376,24 @@ def test_scaling_extremes(gpu_lib):
     n = 120
     A0 = layout.random_symmetric(n, seed=4)
     wr = np.linalg.eigvalsh(A0)
+    H0 = _herm_random(n, seed=4)
+    whr = np.linalg.eigvalsh(H0)
     for f in (1e-200, 1e200, 1e80, 1e-120):
         a = np.asfortranarray(A0 * f)
         z = np.zeros((n, n), order="F")
         w = np.zeros(n)
         ee.eigen_sx(n, n, a, n, w, z, n)
         assert np.abs(w / f - wr).max() < 1e-12 * np.abs(wr).max()
+        # eigen_h (src/eigen_scaling_h.F): the same rule on a complex Hermitian matrix, at the factors the rule rescales
+        # (unscaled, eigen_h's reduction squares |beta| ~ f^2 and overflows above f ~ 1e77: 1e80 is not solved today)
+        if f == 1e80:
+            continue
+        a = np.asfortranarray(H0 * f)
+        z = np.zeros((n, n), dtype=np.complex128, order="F")
+        w = np.zeros(n)
+        ee.eigen_h(n, n, a, n, w, z, n)
+        assert ee.api.last_status() == 0
+        assert np.abs(w / f - whr).max() < 1e-12 * np.abs(whr).max(), f
 
 
 @pytest.mark.parametrize("route", ["sx", "s"])
@@ -641,9 +653,10 @@ def test_ka_load_batch_sizes_do_not_change_the_result(gpu_lib, band, n, m):
     assert np.abs(np.linalg.eigvalsh(_band_matrix(out[0][0], eg[:band], band)) - wr).max() < 1e-13 * n * np.abs(wr).max()
 
 
-@pytest.mark.parametrize("world,n,route,dims", [(4, 210, "edge-sx", ""), (2, 170, "edge-s", "2x1")])
+@pytest.mark.parametrize("world,n,route,dims", [(4, 210, "edge-sx", ""), (2, 170, "edge-s", "2x1"), (3, 190, "edge-h", "")])
 def test_multi_rank_error_behaviour_and_scaling(world, n, route, dims):
-    """NaN / Inf input, matrices scaled by 1e+-200 and a NaN-poisoned strict lower triangle on the process grid"""
+    """NaN / Inf input, matrices scaled by 1e+-200 and a NaN-poisoned strict lower triangle on the process grid
+    (eigen_h: also NaN in Im(a_jj), which is not read)"""
     _run_multi_rank(world, n, route, 0, dims)
 
 
@@ -1392,6 +1405,12 @@ def test_eigen_h_known_spectrum_and_modes(gpu_lib, orc):
     z = np.zeros((20, 20), dtype=np.complex128, order="F")
     ee.eigen_h(20, 20, a, 20, w, z, 20)
     assert np.isnan(w).all()
+    # Im(a_jj) is never read: NaN there solves normally
+    Hn = _herm_random(20)
+    a = np.asfortranarray(np.triu(Hn))
+    a.imag[5, 5] = np.nan
+    ee.eigen_h(20, 20, a, 20, w, z, 20)
+    assert ee.api.last_status() == 0 and np.abs(w - np.linalg.eigvalsh(Hn)).max() < 1e-12 * np.abs(Hn).sum(axis=1).max()
 
 
 def test_fortran_caller_over_iso_c_binding(gpu_lib):

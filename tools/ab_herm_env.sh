@@ -1,6 +1,6 @@
 #!/bin/bash
 # Lab script: eigen_h at N=8192 under different environment settings, alternating processes, three rounds.
-#   gpurun -- tools/ab_herm_env.sh "EIGX_H_HEMV8_NT=0" "EIGX_H_HEMV8_NT=22" ...
+#   tools/ab_herm_env.sh "EIGX_LD_EXTRA=0" "EIGX_LD_EXTRA=64" ...
 cd "$(dirname "$0")/.."
 for i in 1 2 3; do
   for e in "$@"; do

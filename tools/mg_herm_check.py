@@ -1,5 +1,5 @@
-"""Lab tool: eigen_h on `world` processes sharing GPU 0 at a size the unit tests do not reach (sharded reduction by default,
-EIGX_H_GATHER=1: the first, gathering version), timed per stage, checked on rank 0 through GPU matmuls of the GATHERED
+"""Lab tool: eigen_h on `world` processes sharing GPU 0 at a size the unit tests do not reach (sharded
+reduction), timed per stage, checked on rank 0 through GPU matmuls of the GATHERED
 eigenvectors: residual ||A Z - Z W||_F / (N eps ||A||_F) < 768, ||Z^H Z - I||_F / (N eps) < 8; w identical on every rank;
 bytes the library holds.   argv: rank world port n [PxxPy]      launcher: tools/mg_herm_check.sh WORLD N [PxxPy]"""
 import os
@@ -44,7 +44,7 @@ for rep in range(2):
     assert rc == 0, f"rank {rank}: status {rc}"
     tm = np.zeros(16)
     lib.eigx_get_timers(tm.ctypes.data_as(C.POINTER(C.c_double)))
-    print(f"[rank {rank}] rep {rep} grid {Px}x{Py} n={n} eigen_h ({'gathered' if os.environ.get('EIGX_H_GATHER') == '1' else 'sharded'}): "
+    print(f"[rank {rank}] rep {rep} grid {Px}x{Py} n={n} eigen_h (sharded): "
           f"{dt:.2f} s (reduction {tm[1]:.2f}, D&C {tm[2]:.2f}, back-transform {tm[3]:.2f}); held {lib.eigx_held_bytes() / 2**20:.0f} MiB "
           f"(hs. {lib.eigx_held_bytes_named(b'hs.') / 2**20:.0f}, hm. {lib.eigx_held_bytes_named(b'hm.') / 2**20:.0f})", flush=True)
 wl = [torch.zeros(n, dtype=torch.float64) for _ in range(world)]
