@@ -331,3 +331,45 @@ def KMATH_EIGEN_GEV(n, a, lda, b, ldb, w, z, ldz):
     _state["last_status"] = rc
     if rc not in (0, -7):
         print(f"Warning: KMATH_EIGEN_GEV returned without computing (status {rc})", file=sys.stderr)
+
+
+def KMATH_EIGEN_HGEV(n, a, lda, b, ldb, w, z, ldz):
+    """EXTENSION, not in the reference (it has no complex generalised solver): the complex Hermitian-definite problem
+    A x = lambda B x by the method of KMATH_EIGEN_GEV over complex numbers (two eigen_h solves, three complex products).
+    ``a``, ``b``, ``z``: complex128, column-major (numpy, Fortran order) or GPU tensors holding the column-major image
+    (``a[j, i] = A(i, j)``), leading dimensions in complex elements; ``w`` float64.  Upper triangles of ``a``, ``b``
+    significant; ``w`` ascending, ``z^H B z = I``; on exit ``a`` holds Y and ``b`` holds F = U mu^-1/2, as in
+    KMATH_EIGEN_GEV.  If B is not positive definite a message is printed and the call returns (status -7)."""
+    lib = _lib.load()
+    if not _state["initialized"]:
+        _state["last_status"] = -1
+        return
+    dev = _is_torch(a)
+
+    def cptr(x, name, real=False):
+        if dev:
+            import torch
+
+            if not (_is_torch(x) and x.is_cuda):
+                raise ValueError("a, b, w, z must all be host arrays or all be device tensors")
+            if x.dtype != (torch.float64 if real else torch.complex128):
+                raise ValueError(f"{name}: {'float64' if real else 'complex128'} required")
+            return x.data_ptr()
+        if _is_torch(x):
+            raise ValueError("a, b, w, z must all be host arrays or all be device tensors")
+        if x.dtype != (np.float64 if real else np.complex128):
+            raise ValueError(f"{name}: {'float64' if real else 'complex128'} required")
+        if x.ndim == 2 and not x.flags.f_contiguous:
+            raise ValueError(f"{name}: Fortran (column-major) order required, as in the reference")
+        return x.ctypes.data
+
+    if dev:
+        import torch
+
+        torch.cuda.current_stream().synchronize()
+    pa, pb, pw, pz = cptr(a, "a"), cptr(b, "b"), cptr(w, "w", real=True), cptr(z, "z")
+    fn = lib.eigx_hgev_dev if dev else lib.eigx_hgev
+    rc = fn(int(n), pa, int(lda), pb, int(ldb), pw, pz, int(ldz))
+    _state["last_status"] = rc
+    if rc not in (0, -5, -7):
+        print(f"Warning: KMATH_EIGEN_HGEV returned without computing (status {rc})", file=sys.stderr)

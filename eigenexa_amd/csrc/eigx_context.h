@@ -163,5 +163,16 @@ int eigen_scaling(Context& ctx, const double* a, int lda, bool cplx, int n, doub
 inline int host_ld(int nr) { return pad_ld(nr + 2); }
 void* host_to_dev(Context& ctx, const char* name, const void* h, int ld, int nr, int nc, int esz);
 void dev_to_host(void* h, int ld, const void* d, int ldd, int nr, int nc, int esz);
+// Building blocks of the multi-rank KMATH_EIGEN_GEV, shared with the complex generalised solver (hgev.hip):
+// z = a^T on the 2-D cyclic blocks of n x n matrices (exchange buffers in the pool as `tag`.tsend / `tag`.trecv), and the
+// SUMMA panel packing of a's columns lc0 .. lc0 + kbl - 1 (out[c * nrp + r]) and of b's rows lr0 .. lr0 + kbl - 1
+// (out[j * kbl + rr])
+void dist_transpose(Context& ctx, int n, const double* a, int lda, double* z, int ldz, hipStream_t st, const char* tag = "gev");
+__global__ void mm_pack_a_kernel(const double* __restrict__ a, int lda, int nr, int nc, int lc0, int nrp, double* __restrict__ out);
+__global__ void mm_pack_b_kernel(const double* __restrict__ b, int ldb, int nr, int nc, int lr0, int kbl, double* __restrict__ out);
+
+// herm.hip: eigen_h on device arrays (interleaved complex; one GPU, or this rank's 2-D cyclic blocks)
+int herm_solve_dev(Context& ctx, int n, int nvec, double* a, int lda, double* w, double* z, int ldz, int mf, int mb,
+                   char mode);
 
 }  // namespace eigx

@@ -1,0 +1,350 @@
+// hgev.hip -- KMATH_EIGEN_HGEV: the complex Hermitian-definite generalised problem A x = lambda B x.
+//
+// EXTENSION: the reference has no complex generalised solver.  This one follows the reference's method for the real case
+// (KMATH_EIGEN_GEV_1, src/KMATH_EIGEN_GEV_1.F:57-139: two eigensolves and three products) over complex numbers, with the
+// same argument list and on-exit contract as KMATH_EIGEN_GEV (solver.hip gev_dev / gev_dev_mg):
+//   eigen_h(B, 'X'):  B = U diag(mu) U^H          (mu_min <= 0: "Matrix B is not positive definite!", EIGX_ERR_NOT_SPD)
+//   F = U diag(mu)^-1/2 ;  C = F^H (A F) ;  eigen_h(C, 'X'):  C = Y diag(w) Y^H ;  Z = F Y       (Z^H B Z = I)
+// On exit a holds Y, b holds F, w is ascending, z = F Y; timers [0..4] = total, eigen_h(B), forming C, eigen_h(C), Z = F Y.
+// Inputs as for eigen_h: interleaved complex(8), leading dimensions in complex elements, only the upper triangles of a and
+// b are read, Im of their diagonals is ignored; a non-finite significant entry of a or b returns EIGX_ERR_NONFINITE with
+// w = NaN (a is scanned before B's solve).  A is never scaled here, so eigen_h's overflow above a matrix scale of about
+// 1e77 is inherited.
+//
+// The three complex products are real fp64 MFMA GEMMs (dgemm_dev) on split planes, as in herm.hip:
+//   one GPU: four real products per complex product with beta accumulation (Tr = Ar Fr - Ai Fi, Ti = Ar Fi + Ai Fr).
+//            Stacking K to 2n instead would need two more n^2 planes for the same flops; the extra pass over C that
+//            the four-product form costs is ~1 ms at N = 8192 against ~45 ms of MFMA work per complex product.
+//            C = F^H T computes only the tiles that meet the upper triangle (tri_mode 1): eigen_h reads nothing else.
+//   several ranks: the 2-D cyclic blocks, nothing gathered.  A's lower triangle and F^H come from dist_transpose of each
+//            plane; a complex SUMMA gathers both planes of a panel in one message and runs two products with K = 2 kb
+//            ([Xr | Xi] times stacked panels of B; the conjugation of F^H is folded into the stacked panels' signs);
+//            C's product runs tri_mode 2.  Workspace: 8 planes of n^2/P (A, the transposes / C, F, T), the transposes'
+//            exchange buffers (~2 n^2/P) and the panels: within 12 n^2/P doubles + 1 MiB.
+#include "eigx_context.h"
+#include "eigx_comm.h"
+#include "../../include/eigenexa_amd.h"
+#include <string>
+
+namespace eigx {
+
+namespace {
+
+// one GPU: interleaved upper triangle of a -> planes of the full Hermitian matrix (lower = conj(upper), Im of the diagonal
+// := 0).  One 32 x 32 tile of the upper block triangle per workgroup; the mirrored tile goes through LDS, so both writes
+// are coalesced.
+__global__ __launch_bounds__(256) void hg_expand_kernel(const double* __restrict__ a, int lda, int n, double* __restrict__ Ar,
+                                                        double* __restrict__ Ai, int ld) {
+  __shared__ double sr[32][33], si[32][33];
+  const int ti = blockIdx.x, tj = blockIdx.y;   // tile row, tile column
+  if (ti > tj) return;
+  const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
+  const int i = ti * 32 + tx;
+  for (int c = ty; c < 32; c += 8) {
+    const int j = tj * 32 + c;
+    double re = 0.0, im = 0.0;
+    if (i <= j && j < n) {
+      const size_t o = (size_t)i + (size_t)j * lda;
+      re = a[2 * o];
+      im = (i == j) ? 0.0 : a[2 * o + 1];
+      Ar[(size_t)i + (size_t)j * ld] = re;
+      Ai[(size_t)i + (size_t)j * ld] = im;
+    }
+    sr[c][tx] = re; si[c][tx] = im;   // element (ti*32 + tx, tj*32 + c)
+  }
+  __syncthreads();
+  for (int c = ty; c < 32; c += 8) {
+    const int r = tj * 32 + tx, col = ti * 32 + c;   // (r, col) = conj of (col, r) = sr[tx][c]
+    if (r < n && col < r) {
+      Ar[(size_t)r + (size_t)col * ld] = sr[tx][c];
+      Ai[(size_t)r + (size_t)col * ld] = -si[tx][c];
+    }
+  }
+}
+
+// interleaved local block x (nr x nc) -> planes, column lc scaled by w[global column]^(-1/2) when w is given (F from U in
+// one pass).  herm: x holds the upper triangle of a Hermitian matrix on the 2-D cyclic blocks -- entries below the global
+// diagonal are not read (the planes keep what they hold there), Im of the diagonal := 0.
+__global__ void hg_split_kernel(const double* __restrict__ x, int ldx, const double* __restrict__ w, int nr, int nc, int Px,
+                                int px, int Py, int py, int herm, double* __restrict__ Pr, double* __restrict__ Pi, int ld) {
+  for (int lc = blockIdx.y; lc < nc; lc += gridDim.y) {
+    const int gc = lc * Py + py;
+    const double s = w ? 1.0 / sqrt(w[gc]) : 1.0;
+    for (int lr = blockIdx.x * blockDim.x + threadIdx.x; lr < nr; lr += gridDim.x * blockDim.x) {
+      const int gr = lr * Px + px;
+      if (herm && gr > gc) continue;
+      const size_t o = (size_t)lr + (size_t)lc * ldx;
+      const double re = x[2 * o];
+      const double im = (herm && gr == gc) ? 0.0 : x[2 * o + 1];
+      Pr[(size_t)lr + (size_t)lc * ld] = re * s;
+      Pi[(size_t)lr + (size_t)lc * ld] = im * s;
+    }
+  }
+}
+
+// several ranks: below the global diagonal A := conj(A^T), from the transposed planes (Xr, Xi) = (Ar^T, Ai^T)
+__global__ void hg_merge_kernel(double* __restrict__ Ar, double* __restrict__ Ai, const double* __restrict__ Xr,
+                                const double* __restrict__ Xi, int ld, int nr, int nc, int Px, int px, int Py, int py) {
+  for (int lc = blockIdx.y; lc < nc; lc += gridDim.y) {
+    const int gc = lc * Py + py;
+    for (int lr = blockIdx.x * blockDim.x + threadIdx.x; lr < nr; lr += gridDim.x * blockDim.x) {
+      if (lr * Px + px <= gc) continue;
+      const size_t o = (size_t)lr + (size_t)lc * ld;
+      Ar[o] = Xr[o];
+      Ai[o] = -Xi[o];
+    }
+  }
+}
+
+// planes -> interleaved local block x (nr x nc); upper: only the entries on or above the global diagonal
+__global__ void hg_join_kernel(const double* __restrict__ Pr, const double* __restrict__ Pi, int ld, int nr, int nc, int Px,
+                               int px, int Py, int py, int upper, double* __restrict__ x, int ldx) {
+  for (int lc = blockIdx.y; lc < nc; lc += gridDim.y) {
+    const int gc = lc * Py + py;
+    for (int lr = blockIdx.x * blockDim.x + threadIdx.x; lr < nr; lr += gridDim.x * blockDim.x) {
+      if (upper && lr * Px + px > gc) continue;
+      const size_t o = (size_t)lr + (size_t)lc * ldx;
+      x[2 * o] = Pr[(size_t)lr + (size_t)lc * ld];
+      x[2 * o + 1] = Pi[(size_t)lr + (size_t)lc * ld];
+    }
+  }
+}
+
+// complex SUMMA, B side: gathered rows of both planes recv[q'][pl][j][rr] (global k = k0 + rr Px + q') -> the two stacked
+// panels, rows in the order of the gathered A columns (pos = q 2 kbl_y + pl kbl_y + c for k - k0 = c Py + q, plane pl).
+// With X = Xr + i sa Xi on the A side:  Re(X B) = [Xr | Xi] B1,  B1 = [Br; -sa Bi];  Im(X B) = [Xr | Xi] B2,  B2 = [Bi; sa Br]
+__global__ void hg_unpack_b_kernel(const double* __restrict__ recv, int Px, int Py, int kbl_x, int kbl_y, int ncp, int kb,
+                                   double sa, double* __restrict__ B1, double* __restrict__ B2) {
+  const int j = blockIdx.y, q = blockIdx.z;
+  for (int rr = blockIdx.x * blockDim.x + threadIdx.x; rr < kbl_x; rr += gridDim.x * blockDim.x) {
+    const int dk = rr * Px + q;
+    const size_t pos = (size_t)j * 2 * kb + (size_t)(dk % Py) * 2 * kbl_y + dk / Py;
+    const double br = recv[(((size_t)q * 2) * ncp + j) * kbl_x + rr];
+    const double bi = recv[(((size_t)q * 2 + 1) * ncp + j) * kbl_x + rr];
+    B1[pos] = br; B1[pos + kbl_y] = -sa * bi;
+    B2[pos] = bi; B2[pos + kbl_y] = sa * br;
+  }
+}
+
+inline dim3 col_grid(int nr, int nc) { return dim3(ceil_div(nr, 256) < 8 ? ceil_div(nr, 256) : 8, nc < 65535 ? nc : 65535); }
+
+// C = X B on the 2-D cyclic blocks (all n x n, complete matrices), complex on split planes, X = Xr + i sa Xi (sa = -1:
+// the conjugate of the stored planes).  tri: only the tiles of C that meet the upper triangle (tri_mode 2).  Synchronous.
+int zsumma(Context& ctx, int n, const double* Xr, const double* Xi, int ldx, double sa, const double* Br, const double* Bi,
+           int ldb, double* Cr, double* Ci, int ldc, bool tri) {
+  const Grid& G = ctx.grid;
+  hipStream_t st = ctx.stream;
+  const int nr = local_count(n, G.Px, G.px), nc = local_count(n, G.Py, G.py);
+  int g = G.Px, h = G.Py;
+  while (h) { const int t = g % h; g = h; h = t; }
+  const int L = G.Px / g * G.Py;
+  const int unit = 2 * L;                        // panels start at multiples of Px and Py; even widths
+  // panel width about n / 16 between 64 and 512: both planes travel, and the panels stay within ~2 n^2/P + 1 MiB
+  const int kb_want = (n < 64) ? n : (n / 16 < 64 ? 64 : (n / 16 > 512 ? 512 : n / 16));
+  const int kb = unit * ceil_div(kb_want, unit);
+  const int kbl_x = kb / G.Px, kbl_y = kb / G.Py;
+  const int nrp = ((nr > 2 ? nr : 2) + 1) & ~1, ncp = nc > 1 ? nc : 1;
+  double* sendA = ctx.pool.get_t<double>("hgev.sa", (size_t)2 * nrp * kbl_y);
+  double* Ap = ctx.pool.get_t<double>("hgev.pa", (size_t)2 * nrp * kb);
+  double* sendB = ctx.pool.get_t<double>("hgev.sb", (size_t)2 * kbl_x * ncp);
+  double* recvB = ctx.pool.get_t<double>("hgev.rb", (size_t)2 * kb * ncp);
+  double* B1 = ctx.pool.get_t<double>("hgev.pb", (size_t)4 * kb * ncp);
+  double* B2 = B1 + (size_t)2 * kb * ncp;
+  for (int k0 = 0; k0 < n; k0 += kb) {
+    hipLaunchKernelGGL(mm_pack_a_kernel, dim3(ceil_div(nrp, 256), kbl_y), dim3(256), 0, st, Xr, ldx, nr, nc, k0 / G.Py, nrp, sendA);
+    hipLaunchKernelGGL(mm_pack_a_kernel, dim3(ceil_div(nrp, 256), kbl_y), dim3(256), 0, st, Xi, ldx, nr, nc, k0 / G.Py, nrp,
+                       sendA + (size_t)nrp * kbl_y);
+    comm_allgather(ctx, COMM_Y, sendA, Ap, (size_t)2 * nrp * kbl_y, st);     // Ap(:, q 2kbl_y + pl kbl_y + c)
+    hipLaunchKernelGGL(mm_pack_b_kernel, dim3(ceil_div(kbl_x, 256), ncp), dim3(256), 0, st, Br, ldb, nr, nc, k0 / G.Px, kbl_x, sendB);
+    hipLaunchKernelGGL(mm_pack_b_kernel, dim3(ceil_div(kbl_x, 256), ncp), dim3(256), 0, st, Bi, ldb, nr, nc, k0 / G.Px, kbl_x,
+                       sendB + (size_t)kbl_x * ncp);
+    comm_allgather(ctx, COMM_X, sendB, recvB, (size_t)2 * kbl_x * ncp, st);
+    hipLaunchKernelGGL(hg_unpack_b_kernel, dim3(ceil_div(kbl_x, 256), ncp, G.Px), dim3(256), 0, st, (const double*)recvB, G.Px,
+                       G.Py, kbl_x, kbl_y, ncp, kb, sa, B1, B2);
+    const double beta = k0 == 0 ? 0.0 : 1.0;
+    if (nr > 0 && nc > 0) {
+      dgemm_dev(st, 'N', 'N', nr, nc, 2 * kb, 1.0, Ap, nrp, B1, 2 * kb, beta, Cr, ldc, tri ? 2 : 0, tri ? &G : nullptr);
+      dgemm_dev(st, 'N', 'N', nr, nc, 2 * kb, 1.0, Ap, nrp, B2, 2 * kb, beta, Ci, ldc, tri ? 2 : 0, tri ? &G : nullptr);
+    }
+  }
+  EIGX_HIP_CHECK(hipStreamSynchronize(st));
+  return comm_failed(ctx) ? EIGX_ERR_INTERNAL : EIGX_OK;
+}
+
+bool b_is_positive_definite(const Context& ctx, const double* w) {
+  double wmin = 0.0;
+  EIGX_HIP_CHECK(hipMemcpy(&wmin, w, 8, hipMemcpyDeviceToHost));
+  if (wmin > 0.0) return true;
+  // w is replicated bit for bit on several ranks: every rank takes the same way out
+  if (ctx.grid.rank == 0) fprintf(stderr, "[eigx] Matrix B is not positive definite!\n");   // src/KMATH_EIGEN_GEV_1.F:75-80
+  return false;
+}
+
+// eigen_h's default panel widths (eigen_NB_f, eigen_NB_b)
+constexpr int HG_MF = 48, HG_MB = 128;
+
+// Several ranks: the 2-D cyclic blocks, nothing gathered
+int hgev_dev_mg(Context& ctx, int n, double* a, int lda, double* b, int ldb, double* w, double* z, int ldz) {
+  const Grid G = ctx.grid;
+  const int nr = local_count(n, G.Px, G.px), nc = local_count(n, G.Py, G.py);
+  const int lmin = nr > 1 ? nr : 1;
+  if (n <= 0 || !a || !b || !w || !z || lda < lmin || ldb < lmin || ldz < lmin) return EIGX_ERR_BAD_ARG;
+  EIGX_HIP_CHECK(hipSetDevice(ctx.device));
+  EIGX_HIP_CHECK(hipStreamSynchronize(nullptr));   // the caller's default-stream work on the arguments (see solve_dev)
+  hipStream_t st = ctx.stream;
+  const double t0 = now_s();
+  double sigma = 1.0;
+  int rc = eigen_scaling(ctx, a, lda, true, n, w, &sigma);   // NaN / Inf in A: eigen_h's status, before B's solve
+  if (rc != EIGX_OK) return rc;
+  const int ldt = ((nr > 2 ? nr : 2) + 1) & ~1;
+  const size_t pl = (size_t)ldt * (nc > 0 ? nc : 1);
+  double* Ar = ctx.pool.get_t<double>("hgev.planes", 8 * pl);
+  double* Ai = Ar + pl;
+  double* Xr = Ai + pl;   // A^T, later C
+  double* Xi = Xr + pl;
+  double* Fr = Xi + pl;
+  double* Fi = Fr + pl;
+  double* Tr = Fi + pl;   // A F, later Z
+  double* Ti = Tr + pl;
+  const bool mine = nr > 0 && nc > 0;
+  const dim3 cg = col_grid(nr, nc);
+  if (mine)
+    hipLaunchKernelGGL(hg_split_kernel, cg, dim3(256), 0, st, (const double*)a, lda, (const double*)nullptr, nr, nc, G.Px, G.px,
+                       G.Py, G.py, 1, Ar, Ai, ldt);
+  dist_transpose(ctx, n, Ar, ldt, Xr, ldt, st, "hgev");
+  dist_transpose(ctx, n, Ai, ldt, Xi, ldt, st, "hgev");
+  if (mine)
+    hipLaunchKernelGGL(hg_merge_kernel, cg, dim3(256), 0, st, Ar, Ai, (const double*)Xr, (const double*)Xi, ldt, nr, nc, G.Px,
+                       G.px, G.Py, G.py);
+  EIGX_HIP_CHECK(hipStreamSynchronize(st));
+  if (comm_failed(ctx)) return EIGX_ERR_INTERNAL;
+  rc = herm_solve_dev(ctx, n, n, b, ldb, w, z, ldz, HG_MF, HG_MB, 'X');                   // B = U diag(mu) U^H
+  if (rc != EIGX_OK) return rc;
+  const double t1 = now_s();
+  if (!b_is_positive_definite(ctx, w)) return EIGX_ERR_NOT_SPD;
+  if (mine) {
+    hipLaunchKernelGGL(hg_split_kernel, cg, dim3(256), 0, st, (const double*)z, ldz, (const double*)w, nr, nc, G.Px, G.px, G.Py,
+                       G.py, 0, Fr, Fi, ldt);                                                // F = U diag(mu)^-1/2
+    hipLaunchKernelGGL(hg_join_kernel, cg, dim3(256), 0, st, (const double*)Fr, (const double*)Fi, ldt, nr, nc, G.Px, G.px, G.Py,
+                       G.py, 0, b, ldb);
+  }
+  rc = zsumma(ctx, n, Ar, Ai, ldt, 1.0, Fr, Fi, ldt, Tr, Ti, ldt, false);                  // T = A F
+  if (rc != EIGX_OK) return rc;
+  dist_transpose(ctx, n, Fr, ldt, Ar, ldt, st, "hgev");                                     // F^T planes (A is done)
+  dist_transpose(ctx, n, Fi, ldt, Ai, ldt, st, "hgev");
+  rc = zsumma(ctx, n, Ar, Ai, ldt, -1.0, Tr, Ti, ldt, Xr, Xi, ldt, true);                  // C = F^H T, upper tiles
+  if (rc != EIGX_OK) return rc;
+  if (mine)
+    hipLaunchKernelGGL(hg_join_kernel, cg, dim3(256), 0, st, (const double*)Xr, (const double*)Xi, ldt, nr, nc, G.Px, G.px, G.Py,
+                       G.py, 1, z, ldz);
+  EIGX_HIP_CHECK(hipStreamSynchronize(st));
+  const double t2 = now_s();
+  rc = herm_solve_dev(ctx, n, n, z, ldz, w, a, lda, HG_MF, HG_MB, 'X');                   // C = Y diag(w) Y^H, Y in a
+  if (rc != EIGX_OK) return rc;
+  const double t3 = now_s();
+  if (mine)
+    hipLaunchKernelGGL(hg_split_kernel, cg, dim3(256), 0, st, (const double*)a, lda, (const double*)nullptr, nr, nc, G.Px, G.px,
+                       G.Py, G.py, 0, Ar, Ai, ldt);
+  rc = zsumma(ctx, n, Fr, Fi, ldt, 1.0, Ar, Ai, ldt, Tr, Ti, ldt, false);                  // Z = F Y
+  if (rc != EIGX_OK) return rc;
+  if (mine)
+    hipLaunchKernelGGL(hg_join_kernel, cg, dim3(256), 0, st, (const double*)Tr, (const double*)Ti, ldt, nr, nc, G.Px, G.px, G.Py,
+                       G.py, 0, z, ldz);
+  EIGX_HIP_CHECK(hipStreamSynchronize(st));
+  const double t4 = now_s();
+  ctx.timers[0] = t4 - t0; ctx.timers[1] = t1 - t0; ctx.timers[2] = t2 - t1; ctx.timers[3] = t3 - t2; ctx.timers[4] = t4 - t3;
+  return EIGX_OK;
+}
+
+}  // namespace
+
+int hgev_dev(Context& ctx, int n, double* a, int lda, double* b, int ldb, double* w, double* z, int ldz) {
+  if (!ctx.initialized) return EIGX_ERR_NOT_INITIALIZED;
+  if (ctx.grid.nranks != 1) return hgev_dev_mg(ctx, n, a, lda, b, ldb, w, z, ldz);
+  if (n <= 0 || !a || !b || !w || !z || lda < n || ldb < n || ldz < n) return EIGX_ERR_BAD_ARG;
+  EIGX_HIP_CHECK(hipSetDevice(ctx.device));
+  EIGX_HIP_CHECK(hipStreamSynchronize(nullptr));   // the caller's default-stream work on the arguments (see solve_dev)
+  hipStream_t st = ctx.stream;
+  const double t0 = now_s();
+  double sigma = 1.0;
+  int rc = eigen_scaling(ctx, a, lda, true, n, w, &sigma);   // NaN / Inf in A: eigen_h's status, before B's solve
+  if (rc != EIGX_OK) return rc;
+  const int ld = pad_ld(n);
+  const size_t pl = (size_t)ld * n;
+  double* Ar = ctx.pool.get_t<double>("hgev.ar", pl);   // A, later C, later Z
+  double* Ai = ctx.pool.get_t<double>("hgev.ai", pl);
+  double* Fr = ctx.pool.get_t<double>("hgev.fr", pl);
+  double* Fi = ctx.pool.get_t<double>("hgev.fi", pl);
+  double* Tr = ctx.pool.get_t<double>("hgev.tr", pl);   // A F, later Y
+  double* Ti = ctx.pool.get_t<double>("hgev.ti", pl);
+  const int nt = ceil_div(n, 32);
+  hipLaunchKernelGGL(hg_expand_kernel, dim3(nt, nt), dim3(256), 0, st, (const double*)a, lda, n, Ar, Ai, ld);
+  rc = herm_solve_dev(ctx, n, n, b, ldb, w, z, ldz, HG_MF, HG_MB, 'X');                   // B = U diag(mu) U^H
+  if (rc != EIGX_OK) return rc;
+  const double t1 = now_s();
+  if (!b_is_positive_definite(ctx, w)) return EIGX_ERR_NOT_SPD;
+  const dim3 cg = col_grid(n, n);
+  hipLaunchKernelGGL(hg_split_kernel, cg, dim3(256), 0, st, (const double*)z, ldz, (const double*)w, n, n, 1, 0, 1, 0, 0, Fr, Fi,
+                     ld);                                                                    // F = U diag(mu)^-1/2
+  hipLaunchKernelGGL(hg_join_kernel, cg, dim3(256), 0, st, (const double*)Fr, (const double*)Fi, ld, n, n, 1, 0, 1, 0, 0, b, ldb);
+  dgemm_dev(st, 'N', 'N', n, n, n, 1.0, Ar, ld, Fr, ld, 0.0, Tr, ld);                       // Tr = Ar Fr - Ai Fi
+  dgemm_dev(st, 'N', 'N', n, n, n, -1.0, Ai, ld, Fi, ld, 1.0, Tr, ld);
+  dgemm_dev(st, 'N', 'N', n, n, n, 1.0, Ar, ld, Fi, ld, 0.0, Ti, ld);                       // Ti = Ar Fi + Ai Fr
+  dgemm_dev(st, 'N', 'N', n, n, n, 1.0, Ai, ld, Fr, ld, 1.0, Ti, ld);
+  dgemm_dev(st, 'T', 'N', n, n, n, 1.0, Fr, ld, Tr, ld, 0.0, Ar, ld, 1);                    // Cr = Fr^T Tr + Fi^T Ti
+  dgemm_dev(st, 'T', 'N', n, n, n, 1.0, Fi, ld, Ti, ld, 1.0, Ar, ld, 1);
+  dgemm_dev(st, 'T', 'N', n, n, n, 1.0, Fr, ld, Ti, ld, 0.0, Ai, ld, 1);                    // Ci = Fr^T Ti - Fi^T Tr
+  dgemm_dev(st, 'T', 'N', n, n, n, -1.0, Fi, ld, Tr, ld, 1.0, Ai, ld, 1);
+  hipLaunchKernelGGL(hg_join_kernel, cg, dim3(256), 0, st, (const double*)Ar, (const double*)Ai, ld, n, n, 1, 0, 1, 0, 1, z, ldz);
+  EIGX_HIP_CHECK(hipStreamSynchronize(st));
+  const double t2 = now_s();
+  rc = herm_solve_dev(ctx, n, n, z, ldz, w, a, lda, HG_MF, HG_MB, 'X');                   // C = Y diag(w) Y^H, Y in a
+  if (rc != EIGX_OK) return rc;
+  const double t3 = now_s();
+  hipLaunchKernelGGL(hg_split_kernel, cg, dim3(256), 0, st, (const double*)a, lda, (const double*)nullptr, n, n, 1, 0, 1, 0, 0, Tr,
+                     Ti, ld);
+  dgemm_dev(st, 'N', 'N', n, n, n, 1.0, Fr, ld, Tr, ld, 0.0, Ar, ld);                       // Zr = Fr Yr - Fi Yi
+  dgemm_dev(st, 'N', 'N', n, n, n, -1.0, Fi, ld, Ti, ld, 1.0, Ar, ld);
+  dgemm_dev(st, 'N', 'N', n, n, n, 1.0, Fr, ld, Ti, ld, 0.0, Ai, ld);                       // Zi = Fr Yi + Fi Yr
+  dgemm_dev(st, 'N', 'N', n, n, n, 1.0, Fi, ld, Tr, ld, 1.0, Ai, ld);
+  hipLaunchKernelGGL(hg_join_kernel, cg, dim3(256), 0, st, (const double*)Ar, (const double*)Ai, ld, n, n, 1, 0, 1, 0, 0, z, ldz);
+  EIGX_HIP_CHECK(hipStreamSynchronize(st));
+  const double t4 = now_s();
+  ctx.timers[0] = t4 - t0; ctx.timers[1] = t1 - t0; ctx.timers[2] = t2 - t1; ctx.timers[3] = t3 - t2; ctx.timers[4] = t4 - t3;
+  return EIGX_OK;
+}
+
+int hgev_host(Context& ctx, int n, double* a, int lda, double* b, int ldb, double* w, double* z, int ldz) {
+  if (!ctx.initialized) return EIGX_ERR_NOT_INITIALIZED;
+  // host arrays: the rank's 2-D cyclic blocks a(lda, *), b(ldb, *), z(ldz, *), interleaved complex (one rank: the whole matrices)
+  const int nr = local_count(n, ctx.grid.Px, ctx.grid.px), nc = local_count(n, ctx.grid.Py, ctx.grid.py);
+  if (n <= 0 || !a || !b || !w || !z || lda < nr || ldb < nr || ldz < nr) return EIGX_ERR_BAD_ARG;
+  EIGX_HIP_CHECK(hipSetDevice(ctx.device));
+  const int ldd = host_ld(nr);
+  double* ad = (double*)host_to_dev(ctx, "host.ha", a, lda, nr, nc, 16);
+  double* bd = (double*)host_to_dev(ctx, "host.hb", b, ldb, nr, nc, 16);
+  double* zd = (double*)host_to_dev(ctx, "host.hz", nullptr, 0, nr, nc, 16);
+  double* wd = ctx.pool.get_t<double>("host.w", (size_t)n);
+  const int rc = hgev_dev(ctx, n, ad, ldd, bd, ldd, wd, zd, ldd);
+  EIGX_HIP_CHECK(hipMemcpy(w, wd, (size_t)n * 8, hipMemcpyDeviceToHost));   // NaN for a non-finite input, as eigen_h
+  if (rc != EIGX_OK) return rc;
+  dev_to_host(z, ldz, zd, ldd, nr, nc, 16);
+  dev_to_host(a, lda, ad, ldd, nr, nc, 16);
+  dev_to_host(b, ldb, bd, ldd, nr, nc, 16);
+  return EIGX_OK;
+}
+
+}  // namespace eigx
+
+using namespace eigx;
+
+extern "C" {
+
+int eigx_hgev(int n, double* a, int lda, double* b, int ldb, double* w, double* z, int ldz) {
+  return eigx_guard(g_ctx, [&] { return hgev_host(g_ctx, n, a, lda, b, ldb, w, z, ldz); });
+}
+int eigx_hgev_dev(int n, double* a, int lda, double* b, int ldb, double* w, double* z, int ldz) {
+  return eigx_guard(g_ctx, [&] { return hgev_dev(g_ctx, n, a, lda, b, ldb, w, z, ldz); });
+}
+
+}  // extern "C"

@@ -511,7 +511,11 @@ __global__ void scale_cols_rsqrt_kernel(const double* __restrict__ z, int ldz, c
 }
 
 
+}  // namespace
+
 // ---- multi-rank KMATH_EIGEN_GEV on the 2-D cyclic blocks -------------------------------------------------------------
+// (outside the anonymous namespace: hgev.hip builds the complex generalised solver from the same transpose and packing
+// kernels; declared in eigx_context.h)
 // Two building blocks, both O(n^2 / P) memory per rank:
 //   dist_transpose : Z = A^T.  Element A(j, i) lives on rank (j % Px, i % Py) and goes to rank (i % Px, j % Py): on a
 //                    non-square grid that is a genuine all-to-all.  The rows i that rank (px, .) receives from a source in
@@ -579,16 +583,16 @@ static void transpose_plan(int Px, int Py, int px, int py, int qx, int qy, int* 
 
 // z(ldz, nc) = (a(lda, nc))^T on the cyclic blocks (both n x n); enqueued on st.  The all-to-all's pieces are uniform, and
 // only gcd(Px, Py)^-2 of the rank pairs exchange anything, so the exchange runs in rounds over the pieces' columns u that
-// keep the send + receive buffers at about one local block each.
-static void dist_transpose(Context& ctx, int n, const double* a, int lda, double* z, int ldz, hipStream_t st) {
+// keep the send + receive buffers (pool entries `tag`.tsend / `tag`.trecv) at about one local block each.
+void dist_transpose(Context& ctx, int n, const double* a, int lda, double* z, int ldz, hipStream_t st, const char* tag) {
   const Grid& G = ctx.grid;
   const int g = gcd_int(G.Px, G.Py);
   const int P = G.nranks, L = G.Px / g * G.Py;
   const int nimax = ceil_div(n, L);
   const int ucw = ceil_div(nimax, g * g);                      // piece columns per round
   const size_t count = (size_t)nimax * ucw;
-  double* sendb = ctx.pool.get_t<double>("gev.tsend", count * P);
-  double* recvb = ctx.pool.get_t<double>("gev.trecv", count * P);
+  double* sendb = ctx.pool.get_t<double>(std::string(tag) + ".tsend", count * P);
+  double* recvb = ctx.pool.get_t<double>(std::string(tag) + ".trecv", count * P);
   TrPeers to, from;
   for (int q = 0; q < P; ++q) {
     const int qx = G.row_major ? q / G.Py : q % G.Px, qy = G.row_major ? q % G.Py : q / G.Px;
@@ -642,6 +646,9 @@ __global__ void mm_unpack_b_kernel(const double* __restrict__ recv, int Px, int 
     Bp[(size_t)j * kb + (size_t)(dk % Py) * kbl_y + dk / Py] = recv[((size_t)q * ncp + j) * kbl_x + rr];
   }
 }
+
+namespace {
+
 // C(ldc, nc) = A B on the cyclic blocks (all n x n, A and B complete -- not triangles); synchronous
 static int dist_gemm_nn(Context& ctx, int n, const double* A, int lda, const double* B, int ldb, double* C, int ldc) {
   const Grid& G = ctx.grid;

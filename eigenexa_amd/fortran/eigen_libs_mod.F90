@@ -734,3 +734,24 @@ subroutine KMATH_EIGEN_GEV(n, a, lda, b, ldb, w, z, ldz)
   integer(c_int) :: rc
   rc = eigx_gev(int(n, c_int), a, int(lda, c_int), b, int(ldb, c_int), w, z, int(ldz, c_int))
 end subroutine KMATH_EIGEN_GEV
+
+! KMATH_EIGEN_HGEV -- EXTENSION, not in the reference (it has no complex generalised solver): the complex Hermitian-definite
+! problem A x = lambda B x by the method of KMATH_EIGEN_GEV over complex numbers.  Same argument list and on-exit contract
+! as KMATH_EIGEN_GEV with complex(8) a, b, z: upper triangles significant, w ascending, z^H B z = I, a holds Y, b holds F.
+subroutine KMATH_EIGEN_HGEV(n, a, lda, b, ldb, w, z, ldz)
+  use, intrinsic :: iso_c_binding
+  implicit none
+  integer, intent(inout) :: n, lda, ldb, ldz
+  complex(8), intent(inout) :: a(lda, *), b(ldb, *), z(ldz, *)
+  real(8), intent(inout) :: w(*)
+  interface
+    integer(c_int) function eigx_hgev(n, a, lda, b, ldb, w, z, ldz) bind(C, name="eigx_hgev")
+      import :: c_int, c_double, c_double_complex
+      integer(c_int), value :: n, lda, ldb, ldz
+      complex(c_double_complex), intent(inout) :: a(lda, *), b(ldb, *), z(ldz, *)
+      real(c_double), intent(inout) :: w(*)
+    end function
+  end interface
+  integer(c_int) :: rc
+  rc = eigx_hgev(int(n, c_int), a, int(lda, c_int), b, int(ldb, c_int), w, z, int(ldz, c_int))
+end subroutine KMATH_EIGEN_HGEV

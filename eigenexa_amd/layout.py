@@ -287,6 +287,19 @@ def random_hermitian(n, seed=20240807, rows=None, cols=None):
         return s(i, j) + s(j, i).conj().T
 
 
+def random_hpd(n, seed=11, lo=1.0, hi=10.0, real=False):
+    """B = Q diag(mu) Q^H with Q the unitary (orthogonal if real) QR factor of a seeded Gaussian matrix and mu uniform in
+    [lo, hi]: a Hermitian positive-definite matrix with a known spectrum (the B of the KMATH_EIGEN_HGEV tests)"""
+    rng = np.random.default_rng(seed)
+    X = rng.standard_normal((n, n))
+    if not real:
+        X = X + 1j * rng.standard_normal((n, n))
+    Q, _ = np.linalg.qr(X)
+    mu = rng.uniform(lo, hi, n)
+    B = (Q * mu[None, :]) @ Q.conj().T
+    return (B + B.conj().T) / 2
+
+
 def accuracy_metrics(A, w, Z):
     """the reference's three gates: residual ||AZ-ZW||_F/(N eps ||A||_F) (< 768), orthogonality
     ||Z^T Z - I||_F/(N eps) (< 8)  (benchmark/ev_test.f:181-204)."""

@@ -22,7 +22,8 @@
  *   eigx_sx / eigx_s          host arrays in, host arrays out     (drop-in for the Fortran API)
  *   eigx_sx_dev / eigx_s_dev  device (HBM-resident) arrays        (what bench.py times)
  * and, on top of them: eigx_solve_bc[_dev] (block-cyclic local blocks of a ScaLAPACK descriptor),
- * eigx_gev[_dev] (KMATH_EIGEN_GEV), eigx_h[_dev] (complex Hermitian eigen_h).
+ * eigx_gev[_dev] (KMATH_EIGEN_GEV), eigx_h[_dev] (complex Hermitian eigen_h), eigx_hgev[_dev] (KMATH_EIGEN_HGEV, an
+ * extension: complex Hermitian generalised problem).
  */
 #ifndef EIGENEXA_AMD_H
 #define EIGENEXA_AMD_H
@@ -215,6 +216,17 @@ int eigx_band_dc_dev(int n, int nvec, const double* d_dev, const double* e_dev, 
  * distributed, src/KMATH_EIGEN_GEV_1.F:57-139). */
 int eigx_gev(int n, double* a, int lda, double* b, int ldb, double* w, double* z, int ldz);
 int eigx_gev_dev(int n, double* a_dev, int lda, double* b_dev, int ldb, double* w_dev, double* z_dev, int ldz);
+
+/* KMATH_EIGEN_HGEV -- EXTENSION, not in the reference (which has no complex generalised solver): the complex
+ * Hermitian-definite problem A x = lambda B x by the reference's method for the real case (src/KMATH_EIGEN_GEV_1.F:57-139)
+ * over complex numbers: eigen_h(B) -> F = U mu^-1/2 -> C = F^H A F -> eigen_h(C) -> z = F Y.  Same argument list and
+ * on-exit contract as eigx_gev: a, b, z complex(8) as interleaved (re, im) doubles, column-major, leading dimensions in
+ * COMPLEX elements; upper triangles of a, b significant (Im of their diagonals ignored); w ascending; z^H B z = I; on exit
+ * a holds Y, b holds F.  EIGX_ERR_NOT_SPD if B is not positive definite (message printed), EIGX_ERR_NONFINITE with
+ * w = NaN for a non-finite significant entry.  Timers [0..4] as for eigx_gev.  Several ranks: a, b, z are the ranks'
+ * 2-D cyclic blocks, nothing is gathered.  Inherits eigen_h's overflow above a matrix scale of about 1e77. */
+int eigx_hgev(int n, double* a, int lda, double* b, int ldb, double* w, double* z, int ldz);
+int eigx_hgev_dev(int n, double* a_dev, int lda, double* b_dev, int ldb, double* w_dev, double* z_dev, int ldz);
 
 /* replaces eigen_bisect(d,e,w,n,mode) src/bisect.F:67-397 (band=1) / eigen_bisect2(d,e,f,w,n,mode)
  * src/bisect2.F:71-718 (band=2): all eigenvalues of the band matrix by Sturm counts, w_dev ascending.
