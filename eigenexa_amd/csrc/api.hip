@@ -359,16 +359,11 @@ int eigx_tune(int key, int value) {
   if (key == 0) return set_gemm_variant(value);
   if (key == 1) return set_bisect_threads(value);
   if (key == 2) return set_bt_q(value);
-  if (key == 3) return set_symv_threshold(0, value);
-  if (key == 4) return set_symv_threshold(1, value);
-  if (key == 5) return set_symv_threshold(2, value);
+  if (key == 3 || key == 4 || key == 5 || key == 10 || key == 11) return set_reduce_knob(key, value);
   if (key == 6) return set_gemm_cstream(value);
-  if (key == 7) return value > 0 ? set_symv_threshold(3, value) : -1;
+  if (key == 7) return value > 0 ? set_reduce_knob(key, value) : -1;
   if (key == 8) return set_dc_chunk(value);
   if (key == 9) return comm_set_bounce(value);
-  if (key == 10) return set_symv_threshold(4, value);
-  if (key == 11) return set_symv_threshold(5, value);   // branch-free pipelined form of the mat-vec up to this active size
-  if (key == 12) return set_symv_threshold(6, value);   // (removed in round 4: step exchange folded into the mat-vec launch; accepted, ignored)
   if (key == 15) return set_dc_pipe(value);    // D&C on one GPU: next pass's deflation / secular equations under this pass's product
   if (key == 16) return set_dc_batch(value);   // D&C on one GPU: one product launch per low height
   return -1;

@@ -30,8 +30,10 @@
 #include "eigx_context.h"
 #include "eigx_comm.h"
 #include "../../include/eigenexa_amd.h"
+#include <algorithm>
 #include <chrono>
 #include <cstring>
+#include <type_traits>
 
 // Floating-point contraction by SOURCE FORM only (a * b + c written in one expression becomes an fma, nothing is fused
 // across statements): the same source then rounds the same way in every template instantiation and role of these kernels.
@@ -127,10 +129,20 @@ int g_ka_fit = 1;     // K_A (eigx_tune key 10): 1 = load batches matched to the
 int g_ka_wgs = 256;   // K_A (eigx_tune key 7): beyond 2 * this many row groups a workgroup takes several of them, ~this many workgroups
 int g_symv_t128 = 4500, g_symv_t256 = 40000;
 int g_symv_nt = 9000;
-// (eigx_tune key 12, once EIGX_FOLD_KL: the Y exchange inside the mat-vec launch -- its last-arriving tiles reduced and pushed.
-// In the rehearsal of one rank of a 2 x 4 grid at N = 32768 it made the mat-vec 23 us longer to save a 20-us kernel: the last
-// tile's workgroup did a whole row block's and column block's reduction alone, on the critical path.  Removed in round 4.)
 int g_symv_unc = 9000;   // the fused mat-vec's branch-free pipelined form up to this active size (eigx_tune key 11)
+}  // namespace
+
+// eigx_tune keys 3, 4, 5, 7, 10, 11 -> the knobs above (previous value; -1: not a key of the reduction)
+int set_reduce_knob(int key, int v) {
+  int* t = key == 3 ? &g_symv_t128 : key == 4 ? &g_symv_t256 : key == 5 ? &g_symv_nt : key == 7 ? &g_ka_wgs
+         : key == 10 ? &g_ka_fit : key == 11 ? &g_symv_unc : nullptr;
+  if (!t) return -1;
+  const int old = *t;
+  *t = v;
+  return old;
+}
+
+namespace {
 
 inline SymvGeom symv_geom(int L) {
   SymvGeom g;
@@ -395,7 +407,7 @@ __device__ __forceinline__ void ka_body(const RedArgs& R, const KAArgs& S, const
   // Addresses = wave-uniform base (SGPR pair, one scalar add per load) + ONE 32-bit lane offset per family: the
   // kernel's instruction issue is as long as its memory wait (PMC: SQ_ACTIVE_INST_ANY = SQ_WAIT_INST_ANY), and 64-bit
   // per-lane address arithmetic with clamps was most of it.  The buffers are padded so that unclamped slots stay
-  // inside the allocation (band_reduce_impl).
+  // inside the allocation (reduce_setup).
   // row loads of one row group (this thread's row rg of it): unconditional, clamped / padded addresses
   // the row's share of the previous mat-vec's result: partial sums (one GPU) / message entries (several GPUs)
   auto load_rows_msg = [&](int rg, RowRegs& Q) {
@@ -403,7 +415,7 @@ __device__ __forceinline__ void ka_body(const RedArgs& R, const KAArgs& S, const
     const bool okp = hp && ok && rg < S.Lprev;
     // SYMV partial sums of the row: t-th partial, t in [0, nt]: t <= ty -> column result of tile row t
     // (column r of tile (t, ty)); t > ty -> row result of tile column t-1 (row r of tile (ty, t-1))
-    if (!mg) {   // (compile-time)  one GPU: slot t of the unified array Y = YC (see band_reduce_impl)
+    if (!mg) {   // (compile-time)  one GPU: slot t of the unified array Y = YC (see reduce_setup)
       const unsigned voff = (unsigned)ks * (unsigned)(NB * ldp) + (unsigned)(okp ? rg : 0);
 #pragma unroll
       for (int j = 0; j < RPB; ++j) {
@@ -1911,11 +1923,19 @@ __global__ void mg_tail_kernel(RedArgs R, int xpar, int i, int ncols, StepWait W
   }
 }
 
+// ---- host side: what both drivers share -----------------------------------------------------------------------------
+inline double wall_seconds() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
+inline StepWait no_wait() { return StepWait{nullptr, nullptr, nullptr, 0, 0, 0, 1}; }   // n = 0: nothing to wait for
+// the panel [U | W | U] to zero: at the start and behind every trailing update
+inline void clear_panel(const RedArgs& R, hipStream_t st) {
+  hipLaunchKernelGGL(fill_kernel, dim3(1024), dim3(256), 0, st, R.UW, (size_t)R.ldp * R.m * 3, 0.0);
+}
+
+// RedArgs, the buffers that both drivers use and their zero fills.  The mat-vec's partial sums and the panel dots are laid
+// out per path; they are requested here as well, so that the pool sees the same requests in the same order.
 template <int NB>
-void band_reduce_impl(Context& ctx, int n, double* A, int lda, double* d, double* e, int lde, int m) {
-  hipStream_t st = ctx.stream;
-  if (m < NB) m = NB;
-  if (m > 256) m = 256;
+RedArgs reduce_setup(Context& ctx, int n, double* A, int lda, double* d, double* e, int lde, int m) {
+  m = std::min(std::max(m, NB), 256);
   if (NB == 2 && (m & 1)) ++m;
   const int ldp = pad_ld((n + 127) / 128 * 128 + 128);
   const Grid& G = ctx.grid;
@@ -1925,8 +1945,7 @@ void band_reduce_impl(Context& ctx, int n, double* A, int lda, double* d, double
   R.d = d; R.e = e; R.lde = lde;
   R.P = G.nranks; R.me = G.rank; R.invP = 1.0f / (float)G.nranks;
   R.Px = G.Px; R.Py = G.Py; R.px = G.px; R.py = G.py; R.row_major = G.row_major;
-  R.nxs = (ceil_div(n, G.Px) + 7) / 8 * 8;
-  R.nys = (ceil_div(n, G.Py) + 7) / 8 * 8;
+  R.nxs = (ceil_div(n, G.Px) + 7) / 8 * 8; R.nys = (ceil_div(n, G.Py) + 7) / 8 * 8;
   R.msg_stride = NB * (R.nxs + R.nys) + 8 + 2 * NB * m;          // Y: row sums | column sums | 8 scalar slots | share of the panel dots
   R.ypar_stride = (size_t)G.nranks * R.msg_stride; R.ysrc_stride = R.msg_stride;
   R.nown = ceil_div(ceil_div(n, KA_ROWS), G.nranks) * KA_ROWS;   // rows a rank can own (groups of KA_ROWS dealt round-robin)
@@ -1934,18 +1953,10 @@ void band_reduce_impl(Context& ctx, int n, double* A, int lda, double* d, double
   R.xpar_stride = (size_t)G.nranks * R.xmsg_stride;
   R.MSG = nullptr; R.XW = nullptr; R.PAN = nullptr; R.ldpan = ldp;
   int maxseg = 0;
-  if (!mg) {
-    for (int L = n; L >= 1; --L) {  // nt is not monotone in L: scan
-      const SymvGeom g = symv_geom(L);
-      if (g.nt > maxseg) maxseg = g.nt;
-    }
-  } else {
-    maxseg = ceil_div(R.nxs > R.nys ? R.nxs : R.nys, 128) + 1;
-  }
+  if (mg) maxseg = ceil_div(R.nxs > R.nys ? R.nxs : R.nys, 128) + 1;
+  else for (int L = n; L >= 1; --L) maxseg = std::max(maxseg, symv_geom(L).nt);   // nt is not monotone in L: scan
   maxseg += 1;
-  R.maxseg = maxseg;
-  R.maxrs = maxseg;
-  R.maxchunk = 4 + 1;
+  R.maxseg = maxseg; R.maxrs = maxseg; R.maxchunk = 4 + 1;
   // + 128 columns: K_A loads panel columns kk < 128 of the U and of the W region without clamping kk (masked afterwards)
   R.UW = ctx.pool.get_t<double>("red.UW", (size_t)ldp * (m * 3 + 128));
   R.X = ctx.pool.get_t<double>("red.X", (size_t)ldp * 3);
@@ -1958,187 +1969,333 @@ void band_reduce_impl(Context& ctx, int n, double* A, int lda, double* d, double
     const int nslot = (maxseg + 2 > 162) ? maxseg + 2 : 162;
     R.YC = ctx.pool.get_t<double>("red.Y", (size_t)nslot * NB * ldp);
     R.YR = R.YC + (size_t)NB * ldp;
+    R.kdab_off = R.maxchunk * 2 * NB * m;
+    R.KD = ctx.pool.get_t<double>("red.KD", (size_t)R.kdab_off + R.maxchunk + 8 + 512);   // + slack: K_A loads kk < 256 unclamped
   } else {
     R.YR = ctx.pool.get_t<double>("red.YR", (size_t)maxseg * NB * ldp);
     R.YC = ctx.pool.get_t<double>("red.YC", (size_t)R.maxrs * NB * ldp);
+    // several GPUs: first-level panel dots of up to 12 chunks of the rank's own rows (kl_kernel sums them and sends the
+    // rank's share to everybody), then the uA.uB partial sums of up to 4 P + 4 chunks of the replicated reflector store
+    const int maxchunk2 = 12;
+    R.kdab_off = maxchunk2 * 2 * NB * m;
+    R.KD = ctx.pool.get_t<double>("red.KD2", (size_t)R.kdab_off + 4 * G.nranks + 4 + 8 + 512);
   }
-  R.kdab_off = R.maxchunk * 2 * NB * m;
-  R.KD = ctx.pool.get_t<double>("red.KD", (size_t)R.kdab_off + R.maxchunk + 8 + 512);   // + slack: K_A loads kk < 256 unclamped
-  // several GPUs: first-level panel dots of up to 12 chunks of the rank's own rows (kl_kernel sums them and sends the
-  // rank's share to everybody), then the uA.uB partial sums of up to 4 P + 4 chunks of the replicated reflector store
-  const int maxchunk2 = 12;
-  const int kdab2_off = maxchunk2 * 2 * NB * m;
-  if (mg) {
-    R.KD = ctx.pool.get_t<double>("red.KD2", (size_t)kdab2_off + 4 * G.nranks + 4 + 8 + 512);
-    R.kdab_off = kdab2_off;
-  }
-  const size_t sp_count = (size_t)(maxseg * maxseg) * 3 + 8;
-  R.SP = ctx.pool.get_t<double>("red.SP", sp_count);
-  const int maxgp = (n + KA_ROWS - 1) / KA_ROWS + 2;
+  R.SP = ctx.pool.get_t<double>("red.SP", (size_t)(maxseg * maxseg) * 3 + 8);
   R.gp2_off = 0;
-  R.GP = ctx.pool.get_t<double>("red.GP", (size_t)maxgp * 3 + 8);
+  R.GP = ctx.pool.get_t<double>("red.GP", (size_t)((n + KA_ROWS - 1) / KA_ROWS + 2) * 3 + 8);
   R.sc = ctx.pool.get_t<double>("red.sc", SC_COUNT + 8);
   R.zero16 = R.sc + SC_COUNT;             // zero-filled below with the scalars, never written afterwards
-  R.dbg = nullptr;
+  R.dbg = nullptr; R.abl = 0; R.stamp_i = -1;
+#ifdef EIGX_STAMPS
   R.abl = getenv("EIGX_ABL") ? atoi(getenv("EIGX_ABL")) : 0;
   R.stamp_i = getenv("EIGX_STAMP_I") ? atoi(getenv("EIGX_STAMP_I")) : -1;
-#ifdef EIGX_STAMPS
   R.dbg = ctx.pool.get_t<unsigned long long>("red.dbg", 4096);
-  EIGX_HIP_CHECK(hipMemsetAsync(R.dbg, 0, 4096 * sizeof(unsigned long long), st));
+  EIGX_HIP_CHECK(hipMemsetAsync(R.dbg, 0, 4096 * sizeof(unsigned long long), ctx.stream));
 #endif
-  // ---- multi-GPU state: step window, gathered panel, compact panels ------------------------------------------
+  clear_panel(R, ctx.stream);
+  hipLaunchKernelGGL(fill_kernel, dim3(8), dim3(256), 0, ctx.stream, e, (size_t)lde * NB, 0.0);
+  hipLaunchKernelGGL(fill_kernel, dim3(1), dim3(64), 0, ctx.stream, R.sc, (size_t)SC_COUNT + 8, 0.0);
+  hipLaunchKernelGGL(fill_kernel, dim3(16), dim3(256), 0, ctx.stream, R.SP, (size_t)(maxseg * maxseg) * 3 + 8, 0.0);
+  return R;
+}
+
+// counts of a reduction (ctx.timers 6, 7: trailing updates and their flops; 9, 10: mat-vecs and their bytes)
+struct RedCounters {
+  long n_symv = 0, n_k1 = 0; double symv_bytes = 0.0, k1_flops = 0.0;
+  bool sampled(const Context& ctx) const { return ctx.prof_stride > 0 && (n_symv % ctx.prof_stride) == 0; }
+  void step(int L) { symv_bytes += 8.0 * ((double)L * (L + 1) / 2); ++n_symv; }
+  void panel(int nr, int m) { k1_flops += 2.0 * (double)nr * nr * m; ++n_k1; }   // 2*nr*nr*(2m)/2 : upper triangle only
+  void write(Context& ctx) const { ctx.timers[6] = (double)n_k1; ctx.timers[7] = k1_flops; ctx.timers[9] = (double)n_symv; ctx.timers[10] = symv_bytes; }
+};
+// K_A before the first step: nothing pending, nothing to wait for
+inline KAArgs ka_first_args() { KAArgs S{}; S.lgT_prev = 7; S.G = 1; S.wait = no_wait(); return S; }
+// K_A of the step with top column i at panel fill k: a full block of columns while reflectors remain, otherwise the last
+// <= NB columns; rows to cover.  Returns L = rows above the block (< 1: no mat-vec, the reduction ends).
+template <int NB>
+inline int ka_step_args(KAArgs& S, int i, int k) {
+  const int L = i - NB + 1;
+  S.ncols = (L >= 1) ? NB : (i >= 0 ? (i + 1 < NB ? i + 1 : NB) : 0);
+  S.i = i; S.L = (L >= 1) ? L : 0; S.k = k;
+  S.rows = (S.has_prev && S.iprev + 1 > i + 1) ? S.iprev + 1 : i + 1;
+  return L;
+}
+// behind the step's mat-vec (nt tiles of edge T per dimension): the next K_A finishes this step, adding nchunk shares of
+// the panel dots (one per K_P row chunk / per rank) and nchunk_ab partial sums of uA.uB; the cursor moves on by NB columns
+template <int NB>
+inline void step_done(KAArgs& S, RedCounters& C, int& i, int& k, int L, int nt, int T, int nchunk, int nchunk_ab) {
+  C.step(L);
+  S.has_prev = 1; S.iprev = i; S.Lprev = L; S.kprev = k; S.nchunk_prev = nchunk; S.nchunk_ab = nchunk_ab;
+  S.nt_prev = nt; S.lgT_prev = (T == 128) ? 7 : (T == 256 ? 8 : 9);
+  k += NB;
+  i -= NB;
+}
+// panel full and more reflectors to come: finish W, trailing update, start a new panel
+template <int NB>
+inline bool panel_full(int k, int m, int i) { return k >= m && i - NB + 1 >= 1; }
+// behind the trailing update of nr rows: a new panel starts
+inline void panel_restart(const RedArgs& R, RedCounters& C, KAArgs& S, int& k, int nr, hipStream_t st) {
+  C.panel(nr, R.m); clear_panel(R, st); S.has_prev = 0; k = 0;
+}
+// the panel-closing K_A: finishes the last step's W columns, forms none
+inline KAArgs ka_close_args(const KAArgs& S, int i, int k) { KAArgs F = S; F.ncols = 0; F.i = i; F.L = 0; F.k = k; F.rows = S.iprev + 1; return F; }
+// the mat-vec's fields of a step as one GPU has them (several ranks then set their own K_P chunks and tiling)
+inline KBArgs kb_step_args(int i, int L, int k) {
+  KBArgs B;
+  B.i = i; B.L = L; B.k = k;
+  B.ncg = (k + PD_COLS - 1) / PD_COLS; B.toprows = i + 1; B.pdr = pd_rows_for(B.toprows);
+  B.nown_L = 0; B.npd_s = 0; B.pdr_s = 0; B.wk = -1; B.xpar = 0; B.xwait = no_wait();
+  B.Lr = L; B.Lc = L; B.ntc = 0; B.nty_last = 0; B.slope = 0; B.c1 = 0;
+  return B;
+}
+// EIGX_TRACE_ENQUEUE: host time of the step loop (from t_begin), then the time until the stream drained
+inline void trace_enqueue(double t_begin, hipStream_t st) {
+  if (!getenv("EIGX_TRACE_ENQUEUE")) return;
+  const double te = wall_seconds();
+  EIGX_HIP_CHECK(hipStreamSynchronize(st));
+  fprintf(stderr, "[eigx] reduction: enqueue loop %.1f ms, then %.1f ms until the stream drained\n", (te - t_begin) * 1e3, (wall_seconds() - te) * 1e3);
+}
+// diagnostic build: report of the stamps the kernels accumulated in R.dbg (release: nothing)
+inline void stamps_report(const RedArgs& R, int NB, hipStream_t st) {
+#ifdef EIGX_STAMPS
+  const bool mg = R.P > 1;
+  unsigned long long h[32];
+  EIGX_HIP_CHECK(hipStreamSynchronize(st));
+  EIGX_HIP_CHECK(hipMemcpy(h, R.dbg, sizeof(h), hipMemcpyDeviceToHost));
+  if (mg && h[24]) fprintf(stderr, "[eigx stamps] step launch timeline (100-MHz clock, averages over %llu full launches, from workgroup 0's entry): Y flags "
+                           "raised at %.2f us, X flags at %.2f us, next launch's workgroup 0 enters at %.2f us\n", h[24], 0.01 * h[22] / h[24],
+                           0.01 * h[23] / h[24], 0.01 * h[21] / h[24]);
+  if (R.stamp_i >= 0 && mg) {
+    // one sampled step (EIGX_STAMP_I = its top column): per-workgroup times of the three roles on the 100-MHz clock
+    std::vector<unsigned long long> big(4096);
+    EIGX_HIP_CHECK(hipMemcpy(big.data(), R.dbg, 4096 * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+    unsigned long long t0 = ~0ull; int nw = 0, nk = 0;
+    for (int b = 0; b < 256; ++b) if (big[3136 + b]) { ++nk; if (big[3136 + b] < t0) t0 = big[3136 + b]; }
+    for (int b = 0; b < 1024; ++b) if (big[64 + b]) { ++nw; if (big[64 + b] < t0) t0 = big[64 + b]; }
+    double mk[3] = {0, 0, 0}, mx[3] = {0, 0, 0};
+    for (int b = 0; b < nk; ++b) for (int q = 0; q < 3; ++q) { const double v = 0.01 * (big[3136 + 256 * q + b] - t0); if (v > mk[q]) mk[q] = v; }
+    for (int b = 0; b < nw; ++b) for (int q = 0; q < 3; ++q) { const double v = 0.01 * (big[64 + 1024 * q + b] - t0); if (v > mx[q]) mx[q] = v; }
+    fprintf(stderr, "[eigx stamps] step with top column %d, us after the launch's first workgroup: kl role (%d workgroups) latest entry %.2f, partial sums in %.2f, "
+            "stores drained %.2f | ka role (%d) latest entry %.2f, Y seen %.2f, pushes issued %.2f; count complete %.2f, X flags stored %.2f | mat-vec role "
+            "(%llu tiles): X seen first %.2f last %.2f, tile ends first %.2f last %.2f\n", R.stamp_i, nk, mk[0], mk[1], mk[2], nw, mx[0], mx[1], mx[2],
+            0.01 * (big[3904] - t0), 0.01 * (big[3905] - t0), big[3910], 0.01 * (~big[3906] - t0), 0.01 * (big[3907] - t0), 0.01 * (~big[3909] - t0),
+            0.01 * (big[3908] - t0));
+  }
+  if (h[30]) fprintf(stderr, "[eigx stamps] K_A workgroup in the middle: %.2f us of wall clock per launch, %.0f s_memtime ticks: %.0f MHz\n",
+                     0.01 * h[30] / h[7], (double)h[31] / h[7], (double)h[31] / (0.01 * h[30]));
+  if (mg && h[24]) fprintf(stderr, "[eigx stamps] ka role, workgroup in the middle: enters at %.2f us, sees the Y flags at %.2f, has issued its pushes at %.2f; "
+                           "the watcher sees the count complete at %.2f us\n", 0.01 * h[26] / h[7], 0.01 * h[27] / h[7], 0.01 * h[28] / h[7], 0.01 * h[29] / h[14]);
+  if (mg) fprintf(stderr, "[eigx stamps] K_A several GPUs: wait %.0f | to the end of the pushes %.0f, drain + barrier %.0f | last arriver (from its previous stamp "
+                  "to the flag store) %.0f x %llu\n", (double)h[5] / h[7], (double)h[6] / h[7], (double)h[12] / h[7], (double)h[13] / (h[14] ? h[14] : 1), h[14]);
+  fprintf(stderr, "[eigx stamps] NB=%d n=%d K_A launches %llu: avg cycles issue %.0f consume %.0f reduce %.0f rows %.0f tail %.0f | SYMV %llu: "
+          "entry %.0f scalars %.0f stream %.0f tail %.0f\n", NB, R.n, h[7], (double)h[0] / h[7], (double)h[1] / h[7], (double)h[2] / h[7],
+          (double)h[3] / h[7], (double)h[4] / h[7], h[15], (double)h[8] / (h[15] ? h[15] : 1), (double)h[9] / (h[15] ? h[15] : 1),
+          (double)h[10] / (h[15] ? h[15] : 1), (double)h[11] / (h[15] ? h[15] : 1));
+#endif
+}
+
+// ---- one GPU --------------------------------------------------------------------------------------------------------
+// K_A's grid: G row groups per workgroup, one wave per SIMD at most (1024 SIMDs = 256 workgroups of 4 waves)
+inline int ka_grid_one_gpu(int rows, int& G) {
+  const int ng = (rows + KA_ROWS - 1) / KA_ROWS;
+  G = (ng > 2 * g_ka_wgs) ? (ng + g_ka_wgs - 1) / g_ka_wgs : 1;
+  const int nwg = (ng + G - 1) / G;
+  return nwg > 0 ? nwg : 1;
+}
+
+// ka_kernel's first batches of loads are unconditional (clamped), so their sizes are template parameters matched to the
+// step: partial sums of a row (nt + 1 slots: RPB = 1 / 2 / 3 / 5 / 10 batches of KA_SL = 16), folded rows of tile scalars
+// (nt <= 15 / 31 / 63: SPB = 2 / 4 / 8 per wave), panel columns (k <= 32 / 64 / more: KB = 2 / 4 / 8 per slice)
+template <int NB>
+void launch_ka(hipStream_t st, int nwg, const RedArgs& R, const KAArgs& K) {
+  const bool fit = g_ka_fit != 0;
+  const int nslot = fit ? K.nt_prev + 1 : 1 << 30, ntp = fit ? K.nt_prev : 1 << 30;
+  const int kk = fit ? (K.has_prev ? K.kprev : K.k) : 1 << 30;
+  auto go = [&](auto rpb, auto spb) {
+    auto go_kb = [&](auto kb) {   // (LG: several row groups per workgroup)
+      constexpr int RPB = decltype(rpb)::value, SPB = decltype(spb)::value, KB = decltype(kb)::value;
+      if (K.G > 1) hipLaunchKernelGGL((ka_kernel<NB, false, true, RPB, SPB, KB>), dim3(nwg), dim3(256), 0, st, R, K);
+      else hipLaunchKernelGGL((ka_kernel<NB, false, false, RPB, SPB, KB>), dim3(nwg), dim3(256), 0, st, R, K);
+    };
+    if (kk <= 2 * KA_SL) go_kb(IC<2>{}); else if (kk <= 4 * KA_SL) go_kb(IC<4>{}); else go_kb(IC<8>{});
+  };
+  if (nslot <= 1 * KA_SL && ntp <= 15) go(IC<1>{}, IC<2>{});
+  else if (nslot <= 2 * KA_SL && ntp <= 31) go(IC<2>{}, IC<4>{});
+  else if (nslot <= 3 * KA_SL) go(IC<3>{}, IC<8>{});
+  else if (nslot <= 5 * KA_SL) go(IC<5>{}, IC<8>{});
+  else go(IC<10>{}, IC<8>{});
+}
+
+// the mat-vec's instantiation (one GPU and the step launch alike): tile edge T = 128 / 256 / 512 (RB = 1 / 2 / 4),
+// non-temporal loads (256 and 512 only), branch-free form; go(IC<RB>, bool_constant<NTL>, bool_constant<UNC>) launches it
+template <class Go>
+void symv_variant(int T, bool nt_loads, bool unc, Go&& go) {
+  auto u = [&](auto rb, auto ntl) { if (unc) go(rb, ntl, std::true_type{}); else go(rb, ntl, std::false_type{}); };
+  if (T == 128) u(IC<1>{}, std::false_type{});
+  else if (T == 256 && !nt_loads) u(IC<2>{}, std::false_type{});
+  else if (T == 256) u(IC<2>{}, std::true_type{});
+  else if (!nt_loads) u(IC<4>{}, std::false_type{});
+  else u(IC<4>{}, std::true_type{});
+}
+template <int NB>
+void launch_symv(hipStream_t st, int gx, const RedArgs& R, const KBArgs& B, int T, bool nt_loads, bool unc) {
+  symv_variant(T, nt_loads, unc, [&](auto rb, auto ntl, auto un) {
+    hipLaunchKernelGGL((symv_kernel<NB, decltype(rb)::value, decltype(ntl)::value, false, decltype(un)::value>), dim3(gx), dim3(256), 0, st, R, B);
+  });
+}
+
+// One GPU, per step: K_A (finish the previous step's W, form the next columns), then the fused mat-vec with the panel
+// dots; per panel: the panel-closing K_A and the trailing update A(0:nr, 0:nr) -= [U W][W U]^T on upper-triangle tiles.
+template <int NB>
+void reduce_one_gpu(Context& ctx, const RedArgs& R, RedCounters& C) {
+  const hipStream_t st = ctx.stream;
+  const int m = R.m, ldp = R.ldp;
+  const double t_begin = wall_seconds();
+  KAArgs S = ka_first_args();
+  int k = 0, i = R.n - 1;   // panel fill, top column of the current block
+  while (true) {
+    const int L = ka_step_args<NB>(S, i, k);
+    const int nb_ka = ka_grid_one_gpu(S.rows, S.G);
+    if (S.rows > 0 && (S.has_prev || S.ncols > 0)) launch_ka<NB>(st, nb_ka, R, S);
+    if (L < 1) break;
+    KBArgs B = kb_step_args(i, L, k);
+    const SymvGeom g = symv_geom(L);
+    B.npd = (B.toprows + B.pdr - 1) / B.pdr; B.ngp = nb_ka; B.nt = g.nt; B.ng = g.T / 32;
+    const int gx = g.nt * (g.nt + 1) / 2 + B.npd * (B.ncg + 1);   // tiles of the upper block triangle + K_P workgroups
+    const bool prof = C.sampled(ctx);
+    if (prof) ctx.prof_begin(0, 8.0 * ((double)L * (L + 1) / 2), st);
+    launch_symv<NB>(st, gx, R, B, g.T, L > g_symv_nt, L <= g_symv_unc);
+    if (prof) ctx.prof_end(st);
+    step_done<NB>(S, C, i, k, L, g.nt, g.T, B.npd, B.npd);
+    if (panel_full<NB>(k, m, i)) {
+      KAArgs F = ka_close_args(S, i, k);
+      const int nb_kf = ka_grid_one_gpu(F.rows, F.G);
+      launch_ka<NB>(st, nb_kf, R, F);
+      const int nr = i + 1;
+      if (ctx.prof_stride > 0) ctx.prof_begin(1, 2.0 * (double)nr * nr * m, st);
+      dgemm_dev(st, 'N', 'T', nr, nr, 2 * m, -1.0, R.UW, ldp, R.UW + (size_t)ldp * m, ldp, 1.0, R.A, R.lda, 1);
+      if (ctx.prof_stride > 0) ctx.prof_end(st);
+      panel_restart(R, C, S, k, nr, st);
+    }
+  }
+  trace_enqueue(t_begin, st);
+}
+
+// ---- several ranks --------------------------------------------------------------------------------------------------
+// the step launch: mg_step_kernel with the mat-vec role's instantiation (symv_T = 0: no mat-vec in this launch)
+template <int NB>
+void launch_mg_step(hipStream_t st, int gx, const RedArgs& R, const KLArgs& KL, const KAArgs& S, const KBArgs& B,
+                    const MGStep& M, int symv_T, bool nt_loads, bool unc) {
+  if (symv_T == 0) hipLaunchKernelGGL((mg_step_kernel<NB, 1, false, true>), dim3(gx), dim3(256), 0, st, R, KL, S, B, M);
+  else symv_variant(symv_T, nt_loads, unc, [&](auto rb, auto ntl, auto un) {
+    hipLaunchKernelGGL((mg_step_kernel<NB, decltype(rb)::value, decltype(ntl)::value, decltype(un)::value>), dim3(gx), dim3(256), 0, st,
+                       R, KL, S, B, M);
+  });
+}
+
+// The mat-vec of a step on several ranks.  K_P: the panel dots over the rank's own rows below L in <= 8 chunks (>= 512
+// rows each; kl adds them up and sends the share), the reflector store over all rows in <= 4 P chunks (the local tile
+// stream is 1 / P of one GPU's: a long K_P chunk would outlast it).  Tiles of the local block below L (Lr x Lc), edge from
+// the size of the local trapezoid: returned, ntiles = their number.
+inline int mg_step_geom(KBArgs& B, const Grid& G, int L, int& ntiles) {
+  const int gfull = L / KA_ROWS, rem = L % KA_ROWS;   // rows below L that this rank owns (first in its owned index order)
+  B.nown_L = local_count(gfull, G.nranks, G.rank) * KA_ROWS + ((rem > 0 && gfull % G.nranks == G.rank) ? rem : 0);
+  B.pdr = std::max(512, ((B.nown_L + 7) / 8 + 63) / 64 * 64);
+  B.npd = (B.nown_L + B.pdr - 1) / B.pdr;
+  B.pdr_s = std::max(512, ((B.toprows + 4 * G.nranks - 1) / (4 * G.nranks) + 63) / 64 * 64);
+  B.npd_s = (B.toprows + B.pdr_s - 1) / B.pdr_s;
+  B.ngp = G.nranks;
+  B.Lr = local_count(L, G.Px, G.px); B.Lc = local_count(L, G.Py, G.py);
+  const double leq = sqrt((double)(B.Lr > 1 ? B.Lr : 1) * (double)(B.Lc > 1 ? B.Lc : 1));
+  const int T = (leq <= g_symv_t128) ? 128 : (leq <= g_symv_t256 ? 256 : 512);
+  B.ntc = B.nt = ceil_div(B.Lc, T); B.ng = T / 32;
+  ntiles = B.nty_last = B.ntc > 0 ? mg_nty(B.ntc - 1, T, B.Lc, G.Px, G.px, G.Py, G.py) : 0;
+  for (int tx = 0; tx + 1 < B.ntc; ++tx) ntiles += mg_nty(tx, T, B.Lc, G.Px, G.px, G.Py, G.py);
+  if (G.Py % G.Px == 0) { B.slope = G.Py / G.Px; B.c1 = (int)(((long)(T - 1) * G.Py + G.py - G.px) / ((long)G.Px * T)) + 1; }
+  return T;
+}
+
+// Several ranks, per step: [kl of the previous step | K_A | mat-vec] as one mg_step_kernel launch whose consumers spin on
+// the peers' flags (fuse_wait), or the roles one by one with a wait kernel or an allgather (step_coll) between them.
+// Per panel: the panel-closing K_A, its W columns, the local trailing update, the next panel's gather on the side stream.
+template <int NB>
+void reduce_multi_rank(Context& ctx, RedArgs& R, RedCounters& C) {
+  const hipStream_t st = ctx.stream;
+  const Grid& G = ctx.grid;
+  const int n = R.n, m = R.m, ldp = R.ldp;
   StepPeers peers, xpeers;
-  unsigned long long epoch = 0;          // epoch of the Y message that the NEXT K_A consumes
-  unsigned long long xepoch = 0;         // epoch of the X message that the last K_A launch wrote
-  PeerBuf* panr = nullptr;               // receive window of the panel gather: [rank][mloc_max][nxs]
-  double *pan = nullptr, *pan_send = nullptr, *UWr = nullptr, *UWc = nullptr;
-  // a gathered panel holds the m columns of the next panel and, when fewer than NB + 1 columns would remain below it,
-  // those too (they are finished without another trailing update)
-  auto panel_lo = [&](int itop) { const int clo = itop - m + 1; return clo <= NB ? 0 : clo; };
+  R.MSG = comm_step_window(ctx, 0, (size_t)R.msg_stride, &peers); R.ysrc_stride = (int)peers.src_stride;
+  R.XW = comm_step_window(ctx, 1, (size_t)R.xmsg_stride, &xpeers);
+  unsigned long long epoch = comm_step_epoch_base(ctx, 0, (unsigned long long)(n / NB + 2));            // Y message the NEXT K_A consumes
+  unsigned long long xepoch = comm_step_epoch_base(ctx, 1, (unsigned long long)(n / NB + n / m + 8));   // X message the last K_A wrote
   const int mloc_max = ceil_div(m + NB, G.Py) + 1;
   const size_t pan_count = (size_t)mloc_max * R.nxs;
   const int ldr = pad_ld(R.nxs + 2), ldc = pad_ld(R.nys + 2);
-  if (mg) {
-    R.MSG = comm_step_window(ctx, 0, (size_t)R.msg_stride, &peers);
-    R.ysrc_stride = (int)peers.src_stride;
-    R.XW = comm_step_window(ctx, 1, (size_t)R.xmsg_stride, &xpeers);
-    epoch = comm_step_epoch_base(ctx, 0, (unsigned long long)(n / NB + 2));
-    xepoch = comm_step_epoch_base(ctx, 1, (unsigned long long)(n / NB + n / m + 8));
-    panr = comm_buffer(ctx, "red.panr", (size_t)G.nranks * pan_count * sizeof(double));
-    pan = ctx.pool.get_t<double>("red.pan", (size_t)ldp * (m + NB));
-    pan_send = ctx.pool.get_t<double>("red.pansend", pan_count);
-    UWr = ctx.pool.get_t<double>("red.UWr", (size_t)ldr * 2 * m);
-    UWc = ctx.pool.get_t<double>("red.UWc", (size_t)ldc * 2 * m);
-    R.PAN = pan;
-    EIGX_HIP_CHECK(hipMemsetAsync(pan_send, 0, pan_count * sizeof(double), st));
-  }
+  PeerBuf* panr = comm_buffer(ctx, "red.panr", (size_t)G.nranks * pan_count * sizeof(double));   // [rank][mloc_max][nxs]
+  double* pan = ctx.pool.get_t<double>("red.pan", (size_t)ldp * (m + NB));
+  double* pan_send = ctx.pool.get_t<double>("red.pansend", pan_count);
+  double* UWr = ctx.pool.get_t<double>("red.UWr", (size_t)ldr * 2 * m);
+  double* UWc = ctx.pool.get_t<double>("red.UWc", (size_t)ldc * 2 * m);
+  R.PAN = pan;
+  EIGX_HIP_CHECK(hipMemsetAsync(pan_send, 0, pan_count * sizeof(double), st));
+  // a gathered panel holds the m columns of the next panel and, when fewer than NB + 1 columns would remain below it,
+  // those too (they are finished without another trailing update)
+  auto panel_lo = [&](int itop) { const int clo = itop - m + 1; return clo <= NB ? 0 : clo; };
   // gather the panel columns [clo, chi], rows < chi + 1, from their owners into `pan` (enqueued on stream s)
   auto gather_panel = [&](int clo, int chi, hipStream_t s, CommChannel ch) {
     const int toprows = chi + 1;
     const int nxc = (ceil_div(toprows, G.Px) + 7) / 8 * 8;       // row stride of this gather (same on every rank)
     const size_t cnt = (size_t)mloc_max * nxc;
-    const int lj0 = (clo - G.py + G.Py - 1) / G.Py;
-    const int lj1 = chi >= G.py ? (chi - G.py) / G.Py : -1;
+    const int lj0 = (clo - G.py + G.Py - 1) / G.Py, lj1 = chi >= G.py ? (chi - G.py) / G.Py : -1;
     const int mloc = lj1 - lj0 + 1;
     const int nrl = local_count(toprows, G.Px, G.px);
     if (mloc > 0 && nrl > 0)
       hipLaunchKernelGGL(pack_panel_kernel, dim3(ceil_div(nrl, 256) < 64 ? ceil_div(nrl, 256) : 64, mloc), dim3(256), 0, s,
-                         (const double*)A, lda, lj0, mloc, nrl, nxc, pan_send);
+                         (const double*)R.A, R.lda, lj0, mloc, nrl, nxc, pan_send);
     comm_exchange(ctx, COMM_WORLD, pan_send, 0, panr, 0, cnt, s, ch);
     hipLaunchKernelGGL(unpack_panel_kernel, dim3(ceil_div(toprows, 256) < 64 ? ceil_div(toprows, 256) : 64, chi - clo + 1),
                        dim3(256), 0, s, (const double*)panr->local, cnt, nxc, clo, chi, toprows, G.Px, G.Py,
                        G.row_major, pan, ldp);
   };
-  hipLaunchKernelGGL(fill_kernel, dim3(1024), dim3(256), 0, st, R.UW, (size_t)ldp * m * 3, 0.0);
-  hipLaunchKernelGGL(fill_kernel, dim3(8), dim3(256), 0, st, e, (size_t)lde * NB, 0.0);
-  hipLaunchKernelGGL(fill_kernel, dim3(1), dim3(64), 0, st, R.sc, (size_t)SC_COUNT + 8, 0.0);
-  hipLaunchKernelGGL(fill_kernel, dim3(16), dim3(256), 0, st, R.SP, sp_count, 0.0);
-
-  const double t_begin = std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count();
-  KAArgs S;
-  // ka_kernel's first batches of loads are unconditional (clamped), so their sizes are template parameters matched to
-  // the step: partial sums of a row (nt + 1 slots: 1 / 2 / 3 / 5 / 10 batches of KA_SL = 16), folded rows of tile
-  // scalars (nt <= 15 / 31 / 63: 2 / 4 / 8 per wave), panel columns (k <= 32 / 64 / more: 2 / 4 / 8 per slice)
-  auto launch_ka = [&](int nwg, const KAArgs& K) {   // (one GPU)
-    const bool fit = g_ka_fit != 0;
-    const int nslot = fit ? K.nt_prev + 1 : 1 << 30, ntp = fit ? K.nt_prev : 1 << 30;
-    const int kk = fit ? (K.has_prev ? K.kprev : K.k) : 1 << 30;
-#define EIGX_KA3(RPBV, SPBV, KBV)                                                                                        \
-    do {                                                                                                                \
-      if (K.G > 1) hipLaunchKernelGGL((ka_kernel<NB, false, true, RPBV, SPBV, KBV>), dim3(nwg), dim3(256), 0, st, R, K); \
-      else hipLaunchKernelGGL((ka_kernel<NB, false, false, RPBV, SPBV, KBV>), dim3(nwg), dim3(256), 0, st, R, K);        \
-    } while (0)
-#define EIGX_KA2(RPBV, SPBV)                                                                                             \
-    do {                                                                                                                \
-      if (kk <= 2 * KA_SL) EIGX_KA3(RPBV, SPBV, 2);                                                                      \
-      else if (kk <= 4 * KA_SL) EIGX_KA3(RPBV, SPBV, 4);                                                                 \
-      else EIGX_KA3(RPBV, SPBV, 8);                                                                                      \
-    } while (0)
-    if (nslot <= 1 * KA_SL && ntp <= 15) EIGX_KA2(1, 2);
-    else if (nslot <= 2 * KA_SL && ntp <= 31) EIGX_KA2(2, 4);
-    else if (nslot <= 3 * KA_SL) EIGX_KA2(3, 8);
-    else if (nslot <= 5 * KA_SL) EIGX_KA2(5, 8);
-    else EIGX_KA2(10, 8);
-#undef EIGX_KA2
-#undef EIGX_KA3
-  };
-  S.has_prev = 0; S.iprev = 0; S.Lprev = 0; S.kprev = 0; S.nchunk_prev = 0; S.nt_prev = 0; S.lgT_prev = 7;
-  S.par = 0; S.pan_c0 = 0; S.G = 1;
-  S.wait.n = 0; S.wait.flag = nullptr; S.wait.err = nullptr; S.wait.ticks = nullptr; S.wait.limit_ticks = 0; S.wait.epoch = 0; S.wait.naps = 1;
-  S.nchunk_ab = 0; S.xpar = 0; S.xepoch = 0;
-  const StepWait no_wait = S.wait;
-  const bool fuse_wait = mg && comm_step_wait_fused(ctx);
-  const bool step_coll = mg && comm_step_collective(ctx);   // per-step exchanges as allgathers (RCCL / emulated)
+  const double t_begin = wall_seconds();
+  KAArgs S = ka_first_args();   // (S.G stays 1: one row group per K_A workgroup)
+  const StepWait none = no_wait();
+  const bool fuse_wait = comm_step_wait_fused(ctx);
+  const bool step_coll = comm_step_collective(ctx);   // per-step exchanges as allgathers (RCCL / emulated)
   const int step_fence = (getenv("EIGX_STEP_FENCE") && atoi(getenv("EIGX_STEP_FENCE")) != 0) ? 1 : 0;
-  // K_A's grid.  Several GPUs: K_A runs over this rank's row groups only, one group per workgroup
-  auto ka_grid = [&](int rows, int& Gout) {
-    const int ng = (rows + KA_ROWS - 1) / KA_ROWS;
-    if (mg) { Gout = 1; const int own = local_count(ng, G.nranks, G.rank); return own > 0 ? own : 1; }
-    Gout = (ng > 2 * g_ka_wgs) ? (ng + g_ka_wgs - 1) / g_ka_wgs : 1;
-    const int nwg = (ng + Gout - 1) / Gout;
-    return nwg > 0 ? nwg : 1;
-  };
-  // rows below L that this rank owns (they come first in its owned index order)
-  auto own_count = [&](int L) {
-    const int gfull = L / KA_ROWS, rem = L % KA_ROWS;
-    return local_count(gfull, G.nranks, G.rank) * KA_ROWS + ((rem > 0 && gfull % G.nranks == G.rank) ? rem : 0);
-  };
-  // ---- several GPUs: the step launch (mg_step_kernel) with whatever roles are due --------------------------------
-  // fuse_wait (every rank on its own GPU): one launch per step, [kl of the previous step | K_A | mat-vec], the consumers
-  // spin on the flags in their prologues.  Otherwise (ranks sharing a card: wait kernels; collective exchanges) the roles
-  // are launched one by one with the wait kernel / allgather between them.
   // polls of a spinning consumer: naps of ~60 ns between two looks at the flags (lab knob EIGX_SPIN_NAPS="ka,x"; with
   // relaxed polls 1 .. 64 naps all give the same time within 2 %)
   int naps_ka = 1, naps_x = 2;
   if (const char* e = getenv("EIGX_SPIN_NAPS")) { if (sscanf(e, "%d,%d", &naps_ka, &naps_x) < 2) naps_x = naps_ka; }
-  MGStep MS;
-  memset(&MS, 0, sizeof(MS));
-  MS.xpeers = xpeers;
-  KLArgs KLnone;
-  memset(&KLnone, 0, sizeof(KLnone));
-  KBArgs Bnone;
-  memset(&Bnone, 0, sizeof(Bnone));
-  Bnone.xwait = no_wait;
-  // symv_T: tile edge of the mat-vec role (0: no mat-vec in this launch)
+  MGStep MS{}; MS.xpeers = xpeers;
+  KBArgs Bnone{}; Bnone.xwait = none;
+  const KLArgs KLnone{};
+  // the step launch with whatever roles are due; symv_T: tile edge of the mat-vec role (0: no mat-vec in this launch)
   auto launch_roles = [&](int nkl, const KLArgs& KLa, int nka, const KAArgs& Ka, int nsymv, const KBArgs& Ba, int symv_T, bool nt_loads, bool unc) {
-    MGStep M = MS;
-    M.nkl = nkl; M.nka = nka;
-    const int gx = nkl + nka + nsymv;
-    if (gx <= 0) return;
-#define EIGX_STEP(RBv, NTv)                                                                                             \
-  do {                                                                                                                  \
-    if (unc) hipLaunchKernelGGL((mg_step_kernel<NB, RBv, NTv, true>), dim3(gx), dim3(256), 0, st, R, KLa, Ka, Ba, M);    \
-    else hipLaunchKernelGGL((mg_step_kernel<NB, RBv, NTv, false>), dim3(gx), dim3(256), 0, st, R, KLa, Ka, Ba, M);       \
-  } while (0)
-    if (symv_T == 0) hipLaunchKernelGGL((mg_step_kernel<NB, 1, false, true>), dim3(gx), dim3(256), 0, st, R, KLa, Ka, Ba, M);
-    else if (symv_T == 128) EIGX_STEP(1, false);
-    else if (symv_T == 256 && !nt_loads) EIGX_STEP(2, false);
-    else if (symv_T == 256) EIGX_STEP(2, true);
-    else if (!nt_loads) EIGX_STEP(4, false);
-    else EIGX_STEP(4, true);
-#undef EIGX_STEP
+    MGStep M = MS; M.nkl = nkl; M.nka = nka;
+    if (nkl + nka + nsymv > 0) launch_mg_step<NB>(st, nkl + nka + nsymv, R, KLa, Ka, Ba, M, symv_T, nt_loads, unc);
   };
-  int wk_last = -1;                       // W columns that the last K_A launch finished (-1: none), for the next mat-vec's copy
-  int last_ka_i = -1, last_ka_ncols = 0;
-  bool kl_pending = false;                // fuse_wait: the last mat-vec's kl role rides in the next launch
-  KLArgs KLp = KLnone;
+  int wk_last = -1, last_ka_i = -1, last_ka_ncols = 0;   // W columns the last K_A finished (-1: none, for the mat-vec's copy), its block
+  KLArgs KLp = KLnone;                    // fuse_wait: the last mat-vec's kl role (nkl_p > 0 workgroups) rides in the next launch
   int nkl_p = 0;
+  bool prof_step = false;                 // the previous step's mat-vec was sampled -> sample its wait and K_A as well
+  auto ka_grid = [&](int rows) { const int own = local_count(ceil_div(rows, KA_ROWS), G.nranks, G.rank); return own > 0 ? own : 1; };
+  auto wait_kernel = [&](int which, unsigned long long ep, int prof_kind) {   // (prof_kind >= 0: sampled)
+    if (prof_kind >= 0) ctx.prof_begin(prof_kind, 0.0, st);
+    comm_step_wait(ctx, which, ep, st);
+    if (prof_kind >= 0) ctx.prof_end(st);
+  };
   // a K_A launch writes X message ++xepoch
-  auto ka_mg_begin = [&](KAArgs& K) {
+  auto ka_begin = [&](KAArgs& K) {
     ++xepoch;
     K.xpar = (int)(xepoch & 1); K.xepoch = xepoch;
-    wk_last = K.has_prev ? K.kprev : -1;
-    last_ka_i = K.i; last_ka_ncols = K.ncols;
-    K.wait = (fuse_wait && K.has_prev) ? comm_step_wait_args(ctx, 0, epoch) : no_wait;
+    wk_last = K.has_prev ? K.kprev : -1; last_ka_i = K.i; last_ka_ncols = K.ncols;
+    K.wait = (fuse_wait && K.has_prev) ? comm_step_wait_args(ctx, 0, epoch) : none;
     K.wait.naps = naps_ka;
   };
-  // roles one by one (no fused waits): [kl] was launched behind its mat-vec; here: wait / allgather Y, then [K_A]
-  auto ka_mg_alone = [&](int nwg, const KAArgs& K, bool prof_it) {
-    if (K.has_prev && !step_coll) {
-      if (prof_it) ctx.prof_begin(3, 0.0, st);
-      comm_step_wait(ctx, 0, epoch, st);
-      if (prof_it) ctx.prof_end(st);
-    }
+  // K_A in a launch without a mat-vec: with the pending kl role (fuse_wait), or alone behind the wait / allgather of Y
+  auto ka_launch = [&](int nwg, const KAArgs& K, bool prof_it) {
+    if (fuse_wait) { launch_roles(nkl_p, KLp, nwg, K, 0, Bnone, 0, false, true); nkl_p = 0; return; }
+    if (K.has_prev && !step_coll) wait_kernel(0, epoch, prof_it ? 3 : -1);
     if (prof_it) ctx.prof_begin(4, 0.0, st);
     launch_roles(0, KLnone, nwg, K, 0, Bnone, 0, false, true);
     if (step_coll) comm_step_allgather(ctx, 1, xpeers.slot[0], K.xpar, st);
@@ -2147,279 +2304,115 @@ void band_reduce_impl(Context& ctx, int n, double* A, int lda, double* d, double
   // consumer side of the X message outside the step launch: a StepWait for the kernel's prologue, or a wait kernel in
   // front of it (then n = 0)
   auto x_wait = [&](int prof_kind) -> StepWait {
-    if (!mg || step_coll) return no_wait;
+    if (step_coll) return none;
     if (fuse_wait) { StepWait w = comm_step_wait_args(ctx, 1, xepoch); w.naps = naps_x; return w; }
-    if (prof_kind >= 0) ctx.prof_begin(prof_kind, 0.0, st);
-    comm_step_wait(ctx, 1, xepoch, st);
-    if (prof_kind >= 0) ctx.prof_end(st);
-    return no_wait;
+    wait_kernel(1, xepoch, prof_kind);
+    return none;
   };
-  int k = 0;        // panel fill
-  int i = n - 1;    // top column of the current block
-  if (mg) {
-    S.pan_c0 = panel_lo(n - 1);
-    gather_panel(S.pan_c0, n - 1, st, CH_BULK);
-  }
-  double t_symv_bytes = 0.0;
-  long n_symv = 0, n_k1 = 0;
-  bool prof_step = false;   // several ranks: the previous step's mat-vec was sampled -> sample its wait and K_A as well
-  double k1_flops = 0.0;
+  int k = 0, i = n - 1;   // panel fill, top column of the current block
+  S.pan_c0 = panel_lo(n - 1);
+  gather_panel(S.pan_c0, n - 1, st, CH_BULK);
   while (true) {
-    const int L = i - NB + 1;  // rows above the block
-    const bool do_step = (L >= 1);
-    // columns to form: a full block while reflectors remain, otherwise the last <= NB columns
-    const int ncols = do_step ? NB : (i >= 0 ? (i + 1 < NB ? i + 1 : NB) : 0);
-    S.ncols = ncols;
-    S.i = i;
-    S.L = do_step ? L : 0;
-    S.k = k;
-    S.rows = i + 1;
-    if (S.has_prev && S.iprev + 1 > S.rows) S.rows = S.iprev + 1;
-    // row groups per workgroup: one wave per SIMD at most (1024 SIMDs = 256 workgroups of 4 waves); the scalar work
-    // of a workgroup is done once for all its groups
-    const int nb_ka = ka_grid(S.rows, S.G);
-    const bool need_ka = S.rows > 0 && (S.has_prev || ncols > 0);
-    bool ka_held = false;      // several GPUs, fuse_wait: K_A rides in the step launch below
-    if (need_ka && !mg) {
-      launch_ka(nb_ka, S);
-    } else if (need_ka) {
-      ka_mg_begin(S);
-      if (fuse_wait) ka_held = true;
-      else ka_mg_alone(nb_ka, S, prof_step);
-    }
-    if (!do_step) {
-      if (ka_held) launch_roles(kl_pending ? nkl_p : 0, KLp, nb_ka, S, 0, Bnone, 0, false, true);
-      kl_pending = false;
-      prof_step = false;
-      break;
-    }
-    KBArgs B;
-    B.i = i; B.L = L; B.k = k;
-    B.ncg = (k + PD_COLS - 1) / PD_COLS;
-    B.toprows = i + 1;
-    B.pdr = pd_rows_for(B.toprows);
-    B.nown_L = 0; B.npd_s = 0; B.pdr_s = 0; B.wk = -1; B.xpar = 0; B.xwait = no_wait;
-    int npd = (B.toprows + B.pdr - 1) / B.pdr;
-    if (mg) {
-      // several GPUs: the panel dots over the rank's own rows below L in <= 8 chunks (>= 512 rows each; kl adds them up
-      // and sends the share), the reflector store over all rows in <= 4 P chunks (the local tile stream is 1 / P of
-      // one GPU's: a long K_P chunk would outlast it)
-      B.nown_L = own_count(L);
-      int r_ = ((B.nown_L + 7) / 8 + 63) / 64 * 64;
-      B.pdr = r_ < 512 ? 512 : r_;
-      npd = (B.nown_L + B.pdr - 1) / B.pdr;
-      r_ = ((B.toprows + 4 * G.nranks - 1) / (4 * G.nranks) + 63) / 64 * 64;
-      B.pdr_s = r_ < 512 ? 512 : r_;
-      B.npd_s = (B.toprows + B.pdr_s - 1) / B.pdr_s;
-      B.wk = wk_last;
-      B.xpar = (int)(xepoch & 1);
-      B.xwait = x_wait(prof_step ? 5 : -1);
-    }
-    prof_step = false;
-    B.npd = npd;
-    B.ngp = mg ? G.nranks : nb_ka;
-    B.Lr = L; B.Lc = L; B.ntc = 0; B.nty_last = 0; B.slope = 0; B.c1 = 0;
-    int T, ntiles;
-    if (!mg) {
-      const SymvGeom g = symv_geom(L);
-      T = g.T;
-      B.nt = g.nt;
-      ntiles = g.nt * (g.nt + 1) / 2;                        // tiles of the upper block triangle
-    } else {
-      // local block below L: Lr x Lc; tile edge from the size of the local trapezoid
-      B.Lr = local_count(L, G.Px, G.px);
-      B.Lc = local_count(L, G.Py, G.py);
-      const double leq = sqrt((double)(B.Lr > 1 ? B.Lr : 1) * (double)(B.Lc > 1 ? B.Lc : 1));
-      T = (leq <= g_symv_t128) ? 128 : (leq <= g_symv_t256 ? 256 : 512);
-      B.ntc = ceil_div(B.Lc, T);
-      B.nt = B.ntc;
-      B.nty_last = B.ntc > 0 ? mg_nty(B.ntc - 1, T, B.Lc, G.Px, G.px, G.Py, G.py) : 0;
-      ntiles = B.nty_last;
-      for (int tx = 0; tx + 1 < B.ntc; ++tx) ntiles += mg_nty(tx, T, B.Lc, G.Px, G.px, G.Py, G.py);
-      if (G.Py % G.Px == 0) {
-        B.slope = G.Py / G.Px;
-        B.c1 = (int)(((long)(T - 1) * G.Py + G.py - G.px) / ((long)G.Px * T)) + 1;
-      }
-    }
-    B.ng = T / 32;
-    const int gx = ntiles + (mg ? npd * B.ncg + B.npd_s : npd * (B.ncg + 1));   // + K_P workgroups
-    const bool prof = ctx.prof_stride > 0 && (n_symv % ctx.prof_stride) == 0;
+    const int L = ka_step_args<NB>(S, i, k);
+    const int nb_ka = ka_grid(S.rows);
+    const bool need_ka = S.rows > 0 && (S.has_prev || S.ncols > 0);
+    const bool ka_held = need_ka && fuse_wait;   // K_A rides in the step launch below
+    if (need_ka) ka_begin(S);
+    if (need_ka && !fuse_wait) ka_launch(nb_ka, S, prof_step);
+    if (L < 1) { if (ka_held) ka_launch(nb_ka, S, false); break; }   // the last <= NB columns: no mat-vec
+    KBArgs B = kb_step_args(i, L, k);
+    int ntiles;
+    const int T = mg_step_geom(B, G, L, ntiles);
+    B.wk = wk_last; B.xpar = (int)(xepoch & 1);
+    B.xwait = x_wait(prof_step ? 5 : -1); prof_step = false;
+    const int gx = ntiles + B.npd * B.ncg + B.npd_s;   // + K_P workgroups
+    const bool prof = C.sampled(ctx);
     if (prof) ctx.prof_begin(0, 8.0 * ((double)L * (L + 1) / 2) / R.P, st);  // this rank's share of the triangle
-    const bool nt_loads = (mg ? sqrt((double)B.Lr * B.Lc) : (double)L) > g_symv_nt;
-    const bool unc = (mg ? sqrt((double)B.Lr * B.Lc) : (double)L) <= g_symv_unc;   // latency-bound sizes: the true two-unit pipeline
-    if (!mg) {
-#define EIGX_SYMV(RBv, NTv)                                                                                         \
-  do {                                                                                                              \
-    if (unc) hipLaunchKernelGGL((symv_kernel<NB, RBv, NTv, false, true>), dim3(gx), dim3(256), 0, st, R, B);        \
-    else hipLaunchKernelGGL((symv_kernel<NB, RBv, NTv, false, false>), dim3(gx), dim3(256), 0, st, R, B);           \
-  } while (0)
-      if (T == 128) EIGX_SYMV(1, false);
-      else if (T == 256 && !nt_loads) EIGX_SYMV(2, false);
-      else if (T == 256) EIGX_SYMV(2, true);
-      else if (!nt_loads) EIGX_SYMV(4, false);
-      else EIGX_SYMV(4, true);
-#undef EIGX_SYMV
+    const double leq = sqrt((double)B.Lr * B.Lc);
+    // the step launch: [kl of the previous step | K_A | this mat-vec] (fuse_wait), or the mat-vec alone
+    if (ka_held) launch_roles(nkl_p, KLp, nb_ka, S, gx, B, T, leq > g_symv_nt, leq <= g_symv_unc);
+    else launch_roles(0, KLnone, 0, S, gx, B, T, leq > g_symv_nt, leq <= g_symv_unc);
+    nkl_p = 0;
+    if (prof) ctx.prof_end(st);
+    // the Y exchange behind the mat-vec: kl reduces this rank's tile partial sums, writes them into the owners' windows
+    // and publishes the flag -- in the next launch (fuse_wait) or right away
+    KLArgs KL{};
+    ++epoch;
+    KL.L = L; KL.Lr = B.Lr; KL.Lc = B.Lc; KL.T = T; KL.ntc = B.ntc;
+    KL.nbr = ceil_div(B.Lr > 0 ? B.Lr : 1, KL_ROWS);
+    KL.par = (int)(epoch & 1); KL.epoch = epoch; KL.peers = peers;
+    KL.kd2 = R.KD; KL.npd2 = B.npd; KL.kfill = k; KL.fence = step_fence;
+    for (int tx = 0; tx < B.ntc; ++tx) { const int c_ = mg_nty(tx, T, B.Lc, G.Px, G.px, G.Py, G.py); if (c_ > KL.ntr) KL.ntr = c_; }
+    const int nkl = KL.nbr + ceil_div(B.Lc > 0 ? B.Lc : 1, KL_ROWS) + 2 * NB + 1;   // + the scalar workgroup
+    if (fuse_wait) { KLp = KL; nkl_p = nkl; }
+    else {
+      if (prof) ctx.prof_begin(2, 8.0 * R.msg_stride, st);
+      launch_roles(nkl, KL, 0, S, 0, Bnone, 0, false, true);
+      if (step_coll) comm_step_allgather(ctx, 0, peers.slot[0], KL.par, st);
       if (prof) ctx.prof_end(st);
-    } else {
-      // the step launch: [kl of the previous step | K_A | this mat-vec] (fuse_wait), or the mat-vec alone
-      if (ka_held) launch_roles(kl_pending ? nkl_p : 0, KLp, nb_ka, S, gx, B, T, nt_loads, unc);
-      else launch_roles(0, KLnone, 0, S, gx, B, T, nt_loads, unc);
-      kl_pending = false;
-      if (prof) ctx.prof_end(st);
-      // the Y exchange behind the mat-vec: kl reduces this rank's tile partial sums, writes them into the owners' windows
-      // and publishes the flag -- in the next launch (fuse_wait) or right away
-      KLArgs KL;
-      memset(&KL, 0, sizeof(KL));
-      ++epoch;
-      KL.L = L; KL.Lr = B.Lr; KL.Lc = B.Lc; KL.T = T; KL.ntc = B.ntc;
-      KL.nbr = ceil_div(B.Lr > 0 ? B.Lr : 1, KL_ROWS);
-      KL.par = (int)(epoch & 1);
-      KL.epoch = epoch;
-      KL.peers = peers;
-      KL.kd2 = R.KD; KL.npd2 = npd; KL.kfill = k;
-      KL.fence = step_fence;
-      KL.ntr = 0;
-      for (int tx = 0; tx < B.ntc; ++tx) { const int c_ = mg_nty(tx, T, B.Lc, G.Px, G.px, G.Py, G.py); if (c_ > KL.ntr) KL.ntr = c_; }
-      const int nkl = KL.nbr + ceil_div(B.Lc > 0 ? B.Lc : 1, KL_ROWS) + 2 * NB + 1;   // + the scalar workgroup
-      if (fuse_wait) { kl_pending = true; KLp = KL; nkl_p = nkl; }
-      else {
-        if (prof) ctx.prof_begin(2, 8.0 * R.msg_stride, st);
-        launch_roles(nkl, KL, 0, S, 0, Bnone, 0, false, true);
-        if (step_coll) comm_step_allgather(ctx, 0, peers.slot[0], KL.par, st);
-        if (prof) ctx.prof_end(st);
-      }
-      prof_step = prof && !fuse_wait;
-      S.par = KL.par;
     }
-    t_symv_bytes += 8.0 * ((double)L * (L + 1) / 2);
-    ++n_symv;
-    // bookkeeping for the next K_A
-    S.has_prev = 1; S.iprev = i; S.Lprev = L; S.kprev = k;
-    S.nchunk_prev = mg ? G.nranks : npd;   // shares of the panel dots that the next K_A adds: one per rank / one per K_P row chunk
-    S.nchunk_ab = mg ? B.npd_s : npd;
-    S.nt_prev = B.nt; S.lgT_prev = (T == 128) ? 7 : (T == 256 ? 8 : 9);
-    k += NB;
-    i -= NB;
-    if (k >= m && i - NB + 1 >= 1) {
-      // panel full and more reflectors to come: finish W, trailing update, start a new panel
-      KAArgs F = S;
+    prof_step = prof && !fuse_wait;
+    S.par = KL.par;
+    step_done<NB>(S, C, i, k, L, B.nt, T, G.nranks, B.npd_s);
+    if (panel_full<NB>(k, m, i)) {
+      KAArgs F = ka_close_args(S, i, k);
       prof_step = false;   // (the panel-closing K_A is not part of the sampled step breakdown)
-      F.ncols = 0; F.i = i; F.L = 0; F.k = k; F.rows = S.iprev + 1;
-      const int nb_kf = ka_grid(F.rows, F.G);
-      F.wait.n = 0;
-      if (!mg) launch_ka(nb_kf, F);
-      else {
-        ka_mg_begin(F);
-        if (fuse_wait) launch_roles(kl_pending ? nkl_p : 0, KLp, nb_kf, F, 0, Bnone, 0, false, true);
-        else ka_mg_alone(nb_kf, F, false);
-        kl_pending = false;
-        // the last W columns of the panel, finished by their owners just now, into the local panel (all rows)
-        const StepWait xw = x_wait(-1);
-        hipLaunchKernelGGL((mg_wcopy_kernel<NB>), dim3(ceil_div(F.rows, 256) < 64 ? ceil_div(F.rows, 256) : 64), dim3(256), 0, st, R,
-                           F.xpar, F.kprev, F.rows, xw);
-        wk_last = -1;
-      }
+      ka_begin(F);
+      ka_launch(ka_grid(F.rows), F, false);
+      // the last W columns of the panel, finished by their owners just now, into the local panel (all rows)
+      const StepWait xw = x_wait(-1);
+      hipLaunchKernelGGL((mg_wcopy_kernel<NB>), dim3(ceil_div(F.rows, 256) < 64 ? ceil_div(F.rows, 256) : 64), dim3(256), 0, st, R,
+                         F.xpar, F.kprev, F.rows, xw);
+      wk_last = -1;
       const int nr = i + 1;
       if (ctx.prof_stride > 0) ctx.prof_begin(1, 2.0 * (double)nr * nr * m / R.P, st);
-      if (!mg) {
-        dgemm_dev(st, 'N', 'T', nr, nr, 2 * m, -1.0, R.UW, ldp, R.UW + (size_t)ldp * m, ldp, 1.0, A, lda, 1);
-      } else {
-        // Local trailing update A_loc -= [U W](rows) [W U](cols)^T: needs no communication (src/eigen_t1.F:250-306).
-        // Look-ahead: the local tile columns that hold the NEXT panel, global columns (i-m, i], are updated first;
-        // they are then gathered from their owners on the side stream (the reference's panel-load allgather,
-        // src/eigen_prd_t7.F:114-128) while the compute stream updates the rest of the trailing matrix.
-        const int nrl = local_count(nr, G.Px, G.px), ncl = local_count(nr, G.Py, G.py);
-        const int clo = panel_lo(i);
-        const int lj0 = (clo - G.py + G.Py - 1) / G.Py;
-        const int tb0 = lj0 / 128;
-        const int lmax = nrl > ncl ? nrl : ncl;
-        if (lmax > 0)
-          hipLaunchKernelGGL(compact_panel_kernel, dim3(ceil_div(lmax, 256) < 64 ? ceil_div(lmax, 256) : 64, 2 * m), dim3(256),
-                             0, st, (const double*)R.UW, ldp, m, nrl, ncl, G.Px, G.px, G.Py, G.py, UWr, ldr, UWc, ldc);
-        if (nrl > 0 && ncl > 0)
-          dgemm_dev(st, 'N', 'T', nrl, ncl, 2 * m, -1.0, UWr, ldr, UWc, ldc, 1.0, A, lda, 2, &G, nullptr, nullptr, 1, 0, 0,
-                    0, 1, 0, 0, 0, 1, 0, nullptr, tb0, 0x7fffffff);
-        EIGX_HIP_CHECK(hipEventRecord(ctx.aux_ev[0], st));
-        if (tb0 > 0 && nrl > 0 && ncl > 0)
-          dgemm_dev(st, 'N', 'T', nrl, ncl, 2 * m, -1.0, UWr, ldr, UWc, ldc, 1.0, A, lda, 2, &G, nullptr, nullptr, 1, 0, 0,
-                    0, 1, 0, 0, 0, 1, 0, nullptr, 0, tb0);
-        hipStream_t sd = ctx.side_stream;
-        EIGX_HIP_CHECK(hipStreamWaitEvent(sd, ctx.aux_ev[0], 0));
-        gather_panel(clo, i, sd, CH_SIDE);
-        EIGX_HIP_CHECK(hipEventRecord(ctx.aux_ev[1], sd));
-        EIGX_HIP_CHECK(hipStreamWaitEvent(st, ctx.aux_ev[1], 0));
-        S.pan_c0 = clo;
-      }
+      // Local trailing update A_loc -= [U W](rows) [W U](cols)^T: needs no communication (src/eigen_t1.F:250-306).
+      // Look-ahead: the local tile columns that hold the NEXT panel, global columns (i-m, i], are updated first;
+      // they are then gathered from their owners on the side stream (the reference's panel-load allgather,
+      // src/eigen_prd_t7.F:114-128) while the compute stream updates the rest of the trailing matrix.
+      const int nrl = local_count(nr, G.Px, G.px), ncl = local_count(nr, G.Py, G.py);
+      const int clo = panel_lo(i);
+      const int tb0 = ((clo - G.py + G.Py - 1) / G.Py) / 128;   // first local tile column of the next panel
+      const int lmax = nrl > ncl ? nrl : ncl;
+      auto update = [&](int tn_lo, int tn_hi) {   // the local tile columns [tn_lo, tn_hi)
+        dgemm_dev(st, 'N', 'T', nrl, ncl, 2 * m, -1.0, UWr, ldr, UWc, ldc, 1.0, R.A, R.lda, 2, &G, nullptr, nullptr, 1, 0, 0,
+                  0, 1, 0, 0, 0, 1, 0, nullptr, tn_lo, tn_hi);
+      };
+      if (lmax > 0)
+        hipLaunchKernelGGL(compact_panel_kernel, dim3(ceil_div(lmax, 256) < 64 ? ceil_div(lmax, 256) : 64, 2 * m), dim3(256),
+                           0, st, (const double*)R.UW, ldp, m, nrl, ncl, G.Px, G.px, G.Py, G.py, UWr, ldr, UWc, ldc);
+      if (nrl > 0 && ncl > 0) update(tb0, 0x7fffffff);
+      EIGX_HIP_CHECK(hipEventRecord(ctx.aux_ev[0], st));
+      if (tb0 > 0 && nrl > 0 && ncl > 0) update(0, tb0);
+      EIGX_HIP_CHECK(hipStreamWaitEvent(ctx.side_stream, ctx.aux_ev[0], 0));
+      gather_panel(clo, i, ctx.side_stream, CH_SIDE);
+      EIGX_HIP_CHECK(hipEventRecord(ctx.aux_ev[1], ctx.side_stream));
+      EIGX_HIP_CHECK(hipStreamWaitEvent(st, ctx.aux_ev[1], 0));
+      S.pan_c0 = clo;
       if (ctx.prof_stride > 0) ctx.prof_end(st);
-      k1_flops += 2.0 * (double)nr * nr * m;  // 2*nr*nr*(2m)/2 : upper triangle only
-      ++n_k1;
-      hipLaunchKernelGGL(fill_kernel, dim3(1024), dim3(256), 0, st, R.UW, (size_t)ldp * m * 3, 0.0);
-      S.has_prev = 0;
-      k = 0;
+      panel_restart(R, C, S, k, nr, st);
     }
   }
-  if (mg && last_ka_ncols > 0) {
+  if (last_ka_ncols > 0) {
     // the last <= NB columns: no mat-vec follows whose publisher would take d, e from the X message
     const StepWait xw = x_wait(-1);
     hipLaunchKernelGGL((mg_tail_kernel<NB>), dim3(1), dim3(64), 0, st, R, (int)(xepoch & 1), last_ka_i, last_ka_ncols, xw);
   }
-  if (getenv("EIGX_TRACE_ENQUEUE")) {
-    const double te = std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count();
-    EIGX_HIP_CHECK(hipStreamSynchronize(st));
-    const double ts = std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count();
-    fprintf(stderr, "[eigx] reduction: enqueue loop %.1f ms, then %.1f ms until the stream drained\n", (te - t_begin) * 1e3, (ts - te) * 1e3);
-  }
-#ifdef EIGX_STAMPS
-  {
-    unsigned long long h[32];
-    EIGX_HIP_CHECK(hipStreamSynchronize(st));
-    EIGX_HIP_CHECK(hipMemcpy(h, R.dbg, sizeof(h), hipMemcpyDeviceToHost));
-    if (mg && h[24]) fprintf(stderr, "[eigx stamps] step launch timeline (100-MHz clock, averages over %llu full launches, from workgroup 0's entry): Y flags "
-                             "raised at %.2f us, X flags at %.2f us, next launch's workgroup 0 enters at %.2f us\n", h[24], 0.01 * h[22] / h[24],
-                             0.01 * h[23] / h[24], 0.01 * h[21] / h[24]);
-    if (R.stamp_i >= 0 && mg) {
-      // one sampled step (EIGX_STAMP_I = its top column): per-workgroup times of the three roles on the 100-MHz clock
-      std::vector<unsigned long long> big(4096);
-      EIGX_HIP_CHECK(hipMemcpy(big.data(), R.dbg, 4096 * sizeof(unsigned long long), hipMemcpyDeviceToHost));
-      unsigned long long t0 = ~0ull; int nw = 0, nk = 0;
-      for (int b = 0; b < 256; ++b) if (big[3136 + b]) { ++nk; if (big[3136 + b] < t0) t0 = big[3136 + b]; }
-      for (int b = 0; b < 1024; ++b) if (big[64 + b]) { ++nw; if (big[64 + b] < t0) t0 = big[64 + b]; }
-      double mk[3] = {0, 0, 0}, mx[3] = {0, 0, 0};
-      for (int b = 0; b < nk; ++b) for (int q = 0; q < 3; ++q) { const double v = 0.01 * (big[3136 + 256 * q + b] - t0); if (v > mk[q]) mk[q] = v; }
-      for (int b = 0; b < nw; ++b) for (int q = 0; q < 3; ++q) { const double v = 0.01 * (big[64 + 1024 * q + b] - t0); if (v > mx[q]) mx[q] = v; }
-      fprintf(stderr, "[eigx stamps] step with top column %d, us after the launch's first workgroup: kl role (%d workgroups) latest entry %.2f, partial sums in %.2f, "
-              "stores drained %.2f | ka role (%d) latest entry %.2f, Y seen %.2f, pushes issued %.2f; count complete %.2f, X flags stored %.2f | mat-vec role "
-              "(%llu tiles): X seen first %.2f last %.2f, tile ends first %.2f last %.2f\n", R.stamp_i, nk, mk[0], mk[1], mk[2], nw, mx[0], mx[1], mx[2],
-              0.01 * (big[3904] - t0), 0.01 * (big[3905] - t0), big[3910], 0.01 * (~big[3906] - t0), 0.01 * (big[3907] - t0), 0.01 * (~big[3909] - t0),
-              0.01 * (big[3908] - t0));
-    }
-    if (h[30]) fprintf(stderr, "[eigx stamps] K_A workgroup in the middle: %.2f us of wall clock per launch, %.0f s_memtime ticks: %.0f MHz\n",
-                       0.01 * h[30] / h[7], (double)h[31] / h[7], (double)h[31] / (0.01 * h[30]));
-    if (mg && h[24]) fprintf(stderr, "[eigx stamps] ka role, workgroup in the middle: enters at %.2f us, sees the Y flags at %.2f, has issued its pushes at %.2f; "
-                             "the watcher sees the count complete at %.2f us\n", 0.01 * h[26] / h[7], 0.01 * h[27] / h[7], 0.01 * h[28] / h[7], 0.01 * h[29] / h[14]);
-    if (mg) fprintf(stderr, "[eigx stamps] K_A several GPUs: wait %.0f | to the end of the pushes %.0f, drain + barrier %.0f | last arriver (from its previous stamp "
-                    "to the flag store) %.0f x %llu\n", (double)h[5] / h[7], (double)h[6] / h[7], (double)h[12] / h[7], (double)h[13] / (h[14] ? h[14] : 1), h[14]);
-    fprintf(stderr, "[eigx stamps] NB=%d n=%d K_A launches %llu: avg cycles issue %.0f consume %.0f reduce %.0f rows %.0f tail %.0f | SYMV %llu: "
-            "entry %.0f scalars %.0f stream %.0f tail %.0f\n", NB, n, h[7], (double)h[0] / h[7], (double)h[1] / h[7], (double)h[2] / h[7],
-            (double)h[3] / h[7], (double)h[4] / h[7], h[15], (double)h[8] / (h[15] ? h[15] : 1), (double)h[9] / (h[15] ? h[15] : 1),
-            (double)h[10] / (h[15] ? h[15] : 1), (double)h[11] / (h[15] ? h[15] : 1));
-  }
-#endif
+  trace_enqueue(t_begin, st);
+}
+
+template <int NB>
+void band_reduce_impl(Context& ctx, int n, double* A, int lda, double* d, double* e, int lde, int m) {
+  RedArgs R = reduce_setup<NB>(ctx, n, A, lda, d, e, lde, m);
+  RedCounters C;
+  if (ctx.grid.nranks > 1) reduce_multi_rank<NB>(ctx, R, C);
+  else reduce_one_gpu<NB>(ctx, R, C);
+  stamps_report(R, NB, ctx.stream);
   EIGX_HIP_CHECK(hipGetLastError());
-  ctx.timers[6] = (double)n_k1;
-  ctx.timers[7] = k1_flops;
-  ctx.timers[9] = (double)n_symv;
-  ctx.timers[10] = t_symv_bytes;
+  C.write(ctx);
 }
 
 }  // namespace
-
-int set_symv_threshold(int which, int v) {
-  if (which == 5) { const int old = g_symv_unc; g_symv_unc = v; return old; }
-  if (which == 6) return 0;   // (removed: folded step exchange)
-  int& t = (which == 4) ? g_ka_fit : (which == 3) ? g_ka_wgs : (which == 2) ? g_symv_nt : (which ? g_symv_t256 : g_symv_t128);
-  const int old = t; t = v; return old;
-}
 
 void band_reduce_dev(Context& ctx, int n, double* A, int lda, double* d, double* e, int lde, int m, int band) {
   if (band == 1) band_reduce_impl<1>(ctx, n, A, lda, d, e, lde, m);

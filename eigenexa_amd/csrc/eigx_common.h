@@ -146,8 +146,8 @@ int set_gemm_cstream(int v);
 int set_bisect_threads(int v);
 // tuning hook (eigx_tune key 2): super-block factor of the back-transformation (0 = automatic, 1, 2, 4)
 int set_bt_q(int v);
-// tuning hook (eigx_tune keys 3, 4): largest L that uses the 128 / 256 SYMV tile
-int set_symv_threshold(int which, int v);
+// tuning hooks of the reduction, by eigx_tune key (3, 4, 5, 7, 10, 11); returns the previous value, -1 for another key
+int set_reduce_knob(int key, int v);
 // tuning hook (eigx_tune key 8): chunk width (roots) of the multi-rank D&C's eigenvector-row buffer, 64 .. 2048
 int set_dc_chunk(int v);
 // lab switches (eigx_tune keys 15, 16): pipelined D&C passes / one product launch per low height (one GPU)
