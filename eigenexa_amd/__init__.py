@@ -23,6 +23,9 @@ from .api import (  # noqa: F401
     eigen_sx,
     eigen_s,
     eigen_h,
+    eigen_sx_range,
+    eigen_s_range,
+    range_info,
     eigen_sx_bc,
     eigen_s_bc,
     numroc,

@@ -253,6 +253,60 @@ def eigen_s(n, nvec, a, lda, w, z, ldz, m_forward=None, m_backward=None, mode="A
     _solve("s", n, nvec, a, lda, w, z, ldz, m_forward, m_backward, mode)
 
 
+def _solve_range(which, n, il, iu, a, lda, w, z, ldz, m_forward, m_backward, mode):
+    # the window and the mode are checked here, before the library is touched (status -2 = EIGX_ERR_BAD_ARG)
+    md = _char(mode, "A").upper()
+    try:
+        ok = 1 <= int(il) <= int(iu) <= int(n) and md in (b"A", b"N") and not (md == b"A" and z is None)
+    except (TypeError, ValueError):
+        ok = False
+    if not ok:
+        _state["last_status"] = -2
+        print(f"Warning: eigen_{which}_range: invalid window / mode (n={n}, il={il}, iu={iu}, mode={mode!r})", file=sys.stderr)
+        return
+    lib = _lib.load()
+    if not _state["initialized"]:
+        _state["last_status"] = -1
+        return
+    dev = _is_torch(a)
+    if dev:
+        import torch
+
+        torch.cuda.current_stream().synchronize()
+    pa, pw, pz = _ptr(a, "a", dev), _ptr(w, "w", dev), _ptr(z, "z", dev)
+    mf = eigen_NB_f if m_forward is None else int(m_forward)
+    mb = eigen_NB_b if m_backward is None else int(m_backward)
+    fn = getattr(lib, f"eigx_{which}_range" + ("_dev" if dev else ""))
+    rc = fn(int(n), int(il), int(iu), pa, int(lda), pw, pz, int(ldz), mf, mb, md)
+    _state["last_status"] = rc
+    if rc not in (0, -5):
+        print(f"Warning: eigen_{which}_range returned without computing (status {rc})", file=sys.stderr)
+
+
+def eigen_sx_range(n, il, iu, a, lda, w, z, ldz, m_forward=None, m_backward=None, mode="A"):
+    """EXTENSION (not in the reference): eigenpairs ``il .. iu`` (1-based, inclusive) of the ascending spectrum by the
+    pentadiagonal route, one GPU.  ``w[:m]``, ``z[:, :m]`` with ``m = iu - il + 1``; modes 'A' and 'N'.  Work and memory
+    after the reduction scale with ``m`` (Sturm multi-section on the window, inverse iteration, CholQR2 + Rayleigh-Ritz);
+    ``range_info()`` tells whether that path or the full divide and conquer produced the result."""
+    _solve_range("sx", n, il, iu, a, lda, w, z, ldz, m_forward, m_backward, mode)
+
+
+def eigen_s_range(n, il, iu, a, lda, w, z, ldz, m_forward=None, m_backward=None, mode="A"):
+    """EXTENSION: ``eigen_sx_range`` by the tridiagonal route."""
+    _solve_range("s", n, il, iu, a, lda, w, z, ldz, m_forward, m_backward, mode)
+
+
+def range_info():
+    """What the last range call did: ``path`` (1 subset path, 2 fell back to the full divide and conquer, 3 full divide
+    and conquer by the size rule), ``m`` and ``cond`` (the conditioning estimate of the acceptance test)."""
+    import collections
+
+    lib = _lib.load()
+    p, m, c = C.c_int(), C.c_int(), C.c_double()
+    _lib.check(lib.eigx_range_info(C.byref(p), C.byref(m), C.byref(c)), "eigx_range_info")
+    return collections.namedtuple("RangeInfo", "path m cond")(p.value, m.value, c.value)
+
+
 def eigen_h(n, nvec, a, lda, w, z, ldz, m_forward=None, m_backward=None, mode="A"):
     """Complex Hermitian solver (src/eigen_h.F:30-322: eigen_hrd -> dc2 -> eigen_hrbakwyx).  ``a``, ``z``: complex128,
     column-major (numpy, Fortran order) or GPU tensors holding the column-major image (``a[j, i] = A(i, j)``); upper

@@ -30,9 +30,10 @@ constexpr int BS_TILE = 1024;   // matrix rows staged per LDS tile
 
 struct BisArgs {
   int n, lde, band, S;
+  int m, k0;                  // index window: eigenvalues k0 .. k0 + m - 1 (0-based, ascending) of the n; all: k0 = 0, m = n
   const double* d; const double* e;
-  double* lb; double* ub;     // [n] current brackets
-  int* cnt;                   // [n * S] counts of the round
+  double* lb; double* ub;     // [m] current brackets
+  int* cnt;                   // [m * S] counts of the round
   double* scal;               // {glb, gub, pivmin, eps_abs}
 };
 
@@ -207,11 +208,11 @@ __device__ int sturm_count(const BisArgs& a, double x, double pivmin, double* sd
   return ps.cnt + pen_finish(ps, pivmin);
 }
 
-// round 0: G = n*S points on the Gershgorin interval
+// round 0: G = m*S points on the Gershgorin interval
 template <int BAND>
 __global__ __launch_bounds__(256) void bis_grid_kernel(BisArgs a) {
   __shared__ double sd[BS_TILE], se1[BS_TILE], se2[BS_TILE];
-  const long G = (long)a.n * a.S;
+  const long G = (long)a.m * a.S;
   const long t = (long)blockIdx.x * 256 + threadIdx.x;
   const double lo = a.scal[0], hi = a.scal[1], pivmin = a.scal[2];
   const long tc = t < G ? t : G - 1;
@@ -220,16 +221,16 @@ __global__ __launch_bounds__(256) void bis_grid_kernel(BisArgs a) {
   if (t < G) a.cnt[t] = c;
 }
 
-// bracket eigenvalue k (0-based, ascending): smallest grid point with count >= k + 1 is the upper end
+// bracket eigenvalue k0 + k (0-based, ascending): smallest grid point with count >= k0 + k + 1 is the upper end
 __global__ void bis_bracket_kernel(BisArgs a) {
   const int k = blockIdx.x * blockDim.x + threadIdx.x;
-  if (k >= a.n) return;
-  const long G = (long)a.n * a.S;
+  if (k >= a.m) return;
+  const long G = (long)a.m * a.S;
   const double lo = a.scal[0], hi = a.scal[1];
   long l = 0, r = G;   // first index in [0, G] with cnt >= k+1 (G = none)
   while (l < r) {
     const long mid = (l + r) >> 1;
-    if (a.cnt[mid] >= k + 1) r = mid; else l = mid + 1;
+    if (a.cnt[mid] >= a.k0 + k + 1) r = mid; else l = mid + 1;
   }
   auto xg = [&](long t) { return lo + (hi - lo) * ((double)(t + 1) / (double)(G + 1)); };
   a.lb[k] = (l == 0) ? lo : xg(l - 1);
@@ -240,7 +241,7 @@ __global__ void bis_bracket_kernel(BisArgs a) {
 template <int BAND>
 __global__ __launch_bounds__(256) void bis_refine_kernel(BisArgs a) {
   __shared__ double sd[BS_TILE], se1[BS_TILE], se2[BS_TILE];
-  const long G = (long)a.n * a.S;
+  const long G = (long)a.m * a.S;
   const long t = (long)blockIdx.x * 256 + threadIdx.x;
   const long tc = t < G ? t : G - 1;
   const int k = (int)(tc / a.S), s = (int)(tc - (long)k * a.S);
@@ -252,13 +253,13 @@ __global__ __launch_bounds__(256) void bis_refine_kernel(BisArgs a) {
 
 __global__ void bis_update_kernel(BisArgs a) {
   const int k = blockIdx.x * blockDim.x + threadIdx.x;
-  if (k >= a.n) return;
+  if (k >= a.m) return;
   const double lb = a.lb[k], ub = a.ub[k];
   double nlb = lb, nub = ub;
   for (int s = 0; s < a.S; ++s) {
     const double x = lb + (ub - lb) * ((double)(s + 1) / (double)(a.S + 1));
     if (!(x > nlb && x < ub)) continue;          // bracket exhausted in floating point
-    if (a.cnt[(long)k * a.S + s] >= k + 1) { nub = x; break; }
+    if (a.cnt[(long)k * a.S + s] >= a.k0 + k + 1) { nub = x; break; }
     nlb = x;
   }
   a.lb[k] = nlb; a.ub[k] = nub;
@@ -266,7 +267,7 @@ __global__ void bis_update_kernel(BisArgs a) {
 
 __global__ void bis_final_kernel(BisArgs a, double* w) {
   const int k = blockIdx.x * blockDim.x + threadIdx.x;
-  if (k < a.n) w[k] = 0.5 * (a.lb[k] + a.ub[k]);
+  if (k < a.m) w[k] = 0.5 * (a.lb[k] + a.ub[k]);
 }
 
 int g_bis_threads = 65536;   // target number of concurrent Sturm sweeps n*S (eigx_tune key 1)
@@ -275,20 +276,26 @@ int g_bis_threads = 65536;   // target number of concurrent Sturm sweeps n*S (ei
 
 int set_bisect_threads(int v) { const int old = g_bis_threads; if (v > 0) g_bis_threads = v; return old; }
 
-void band_bisect_dev(Context& ctx, int n, const double* d, const double* e, int lde, int band, double* w) {
-  if (n <= 0) return;
+// Eigenvalues il .. iu (1-based, inclusive) of the ascending spectrum into w[0 .. iu - il]: the multi-section on an index
+// window -- the grid and the brackets are sized by m = iu - il + 1, the Gershgorin bounds stay global and the counts are
+// compared against il - 1 + k.  (EXTENSION: the reference's eigen_bisect always computes all n.)
+void band_bisect_range_dev(Context& ctx, int n, int il, int iu, const double* d, const double* e, int lde, int band,
+                           double* w) {
+  if (n <= 0 || il < 1 || iu > n || il > iu) return;
+  const int m = iu - il + 1;
   hipStream_t st = ctx.stream;
   BisArgs a;
   a.n = n; a.lde = lde; a.band = band; a.d = d; a.e = e;
+  a.m = m; a.k0 = il - 1;
   int S = 1;
-  while (S < 64 && (long)n * (2 * S) <= g_bis_threads) S *= 2;
+  while (S < 64 && (long)m * (2 * S) <= g_bis_threads) S *= 2;
   a.S = S;
-  a.lb = ctx.pool.get_t<double>("bis.lb", (size_t)n);
-  a.ub = ctx.pool.get_t<double>("bis.ub", (size_t)n);
-  a.cnt = ctx.pool.get_t<int>("bis.cnt", (size_t)n * S);
+  a.lb = ctx.pool.get_t<double>("bis.lb", (size_t)m);
+  a.ub = ctx.pool.get_t<double>("bis.ub", (size_t)m);
+  a.cnt = ctx.pool.get_t<int>("bis.cnt", (size_t)m * S);
   a.scal = ctx.pool.get_t<double>("bis.scal", 8);
-  const long G = (long)n * S;
-  const int gb = (int)((G + 255) / 256), nb = (n + 255) / 256;
+  const long G = (long)m * S;
+  const int gb = (int)((G + 255) / 256), nb = (m + 255) / 256;
   hipLaunchKernelGGL(bis_bounds_kernel, dim3(1), dim3(256), 0, st, a);
   if (band == 1) hipLaunchKernelGGL(bis_grid_kernel<1>, dim3(gb), dim3(256), 0, st, a);
   else hipLaunchKernelGGL(bis_grid_kernel<2>, dim3(gb), dim3(256), 0, st, a);
@@ -306,15 +313,20 @@ void band_bisect_dev(Context& ctx, int n, const double* d, const double* e, int 
   hipLaunchKernelGGL(bis_final_kernel, dim3(nb), dim3(256), 0, st, a, w);
   // the reference sorts the result (lazy_qsort, src/bisect2.F:682-712); brackets of neighbouring eigenvalues can
   // overlap by an ulp, so do the same (n doubles through the host: microseconds)
-  std::vector<double> h((size_t)n);
-  EIGX_HIP_CHECK(hipMemcpyAsync(h.data(), w, (size_t)n * 8, hipMemcpyDeviceToHost, st));
+  std::vector<double> h((size_t)m);
+  EIGX_HIP_CHECK(hipMemcpyAsync(h.data(), w, (size_t)m * 8, hipMemcpyDeviceToHost, st));
   EIGX_HIP_CHECK(hipStreamSynchronize(st));
   if (!std::is_sorted(h.begin(), h.end())) {
     std::sort(h.begin(), h.end());
-    EIGX_HIP_CHECK(hipMemcpyAsync(w, h.data(), (size_t)n * 8, hipMemcpyHostToDevice, st));
+    EIGX_HIP_CHECK(hipMemcpyAsync(w, h.data(), (size_t)m * 8, hipMemcpyHostToDevice, st));
     EIGX_HIP_CHECK(hipStreamSynchronize(st));
   }
   EIGX_HIP_CHECK(hipGetLastError());
+}
+
+// all n eigenvalues: the window [1, n] of the same code
+void band_bisect_dev(Context& ctx, int n, const double* d, const double* e, int lde, int band, double* w) {
+  band_bisect_range_dev(ctx, n, 1, n, d, e, lde, band, w);
 }
 
 }  // namespace eigx

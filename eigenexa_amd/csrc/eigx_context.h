@@ -148,6 +148,31 @@ void band_dc_dev(Context& ctx, int n, int nvec, const double* d, const double* e
 // bisect.hip: eigenvalues only of the band matrix by Sturm counts (multi-section); w ascending
 void band_bisect_dev(Context& ctx, int n, const double* d, const double* e, int lde, int band, double* w);
 
+// bisect.hip: eigenvalues il .. iu (1-based, inclusive) of the ascending spectrum by the same multi-section, w[0 .. iu - il]
+void band_bisect_range_dev(Context& ctx, int n, int il, int iu, const double* d, const double* e, int lde, int band,
+                           double* w);
+
+// subset.hip (EXTENSION, one GPU): eigenvectors of the band matrix for m chosen eigenvalues by inverse iteration, CholQR2
+// and Rayleigh-Ritz; w_out = Ritz values (ascending), z(ldz, m) orthonormal.  EIGX_OK, or > 0: the acceptance test refused
+// the result (1 Cholesky breakdown, 2 cond(L) above 10^key19); cond_out, stage_s[2] (seconds of the inverse
+// iteration and of the rest) are optional.  Re-enters band_reduce_dev / band_dc_dev / trbak_dev for
+// the m x m Rayleigh-Ritz problem: "red.", "dc.", "bt." buffers and a prepared back-transformation do not survive it.
+int band_eigvec_dev(Context& ctx, int n, int m, const double* d, const double* e, int lde, int band, const double* w_sel,
+                    double* w_out, double* z, int ldz, double* cond_out, double* stage_s);
+// what the last range call did: path 1 subset, 2 fell back to the full D&C, 3 full D&C by the size rule; stage seconds
+// t = {bisection, inverse iteration, orthonormalisation + Rayleigh-Ritz (or the fallback D&C), back-transformation}
+struct RangeInfo { int path, m; double cond; double t[4]; };
+RangeInfo& range_info();
+// eigx_tune keys 17 (size rule, percent), 18 (opt-in of eigx_sx / eigx_s), 19 (log10 of the cond(L) bound)
+int set_range_knob(int key, int v);
+int get_range_knob(int key);
+bool range_takes_subset(int n, int m);   // the size rule of key 17 (negative = automatic, see subset.hip)
+
+// trbak.hip: T factors of the back-transformation ahead of time on stream s, and Z(:, 0:nvec) <- H_n ... H_{1+band} Z
+void trbak_prepare_dev(Context& ctx, int n, double* A, int lda, const double* e, int lde, int mb, int band, hipStream_t s);
+void trbak_dev(Context& ctx, int n, int nvec, double* A, int lda, double* Z, int ldz, const double* e, int lde, int mb,
+               int band);
+
 // solver.hip
 // eigenvector column blocks -> the callers' 2-D (block-)cyclic blocks (one all-to-all); see solver.hip
 void cols_to_cyclic_dev(Context& ctx, int n, int nvec, int nb, int zc, int zc0, int zcnt, const double* zcols, int ldz,

@@ -15,10 +15,6 @@
 
 namespace eigx {
 
-void trbak_prepare_dev(Context& ctx, int n, double* A, int lda, const double* e, int lde, int mb, int band,
-                       hipStream_t s);
-void trbak_dev(Context& ctx, int n, int nvec, double* A, int lda, double* Z, int ldz, const double* e,
-               int lde, int mb, int band);
 void trbak_mg_dev(Context& ctx, int n, int nvec, const double* Aloc, int lda, double* Z, int ldz, const double* e,
                   int lde, int mb, int band);
 
@@ -314,6 +310,171 @@ void dev_to_host(void* h, int ld, const void* d, int ldd, int nr, int nc, int es
 
 namespace {
 
+__global__ void copy_vec_kernel(const double* __restrict__ src, double* __restrict__ dst, int n) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) dst[i] = src[i];
+}
+
+// ---- index-range solve: eigenpairs il .. iu (1-based, inclusive) of the ascending spectrum, one GPU ---------------------
+// EXTENSION, not in the reference (whose nvec only trims the back-transformation, src/eigen_sx.F:200-240).
+//   scaling -> band reduction (as solve_dev) -> Sturm multi-section on the index window -> band_eigvec_dev (inverse
+//   iteration + CholQR2 + Rayleigh-Ritz, subset.hip) -> back-transformation of the m columns.
+// The subset path asks for no D&C workspace of the outer problem.  The full divide and conquer (nvec = iu, columns
+// il .. iu copied out) serves windows beyond the size rule (eigx_tune key 17; path 3) and results that the acceptance
+// test of band_eigvec_dev refused (path 2).  w(1:m), z(:, 1:m); fill_rest (the opt-in route of eigx_sx / eigx_s, il = 1):
+// w(m+1:n) is filled by bisection as well, so that w holds all n eigenvalues like the reference's.
+int range_solve_dev(Context& ctx, int n, int il, int iu, double* a, int lda, double* w, double* z, int ldz, int mf, int mb,
+                    char mode, int band, bool fill_rest) {
+  if (!ctx.initialized) return EIGX_ERR_NOT_INITIALIZED;
+  if (ctx.grid.nranks != 1) {
+    fprintf(stderr, "[eigx] index-range solves run on one GPU only (this grid has %d ranks)\n", ctx.grid.nranks);
+    return EIGX_ERR_BAD_ARG;
+  }
+  if (n <= 0) {
+    fprintf(stderr, "[eigx] warning: non-positive dimension is invalid\n");
+    return EIGX_ERR_BAD_ARG;
+  }
+  if (mode >= 'a' && mode <= 'z') mode = (char)(mode - 'a' + 'A');
+  if (il < 1 || iu > n || il > iu || (mode != 'A' && mode != 'N') || !a || !w || lda < n) return EIGX_ERR_BAD_ARG;
+  const bool want_vec = mode == 'A';
+  if (want_vec && (!z || ldz < n)) return EIGX_ERR_BAD_ARG;
+  const int m = iu - il + 1;
+  if (mf <= 0) mf = 128;
+  if (mb <= 0) mb = 128;
+  EIGX_HIP_CHECK(hipSetDevice(ctx.device));
+  EIGX_HIP_CHECK(hipStreamSynchronize(nullptr));   // the caller's default-stream work on the arguments (see solve_dev)
+  hipStream_t st = ctx.stream;
+  ctx.errinfo = 0;
+  ctx.dc_zero_n = 0;
+  for (int q = 0; q < 16; ++q) ctx.timers[q] = 0.0;
+  RangeInfo& info = range_info();
+  info.path = 0; info.m = m; info.cond = 0.0;
+  for (int q = 0; q < 4; ++q) info.t[q] = 0.0;
+  const double t0 = now_s();
+  const int nw = fill_rest ? n : m;   // entries of w that belong to this call
+
+  double* a_user = a;
+  double* z_user = z;
+  const int ldz_user = ldz;
+  if ((lda & 1) || ((uintptr_t)a & 15)) {   // odd leading dimension / unaligned base: internal padded copy (see solve_dev)
+    const int ldi = pad_ld(n + 2);
+    double* ai = ctx.pool.get_t<double>("sol.apad", (size_t)ldi * n);
+    EIGX_HIP_CHECK(hipMemcpy2DAsync(ai, (size_t)ldi * 8, a, (size_t)lda * 8, (size_t)n * 8, (size_t)n, hipMemcpyDeviceToDevice, st));
+    a = ai;
+    lda = ldi;
+  }
+  if (want_vec && ((ldz & 1) || ((uintptr_t)z & 15))) {
+    ldz = pad_ld(n);
+    z = ctx.pool.get_t<double>("mg.Z", (size_t)ldz * m);
+  }
+
+  // ---- eigen_scaling (writes NaN into n entries on a non-finite input: w may hold m only, so it gets a buffer) ------
+  double* wn = ctx.pool.get_t<double>("sub.wfull", (size_t)n);
+  double sigma = 1.0;
+  const int rc_sc = eigen_scaling(ctx, a, lda, false, n, wn, &sigma);
+  if (rc_sc != EIGX_OK) {
+    if (rc_sc == EIGX_ERR_NONFINITE) {
+      hipLaunchKernelGGL(fill_vec_kernel, dim3((nw + 255) / 256), dim3(256), 0, st, w, nw, std::numeric_limits<double>::quiet_NaN());
+      EIGX_HIP_CHECK(hipStreamSynchronize(st));
+    }
+    return rc_sc;
+  }
+  if (sigma != 1.0) hipLaunchKernelGGL(scale_upper_kernel, dim3(1024), dim3(256), 0, st, a, lda, n, 1, 0, 1, 0, sigma);
+
+  // ---- forward reduction ---------------------------------------------------------------------------------------------
+  const int lde = (n + 3) / 4 * 4;
+  double* d = ctx.pool.get_t<double>("sol.d", (size_t)n);
+  double* e = ctx.pool.get_t<double>("sol.e", (size_t)lde * 2);
+  const double t1 = now_s();
+  band_reduce_dev(ctx, n, a, lda, d, e, lde, mf, band);
+  EIGX_HIP_CHECK(hipStreamSynchronize(st));
+  const double t2 = now_s();
+
+  // ---- eigenvalues il .. iu, then their eigenvectors -------------------------------------------------------------------
+  if (!want_vec) {
+    band_bisect_range_dev(ctx, n, il, iu, d, e, lde, band, w);
+    info.path = 1;
+    info.t[0] = now_s() - t2;
+  } else {
+    int path = range_takes_subset(n, m) ? 1 : 3;
+    if (path == 1) {
+      double* wsel = ctx.pool.get_t<double>("sub.wsel", (size_t)m);
+      band_bisect_range_dev(ctx, n, il, iu, d, e, lde, band, wsel);
+      const double tb = now_s();
+      info.t[0] = tb - t2;
+      double cond = 0.0;
+      double ts[2] = {0.0, 0.0};
+      const int rc_ev = band_eigvec_dev(ctx, n, m, d, e, lde, band, wsel, w, z, ldz, &cond, ts);
+      if (rc_ev < 0) return rc_ev;
+      info.cond = cond; info.t[1] = ts[0]; info.t[2] = ts[1];
+      if (rc_ev > 0) path = 2;   // refused by the acceptance test
+    }
+    if (path != 1) {
+      // the full divide and conquer for the lowest iu pairs; columns il .. iu are the answer
+      const double tf = now_s();
+      double* zf = z;
+      int ldzf = ldz;
+      if (il > 1) {
+        ldzf = pad_ld(n);
+        zf = ctx.pool.get_t<double>("sub.zfull", (size_t)ldzf * iu);
+      }
+      band_dc_dev(ctx, n, iu, d, e, lde, band, wn, zf, ldzf);
+      hipLaunchKernelGGL(copy_vec_kernel, dim3((m + 255) / 256), dim3(256), 0, st, (const double*)(wn + il - 1), w, m);
+      if (il > 1)
+        EIGX_HIP_CHECK(hipMemcpy2DAsync(z, (size_t)ldz * 8, zf + (size_t)(il - 1) * ldzf, (size_t)ldzf * 8, (size_t)n * 8, (size_t)m,
+                                        hipMemcpyDeviceToDevice, st));
+      EIGX_HIP_CHECK(hipStreamSynchronize(st));
+      info.t[2] += now_s() - tf;
+    }
+    info.path = path;
+  }
+  const double t3 = now_s();
+
+  // ---- back-transformation of the m columns (prepared here: the Rayleigh-Ritz solve used the bt.* buffers) -------------
+  if (want_vec) {
+    trbak_dev(ctx, n, m, a, lda, z, ldz, e, lde, mb, band);
+    if (z != z_user)
+      EIGX_HIP_CHECK(hipMemcpy2DAsync(z_user, (size_t)ldz_user * 8, z, (size_t)ldz * 8, (size_t)n * 8, (size_t)m, hipMemcpyDeviceToDevice, st));
+  }
+  if (fill_rest && iu < n) band_bisect_range_dev(ctx, n, iu + 1, n, d, e, lde, band, w + m);
+  if (sigma != 1.0 && sigma != 0.0) hipLaunchKernelGGL(scale_vec_kernel, dim3((nw + 255) / 256), dim3(256), 0, st, w, nw, 1.0 / sigma);
+  EIGX_HIP_CHECK(hipStreamSynchronize(st));
+  const double t4 = now_s();
+  info.t[3] = t4 - t3;
+
+  const double f_red = 4.0 / 3.0 * (double)n * n * n;
+  const double f_bt = want_vec ? 2.0 * (double)m * n * n : 0.0;
+  const double f_mid = want_vec ? (info.path == 1 ? 6.0 * (double)n * m * m : ctx.timers[11]) : 0.0;
+  double ret = f_red + f_mid + f_bt;
+  if (f_mid == 0.0) ret = -ret;
+  ctx.timers[0] = t4 - t0; ctx.timers[1] = t2 - t1; ctx.timers[2] = t3 - t2; ctx.timers[3] = t4 - t3; ctx.timers[12] = ret;
+  const double stats[3] = {ret, t4 - t0, -1.0};
+  EIGX_HIP_CHECK(hipMemcpyAsync(a_user, stats, (size_t)(n >= 3 ? 3 : n) * 8, hipMemcpyHostToDevice, st));
+  EIGX_HIP_CHECK(hipStreamSynchronize(st));
+  return EIGX_OK;
+}
+
+int range_solve_host(Context& ctx, int n, int il, int iu, double* a, int lda, double* w, double* z, int ldz, int mf, int mb,
+                     char mode, int band) {
+  if (!ctx.initialized) return EIGX_ERR_NOT_INITIALIZED;
+  if (ctx.grid.nranks != 1) return range_solve_dev(ctx, n, il, iu, a, lda, w, z, ldz, mf, mb, mode, band, false);   // refuses
+  if (n <= 0 || il < 1 || iu > n || il > iu || !a || !w || lda < n) return EIGX_ERR_BAD_ARG;
+  if (mode >= 'a' && mode <= 'z') mode = (char)(mode - 'a' + 'A');
+  if ((mode != 'A' && mode != 'N') || (mode == 'A' && (!z || ldz < n))) return EIGX_ERR_BAD_ARG;
+  const int m = iu - il + 1;
+  EIGX_HIP_CHECK(hipSetDevice(ctx.device));
+  const int ldd = host_ld(n);
+  double* ad = (double*)host_to_dev(ctx, "host.a", a, lda, n, n, 8);
+  double* zd = (double*)host_to_dev(ctx, "host.z", nullptr, 0, n, mode == 'A' ? m : 1, 8);
+  double* wd = ctx.pool.get_t<double>("host.w", (size_t)m);
+  const int rc = range_solve_dev(ctx, n, il, iu, ad, ldd, wd, zd, ldd, mf, mb, mode, band, false);
+  if (rc == EIGX_OK || rc == EIGX_ERR_NONFINITE) EIGX_HIP_CHECK(hipMemcpy(w, wd, (size_t)m * 8, hipMemcpyDeviceToHost));
+  if (rc != EIGX_OK) return rc;
+  if (mode == 'A') dev_to_host(z, ldz, zd, ldd, n, m, 8);
+  dev_to_host(a, lda, ad, ldd, std::min(n, 3), 1, 8);
+  return EIGX_OK;
+}
+
 // nb = block size of the 2-D block-cyclic layout of a and z over the process grid (1 = the cyclic layout of the
 // EigenExa API; a ScaLAPACK caller passes its descriptor's MB = NB and needs no pdgemr2d redistribution, manual 3.4)
 int solve_dev(Context& ctx, int n, int nvec, double* a, int lda, double* w, double* z, int ldz, int mf, int mb,
@@ -333,6 +494,9 @@ int solve_dev(Context& ctx, int n, int nvec, double* a, int lda, double* w, doub
   nvec = rq.nvec;
   const bool want_vec = rq.want_vec;
   if (want_vec && (!z || ldz < (nloc_r > 1 ? nloc_r : 1))) return EIGX_ERR_BAD_ARG;
+  // opt-in (eigx_tune key 18, default off): the lowest nvec < n eigenpairs by the index-range path (EXTENSION)
+  if (get_range_knob(18) == 1 && P == 1 && nb == 1 && mode == 'A' && nvec > 0 && nvec < n)
+    return range_solve_dev(ctx, n, 1, nvec, a, lda, w, z, ldz, mf, mb, 'A', band, true);
   if (mf <= 0) mf = 128;
   if (mb <= 0) mb = 128;
   EIGX_HIP_CHECK(hipSetDevice(ctx.device));
@@ -848,6 +1012,19 @@ int eigx_sx(int n, int nvec, double* a, int lda, double* w, double* z, int ldz, 
 }
 int eigx_s(int n, int nvec, double* a, int lda, double* w, double* z, int ldz, int mf, int mb, char mode) {
   return eigx_guard(g_ctx, [&] { return solve_host(g_ctx, n, nvec, a, lda, w, z, ldz, mf, mb, mode, 1, 1); });
+}
+// EXTENSION: eigenpairs il .. iu of the ascending spectrum (one GPU); see range_solve_dev
+int eigx_sx_range(int n, int il, int iu, double* a, int lda, double* w, double* z, int ldz, int mf, int mb, char mode) {
+  return eigx_guard(g_ctx, [&] { return range_solve_host(g_ctx, n, il, iu, a, lda, w, z, ldz, mf, mb, mode, 2); });
+}
+int eigx_s_range(int n, int il, int iu, double* a, int lda, double* w, double* z, int ldz, int mf, int mb, char mode) {
+  return eigx_guard(g_ctx, [&] { return range_solve_host(g_ctx, n, il, iu, a, lda, w, z, ldz, mf, mb, mode, 1); });
+}
+int eigx_sx_range_dev(int n, int il, int iu, double* a, int lda, double* w, double* z, int ldz, int mf, int mb, char mode) {
+  return eigx_guard(g_ctx, [&] { return range_solve_dev(g_ctx, n, il, iu, a, lda, w, z, ldz, mf, mb, mode, 2, false); });
+}
+int eigx_s_range_dev(int n, int il, int iu, double* a, int lda, double* w, double* z, int ldz, int mf, int mb, char mode) {
+  return eigx_guard(g_ctx, [&] { return range_solve_dev(g_ctx, n, il, iu, a, lda, w, z, ldz, mf, mb, mode, 1, false); });
 }
 int eigx_sx_dev(int n, int nvec, double* a, int lda, double* w, double* z, int ldz, int mf, int mb, char mode) {
   return eigx_guard(g_ctx, [&] { return solve_dev(g_ctx, n, nvec, a, lda, w, z, ldz, mf, mb, mode, 2, 1); });

@@ -31,6 +31,7 @@ module eigen_libs_mod
   public :: eigen_sx, eigen_s, eigen_s0
   public :: eigen_sx_bc, eigen_s_bc   ! ScaLAPACK block-cyclic local blocks in and out (no pdgemr2d step)
   public :: eigen_h                   ! complex Hermitian solver (src/eigen_h.F)
+  public :: eigen_sx_range, eigen_s_range   ! EXTENSION: eigenpairs il .. iu of the ascending spectrum (one GPU)
 
   interface
     integer(c_int) function eigx_init(device) bind(C, name="eigx_init")
@@ -108,6 +109,21 @@ module eigen_libs_mod
     integer(c_int) function eigx_sx(n, nvec, a, lda, w, z, ldz, mf, mb, mode) bind(C, name="eigx_sx")
       import :: c_int, c_double, c_char
       integer(c_int), value :: n, nvec, lda, ldz, mf, mb
+      real(c_double), intent(inout) :: a(lda, *)
+      real(c_double), intent(out) :: w(*), z(ldz, *)
+      character(kind=c_char), value :: mode
+    end function
+    ! EXTENSION (not in the reference): eigenpairs il .. iu of the ascending spectrum, one GPU
+    integer(c_int) function eigx_sx_range(n, il, iu, a, lda, w, z, ldz, mf, mb, mode) bind(C, name="eigx_sx_range")
+      import :: c_int, c_double, c_char
+      integer(c_int), value :: n, il, iu, lda, ldz, mf, mb
+      real(c_double), intent(inout) :: a(lda, *)
+      real(c_double), intent(out) :: w(*), z(ldz, *)
+      character(kind=c_char), value :: mode
+    end function
+    integer(c_int) function eigx_s_range(n, il, iu, a, lda, w, z, ldz, mf, mb, mode) bind(C, name="eigx_s_range")
+      import :: c_int, c_double, c_char
+      integer(c_int), value :: n, il, iu, lda, ldz, mf, mb
       real(c_double), intent(inout) :: a(lda, *)
       real(c_double), intent(out) :: w(*), z(ldz, *)
       character(kind=c_char), value :: mode
@@ -575,6 +591,40 @@ contains
     rc = eigx_s(n, nvec, a, lda, w, z, ldz, mf, mb, md)
     call timer_print_lines(n, nvec, md, 'TRD-BLK ')
   end subroutine eigen_s
+
+  !> eigen_sx_range(n, il, iu, a, lda, w, z, ldz, m_forward, m_backward, mode) -- EXTENSION, not in the reference (its
+  !> nvec only trims the back-transformation): eigenpairs il .. iu (1-based, inclusive) of the ascending spectrum by the
+  !> pentadiagonal route on one GPU; w(1:iu-il+1), z(:, 1:iu-il+1); modes 'A' and 'N'.  Same contract for a as eigen_sx.
+  subroutine eigen_sx_range(n, il, iu, a, lda, w, z, ldz, m_forward, m_backward, mode)
+    integer, intent(in) :: n, il, iu, lda, ldz
+    real(8), intent(inout) :: a(lda, *)
+    real(8), intent(out) :: w(*), z(ldz, *)
+    integer, intent(in), optional :: m_forward, m_backward
+    character(*), intent(in), optional :: mode
+    integer :: mf, mb, rc
+    character(kind=c_char) :: md
+    mf = eigen_NB_f; mb = eigen_NB_b; md = 'A'
+    if (present(m_forward)) mf = m_forward
+    if (present(m_backward)) mb = m_backward
+    if (present(mode)) md = mode(1:1)
+    rc = eigx_sx_range(n, il, iu, a, lda, w, z, ldz, mf, mb, md)
+  end subroutine eigen_sx_range
+
+  !> eigen_s_range: the same by the tridiagonal route (EXTENSION)
+  subroutine eigen_s_range(n, il, iu, a, lda, w, z, ldz, m_forward, m_backward, mode)
+    integer, intent(in) :: n, il, iu, lda, ldz
+    real(8), intent(inout) :: a(lda, *)
+    real(8), intent(out) :: w(*), z(ldz, *)
+    integer, intent(in), optional :: m_forward, m_backward
+    character(*), intent(in), optional :: mode
+    integer :: mf, mb, rc
+    character(kind=c_char) :: md
+    mf = eigen_NB_f; mb = eigen_NB_b; md = 'A'
+    if (present(m_forward)) mf = m_forward
+    if (present(m_backward)) mb = m_backward
+    if (present(mode)) md = mode(1:1)
+    rc = eigx_s_range(n, il, iu, a, lda, w, z, ldz, mf, mb, md)
+  end subroutine eigen_s_range
 
   !> The reference's per-stage report of a TIMER_PRINT=1 build (src/eigen_sx.F:167-174, :225-232, :252-258, format 10000 at
   !> :304; src/eigen_FS.F likewise): one line per stage on rank 1 -- name, n, seconds, flops of the reference's model, GFLOPS.

@@ -23,7 +23,8 @@
  *   eigx_sx_dev / eigx_s_dev  device (HBM-resident) arrays        (what bench.py times)
  * and, on top of them: eigx_solve_bc[_dev] (block-cyclic local blocks of a ScaLAPACK descriptor),
  * eigx_gev[_dev] (KMATH_EIGEN_GEV), eigx_h[_dev] (complex Hermitian eigen_h), eigx_hgev[_dev] (KMATH_EIGEN_HGEV, an
- * extension: complex Hermitian generalised problem).
+ * extension: complex Hermitian generalised problem), eigx_sx_range / eigx_s_range[_dev] (an extension: eigenpairs il .. iu
+ * of the ascending spectrum, one GPU).
  */
 #ifndef EIGENEXA_AMD_H
 #define EIGENEXA_AMD_H
@@ -122,7 +123,10 @@ int eigx_get_matdims(int n, int* nx, int* ny, int m_forward, int m_backward, cha
 /* the same rule for an explicit x_procs x y_procs grid; pure arithmetic (usable before eigx_init, without a GPU) */
 int eigx_matdims_for_grid(int n, int x_procs, int y_procs, int m_forward, int m_backward, char mode, int* nx, int* ny);
 
-/* replaces eigen_memory_internal src/eigen_libs0.F:1395-1549: bytes of device workspace a solve needs */
+/* replaces eigen_memory_internal src/eigen_libs0.F:1395-1549: bytes of device workspace a solve needs.  It covers the
+ * reference's solvers (eigx_sx / eigx_s); the index-range extension keeps its own pooled buffers ("sub.": inverse-iteration
+ * scratch of at most min(4 GiB, 8 n^2) bytes, about 2 n m + 2 m^2 doubles of bases, n iu doubles on a fallback with il > 1)
+ * on top of whatever earlier solves left in the pool, which never shrinks before eigx_free. */
 int64_t eigx_memory_internal(int n, int lda, int ldz, int m_forward, int m_backward);
 /* bytes of device memory the library holds right now (pooled workspace + communication windows); the tests check it
  * against eigx_memory_internal and that it scales like 1/P on several ranks.  -1 before eigx_init. */
@@ -168,6 +172,36 @@ int eigx_sx_dev(int n, int nvec, double* a_dev, int lda, double* w_dev, double* 
                 int m_forward, int m_backward, char mode);
 int eigx_s_dev(int n, int nvec, double* a_dev, int lda, double* w_dev, double* z_dev, int ldz,
                int m_forward, int m_backward, char mode);
+
+/* Index-range solves -- EXTENSION, not in the reference (whose nvec only trims the back-transformation and always means
+ * "the lowest nvec"; LAPACK callers know this as range = 'I', il, iu).  One GPU only: with more than one rank the four
+ * entries print one line and return EIGX_ERR_BAD_ARG.  il, iu are 1-based and inclusive, 1 <= il <= iu <= n,
+ * m = iu - il + 1; on return w(1:m) holds eigenvalues il .. iu of the ascending spectrum and z(:, 1:m) the matching
+ * orthonormal eigenvectors; w and z need room for m entries / columns only, nothing beyond is touched.  mode 'A'
+ * eigenpairs, 'N' eigenvalues only (z untouched, may be NULL); anything else is EIGX_ERR_BAD_ARG.  a as for eigx_sx: upper
+ * triangle read, destroyed, a(1:3,1) = flops / seconds / -1; same scaling, NaN / Inf check (w(1:m) = NaN,
+ * EIGX_ERR_NONFINITE), odd-lda copy and wait on the default stream.
+ * Method (csrc/subset.hip): band reduction as for eigx_sx / eigx_s, Sturm multi-section on the index
+ * window, inverse iteration on the band matrix with one eigenvector per GPU thread, CholQR2 and Rayleigh-Ritz through the
+ * fp64 MFMA GEMM, back-transformation of the m columns.  Work and workspace after the reduction scale with m; no D&C
+ * workspace of size n is requested.  Fallback rule: when the acceptance test of the stage refuses its result (Cholesky
+ * breakdown, or cond(L) above 10^key19), or when 100 m > key17 n (the size rule), the full divide and conquer computes the
+ * lowest iu pairs and columns il .. iu are returned: the caller always gets a result that meets the reference's gates. */
+int eigx_sx_range(int n, int il, int iu, double* a, int lda, double* w, double* z, int ldz, int m_forward, int m_backward,
+                  char mode);
+int eigx_s_range(int n, int il, int iu, double* a, int lda, double* w, double* z, int ldz, int m_forward, int m_backward,
+                 char mode);
+int eigx_sx_range_dev(int n, int il, int iu, double* a, int lda, double* w, double* z, int ldz, int m_forward,
+                      int m_backward, char mode);
+int eigx_s_range_dev(int n, int il, int iu, double* a, int lda, double* w, double* z, int ldz, int m_forward, int m_backward,
+                     char mode);
+/* the last range call: path 1 = subset path, 2 = fell back to the full D&C, 3 = full D&C by the size rule; m; cond = the
+ * conditioning estimate max / min diag(L) of the acceptance test (0 when it did not run).  Any pointer may be NULL.  Only
+ * the four solver entries (and eigx_sx / eigx_s routed by key 18) write this record; the stage entries do not. */
+int eigx_range_info(int* path, int* m, double* cond);
+/* stage seconds of the last range call: [0] bisection [1] inverse iteration [2] orthonormalisation + Rayleigh-Ritz (or
+ * the fallback D&C) [3] back-transformation (tools/gpu_range_time.py) */
+int eigx_range_timers(double* out4);
 
 /* ScaLAPACK interop without a redistribution step.  The reference asks block-cyclic callers to
  * convert with pdgemr2d into its cyclic layout first (manual 3.4; benchmark/ev_test.f:68-84 does the reverse for the
@@ -233,6 +267,17 @@ int eigx_hgev_dev(int n, double* a_dev, int lda, double* b_dev, int ldb, double*
  * Used by modes 'N', 'S', 'C' (alone) and 'X' (after the divide and conquer), src/eigen_sx.F:200-222. */
 int eigx_band_bisect_dev(int n, const double* d_dev, const double* e_dev, int lde, int band, double* w_dev);
 
+/* EXTENSION (no counterpart in the reference): eigenvalues il .. iu (1-based, inclusive) of the band matrix by the same
+ * multi-section on an index window, w_dev[0 .. iu - il] ascending. */
+int eigx_band_bisect_range_dev(int n, int il, int iu, const double* d_dev, const double* e_dev, int lde, int band,
+                               double* w_dev);
+/* EXTENSION, the counterpart of eigx_band_dc_dev for a chosen set: m approximate eigenvalues w_sel_dev of the band matrix
+ * (d, e(lde, 2), band 1 or 2) -> Ritz values w_out_dev[m] (ascending) and an orthonormal n x m eigenvector basis
+ * z_dev(ldz, m).  One GPU.  Returns EIGX_OK, or a positive value when its acceptance test refused the result (1: a Cholesky
+ * factorisation of CholQR2 broke down, 2: cond(L) above 10^key19); z_dev and w_out_dev are then not to be used. */
+int eigx_band_eigvec_dev(int n, int m, const double* d_dev, const double* e_dev, int lde, int band, const double* w_sel_dev,
+                         double* w_out_dev, double* z_dev, int ldz);
+
 /* replaces eigen_common_trbakwy(n,nvec,a,lda,z,ldz,e,m,nb) src/trbakwy4.F:77-222 */
 int eigx_trbak_dev(int n, int nvec, const double* a_dev, int lda, double* z_dev, int ldz,
                    const double* e_dev, int lde, int m_backward, int band);
@@ -281,7 +326,14 @@ int eigx_profile_read_kinds(double* out, int nkinds);
  * large-N code paths at small sizes); key 10 = 0: the column-formation kernel always uses its largest load batches (A/B);
  * key 11 = largest active size at which the fused symmetric mat-vec uses its branch-free pipelined form; keys 15 / 16 = 0:
  * the one-GPU D&C runs its passes one after the other / one product launch per merge instead of one per low height
- * (key 15 >= 2: merges larger than this use the side stream).  Returns the previous value, or -1 for an unknown key.
+ * (key 15 >= 2: merges larger than this use the side stream).  Index-range solves (extension): key 17 = size rule in
+ * percent (0 .. 100), windows with 100 m > key17 n go straight to the full D&C; a negative value (the default, -1) selects
+ * it from n by the measured table of DESIGN section 8b: 10 from n = 32768 on, 3 from n = 16384 on, 0 below (at n = 8192 the
+ * subset path was slower than the nvec = m route at every m, so it is not taken there unless the key is set); key 18 = 1: eigx_sx / eigx_s / _dev calls with mode 'A' and 0 < nvec < n are routed through the range path
+ * as il = 1, iu = nvec, w(nvec+1:n) filled by bisection (default 0: results bit-identical to earlier versions);
+ * key 19 = log10 of the acceptance bound on cond(L) (default 6; exists so that a test can force the fallback at a small
+ * size, like keys 7-9; 0 .. 16); values outside the stated ranges of keys 17 - 19 are refused.  Returns the previous value, or
+ * -1 for an unknown key or a refused value.
  * Not part of the reference's interface. */
 int eigx_tune(int key, int value);
 
