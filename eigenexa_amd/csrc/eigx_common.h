@@ -85,8 +85,9 @@ struct SolveRequest {
   int nvec;
   bool want_vec;
 };
+inline char upper_case(char c) { return (c >= 'a' && c <= 'z') ? (char)(c - 'a' + 'A') : c; }
 inline SolveRequest normalize_request(int n, int nvec, char mode) {
-  if (mode >= 'a' && mode <= 'z') mode = (char)(mode - 'a' + 'A');
+  mode = upper_case(mode);
   if (nvec == 0) mode = 'N';
   if (nvec < 0) nvec = -nvec;
   if (nvec > n) nvec = n;

@@ -180,9 +180,42 @@ void cols_to_cyclic_dev(Context& ctx, int n, int nvec, int nb, int zc, int zc0, 
 int64_t solver_workspace_bytes(const Context& ctx, int n, int lda, int ldz, int mf, int mb);
 // eigen_scaling of every solver (src/eigen_scaling.F:86-150): max |a| and a non-finite flag over the upper triangle of
 // this rank's 2-D cyclic block of an n x n matrix (real, or interleaved complex with lda in complex elements: max of
-// |Re|, |Im|, Im of the diagonal not read), combined over the ranks.  NaN / Inf anywhere: w(:) = NaN, errinfo = -1,
-// EIGX_ERR_NONFINITE.  Otherwise *sigma = the factor to scale the matrix by (1 = none).
-int eigen_scaling(Context& ctx, const double* a, int lda, bool cplx, int n, double* w, double* sigma);
+// |Re|, |Im|, Im of the diagonal not read), combined over the ranks.  NaN / Inf anywhere: w(1:nw) = NaN (nw < 0: all n;
+// an index-range solve's w may hold fewer), errinfo = -1, EIGX_ERR_NONFINITE.  Otherwise *sigma = the factor to scale
+// the matrix by (1 = none).
+int eigen_scaling(Context& ctx, const double* a, int lda, bool cplx, int n, double* w, double* sigma, int nw = -1);
+
+// The frame of a whole solve: what eigen_sx / eigen_s (solve_dev), the index-range solves (range_solve_dev) and the two
+// eigen_h drivers (herm.hip) open and close with.  A driver calls begin, (real drivers) stage_inputs, scale, marks its
+// stage boundaries in t1 .. t3, and leaves through finish.  Everything is enqueued on ctx.stream in the order of the calls.
+struct SolveFrame {
+  Context& ctx;
+  const int n;
+  const bool cplx;        // eigen_h: a and z are interleaved complex, the statistics go into a(1:2,1)
+  double t0 = 0.0, t1 = 0.0, t2 = 0.0, t3 = 0.0;   // entry; start / end of the reduction; end of the eigenvalue stage
+  double sigma = 1.0;     // scale: the factor the matrix was (real) or is to be (eigen_h) scaled by
+  double* a_user = nullptr;   // stage_inputs (eigen_h: herm_solve_dev): the caller's arrays behind the internal stand-ins
+  double* z_user = nullptr;
+  int ldz_user = 0;
+  int zcols = 0;          // stage_inputs: eigenvector columns per rank of the internal z (0: the caller's z is used as it is)
+  SolveFrame(Context& c, int n_, bool cplx_) : ctx(c), n(n_), cplx(cplx_) {}
+  // Entry: initialised? -> n <= 0 (warning of src/eigen_sx.F:95-98) -> args_ok, the driver's own pointer and
+  // leading-dimension checks -> device, the caller's default stream drained, errinfo / timers / (several ranks)
+  // communication seconds reset -> t0.  EIGX_OK or the status to return.
+  int begin(bool args_ok);
+  // Real drivers: a (and z, if wanted) as the kernels need them -- even leading dimension, 16-byte aligned base, cyclic
+  // layout (nb > 1: block-cyclic in) -- replaced by internal copies where the caller's are not.
+  int stage_inputs(double*& a, int& lda, double*& z, int& ldz, bool want_vec, int nvec, int nb);
+  void return_z(const double* z, int ldz, int ncols);   // one GPU: the stand-in of stage_inputs -> the caller's z
+  // eigen_scaling; a non-finite input fills w(1:nw) with NaN.  Real: the upper triangle of the cyclic block is scaled by
+  // sigma here; eigen_h scales where it splits the planes.
+  int scale(double* a, int lda, double* w, int nw);
+  // Exit: w(1:nw) /= sigma -> drain -> flops = 4/3 n^3 + f_mid + 2 bt_cols n^2 (bt_cols = 0: no back-transformation),
+  // timers 0 .. 4 and 12 -> statistics into the caller's a(1:3,1) (eigen_h: a(1:2,1)) where this rank holds stat_rows > 0
+  // rows of that column -> drain.  Real drivers only, as in the reference: flops negated when f_mid == 0; seconds of
+  // communication in timers[4] and a(3,1) (-1 on one GPU).
+  int finish(double* w, int nw, double f_mid, int bt_cols, int stat_rows);
+};
 // Host staging of a local block of nr x nc elements of esz (8 or 16) bytes: a pooled device buffer with the leading
 // dimension host_ld(nr) (h == nullptr: allocated only), and the copy of a device block back to the host
 inline int host_ld(int nr) { return pad_ld(nr + 2); }

@@ -716,36 +716,143 @@ __global__ void h_identity_kernel(double* __restrict__ z, int ldz, int c0, int c
 }
 }  // namespace
 
-// One GPU.  a, z: device, interleaved complex(8), leading dimensions in complex elements
-static int herm_solve_full(Context& ctx, int n, int nvec, double* a, int lda, double* w, double* z, int ldz, int mf, int mb,
-                           char mode) {
-  if (!ctx.initialized) return EIGX_ERR_NOT_INITIALIZED;
-  if (n <= 0) {
-    fprintf(stderr, "[eigx] warning: non-positive dimension is invalid\n");   // src/eigen_h.F:91-94
-    return EIGX_ERR_BAD_ARG;
-  }
-  if (!a || !w || lda < n) return EIGX_ERR_BAD_ARG;
-  const SolveRequest rq = normalize_request(n, nvec, mode);   // src/eigen_h.F:104-106
-  nvec = rq.nvec;
-  mode = rq.mode;
-  if (mode != 'N' && mode != 'A' && mode != 'X' && mode != 'S') mode = 'A';   // 'S': identity + bisection + back-transformation (src/eigen_h.F:207-210)
-  const bool want_vec = rq.want_vec;
-  if (want_vec && (!z || ldz < n)) return EIGX_ERR_BAD_ARG;
-  int m = mf <= 0 ? 48 : mf;
-  if (m > HM) m = HM;
-  if (m > n) m = n;
-  EIGX_HIP_CHECK(hipSetDevice(ctx.device));
-  EIGX_HIP_CHECK(hipStreamSynchronize(nullptr));   // the caller's default-stream work on the arguments (see solve_dev)
-  hipStream_t st = ctx.stream;
-  ctx.errinfo = 0;
-  for (int q = 0; q < 16; ++q) ctx.timers[q] = 0.0;
-  const double t0 = now_s();
+// ---- host side: what both drivers share ------------------------------------------------------------------------------
+namespace {
 
+// Workspace of the reduction apart from the planes of A (H.Ar / H.Ai and their layout are the driver's: "h." the whole
+// matrix, "hs." this rank's tile columns): the panel U | W of m columns, its packed forms P1 .. P3 for the trailing
+// update, x, beta, d, e and the partial sums of the two kernels of a column.  Fills the rest of H.
+struct HWork { double *P1, *P2, *P3; int lde, nwg; };
+HWork h_workspace(Context& ctx, int n, int m, HArgs& H) {
+  const int ldp = H.ldp;
+  HWork W;
+  H.Ur = ctx.pool.get_t<double>("h.UW", (size_t)4 * ldp * m);   // the four panel planes in one buffer (one fill per panel)
+  H.Ui = H.Ur + (size_t)ldp * m;
+  H.Wr = H.Ui + (size_t)ldp * m;
+  H.Wi = H.Wr + (size_t)ldp * m;
+  W.P1 = ctx.pool.get_t<double>("h.P1", (size_t)ldp * 4 * m);
+  W.P2 = ctx.pool.get_t<double>("h.P2", (size_t)ldp * 4 * m);
+  W.P3 = ctx.pool.get_t<double>("h.P3", (size_t)ldp * 4 * m);
+  H.xr = ctx.pool.get_t<double>("h.xr", (size_t)ldp); H.xi = ctx.pool.get_t<double>("h.xi", (size_t)ldp);
+  H.beta = ctx.pool.get_t<double>("h.beta", (size_t)2 * n + 2);
+  W.lde = (n + 3) / 4 * 4;
+  H.d = ctx.pool.get_t<double>("h.d", (size_t)n);
+  H.e = ctx.pool.get_t<double>("h.e", (size_t)W.lde);
+  W.nwg = ceil_div(n, 64) + 1;
+  const int nt_max = ceil_div(n, HTL) + 1;
+  const int npdc_max = ceil_div(n, PDR) + 1;
+  H.pn = ctx.pool.get_t<double>("h.pn", (size_t)2 * W.nwg);                        // two parities
+  H.ps = ctx.pool.get_t<double>("h.ps", (size_t)nt_max * (nt_max + 1));            // 2 per mat-vec tile
+  H.pd = ctx.pool.get_t<double>("h.pd", (size_t)npdc_max * HM * 4);
+  H.yrr = ctx.pool.get_t<double>("h.yrr", (size_t)nt_max * ldp);
+  H.yri = ctx.pool.get_t<double>("h.yri", (size_t)nt_max * ldp);
+  H.ycr = ctx.pool.get_t<double>("h.ycr", (size_t)nt_max * ldp);
+  H.yci = ctx.pool.get_t<double>("h.yci", (size_t)nt_max * ldp);
+  return W;
+}
+
+// Where the reduction stands.  Two launches per column: K1 (h_step: finish the previous column, form this one) and K3
+// (h_matvec: mat-vec + panel dots); the norm partials alternate between two buffers (K1 reads the previous column's
+// while it writes this column's).
+struct HColumns {
+  int k = 0, par = 0;                              // columns in the panel; parity of the norm partials
+  int Lp = 0, ntp = 0, npdcp = 0, npartsp = 0;     // the column that is waiting to be finished (Lp = 0: none)
+  double* pnb[2];
+};
+void h_zero_panel(hipStream_t st, const HArgs& H, HColumns& C, int m) {
+  hipLaunchKernelGGL(fill_kernel, dim3(512), dim3(256), 0, st, H.Ur, (size_t)4 * H.ldp * m, 0.0);
+  C.k = 0;
+}
+HColumns h_start_reduction(hipStream_t st, const HArgs& H, const HWork& W, int n, int m) {
+  HColumns C;
+  C.pnb[0] = H.pn; C.pnb[1] = H.pn + W.nwg;
+  hipLaunchKernelGGL(fill_kernel, dim3(64), dim3(256), 0, st, H.e, (size_t)W.lde, 0.0);
+  hipLaunchKernelGGL(fill_kernel, dim3(64), dim3(256), 0, st, H.beta, (size_t)2 * n + 2, 0.0);
+  h_zero_panel(st, H, C, m);
+  return C;
+}
+// K1 for column i (do_x = 0: only finish the pending one) on the view Hv of the workspace.  One GPU: the mat-vec's tile
+// partials (ntp + 1 per row, nps tiles of u^H q).  Sharded: their sums over tiles and ranks (ntp = 0, nps = 1) and the raw
+// column i from its owner (acr, aci).  Returns its number of workgroups = norm partials of the new column.
+int h_step(hipStream_t st, HArgs& Hv, const HColumns& C, int i, int do_x, int ntp, int nps, const double* acr, const double* aci) {
+  const int rows = std::max(do_x ? i + 1 : 0, C.Lp);
+  Hv.pn = C.pnb[C.par ^ 1];
+  hipLaunchKernelGGL(h_step_kernel, dim3(ceil_div(rows, 64)), dim3(HS), 0, st, Hv, i, do_x, C.Lp, C.Lp ? C.k - 1 : 0, ntp, C.npdcp,
+                     C.npartsp, C.pnb[C.par], nps, acr, aci);
+  return ceil_div(rows, 64);
+}
+// K3 for the column of L rows that h_step formed, over ntl tiles (the whole triangle, or this rank's share: a rank
+// without an active tile still sends one workgroup for the scalars); the column becomes the pending one
+void h_matvec(hipStream_t st, HArgs& H, HColumns& C, int L, int nparts, int ntl) {
+  const int npdc = ceil_div(L, PDR), nt = ceil_div(L, HTL);
+  const int grid = std::max(1, C.k * npdc + ntl);
+  H.pn = C.pnb[C.par];
+  if (nt <= H_HEMV8_NT)
+    hipLaunchKernelGGL(h_hemv_kernel<8>, dim3(grid), dim3(512), 0, st, H, L, C.k, nt, npdc, 2, nparts, ntl);
+  else
+    hipLaunchKernelGGL(h_hemv_kernel<4>, dim3(grid), dim3(HTH), 0, st, H, L, C.k, nt, npdc, 4, nparts, ntl);
+  C.Lp = L; C.ntp = nt; C.npdcp = npdc; C.npartsp = nparts;
+  C.par ^= 1;
+  ++C.k;
+}
+// panel end, the pending column finished (u, v in the panel): the packed operands of the trailing update of the
+// remaining nr x nr block, two real GEMMs with K = 4k per tile set
+void h_pack_panel(hipStream_t st, const HArgs& H, const HWork& W, HColumns& C, int nr) {
+  C.Lp = 0;
+  hipLaunchKernelGGL(h_pack_kernel, dim3(ceil_div(nr, 256), C.k), dim3(256), 0, st, H, nr, C.k, W.P1, W.P2, W.P3);
+}
+
+// dynamic LDS of h_tinv_kernel (the packed triangle of S^H, two planes): more than a kernel gets without asking
+size_t h_tinv_shm() {
+  const size_t shm = (size_t)2 * (HMB * (HMB + 1) / 2) * sizeof(double);
+  static bool attr = false;
+  if (!attr) {
+    EIGX_HIP_CHECK(hipFuncSetAttribute((const void*)h_tinv_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm));
+    attr = true;
+  }
+  return shm;
+}
+
+// The real tridiagonal eigenproblem (dc2 / bisection): w, and with want_vec the eigenvector columns [c0, c0 + cn) of the
+// first nvec as the planes Zr | Zi (= 0) of pool buffer `name`: both planes in one buffer (V^H Z is one batched product
+// over them), the imaginary plane H_PLANE_SKEW off.  A rank's planes hold zc columns and are sized for zcap; one GPU:
+// c0 = 0, cn = zc = nvec.
+struct HPlanes { double *Zr, *Zi; int ldzp; };
+HPlanes h_tridiagonal_stage(Context& ctx, int n, int nvec, char mode, bool want_vec, const double* d, const double* e, int lde,
+                            double* w, int c0, int cn, int zc, int zcap, const char* name) {
+  hipStream_t st = ctx.stream;
+  HPlanes Z = {nullptr, nullptr, pad_ld(n + 2)};
+  if (!want_vec) {
+    band_bisect_dev(ctx, n, d, e, lde, 1, w);
+    return Z;
+  }
+  const size_t zplane = (size_t)Z.ldzp * (zcap + 1) + H_PLANE_SKEW;
+  Z.Zr = ctx.pool.get_t<double>(name, 2 * zplane);
+  Z.Zi = Z.Zr + zplane;
+  if (mode == 'S') {
+    // Z = I (the first nvec columns), eigenvalues by bisection: the back-transformation then delivers the unitary
+    // matrix of the reduction itself, Z^H A Z = T (src/eigen_h.F:207-210, eigen_identity src/eigen_identity.F)
+    hipLaunchKernelGGL(fill_kernel, dim3(1024), dim3(256), 0, st, Z.Zr, (size_t)Z.ldzp * zc, 0.0);
+    if (cn > 0) hipLaunchKernelGGL(h_identity_kernel, dim3(ceil_div(cn, 256)), dim3(256), 0, st, Z.Zr, Z.ldzp, c0, cn);
+    band_bisect_dev(ctx, n, d, e, lde, 1, w);
+  } else {
+    band_dc_dev(ctx, n, nvec, d, e, lde, 1, w, Z.Zr, Z.ldzp);
+  }
+  if (mode == 'X') band_bisect_dev(ctx, n, d, e, lde, 1, w);
+  hipLaunchKernelGGL(fill_kernel, dim3(1024), dim3(256), 0, st, Z.Zi, (size_t)Z.ldzp * zc, 0.0);
+  return Z;
+}
+}  // namespace
+
+// One GPU.  a, z: device, interleaved complex(8), leading dimensions in complex elements; the request is checked and
+// cleaned up, the frame begun (herm_solve_dev)
+static int herm_solve_full(SolveFrame& F, int n, int nvec, double* a, int lda, double* w, double* z, int ldz, int m, int mb,
+                           char mode, bool want_vec) {
+  Context& ctx = F.ctx;
+  hipStream_t st = ctx.stream;
   // ---- eigen_scaling_h -------------------------------------------------------------------------------------------
-  double sigma = 1.0;
-  const int rc_sc = eigen_scaling(ctx, a, lda, true, n, w, &sigma);
-  if (rc_sc != EIGX_OK) return rc_sc;
-  if (sigma != 1.0) hipLaunchKernelGGL(h_scale_kernel, dim3(8, n), dim3(256), 0, st, a, lda, n, sigma);
+  if (const int rc = F.scale(a, lda, w, n)) return rc;
+  if (F.sigma != 1.0) hipLaunchKernelGGL(h_scale_kernel, dim3(8, n), dim3(256), 0, st, a, lda, n, F.sigma);
 
   // ---- workspace -----------------------------------------------------------------------------------------------------
   const int ld = pad_ld(n + 2);
@@ -754,78 +861,28 @@ static int herm_solve_full(Context& ctx, int n, int nvec, double* a, int lda, do
   H.n = n; H.ld = ld; H.ldp = ldp; H.P = 1; H.p = 0;
   H.Ar = ctx.pool.get_t<double>("h.Ar", (size_t)ld * (n + HMB));   // HMB columns of slack: the batched Gram products of phase A
   H.Ai = ctx.pool.get_t<double>("h.Ai", (size_t)ld * (n + HMB) + H_PLANE_SKEW) + H_PLANE_SKEW;
-  H.Ur = ctx.pool.get_t<double>("h.UW", (size_t)4 * ldp * m);   // the four panel planes in one buffer (one fill per panel)
-  H.Ui = H.Ur + (size_t)ldp * m;
-  H.Wr = H.Ui + (size_t)ldp * m;
-  H.Wi = H.Wr + (size_t)ldp * m;
-  double* P1 = ctx.pool.get_t<double>("h.P1", (size_t)ldp * 4 * m);
-  double* P2 = ctx.pool.get_t<double>("h.P2", (size_t)ldp * 4 * m);
-  double* P3 = ctx.pool.get_t<double>("h.P3", (size_t)ldp * 4 * m);
-  H.xr = ctx.pool.get_t<double>("h.xr", (size_t)ldp); H.xi = ctx.pool.get_t<double>("h.xi", (size_t)ldp);
-  H.beta = ctx.pool.get_t<double>("h.beta", (size_t)2 * n + 2);
-  const int lde = (n + 3) / 4 * 4;
-  H.d = ctx.pool.get_t<double>("h.d", (size_t)n);
-  H.e = ctx.pool.get_t<double>("h.e", (size_t)lde);
-  const int nwg = ceil_div(n, 64) + 1;
-  const int nt_max = ceil_div(n, HTL) + 1;
-  const int npdc_max = ceil_div(n, PDR) + 1;
-  H.pn = ctx.pool.get_t<double>("h.pn", (size_t)2 * nwg);                         // two parities
-  H.ps = ctx.pool.get_t<double>("h.ps", (size_t)nt_max * (nt_max + 1));            // 2 per mat-vec tile
-  H.pd = ctx.pool.get_t<double>("h.pd", (size_t)npdc_max * HM * 4);
-  H.yrr = ctx.pool.get_t<double>("h.yrr", (size_t)nt_max * ldp);
-  H.yri = ctx.pool.get_t<double>("h.yri", (size_t)nt_max * ldp);
-  H.ycr = ctx.pool.get_t<double>("h.ycr", (size_t)nt_max * ldp);
-  H.yci = ctx.pool.get_t<double>("h.yci", (size_t)nt_max * ldp);
-
+  const HWork ws = h_workspace(ctx, n, m, H);
   hipLaunchKernelGGL(h_split_kernel, dim3(8, n), dim3(256), 0, st, a, lda, n, H.Ar, H.Ai, ld);
-  hipLaunchKernelGGL(fill_kernel, dim3(64), dim3(256), 0, st, H.e, (size_t)lde, 0.0);
-  hipLaunchKernelGGL(fill_kernel, dim3(64), dim3(256), 0, st, H.beta, (size_t)2 * n + 2, 0.0);
-  auto zero_panel = [&]() { hipLaunchKernelGGL(fill_kernel, dim3(512), dim3(256), 0, st, H.Ur, (size_t)4 * ldp * m, 0.0); };
-  zero_panel();
+  HColumns C = h_start_reduction(st, H, ws, n, m);
 
   // ---- eigen_hrd: Hermitian -> real tridiagonal ---------------------------------------------------------------------
-  const double t1 = now_s();
-  // two launches per column: K1 (finish the previous column, form this one) and K3 (mat-vec + panel dots); the norm
-  // partials alternate between two buffers (K1 reads the previous column's while it writes this column's)
-  int k = 0, par = 0;
-  int Lp = 0, ntp = 0, npdcp = 0, npartsp = 0;     // the column that is waiting to be finished (Lp = 0: none)
-  double* pnb[2] = {H.pn, H.pn + nwg};
-  auto step = [&](int i, int do_x) {
-    const int rows = std::max(do_x ? i + 1 : 0, Lp);
-    H.pn = pnb[par ^ 1];
-    hipLaunchKernelGGL(h_step_kernel, dim3(ceil_div(rows, 64)), dim3(HS), 0, st, H, i, do_x, Lp, Lp ? k - 1 : 0, ntp, npdcp,
-                       npartsp, pnb[par], ntp * (ntp + 1) / 2, (const double*)nullptr, (const double*)nullptr);
-    return ceil_div(rows, 64);
-  };
+  F.t1 = now_s();
+  auto step = [&](int i, int do_x) { return h_step(st, H, C, i, do_x, C.ntp, C.ntp * (C.ntp + 1) / 2, nullptr, nullptr); };
   for (int i = n - 1; i >= 1; --i) {
-    const int L = i;
+    const int nt = ceil_div(i, HTL);
     const int nparts = step(i, 1);
-    const int npdc = ceil_div(L, PDR);
-    const int nt = ceil_div(L, HTL);
-    H.pn = pnb[par];
-    if (nt <= H_HEMV8_NT)
-      hipLaunchKernelGGL(h_hemv_kernel<8>, dim3(k * npdc + nt * (nt + 1) / 2), dim3(512), 0, st, H, L, k, nt, npdc, 2, nparts,
-                         nt * (nt + 1) / 2);
-    else
-      hipLaunchKernelGGL(h_hemv_kernel<4>, dim3(k * npdc + nt * (nt + 1) / 2), dim3(HTH), 0, st, H, L, k, nt, npdc, 4, nparts,
-                         nt * (nt + 1) / 2);
-    Lp = L; ntp = nt; npdcp = npdc; npartsp = nparts;
-    par ^= 1;
-    ++k;
-    if (k == m || i == 1) {
-      // trailing update of the remaining i x i block, two real GEMMs with K = 4k; the pending column is finished
-      // (u, v into the panel) first
+    h_matvec(st, H, C, i, nparts, nt * (nt + 1) / 2);
+    if (C.k == m || i == 1) {
+      // trailing update of the remaining i x i block; the pending column is finished first
       (void)step(i - 1, 0);
-      Lp = 0;
       const int nr = i;
-      hipLaunchKernelGGL(h_pack_kernel, dim3(ceil_div(nr, 256), k), dim3(256), 0, st, H, nr, k, P1, P2, P3);
+      h_pack_panel(st, H, ws, C, nr);
       // only the tiles that meet the upper triangle: after the split nothing reads the strict lower triangle any more
       // (K1 reads A(0:i, i), the mat-vec the tiles ty <= tx with the lower half of a diagonal tile masked, the
       // back-transformation zeroes below the reflectors first)
-      dgemm_dev(st, 'N', 'T', nr, nr, 4 * k, -1.0, P1, ldp, P3, ldp, 1.0, H.Ar, ld, 1);
-      dgemm_dev(st, 'N', 'T', nr, nr, 4 * k, -1.0, P2, ldp, P3, ldp, 1.0, H.Ai, ld, 1);
-      zero_panel();
-      k = 0;
+      dgemm_dev(st, 'N', 'T', nr, nr, 4 * C.k, -1.0, ws.P1, ldp, ws.P3, ldp, 1.0, H.Ar, ld, 1);
+      dgemm_dev(st, 'N', 'T', nr, nr, 4 * C.k, -1.0, ws.P2, ldp, ws.P3, ldp, 1.0, H.Ai, ld, 1);
+      h_zero_panel(st, H, C, m);
     }
   }
   (void)step(0, 1);   // d_0 = Re A(0,0)
@@ -842,12 +899,7 @@ static int herm_solve_full(Context& ctx, int n, int nvec, double* a, int lda, do
   if (want_vec && n > 1) {
     double* Gall = ctx.pool.get_t<double>("h.Gall", (size_t)nblk * 4 * HMB * HMB);
     Tall = ctx.pool.get_t<double>("h.Tall", (size_t)nblk * 2 * HMB * HMB);
-    const size_t shm = (size_t)2 * (HMB * (HMB + 1) / 2) * sizeof(double);
-    static bool attr = false;
-    if (!attr) {
-      EIGX_HIP_CHECK(hipFuncSetAttribute((const void*)h_tinv_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm));
-      attr = true;
-    }
+    const size_t shm = h_tinv_shm();
     hipLaunchKernelGGL(h_zero_below_kernel, dim3(8, n), dim3(256), 0, st, H.Ar, H.Ai, ld, n, n);
     // block b = columns 1 + b bw ... of A; G_b (ld 2 HMB) = [Vr^T Vr, Vr^T Vi; Vi^T Vr, Vi^T Vi] with the second half at
     // offset bw.  The last block may be narrower: its product reads up to bw - 1 columns past the matrix (allocated,
@@ -860,32 +912,11 @@ static int herm_solve_full(Context& ctx, int n, int nvec, double* a, int lda, do
     hipLaunchKernelGGL(h_tinv_kernel, dim3(nblk), dim3(HMB), shm, st, Gall, H.beta, 1, bw, n, Tall);
   }
   EIGX_HIP_CHECK(hipStreamSynchronize(st));
-  const double t2 = now_s();
+  F.t2 = now_s();
 
   // ---- real tridiagonal eigenproblem (dc2 / bisect) --------------------------------------------------------------------
-  double* Zr = nullptr;
-  double* Zi = nullptr;
-  const int ldzp = pad_ld(n + 2);
-  if (!want_vec) {
-    band_bisect_dev(ctx, n, H.d, H.e, lde, 1, w);
-  } else {
-    // both planes in one buffer (V^H Z is one batched product over them), the imaginary plane H_PLANE_SKEW off
-    const size_t zplane = (size_t)ldzp * (n + 1) + H_PLANE_SKEW;
-    Zr = ctx.pool.get_t<double>("h.Zri", 2 * zplane);
-    Zi = Zr + zplane;
-    if (mode == 'S') {
-      // Z = I (the first nvec columns), eigenvalues by bisection: the back-transformation then delivers the unitary
-      // matrix of the reduction itself, Z^H A Z = T (src/eigen_h.F:207-210, eigen_identity src/eigen_identity.F)
-      hipLaunchKernelGGL(fill_kernel, dim3(1024), dim3(256), 0, st, Zr, (size_t)ldzp * nvec, 0.0);
-      hipLaunchKernelGGL(h_identity_kernel, dim3(ceil_div(nvec, 256)), dim3(256), 0, st, Zr, ldzp, 0, nvec);
-      band_bisect_dev(ctx, n, H.d, H.e, lde, 1, w);
-    } else {
-      band_dc_dev(ctx, n, nvec, H.d, H.e, lde, 1, w, Zr, ldzp);
-    }
-    if (mode == 'X') band_bisect_dev(ctx, n, H.d, H.e, lde, 1, w);
-    hipLaunchKernelGGL(fill_kernel, dim3(1024), dim3(256), 0, st, Zi, (size_t)ldzp * nvec, 0.0);
-  }
-  const double t3 = now_s();
+  const auto [Zr, Zi, ldzp] = h_tridiagonal_stage(ctx, n, nvec, mode, want_vec, H.d, H.e, ws.lde, w, 0, nvec, nvec, n, "h.Zri");
+  F.t3 = now_s();
 
   // ---- eigen_hrbakwyx: z = H_{n-1}^H ... H_1^H y in blocks of HMB reflectors -------------------------------------------
   if (want_vec && n > 1) {
@@ -904,22 +935,7 @@ static int herm_solve_full(Context& ctx, int n, int nvec, double* a, int lda, do
     }
   }
   if (want_vec) hipLaunchKernelGGL(h_join_kernel, dim3(8, nvec), dim3(256), 0, st, Zr, Zi, ldzp, n, nvec, z, ldz);
-  if (sigma != 1.0 && sigma != 0.0)
-    hipLaunchKernelGGL(scale_vec_kernel, dim3((n + 255) / 256), dim3(256), 0, st, w, n, 1.0 / sigma);
-  EIGX_HIP_CHECK(hipStreamSynchronize(st));
-  EIGX_HIP_CHECK(hipGetLastError());
-  const double t4 = now_s();
-
-  // ---- statistics (src/eigen_h.F:284-288): a(1,1) = flops, a(2,1) = seconds (real parts) ------------------------------
-  const double f_red = 4.0 / 3.0 * (double)n * n * n;
-  const double f_dc = ctx.timers[11];
-  const double f_bt = want_vec ? 2.0 * (double)nvec * n * n : 0.0;
-  const double ret = f_red + f_dc + f_bt;
-  ctx.timers[0] = t4 - t0; ctx.timers[1] = t2 - t1; ctx.timers[2] = t3 - t2; ctx.timers[3] = t4 - t3; ctx.timers[12] = ret;
-  const double stats[4] = {ret, 0.0, t4 - t0, 0.0};
-  EIGX_HIP_CHECK(hipMemcpyAsync(a, stats, (size_t)(n >= 2 ? 4 : 2) * 8, hipMemcpyHostToDevice, st));
-  EIGX_HIP_CHECK(hipStreamSynchronize(st));
-  return EIGX_OK;
+  return F.finish(w, n, ctx.timers[11], want_vec ? nvec : 0, n);
 }
 
 // =====================================================================================================================
@@ -1018,31 +1034,17 @@ __global__ void hs_join_cyclic_kernel(const double* __restrict__ zr, const doubl
 }
 }  // namespace
 
-// a, z: this rank's 2-D cyclic blocks (device, interleaved complex)
-static int herm_solve_sharded(Context& ctx, int n, int nvec, double* a, int lda, double* w, double* z, int ldz, int mf, int mb,
-                              char mode) {
+// a, z: this rank's 2-D cyclic blocks (device, interleaved complex); request and frame as for herm_solve_full
+static int herm_solve_sharded(SolveFrame& F, int n, int nvec, double* a, int lda, double* w, double* z, int ldz, int m, int mb,
+                              char mode, bool want_vec) {
+  Context& ctx = F.ctx;
   const Grid G = ctx.grid;
   const int P = G.nranks, me = G.rank;
   const int nloc_r = local_count(n, G.Px, G.px), nloc_c = local_count(n, G.Py, G.py);
-  const SolveRequest rq = normalize_request(n, nvec, mode);   // src/eigen_h.F:104-106
-  nvec = rq.nvec;
-  mode = rq.mode;
-  if (mode != 'N' && mode != 'A' && mode != 'X' && mode != 'S') mode = 'A';
-  const bool want_vec = rq.want_vec;
-  int m = mf <= 0 ? 48 : mf;
-  if (m > HM) m = HM;
-  if (m > n) m = n;
   hipStream_t st = ctx.stream;
-  EIGX_HIP_CHECK(hipStreamSynchronize(nullptr));
-  ctx.errinfo = 0;
-  for (int q = 0; q < 16; ++q) ctx.timers[q] = 0.0;
-  (void)comm_seconds(ctx, true);
-  const double t0 = now_s();
-
   // ---- eigen_scaling_h on the local blocks, maxima combined over the ranks (sigma is applied by hs_pack_kernel) --------
-  double sigma = 1.0;
-  const int rc_sc = eigen_scaling(ctx, a, lda, true, n, w, &sigma);
-  if (rc_sc != EIGX_OK) return rc_sc;
+  if (const int rc = F.scale(a, lda, w, n)) return rc;
+  const double sigma = F.sigma;
 
   // ---- workspace: the rank's tile columns of the two planes ------------------------------------------------------------
   const int ld = pad_ld(n + 2);
@@ -1054,28 +1056,7 @@ static int herm_solve_sharded(Context& ctx, int n, int nvec, double* a, int lda,
   H.n = n; H.ld = ld; H.ldp = ldp; H.P = P; H.p = me;
   H.Ar = ctx.pool.get_t<double>("hs.Ar", (size_t)ld * (nlc + HMB));
   H.Ai = ctx.pool.get_t<double>("hs.Ai", (size_t)ld * (nlc + HMB) + H_PLANE_SKEW) + H_PLANE_SKEW;
-  H.Ur = ctx.pool.get_t<double>("h.UW", (size_t)4 * ldp * m);
-  H.Ui = H.Ur + (size_t)ldp * m;
-  H.Wr = H.Ui + (size_t)ldp * m;
-  H.Wi = H.Wr + (size_t)ldp * m;
-  double* P1 = ctx.pool.get_t<double>("h.P1", (size_t)ldp * 4 * m);
-  double* P2 = ctx.pool.get_t<double>("h.P2", (size_t)ldp * 4 * m);
-  double* P3 = ctx.pool.get_t<double>("h.P3", (size_t)ldp * 4 * m);
-  H.xr = ctx.pool.get_t<double>("h.xr", (size_t)ldp); H.xi = ctx.pool.get_t<double>("h.xi", (size_t)ldp);
-  H.beta = ctx.pool.get_t<double>("h.beta", (size_t)2 * n + 2);
-  const int lde = (n + 3) / 4 * 4;
-  H.d = ctx.pool.get_t<double>("h.d", (size_t)n);
-  H.e = ctx.pool.get_t<double>("h.e", (size_t)lde);
-  const int nwg = ceil_div(n, 64) + 1;
-  const int nt_max = nt_all + 1;
-  const int npdc_max = ceil_div(n, PDR) + 1;
-  H.pn = ctx.pool.get_t<double>("h.pn", (size_t)2 * nwg);
-  H.ps = ctx.pool.get_t<double>("h.ps", (size_t)nt_max * (nt_max + 1));
-  H.pd = ctx.pool.get_t<double>("h.pd", (size_t)npdc_max * HM * 4);
-  H.yrr = ctx.pool.get_t<double>("h.yrr", (size_t)nt_max * ldp);
-  H.yri = ctx.pool.get_t<double>("h.yri", (size_t)nt_max * ldp);
-  H.ycr = ctx.pool.get_t<double>("h.ycr", (size_t)nt_max * ldp);
-  H.yci = ctx.pool.get_t<double>("h.yci", (size_t)nt_max * ldp);
+  const HWork ws = h_workspace(ctx, n, m, H);
   double* ybuf = ctx.pool.get_t<double>("hs.ybuf", (size_t)4 * ldp + 8);
   const size_t ycount = (size_t)4 * ldp + 2;
   hipLaunchKernelGGL(fill_kernel, dim3(1024), dim3(256), 0, st, H.Ar, (size_t)ld * (nlc + HMB), 0.0);
@@ -1117,69 +1098,45 @@ static int herm_solve_sharded(Context& ctx, int n, int nvec, double* a, int lda,
     hipLaunchKernelGGL(hs_unpack_kernel, dim3(ceil_div(nrmax, 256), ncmax, P), dim3(256), 0, st, (const double*)recvb,
                        (const int*)(tab + (size_t)P * ncmax), ncmax, nrmax, n, G.Px, G.Py, G.row_major, H);
   }
-  hipLaunchKernelGGL(fill_kernel, dim3(64), dim3(256), 0, st, H.e, (size_t)lde, 0.0);
-  hipLaunchKernelGGL(fill_kernel, dim3(64), dim3(256), 0, st, H.beta, (size_t)2 * n + 2, 0.0);
-  auto zero_panel = [&]() { hipLaunchKernelGGL(fill_kernel, dim3(512), dim3(256), 0, st, H.Ur, (size_t)4 * ldp * m, 0.0); };
-  zero_panel();
+  HColumns C = h_start_reduction(st, H, ws, n, m);
 
   // ---- eigen_hrd, sharded -------------------------------------------------------------------------------------------------
-  const double t1 = now_s();
+  F.t1 = now_s();
   auto ntl_of = [&](int nt) { long c = 0; for (int tx = me; tx < nt; tx += P) c += tx + 1; return (int)c; };   // my tiles of an nt x nt triangle
-  int k = 0, par = 0;
-  int Lp = 0, ntp = 0, npdcp = 0, npartsp = 0;
-  double* pnb[2] = {H.pn, H.pn + nwg};
   HArgs Hk = H;                               // the panel kernel's view: the summed mat-vec result instead of the tile partials
   Hk.ycr = ybuf; Hk.yci = ybuf + ldp; Hk.ps = ybuf + (size_t)4 * ldp;
   // my share of [y | s | raw column ci] of the pending column, summed over the ranks: every rank gets the same bits
   auto exchange = [&](int ci) {
-    hipLaunchKernelGGL(hs_yreduce_kernel, dim3(ceil_div(ldp, HT)), dim3(HT), 0, st, H, Lp, ntp, ntl_of(ntp), ci, ybuf);
+    hipLaunchKernelGGL(hs_yreduce_kernel, dim3(ceil_div(ldp, HT)), dim3(HT), 0, st, H, C.Lp, C.ntp, ntl_of(C.ntp), ci, ybuf);
     comm_allreduce_sum(ctx, COMM_WORLD, ybuf, ycount, st);
   };
   auto step = [&](int i, int do_x) {
-    const int rows = std::max(do_x ? i + 1 : 0, Lp);
-    Hk.pn = pnb[par ^ 1];
-    hipLaunchKernelGGL(h_step_kernel, dim3(ceil_div(rows, 64)), dim3(HS), 0, st, Hk, i, do_x, Lp, Lp ? k - 1 : 0, 0, npdcp, npartsp,
-                       pnb[par], Lp ? 1 : 0, (const double*)(ybuf + (size_t)2 * ldp), (const double*)(ybuf + (size_t)3 * ldp));
-    return ceil_div(rows, 64);
+    return h_step(st, Hk, C, i, do_x, 0, C.Lp ? 1 : 0, (const double*)(ybuf + (size_t)2 * ldp), (const double*)(ybuf + (size_t)3 * ldp));
   };
   for (int i = n - 1; i >= 1; --i) {
-    const int L = i;
     exchange(i);
     const int nparts = step(i, 1);
-    const int npdc = ceil_div(L, PDR);
-    const int nt = ceil_div(L, HTL);
-    const int ntl = ntl_of(nt);
-    H.pn = pnb[par];
-    const int grid = std::max(1, k * npdc + ntl);
-    if (nt <= H_HEMV8_NT)
-      hipLaunchKernelGGL(h_hemv_kernel<8>, dim3(grid), dim3(512), 0, st, H, L, k, nt, npdc, 2, nparts, ntl);
-    else
-      hipLaunchKernelGGL(h_hemv_kernel<4>, dim3(grid), dim3(HTH), 0, st, H, L, k, nt, npdc, 4, nparts, ntl);
-    Lp = L; ntp = nt; npdcp = npdc; npartsp = nparts;
-    par ^= 1;
-    ++k;
-    if (k == m || i == 1) {
+    h_matvec(st, H, C, i, nparts, ntl_of(ceil_div(i, HTL)));
+    if (C.k == m || i == 1) {
       exchange(-1);
       (void)step(i - 1, 0);
-      Lp = 0;
-      const int nr = i;
-      hipLaunchKernelGGL(h_pack_kernel, dim3(ceil_div(nr, 256), k), dim3(256), 0, st, H, nr, k, P1, P2, P3);
+      const int nr = i, k = C.k;
+      h_pack_panel(st, H, ws, C, nr);
       // my tile columns of the active block: the full ones in one batched product per plane, then the ragged last one
       const int tfull = nr / HTL;                                   // tile columns 0 .. tfull-1 lie inside nr completely
       const int gfull = (tfull > me) ? (tfull - 1 - me) / P + 1 : 0;
       if (gfull > 0) {
-        dgemm_dev(st, 'N', 'T', nr, HTL, 4 * k, -1.0, P1, ldp, P3 + (size_t)me * HTL, ldp, 1.0, H.Ar, ld, 0, nullptr, nullptr,
+        dgemm_dev(st, 'N', 'T', nr, HTL, 4 * k, -1.0, ws.P1, ldp, ws.P3 + (size_t)me * HTL, ldp, 1.0, H.Ar, ld, 0, nullptr, nullptr,
                   nullptr, gfull, 0, (long)P * HTL, (long)HTL * ld);
-        dgemm_dev(st, 'N', 'T', nr, HTL, 4 * k, -1.0, P2, ldp, P3 + (size_t)me * HTL, ldp, 1.0, H.Ai, ld, 0, nullptr, nullptr,
+        dgemm_dev(st, 'N', 'T', nr, HTL, 4 * k, -1.0, ws.P2, ldp, ws.P3 + (size_t)me * HTL, ldp, 1.0, H.Ai, ld, 0, nullptr, nullptr,
                   nullptr, gfull, 0, (long)P * HTL, (long)HTL * ld);
       }
       if (nr % HTL != 0 && tfull % P == me) {
         const int c0_ = tfull * HTL;
-        dgemm_dev(st, 'N', 'T', nr, nr - c0_, 4 * k, -1.0, P1, ldp, P3 + c0_, ldp, 1.0, H.Ar + hcol(H, c0_), ld);
-        dgemm_dev(st, 'N', 'T', nr, nr - c0_, 4 * k, -1.0, P2, ldp, P3 + c0_, ldp, 1.0, H.Ai + hcol(H, c0_), ld);
+        dgemm_dev(st, 'N', 'T', nr, nr - c0_, 4 * k, -1.0, ws.P1, ldp, ws.P3 + c0_, ldp, 1.0, H.Ar + hcol(H, c0_), ld);
+        dgemm_dev(st, 'N', 'T', nr, nr - c0_, 4 * k, -1.0, ws.P2, ldp, ws.P3 + c0_, ldp, 1.0, H.Ai + hcol(H, c0_), ld);
       }
-      zero_panel();
-      k = 0;
+      h_zero_panel(st, H, C, m);
     }
   }
   exchange(0);
@@ -1193,12 +1150,7 @@ static int herm_solve_sharded(Context& ctx, int n, int nvec, double* a, int lda,
   if (want_vec && n > 1) {
     double* G1 = ctx.pool.get_t<double>("h.Gall", (size_t)4 * HMB * HMB);
     Tloc = ctx.pool.get_t<double>("h.Tall", (size_t)ntc * 2 * HMB * HMB);
-    const size_t shm = (size_t)2 * (HMB * (HMB + 1) / 2) * sizeof(double);
-    static bool attr = false;
-    if (!attr) {
-      EIGX_HIP_CHECK(hipFuncSetAttribute((const void*)h_tinv_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm));
-      attr = true;
-    }
+    const size_t shm = h_tinv_shm();
     hipLaunchKernelGGL(hs_zero_below_kernel, dim3(8, nlc), dim3(256), 0, st, H, n, nlc);
     for (int b = me; b < nblk; b += P) {
       const int j0 = blk_j0(b), nb = blk_j1(b) - j0;
@@ -1213,33 +1165,15 @@ static int herm_solve_sharded(Context& ctx, int n, int nvec, double* a, int lda,
   }
   EIGX_HIP_CHECK(hipStreamSynchronize(st));
   if (comm_failed(ctx)) return EIGX_ERR_INTERNAL;
-  const double t2 = now_s();
+  F.t2 = now_s();
 
   // ---- real tridiagonal eigenproblem: distributed D&C (my eigenvector columns, all rows) / bisection --------------------
   const int zc = ceil_div(nvec > 0 ? nvec : 1, P);
   const int c0 = (me * zc < nvec) ? me * zc : nvec;
   const int cn = want_vec ? ((c0 + zc <= nvec) ? zc : nvec - c0) : 0;
-  const int ldzp = pad_ld(n + 2);
-  double* Zr = nullptr;
-  double* Zi = nullptr;
-  if (!want_vec) {
-    band_bisect_dev(ctx, n, H.d, H.e, lde, 1, w);
-  } else {
-    const size_t zplane = (size_t)ldzp * (zc + 1) + H_PLANE_SKEW;
-    Zr = ctx.pool.get_t<double>("hs.Zri", 2 * zplane);
-    Zi = Zr + zplane;
-    if (mode == 'S') {
-      hipLaunchKernelGGL(fill_kernel, dim3(1024), dim3(256), 0, st, Zr, (size_t)ldzp * zc, 0.0);
-      if (cn > 0) hipLaunchKernelGGL(h_identity_kernel, dim3(ceil_div(cn, 256)), dim3(256), 0, st, Zr, ldzp, c0, cn);
-      band_bisect_dev(ctx, n, H.d, H.e, lde, 1, w);
-    } else {
-      band_dc_dev(ctx, n, nvec, H.d, H.e, lde, 1, w, Zr, ldzp);
-    }
-    if (mode == 'X') band_bisect_dev(ctx, n, H.d, H.e, lde, 1, w);
-    hipLaunchKernelGGL(fill_kernel, dim3(1024), dim3(256), 0, st, Zi, (size_t)ldzp * zc, 0.0);
-  }
+  const auto [Zr, Zi, ldzp] = h_tridiagonal_stage(ctx, n, nvec, mode, want_vec, H.d, H.e, ws.lde, w, c0, cn, zc, zc, "hs.Zri");
   if (comm_failed(ctx)) return EIGX_ERR_INTERNAL;
-  const double t3 = now_s();
+  F.t3 = now_s();
 
   // ---- eigen_hrbakwyx on my column block; the reflector blocks stream past in groups of P ---------------------------------
   if (want_vec && n > 1) {
@@ -1285,37 +1219,25 @@ static int herm_solve_sharded(Context& ctx, int n, int nvec, double* a, int lda,
       hipLaunchKernelGGL(hs_join_cyclic_kernel, dim3(ceil_div(nloc_r, 256), nzc), dim3(256), 0, st, (const double*)tr_,
                          (const double*)ti_, ldt, nloc_r, nzc, z, ldz);
   }
-  if (sigma != 1.0 && sigma != 0.0)
-    hipLaunchKernelGGL(scale_vec_kernel, dim3((n + 255) / 256), dim3(256), 0, st, w, n, 1.0 / sigma);
-  EIGX_HIP_CHECK(hipStreamSynchronize(st));
-  EIGX_HIP_CHECK(hipGetLastError());
-  if (comm_failed(ctx)) return EIGX_ERR_INTERNAL;
-  const double t4 = now_s();
-  const double f_red = 4.0 / 3.0 * (double)n * n * n;
-  const double f_dc = ctx.timers[11];
-  const double f_bt = want_vec ? 2.0 * (double)nvec * n * n : 0.0;
-  const double ret = f_red + f_dc + f_bt;
-  ctx.timers[0] = t4 - t0; ctx.timers[1] = t2 - t1; ctx.timers[2] = t3 - t2; ctx.timers[3] = t4 - t3; ctx.timers[12] = ret;
-  if (G.px == 0 && G.py == 0 && nloc_r > 0 && nloc_c > 0) {   // statistics a(1,1), a(2,1) on the owner of the first column
-    const double stats[4] = {ret, 0.0, t4 - t0, 0.0};
-    EIGX_HIP_CHECK(hipMemcpyAsync(a, stats, (size_t)(nloc_r >= 2 ? 4 : 2) * 8, hipMemcpyHostToDevice, st));
-    EIGX_HIP_CHECK(hipStreamSynchronize(st));
-  }
-  return EIGX_OK;
+  // statistics a(1,1), a(2,1) on the owner of the first column
+  return F.finish(w, n, ctx.timers[11], want_vec ? nvec : 0, (G.px == 0 && G.py == 0 && nloc_c > 0) ? nloc_r : 0);
 }
 
 // a, z: this rank's 2-D cyclic blocks (device, interleaved complex), as for eigen_sx / eigen_s
 int herm_solve_dev(Context& ctx, int n, int nvec, double* a, int lda, double* w, double* z, int ldz, int mf, int mb,
                    char mode) {
-  if (!ctx.initialized) return EIGX_ERR_NOT_INITIALIZED;
-  const Grid& G = ctx.grid;
-  if (G.nranks == 1) return herm_solve_full(ctx, n, nvec, a, lda, w, z, ldz, mf, mb, mode);
-  if (n <= 0) return EIGX_ERR_BAD_ARG;
-  const int nloc_r = local_count(n, G.Px, G.px);
-  if (!a || !w || lda < nloc_r) return EIGX_ERR_BAD_ARG;
-  if (normalize_request(n, nvec, mode).want_vec && (!z || ldz < nloc_r)) return EIGX_ERR_BAD_ARG;
-  EIGX_HIP_CHECK(hipSetDevice(ctx.device));
-  return herm_solve_sharded(ctx, n, nvec, a, lda, w, z, ldz, mf, mb, mode);
+  const int nloc_r = local_count(n, ctx.grid.Px, ctx.grid.px);
+  const SolveRequest rq = normalize_request(n, nvec, mode);   // src/eigen_h.F:104-106
+  SolveFrame F(ctx, n, true);
+  if (const int rc = F.begin(a && w && lda >= nloc_r && (!rq.want_vec || (z && ldz >= nloc_r)))) return rc;
+  F.a_user = a;
+  // 'S': identity + bisection + back-transformation (src/eigen_h.F:207-210); any other letter means 'A'
+  mode = (rq.mode == 'N' || rq.mode == 'A' || rq.mode == 'X' || rq.mode == 'S') ? rq.mode : 'A';
+  const int m = std::min(std::min(mf <= 0 ? 48 : mf, HM), n);   // m_forward
+  const int rc = (ctx.grid.nranks == 1 ? herm_solve_full : herm_solve_sharded)(F, n, rq.nvec, a, lda, w, z, ldz, m, mb, mode,
+                                                                                rq.want_vec);
+  if (rc == EIGX_OK) EIGX_HIP_CHECK(hipGetLastError());
+  return rc;
 }
 
 int herm_solve_host(Context& ctx, int n, int nvec, double* a, int lda, double* w, double* z, int ldz, int mf, int mb,

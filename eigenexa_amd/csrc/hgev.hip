@@ -190,7 +190,7 @@ int hgev_dev_mg(Context& ctx, int n, double* a, int lda, double* b, int ldb, dou
   const int lmin = nr > 1 ? nr : 1;
   if (n <= 0 || !a || !b || !w || !z || lda < lmin || ldb < lmin || ldz < lmin) return EIGX_ERR_BAD_ARG;
   EIGX_HIP_CHECK(hipSetDevice(ctx.device));
-  EIGX_HIP_CHECK(hipStreamSynchronize(nullptr));   // the caller's default-stream work on the arguments (see solve_dev)
+  EIGX_HIP_CHECK(hipStreamSynchronize(nullptr));   // the caller's default-stream work on the arguments (see SolveFrame::begin)
   hipStream_t st = ctx.stream;
   const double t0 = now_s();
   double sigma = 1.0;
@@ -263,7 +263,7 @@ int hgev_dev(Context& ctx, int n, double* a, int lda, double* b, int ldb, double
   if (ctx.grid.nranks != 1) return hgev_dev_mg(ctx, n, a, lda, b, ldb, w, z, ldz);
   if (n <= 0 || !a || !b || !w || !z || lda < n || ldb < n || ldz < n) return EIGX_ERR_BAD_ARG;
   EIGX_HIP_CHECK(hipSetDevice(ctx.device));
-  EIGX_HIP_CHECK(hipStreamSynchronize(nullptr));   // the caller's default-stream work on the arguments (see solve_dev)
+  EIGX_HIP_CHECK(hipStreamSynchronize(nullptr));   // the caller's default-stream work on the arguments (see SolveFrame::begin)
   hipStream_t st = ctx.stream;
   const double t0 = now_s();
   double sigma = 1.0;

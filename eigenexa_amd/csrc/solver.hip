@@ -261,7 +261,8 @@ __global__ void scale_vec_kernel(double* __restrict__ w, int n, double s) {
   if (i < n) w[i] *= s;
 }
 
-int eigen_scaling(Context& ctx, const double* a, int lda, bool cplx, int n, double* w, double* sigma) {
+int eigen_scaling(Context& ctx, const double* a, int lda, bool cplx, int n, double* w, double* sigma, int nw) {
+  if (nw < 0) nw = n;
   const Grid& G = ctx.grid;
   hipStream_t st = ctx.stream;
   const int nbk = 512;
@@ -277,7 +278,7 @@ int eigen_scaling(Context& ctx, const double* a, int lda, bool cplx, int n, doub
   if (G.nranks > 1 && comm_failed(ctx)) return EIGX_ERR_INTERNAL;
   const double anrm = hp[0], bad = hp[1];
   if (bad != 0.0) {  // NaN/Inf in the input (on any rank): w(:) = NaN on every rank (src/eigen_sx.F:151-155, src/eigen_h.F:147-150)
-    hipLaunchKernelGGL(fill_vec_kernel, dim3((n + 255) / 256), dim3(256), 0, st, w, n, std::numeric_limits<double>::quiet_NaN());
+    hipLaunchKernelGGL(fill_vec_kernel, dim3((nw + 255) / 256), dim3(256), 0, st, w, nw, std::numeric_limits<double>::quiet_NaN());
     EIGX_HIP_CHECK(hipStreamSynchronize(st));
     ctx.errinfo = -1;
     return EIGX_ERR_NONFINITE;
@@ -308,6 +309,111 @@ void dev_to_host(void* h, int ld, const void* d, int ldd, int nr, int nc, int es
     EIGX_HIP_CHECK(hipMemcpy2D(h, (size_t)ld * esz, d, (size_t)ldd * esz, (size_t)nr * esz, (size_t)nc, hipMemcpyDeviceToHost));
 }
 
+// ---- the solve frame (eigx_context.h) ---------------------------------------------------------------------------------
+int SolveFrame::begin(bool args_ok) {
+  if (!ctx.initialized) return EIGX_ERR_NOT_INITIALIZED;
+  if (n <= 0) {
+    fprintf(stderr, "[eigx] warning: non-positive dimension is invalid\n");  // src/eigen_sx.F:95-98, src/eigen_h.F:91-94
+    return EIGX_ERR_BAD_ARG;
+  }
+  if (!args_ok) return EIGX_ERR_BAD_ARG;
+  EIGX_HIP_CHECK(hipSetDevice(ctx.device));
+  // The library works on its own non-blocking streams: whatever the caller queued on the default stream to fill a
+  // (a copy, a generator kernel) has to be complete before the first kernel here reads it.  (Found by a test that
+  // filled `a` with an asynchronous copy and called the C-ABI directly: the second solve of a process -- workspace
+  // already allocated, nothing else in the way -- overtook the copy.)
+  EIGX_HIP_CHECK(hipStreamSynchronize(nullptr));
+  ctx.errinfo = 0;
+  ctx.dc_zero_n = 0;
+  for (int q = 0; q < 16; ++q) ctx.timers[q] = 0.0;
+  if (ctx.grid.nranks > 1) (void)comm_seconds(ctx, true);
+  t0 = now_s();
+  return EIGX_OK;
+}
+
+int SolveFrame::stage_inputs(double*& a, int& lda, double*& z, int& ldz, bool want_vec, int nvec, int nb) {
+  const Grid& G = ctx.grid;
+  const int P = G.nranks;
+  hipStream_t st = ctx.stream;
+  a_user = a;
+  z_user = z;
+  ldz_user = ldz;
+  // The kernels read columns in 16-byte pieces: an odd leading dimension (eigen_get_matdims mode 'M' with an odd
+  // ceil(n/Px) produces one) is served from an internal padded copy; `a` is destroyed by contract anyway.
+  // Several GPUs: the cyclic block a(lda, *) is used IN PLACE -- nothing of A is replicated; a block-cyclic caller
+  // (nb > 1, the ScaLAPACK interop entry) is converted to the cyclic layout by one all-to-all first.
+  const int clr = local_count(n, G.Px, G.px), clc = local_count(n, G.Py, G.py);   // cyclic local extents
+  if ((lda & 1) || ((uintptr_t)a & 15) || (P > 1 && nb > 1)) {
+    const int ldi = pad_ld(clr + 2);
+    double* ai = ctx.pool.get_t<double>("sol.apad", (size_t)ldi * (clc > 0 ? clc : 1));
+    if (P > 1 && nb > 1) {
+      const int rc_bc = bc_to_cyclic(ctx, a, lda, n, nb, ai, ldi, st);     // one all-to-all: nothing is replicated
+      if (rc_bc != EIGX_OK) return rc_bc;
+    } else if (clr > 0 && clc > 0) {
+      EIGX_HIP_CHECK(hipMemcpy2DAsync(ai, (size_t)ldi * 8, a, (size_t)lda * 8, (size_t)clr * 8, (size_t)clc,
+                                      hipMemcpyDeviceToDevice, st));
+    }
+    a = ai;
+    lda = ldi;
+  }
+  // eigenvector workspace.  One GPU: the caller's z.  Several GPUs: the D&C and the back-transformation work on
+  // whole eigenvector COLUMNS (rank r: columns [r*zc, (r+1)*zc) of the n x nvec matrix); the result is dealt back
+  // into the caller's cyclic z(ldz, *) at the end.
+  zcols = 0;
+  if (P > 1 || (want_vec && ((ldz & 1) || ((uintptr_t)z & 15)))) {
+    zcols = ceil_div(nvec > 0 ? nvec : 1, P);
+    if (want_vec) {
+      ldz = pad_ld(n);
+      z = ctx.pool.get_t<double>("mg.Z", (size_t)ldz * (size_t)zcols);   // this rank's column block only
+    }
+  }
+  return EIGX_OK;
+}
+
+void SolveFrame::return_z(const double* z, int ldz, int ncols) {
+  if (z != z_user)
+    EIGX_HIP_CHECK(hipMemcpy2DAsync(z_user, (size_t)ldz_user * 8, z, (size_t)ldz * 8, (size_t)n * 8, (size_t)ncols,
+                                    hipMemcpyDeviceToDevice, ctx.stream));
+}
+
+int SolveFrame::scale(double* a, int lda, double* w, int nw) {
+  const Grid& G = ctx.grid;
+  const int rc = eigen_scaling(ctx, a, lda, cplx, n, w, &sigma, nw);
+  if (rc == EIGX_OK && !cplx && sigma != 1.0)
+    hipLaunchKernelGGL(scale_upper_kernel, dim3(1024), dim3(256), 0, ctx.stream, a, lda, local_count(n, G.Py, G.py), G.Px, G.px,
+                       G.Py, G.py, sigma);
+  return rc;
+}
+
+int SolveFrame::finish(double* w, int nw, double f_mid, int bt_cols, int stat_rows) {
+  const bool peers = ctx.grid.nranks > 1;
+  hipStream_t st = ctx.stream;
+  if (sigma != 1.0 && sigma != 0.0)
+    hipLaunchKernelGGL(scale_vec_kernel, dim3((nw + 255) / 256), dim3(256), 0, st, w, nw, 1.0 / sigma);
+  stage_trace(ctx.grid.rank, "exit redistribution enqueued");
+  EIGX_HIP_CHECK(hipStreamSynchronize(st));
+  stage_trace(ctx.grid.rank, "stream drained");
+  if (peers && comm_failed(ctx)) return EIGX_ERR_INTERNAL;
+  const double t4 = now_s();
+  // the reference's flop model (src/eigen_sx.F:285-296, src/eigen_h.F:282-288); eigen_sx / eigen_s return it negated
+  // when the middle stage counted none
+  const double f_red = 4.0 / 3.0 * (double)n * n * n;
+  const double f_bt = bt_cols > 0 ? 2.0 * (double)bt_cols * n * n : 0.0;
+  double ret = f_red + f_mid + f_bt;
+  if (!cplx && f_mid == 0.0) ret = -ret;
+  // a(3,1): seconds this rank spent communicating (waits for peers included), as the reference returns; -1 on one
+  // GPU, where there is none.  eigen_h has no a(3,1) and reports none (timers[4] stays 0).
+  const double t_comm = (peers && !cplx) ? comm_seconds(ctx, false) : -1.0;
+  ctx.timers[0] = t4 - t0; ctx.timers[1] = t2 - t1; ctx.timers[2] = t3 - t2; ctx.timers[3] = t4 - t3;
+  ctx.timers[4] = (peers && !cplx) ? t_comm : 0.0; ctx.timers[12] = ret;
+  // a(1:3,1) = flops, seconds, communication seconds; eigen_h: a(1,1), a(2,1) = (flops, 0), (seconds, 0)
+  const double stats_r[3] = {ret, t4 - t0, t_comm}, stats_c[4] = {ret, 0.0, t4 - t0, 0.0};
+  const int nst = cplx ? 2 * std::min(stat_rows, 2) : std::min(stat_rows, 3);
+  if (nst > 0) EIGX_HIP_CHECK(hipMemcpyAsync(a_user, cplx ? stats_c : stats_r, (size_t)nst * 8, hipMemcpyHostToDevice, st));
+  EIGX_HIP_CHECK(hipStreamSynchronize(st));
+  return EIGX_OK;
+}
+
 namespace {
 
 __global__ void copy_vec_kernel(const double* __restrict__ src, double* __restrict__ dst, int n) {
@@ -323,72 +429,43 @@ __global__ void copy_vec_kernel(const double* __restrict__ src, double* __restri
 // il .. iu copied out) serves windows beyond the size rule (eigx_tune key 17; path 3) and results that the acceptance
 // test of band_eigvec_dev refused (path 2).  w(1:m), z(:, 1:m); fill_rest (the opt-in route of eigx_sx / eigx_s, il = 1):
 // w(m+1:n) is filled by bisection as well, so that w holds all n eigenvalues like the reference's.
+// what both entry points of the index-range solves require of their arguments (mode in upper case)
+static bool range_args_ok(int n, int il, int iu, const double* a, int lda, const double* w, const double* z, int ldz, char mode) {
+  if (n <= 0 || il < 1 || iu > n || il > iu || (mode != 'A' && mode != 'N') || !a || !w || lda < n) return false;
+  return mode == 'N' || (z && ldz >= n);
+}
+
 int range_solve_dev(Context& ctx, int n, int il, int iu, double* a, int lda, double* w, double* z, int ldz, int mf, int mb,
                     char mode, int band, bool fill_rest) {
-  if (!ctx.initialized) return EIGX_ERR_NOT_INITIALIZED;
-  if (ctx.grid.nranks != 1) {
+  if (ctx.initialized && ctx.grid.nranks != 1) {
     fprintf(stderr, "[eigx] index-range solves run on one GPU only (this grid has %d ranks)\n", ctx.grid.nranks);
     return EIGX_ERR_BAD_ARG;
   }
-  if (n <= 0) {
-    fprintf(stderr, "[eigx] warning: non-positive dimension is invalid\n");
-    return EIGX_ERR_BAD_ARG;
-  }
-  if (mode >= 'a' && mode <= 'z') mode = (char)(mode - 'a' + 'A');
-  if (il < 1 || iu > n || il > iu || (mode != 'A' && mode != 'N') || !a || !w || lda < n) return EIGX_ERR_BAD_ARG;
+  mode = upper_case(mode);
+  SolveFrame F(ctx, n, false);
+  if (const int rc = F.begin(range_args_ok(n, il, iu, a, lda, w, z, ldz, mode))) return rc;
   const bool want_vec = mode == 'A';
-  if (want_vec && (!z || ldz < n)) return EIGX_ERR_BAD_ARG;
   const int m = iu - il + 1;
   if (mf <= 0) mf = 128;
   if (mb <= 0) mb = 128;
-  EIGX_HIP_CHECK(hipSetDevice(ctx.device));
-  EIGX_HIP_CHECK(hipStreamSynchronize(nullptr));   // the caller's default-stream work on the arguments (see solve_dev)
   hipStream_t st = ctx.stream;
-  ctx.errinfo = 0;
-  ctx.dc_zero_n = 0;
-  for (int q = 0; q < 16; ++q) ctx.timers[q] = 0.0;
   RangeInfo& info = range_info();
   info.path = 0; info.m = m; info.cond = 0.0;
   for (int q = 0; q < 4; ++q) info.t[q] = 0.0;
-  const double t0 = now_s();
   const int nw = fill_rest ? n : m;   // entries of w that belong to this call
 
-  double* a_user = a;
-  double* z_user = z;
-  const int ldz_user = ldz;
-  if ((lda & 1) || ((uintptr_t)a & 15)) {   // odd leading dimension / unaligned base: internal padded copy (see solve_dev)
-    const int ldi = pad_ld(n + 2);
-    double* ai = ctx.pool.get_t<double>("sol.apad", (size_t)ldi * n);
-    EIGX_HIP_CHECK(hipMemcpy2DAsync(ai, (size_t)ldi * 8, a, (size_t)lda * 8, (size_t)n * 8, (size_t)n, hipMemcpyDeviceToDevice, st));
-    a = ai;
-    lda = ldi;
-  }
-  if (want_vec && ((ldz & 1) || ((uintptr_t)z & 15))) {
-    ldz = pad_ld(n);
-    z = ctx.pool.get_t<double>("mg.Z", (size_t)ldz * m);
-  }
-
-  // ---- eigen_scaling (writes NaN into n entries on a non-finite input: w may hold m only, so it gets a buffer) ------
-  double* wn = ctx.pool.get_t<double>("sub.wfull", (size_t)n);
-  double sigma = 1.0;
-  const int rc_sc = eigen_scaling(ctx, a, lda, false, n, wn, &sigma);
-  if (rc_sc != EIGX_OK) {
-    if (rc_sc == EIGX_ERR_NONFINITE) {
-      hipLaunchKernelGGL(fill_vec_kernel, dim3((nw + 255) / 256), dim3(256), 0, st, w, nw, std::numeric_limits<double>::quiet_NaN());
-      EIGX_HIP_CHECK(hipStreamSynchronize(st));
-    }
-    return rc_sc;
-  }
-  if (sigma != 1.0) hipLaunchKernelGGL(scale_upper_kernel, dim3(1024), dim3(256), 0, st, a, lda, n, 1, 0, 1, 0, sigma);
+  if (const int rc = F.stage_inputs(a, lda, z, ldz, want_vec, m, 1)) return rc;
+  double* wn = ctx.pool.get_t<double>("sub.wfull", (size_t)n);   // all n eigenvalues, where the full D&C serves the window
+  if (const int rc = F.scale(a, lda, w, nw)) return rc;
 
   // ---- forward reduction ---------------------------------------------------------------------------------------------
   const int lde = (n + 3) / 4 * 4;
   double* d = ctx.pool.get_t<double>("sol.d", (size_t)n);
   double* e = ctx.pool.get_t<double>("sol.e", (size_t)lde * 2);
-  const double t1 = now_s();
+  F.t1 = now_s();
   band_reduce_dev(ctx, n, a, lda, d, e, lde, mf, band);
   EIGX_HIP_CHECK(hipStreamSynchronize(st));
-  const double t2 = now_s();
+  const double t2 = F.t2 = now_s();
 
   // ---- eigenvalues il .. iu, then their eigenvectors -------------------------------------------------------------------
   if (!want_vec) {
@@ -428,39 +505,26 @@ int range_solve_dev(Context& ctx, int n, int il, int iu, double* a, int lda, dou
     }
     info.path = path;
   }
-  const double t3 = now_s();
+  F.t3 = now_s();
 
   // ---- back-transformation of the m columns (prepared here: the Rayleigh-Ritz solve used the bt.* buffers) -------------
   if (want_vec) {
     trbak_dev(ctx, n, m, a, lda, z, ldz, e, lde, mb, band);
-    if (z != z_user)
-      EIGX_HIP_CHECK(hipMemcpy2DAsync(z_user, (size_t)ldz_user * 8, z, (size_t)ldz * 8, (size_t)n * 8, (size_t)m, hipMemcpyDeviceToDevice, st));
+    F.return_z(z, ldz, m);
   }
   if (fill_rest && iu < n) band_bisect_range_dev(ctx, n, iu + 1, n, d, e, lde, band, w + m);
-  if (sigma != 1.0 && sigma != 0.0) hipLaunchKernelGGL(scale_vec_kernel, dim3((nw + 255) / 256), dim3(256), 0, st, w, nw, 1.0 / sigma);
-  EIGX_HIP_CHECK(hipStreamSynchronize(st));
-  const double t4 = now_s();
-  info.t[3] = t4 - t3;
-
-  const double f_red = 4.0 / 3.0 * (double)n * n * n;
-  const double f_bt = want_vec ? 2.0 * (double)m * n * n : 0.0;
   const double f_mid = want_vec ? (info.path == 1 ? 6.0 * (double)n * m * m : ctx.timers[11]) : 0.0;
-  double ret = f_red + f_mid + f_bt;
-  if (f_mid == 0.0) ret = -ret;
-  ctx.timers[0] = t4 - t0; ctx.timers[1] = t2 - t1; ctx.timers[2] = t3 - t2; ctx.timers[3] = t4 - t3; ctx.timers[12] = ret;
-  const double stats[3] = {ret, t4 - t0, -1.0};
-  EIGX_HIP_CHECK(hipMemcpyAsync(a_user, stats, (size_t)(n >= 3 ? 3 : n) * 8, hipMemcpyHostToDevice, st));
-  EIGX_HIP_CHECK(hipStreamSynchronize(st));
-  return EIGX_OK;
+  const int rc = F.finish(w, nw, f_mid, want_vec ? m : 0, n);
+  info.t[3] = ctx.timers[3];
+  return rc;
 }
 
 int range_solve_host(Context& ctx, int n, int il, int iu, double* a, int lda, double* w, double* z, int ldz, int mf, int mb,
                      char mode, int band) {
   if (!ctx.initialized) return EIGX_ERR_NOT_INITIALIZED;
   if (ctx.grid.nranks != 1) return range_solve_dev(ctx, n, il, iu, a, lda, w, z, ldz, mf, mb, mode, band, false);   // refuses
-  if (n <= 0 || il < 1 || iu > n || il > iu || !a || !w || lda < n) return EIGX_ERR_BAD_ARG;
-  if (mode >= 'a' && mode <= 'z') mode = (char)(mode - 'a' + 'A');
-  if ((mode != 'A' && mode != 'N') || (mode == 'A' && (!z || ldz < n))) return EIGX_ERR_BAD_ARG;
+  mode = upper_case(mode);
+  if (!range_args_ok(n, il, iu, a, lda, w, z, ldz, mode)) return EIGX_ERR_BAD_ARG;
   const int m = iu - il + 1;
   EIGX_HIP_CHECK(hipSetDevice(ctx.device));
   const int ldd = host_ld(n);
@@ -479,91 +543,37 @@ int range_solve_host(Context& ctx, int n, int il, int iu, double* a, int lda, do
 // EigenExa API; a ScaLAPACK caller passes its descriptor's MB = NB and needs no pdgemr2d redistribution, manual 3.4)
 int solve_dev(Context& ctx, int n, int nvec, double* a, int lda, double* w, double* z, int ldz, int mf, int mb,
               char mode, int band, int nb) {
-  if (!ctx.initialized) return EIGX_ERR_NOT_INITIALIZED;
-  if (n <= 0) {
-    fprintf(stderr, "[eigx] warning: non-positive dimension is invalid\n");  // src/eigen_sx.F:95-98
-    return EIGX_ERR_BAD_ARG;
-  }
   const Grid& G = ctx.grid;
   const int P = G.nranks;
-  if (nb < 1) return EIGX_ERR_BAD_ARG;
-  const int nloc_r = numroc(n, nb, G.px, G.Px), nloc_c = numroc(n, nb, G.py, G.Py);
-  if (lda < (nloc_r > 1 ? nloc_r : 1) || !a || !w) return EIGX_ERR_BAD_ARG;
+  const int nloc_r = nb >= 1 ? numroc(n, nb, G.px, G.Px) : 0, nloc_c = nb >= 1 ? numroc(n, nb, G.py, G.Py) : 0;
+  const int ld_min = nloc_r > 1 ? nloc_r : 1;
   const SolveRequest rq = normalize_request(n, nvec, mode);   // src/eigen_sx.F:108-110
   mode = rq.mode;
   nvec = rq.nvec;
   const bool want_vec = rq.want_vec;
-  if (want_vec && (!z || ldz < (nloc_r > 1 ? nloc_r : 1))) return EIGX_ERR_BAD_ARG;
   // opt-in (eigx_tune key 18, default off): the lowest nvec < n eigenpairs by the index-range path (EXTENSION)
   if (get_range_knob(18) == 1 && P == 1 && nb == 1 && mode == 'A' && nvec > 0 && nvec < n)
     return range_solve_dev(ctx, n, 1, nvec, a, lda, w, z, ldz, mf, mb, 'A', band, true);
+  SolveFrame F(ctx, n, false);
+  if (const int rc = F.begin(nb >= 1 && a && w && lda >= ld_min && (!want_vec || (z && ldz >= ld_min)))) return rc;
   if (mf <= 0) mf = 128;
   if (mb <= 0) mb = 128;
-  EIGX_HIP_CHECK(hipSetDevice(ctx.device));
-  // The library works on its own non-blocking streams: whatever the caller queued on the default stream to fill a
-  // (a copy, a generator kernel) has to be complete before the first kernel here reads it.  (Found by a test that
-  // filled `a` with an asynchronous copy and called the C-ABI directly: the second solve of a process -- workspace
-  // already allocated, nothing else in the way -- overtook the copy.)
-  EIGX_HIP_CHECK(hipStreamSynchronize(nullptr));
   hipStream_t st = ctx.stream;
-  ctx.errinfo = 0;
-  ctx.dc_zero_n = 0;
-  for (int q = 0; q < 16; ++q) ctx.timers[q] = 0.0;
-  if (P > 1) (void)comm_seconds(ctx, true);
-  const double t0 = now_s();
-
-  double* a_user = a;
-  double* z_user = z;
-  const int ldz_user = ldz;
-  // The kernels read columns in 16-byte pieces: an odd leading dimension (eigen_get_matdims mode 'M' with an odd
-  // ceil(n/Px) produces one) is served from an internal padded copy; `a` is destroyed by contract anyway.
-  // Several GPUs: the cyclic block a(lda, *) is used IN PLACE -- nothing of A is replicated; a block-cyclic caller
-  // (nb > 1, the ScaLAPACK interop entry) is converted to the cyclic layout by one all-to-all first.
-  const int clr = local_count(n, G.Px, G.px), clc = local_count(n, G.Py, G.py);   // cyclic local extents
-  if ((lda & 1) || ((uintptr_t)a & 15) || (P > 1 && nb > 1)) {
-    const int ldi = pad_ld(clr + 2);
-    double* ai = ctx.pool.get_t<double>("sol.apad", (size_t)ldi * (clc > 0 ? clc : 1));
-    if (P > 1 && nb > 1) {
-      const int rc_bc = bc_to_cyclic(ctx, a, lda, n, nb, ai, ldi, st);     // one all-to-all: nothing is replicated
-      if (rc_bc != EIGX_OK) return rc_bc;
-    } else if (clr > 0 && clc > 0) {
-      EIGX_HIP_CHECK(hipMemcpy2DAsync(ai, (size_t)ldi * 8, a, (size_t)lda * 8, (size_t)clr * 8, (size_t)clc,
-                                      hipMemcpyDeviceToDevice, st));
-    }
-    a = ai;
-    lda = ldi;
-  }
-  // eigenvector workspace.  One GPU: the caller's z.  Several GPUs: the D&C and the back-transformation work on
-  // whole eigenvector COLUMNS (rank r: columns [r*zc, (r+1)*zc) of the n x nvec matrix); the result is dealt back
-  // into the caller's cyclic z(ldz, *) at the end.
-  int zcols_per_rank = 0;
-  if (P > 1 || (want_vec && ((ldz & 1) || ((uintptr_t)z & 15)))) {
-    zcols_per_rank = ceil_div(nvec > 0 ? nvec : 1, P);
-    if (want_vec) {
-      const int ldf = pad_ld(n);
-      z = ctx.pool.get_t<double>("mg.Z", (size_t)ldf * (size_t)zcols_per_rank);   // this rank's column block only
-      ldz = ldf;
-    }
-  }
-
-  // ---- eigen_scaling ---------------------------------------------------------------------------
-  double sigma = 1.0;
-  const int rc_sc = eigen_scaling(ctx, a, lda, false, n, w, &sigma);
-  if (rc_sc != EIGX_OK) return rc_sc;
-  if (sigma != 1.0)
-    hipLaunchKernelGGL(scale_upper_kernel, dim3(1024), dim3(256), 0, st, a, lda, clc, G.Px, G.px, G.Py, G.py, sigma);
+  if (const int rc = F.stage_inputs(a, lda, z, ldz, want_vec, nvec, nb)) return rc;
+  const int zcols_per_rank = F.zcols;
+  if (const int rc = F.scale(a, lda, w, n)) return rc;
 
   // ---- forward reduction --------------------------------------------------------------------------
   const int lde = (n + 3) / 4 * 4;  // nme of src/eigen_sx.F:139
   double* d = ctx.pool.get_t<double>("sol.d", (size_t)n);
   double* e = ctx.pool.get_t<double>("sol.e", (size_t)lde * 2);
-  const double t1 = now_s();
+  F.t1 = now_s();
   // modes that run the D&C: zero its two Q buffers on the side stream underneath the reduction
   if (!(mode == 'N' || mode == 'S' || mode == 'C')) band_dc_prepare(ctx, n);
   band_reduce_dev(ctx, n, a, lda, d, e, lde, mf, band);
   EIGX_HIP_CHECK(hipStreamSynchronize(st));
   if (P > 1 && comm_failed(ctx)) return EIGX_ERR_INTERNAL;
-  const double t2 = now_s();
+  F.t2 = now_s();
   stage_trace(G.rank, "reduction done");
 
   // ---- divide and conquer --------------------------------------------------------------------------
@@ -589,7 +599,7 @@ int solve_dev(Context& ctx, int n, int nvec, double* a, int lda, double* w, doub
     band_dc_dev(ctx, n, nvec, d, e, lde, band, w, z, ldz, side_work);
     if (mode == 'X') band_bisect_dev(ctx, n, d, e, lde, band, w);
   }
-  const double t3 = now_s();
+  F.t3 = now_s();
   stage_trace(G.rank, "eigenvalue stage done");
 
   // ---- back-transformation ---------------------------------------------------------------------------
@@ -603,37 +613,10 @@ int solve_dev(Context& ctx, int n, int nvec, double* a, int lda, double* w, doub
     }
   }
   stage_trace(G.rank, "back-transformation enqueued");
-  if (P > 1 && want_vec) {
-    cols_to_cyclic_dev(ctx, n, nvec, nb, zcols_per_rank, zc0, zcnt, z, ldz, z_user, ldz_user, st);
-  } else if (want_vec && z != z_user) {
-    EIGX_HIP_CHECK(hipMemcpy2DAsync(z_user, (size_t)ldz_user * 8, z, (size_t)ldz * 8, (size_t)n * 8, (size_t)nvec,
-                                    hipMemcpyDeviceToDevice, st));
-  }
-  if (sigma != 1.0 && sigma != 0.0)
-    hipLaunchKernelGGL(scale_vec_kernel, dim3((n + 255) / 256), dim3(256), 0, st, w, n, 1.0 / sigma);
-  stage_trace(G.rank, "exit redistribution enqueued");
-  EIGX_HIP_CHECK(hipStreamSynchronize(st));
-  stage_trace(G.rank, "stream drained");
-  if (P > 1 && comm_failed(ctx)) return EIGX_ERR_INTERNAL;
-  const double t4 = now_s();
-
-  // ---- statistics (src/eigen_sx.F:285-296) -----------------------------------------------------------
-  const double f_red = 4.0 / 3.0 * (double)n * n * n;
-  const double f_dc = ctx.timers[11];
-  const double f_bt = do_bt ? 2.0 * (double)nvec * n * n : 0.0;
-  double ret = f_red + f_dc + f_bt;
-  if (f_dc == 0.0) ret = -ret;
-  // a(3,1): seconds this rank spent communicating (waits for peers included), as the reference returns
-  // (src/eigen_sx.F:285-296); -1 on one GPU, where there is none
-  const double t_comm = (P > 1) ? comm_seconds(ctx, false) : -1.0;
-  ctx.timers[0] = t4 - t0; ctx.timers[1] = t2 - t1; ctx.timers[2] = t3 - t2; ctx.timers[3] = t4 - t3;
-  ctx.timers[4] = (P > 1) ? t_comm : 0.0; ctx.timers[12] = ret;
-  const double stats[3] = {ret, t4 - t0, t_comm};
-  int nst = nloc_r >= 3 ? 3 : nloc_r;  // a(1:3,1) lives in the first local column
-  if (nloc_c == 0) nst = 0;
-  if (nst > 0) EIGX_HIP_CHECK(hipMemcpyAsync(a_user, stats, (size_t)nst * 8, hipMemcpyHostToDevice, st));
-  EIGX_HIP_CHECK(hipStreamSynchronize(st));
-  return EIGX_OK;
+  if (P > 1 && want_vec) cols_to_cyclic_dev(ctx, n, nvec, nb, zcols_per_rank, zc0, zcnt, z, ldz, F.z_user, F.ldz_user, st);
+  else if (want_vec) F.return_z(z, ldz, nvec);
+  // a(1:3,1) lives in the first local column
+  return F.finish(w, n, ctx.timers[11], do_bt ? nvec : 0, nloc_c > 0 ? nloc_r : 0);
 }
 
 int solve_host(Context& ctx, int n, int nvec, double* a, int lda, double* w, double* z, int ldz, int mf, int mb,
@@ -1054,7 +1037,7 @@ int eigx_band_reduce_dev(int n, double* a, int lda, double* d, double* e, int ld
   const int nloc = local_count(n, g_ctx.grid.Px, g_ctx.grid.px);
   if (n <= 0 || lda < (nloc > 1 ? nloc : 1) || (lda & 1) || lde < n || (band != 1 && band != 2)) return EIGX_ERR_BAD_ARG;
   return eigx_guard(g_ctx, [&] {
-    EIGX_HIP_CHECK(hipStreamSynchronize(nullptr));   // the caller's default-stream work on the arguments (see solve_dev)
+    EIGX_HIP_CHECK(hipStreamSynchronize(nullptr));   // the caller's default-stream work on the arguments (see SolveFrame::begin)
     band_reduce_dev(g_ctx, n, a, lda, d, e, lde, mf > 0 ? mf : 128, band);
     EIGX_HIP_CHECK(hipStreamSynchronize(g_ctx.stream));
     return (g_ctx.grid.nranks > 1 && comm_failed(g_ctx)) ? EIGX_ERR_INTERNAL : EIGX_OK;
