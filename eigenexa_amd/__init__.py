@@ -30,6 +30,7 @@ from .api import (  # noqa: F401
     eigen_s_bc,
     numroc,
     KMATH_EIGEN_GEV,
+    KMATH_EIGEN_GEV_RANGE,
     KMATH_EIGEN_HGEV,
     eigen_NB_f,
     eigen_NB_b,

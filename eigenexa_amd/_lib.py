@@ -81,6 +81,14 @@ SIGNATURES = {
                                        C.c_void_p, C.c_void_p, C.c_int]),
     "eigx_range_info": (C.c_int, [_c_int_p, _c_int_p, _c_double_p]),
     "eigx_range_timers": (C.c_int, [_c_double_p]),
+    # extension (not in the reference): Cholesky-route generalised range solver and its triangular stages
+    "eigx_gev_range": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p,
+                                 C.c_void_p, C.c_int, C.c_char]),
+    "eigx_gev_range_dev": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p,
+                                     C.c_void_p, C.c_int, C.c_char]),
+    "eigx_chol_dev": (C.c_int, [C.c_int, C.c_void_p, C.c_int]),
+    "eigx_trsm_upper_dev": (C.c_int, [C.c_char, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int]),
+    "eigx_gev_reduce_dev": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int]),
     "eigx_band_bisect_dev": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
     "eigx_trbak_dev": (C.c_int, [C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int,
                                  C.c_void_p, C.c_int, C.c_int, C.c_int]),

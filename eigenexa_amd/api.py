@@ -387,6 +387,40 @@ def KMATH_EIGEN_GEV(n, a, lda, b, ldb, w, z, ldz):
         print(f"Warning: KMATH_EIGEN_GEV returned without computing (status {rc})", file=sys.stderr)
 
 
+def KMATH_EIGEN_GEV_RANGE(n, il, iu, a, lda, b, ldb, w, z, ldz, mode="A"):
+    """EXTENSION, not in the reference: eigenpairs ``il .. iu`` (1-based, inclusive) of A x = lambda B x by the Cholesky
+    route (B = U^T U, C = U^-T A U^-1, ``eigen_sx_range`` of C, Z = U^-1 Y), one GPU.  ``w[:m]`` ascending, ``z[:, :m]``
+    with ``z^T B z = I``, ``m = iu - il + 1``; modes 'A' and 'N' (``z`` may be None).  Upper triangles of ``a``, ``b``
+    significant; ``a`` is destroyed, ``b`` holds U in its upper triangle.  Status -7 if B is not positive definite, -5
+    (``w[:m]`` = NaN) for a non-finite entry of either triangle.  ``range_info()`` reports on the inner range solve."""
+    # the window and the mode are checked here, before the library is touched (status -2 = EIGX_ERR_BAD_ARG)
+    md = _char(mode, "A").upper()
+    try:
+        ok = 1 <= int(il) <= int(iu) <= int(n) and md in (b"A", b"N") and not (md == b"A" and z is None)
+    except (TypeError, ValueError):
+        ok = False
+    if not ok:
+        _state["last_status"] = -2
+        print(f"Warning: KMATH_EIGEN_GEV_RANGE: invalid window / mode (n={n}, il={il}, iu={iu}, mode={mode!r})",
+              file=sys.stderr)
+        return
+    lib = _lib.load()
+    if not _state["initialized"]:
+        _state["last_status"] = -1
+        return
+    dev = _is_torch(a)
+    if dev:
+        import torch
+
+        torch.cuda.current_stream().synchronize()
+    pa, pb, pw, pz = _ptr(a, "a", dev), _ptr(b, "b", dev), _ptr(w, "w", dev), _ptr(z, "z", dev)
+    fn = lib.eigx_gev_range_dev if dev else lib.eigx_gev_range
+    rc = fn(int(n), int(il), int(iu), pa, int(lda), pb, int(ldb), pw, pz, int(ldz), md)
+    _state["last_status"] = rc
+    if rc not in (0, -5, -7):
+        print(f"Warning: KMATH_EIGEN_GEV_RANGE returned without computing (status {rc})", file=sys.stderr)
+
+
 def KMATH_EIGEN_HGEV(n, a, lda, b, ldb, w, z, ldz):
     """EXTENSION, not in the reference (it has no complex generalised solver): the complex Hermitian-definite problem
     A x = lambda B x by the method of KMATH_EIGEN_GEV over complex numbers (two eigen_h solves, three complex products).

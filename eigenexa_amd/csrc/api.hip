@@ -367,6 +367,7 @@ int eigx_tune(int key, int value) {
   if (key == 15) return set_dc_pipe(value);    // D&C on one GPU: next pass's deflation / secular equations under this pass's product
   if (key == 16) return set_dc_batch(value);   // D&C on one GPU: one product launch per low height
   if (key == 17 || key == 18 || key == 19) return set_range_knob(key, value);   // index-range solves (subset.hip)
+  if (key == 20) return set_tri_nb(value);     // outer block width of the triangular stages (tri.hip)
   return -1;
 }
 

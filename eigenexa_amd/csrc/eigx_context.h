@@ -168,6 +168,20 @@ int set_range_knob(int key, int v);
 int get_range_knob(int key);
 bool range_takes_subset(int n, int m);   // the size rule of key 17 (negative = automatic, see subset.hip)
 
+// tri.hip (EXTENSION, one GPU): the triangular stages of the Cholesky-route generalised solver, upper triangles throughout.
+// chol_upper_dev: B = U^T U in place (synchronous; EIGX_OK or EIGX_ERR_NOT_SPD).  tri_inverses_dev: the inverses of U's
+// diagonal blocks of width nb (eigx_tune key 20) in the pool buffer gevr.inv, block K at v + K nb^2 with leading dimension
+// nb; valid until the next call.  trsm_upper_dev: X(n, nrhs) <- op(U)^-1 X with them, trans 'N' or 'T'; enqueued.  upper_only (trans 'T', nrhs = n): only
+// the upper triangle of the result is wanted, the rest of X is left unspecified.
+struct TriInv { double* v = nullptr; int nb = 0; };
+int chol_upper_dev(Context& ctx, int n, double* B, int ldb);
+TriInv tri_inverses_dev(Context& ctx, int n, const double* U, int ldu);
+void trsm_upper_dev(Context& ctx, char trans, int n, int nrhs, const double* U, int ldu, double* X, int ldx, const TriInv& V,
+                    bool upper_only = false);
+void transpose_dev(hipStream_t st, int n, const double* in, int ldi, double* out, int ldo);   // out = in^T (n x n)
+int set_tri_nb(int v);
+int get_tri_nb();
+
 // trbak.hip: T factors of the back-transformation ahead of time on stream s, and Z(:, 0:nvec) <- H_n ... H_{1+band} Z
 void trbak_prepare_dev(Context& ctx, int n, double* A, int lda, const double* e, int lde, int mb, int band, hipStream_t s);
 void trbak_dev(Context& ctx, int n, int nvec, double* A, int lda, double* Z, int ldz, const double* e, int lde, int mb,

@@ -937,6 +937,85 @@ int gev_host(Context& ctx, int n, double* a, int lda, double* b, int ldb, double
   return EIGX_OK;
 }
 
+// ---- KMATH_EIGEN_GEV_RANGE: eigenpairs il .. iu of A x = lambda B x by the Cholesky route (EXTENSION, one GPU) ----------
+// B = U^T U (tri.hip) -> C = U^-T A U^-1 -> range_solve_dev(C, il, iu) on the eigen_sx route -> Z = U^-1 Y on the m
+// columns.  n^3 / 3 + 2 n^3 + n^2 m flops through the MFMA GEMM where KMATH_EIGEN_GEV spends a whole eigen_s of B and
+// 6 n^3.  B is not scaled: U carries sqrt of B's scale, C its inverse, and a B near the ends of the fp64 range
+// overflows there (range_solve_dev scales C itself, but only once it has been formed).
+
+// upper(c) = U^-T A U^-1 (below the diagonal c is unspecified); a is overwritten.  a: upper triangle significant.
+// 5/3 n^3 flops: a <- U^-T sym(a), c = a^T, c <- U^-T c on the block columns that reach the upper triangle.
+void gev_reduce_dev(Context& ctx, int n, double* a, int lda, const double* u, int ldu, const TriInv& V, double* c, int ldc) {
+  hipStream_t st = ctx.stream;
+  hipLaunchKernelGGL(symmetrize_kernel, dim3(8, n), dim3(256), 0, st, a, lda, n);
+  trsm_upper_dev(ctx, 'T', n, n, u, ldu, a, lda, V);
+  transpose_dev(st, n, a, lda, c, ldc);
+  trsm_upper_dev(ctx, 'T', n, n, u, ldu, c, ldc, V, true);   // the solvers read the upper triangle only
+}
+
+int gev_range_dev(Context& ctx, int n, int il, int iu, double* a, int lda, double* b, int ldb, double* w, double* z, int ldz,
+                  char mode) {
+  if (!ctx.initialized) return EIGX_ERR_NOT_INITIALIZED;
+  if (ctx.grid.nranks != 1) {
+    fprintf(stderr, "[eigx] index-range solves run on one GPU only (this grid has %d ranks)\n", ctx.grid.nranks);
+    return EIGX_ERR_BAD_ARG;
+  }
+  mode = upper_case(mode);
+  if (!range_args_ok(n, il, iu, a, lda, w, z, ldz, mode) || !b || ldb < n || ((lda | ldb) & 1) || (mode == 'A' && (ldz & 1)))
+    return EIGX_ERR_BAD_ARG;
+  EIGX_HIP_CHECK(hipSetDevice(ctx.device));
+  EIGX_HIP_CHECK(hipStreamSynchronize(nullptr));
+  hipStream_t st = ctx.stream;
+  const int m = iu - il + 1;
+  const double t0 = now_s();
+  // both significant triangles are scanned before anything is factored; the scale factors are not used
+  double sigma = 1.0;
+  if (const int rc = eigen_scaling(ctx, a, lda, false, n, w, &sigma, m)) return rc;
+  if (const int rc = eigen_scaling(ctx, b, ldb, false, n, w, &sigma, m)) return rc;
+  if (chol_upper_dev(ctx, n, b, ldb) != EIGX_OK) {
+    fprintf(stderr, "[eigx] Matrix B is not positive definite!\n");
+    return EIGX_ERR_NOT_SPD;
+  }
+  const double t1 = now_s();
+  const TriInv V = tri_inverses_dev(ctx, n, b, ldb);   // once per factor: the three solves below share them
+  const int ldc = pad_ld(n);
+  double* c = ctx.pool.get_t<double>("gevr.c", (size_t)ldc * n);
+  gev_reduce_dev(ctx, n, a, lda, b, ldb, V, c, ldc);
+  EIGX_HIP_CHECK(hipStreamSynchronize(st));
+  const double t2 = now_s();
+  const int rc = range_solve_dev(ctx, n, il, iu, c, ldc, w, z, ldz, 128, 128, mode, 2, false);
+  if (rc != EIGX_OK) return rc;
+  const double t3 = now_s();
+  if (mode == 'A') {
+    trsm_upper_dev(ctx, 'N', n, m, b, ldb, z, ldz, V);   // Z = U^-1 Y
+    EIGX_HIP_CHECK(hipStreamSynchronize(st));
+  }
+  const double t4 = now_s();
+  ctx.timers[0] = t4 - t0; ctx.timers[1] = t1 - t0; ctx.timers[2] = t2 - t1; ctx.timers[3] = t3 - t2; ctx.timers[4] = t4 - t3;
+  return EIGX_OK;
+}
+
+int gev_range_host(Context& ctx, int n, int il, int iu, double* a, int lda, double* b, int ldb, double* w, double* z, int ldz,
+                   char mode) {
+  if (!ctx.initialized) return EIGX_ERR_NOT_INITIALIZED;
+  if (ctx.grid.nranks != 1) return gev_range_dev(ctx, n, il, iu, a, lda, b, ldb, w, z, ldz, mode);   // refuses
+  mode = upper_case(mode);
+  if (!range_args_ok(n, il, iu, a, lda, w, z, ldz, mode) || !b || ldb < n) return EIGX_ERR_BAD_ARG;
+  const int m = iu - il + 1;
+  EIGX_HIP_CHECK(hipSetDevice(ctx.device));
+  const int ldd = host_ld(n);
+  double* ad = (double*)host_to_dev(ctx, "host.a", a, lda, n, n, 8);
+  double* bd = (double*)host_to_dev(ctx, "host.b", b, ldb, n, n, 8);
+  double* zd = (double*)host_to_dev(ctx, "host.z", nullptr, 0, n, mode == 'A' ? m : 1, 8);
+  double* wd = ctx.pool.get_t<double>("host.w", (size_t)m);
+  const int rc = gev_range_dev(ctx, n, il, iu, ad, ldd, bd, ldd, wd, zd, ldd, mode);
+  if (rc == EIGX_OK || rc == EIGX_ERR_NONFINITE) EIGX_HIP_CHECK(hipMemcpy(w, wd, (size_t)m * 8, hipMemcpyDeviceToHost));
+  if (rc != EIGX_OK) return rc;
+  if (mode == 'A') dev_to_host(z, ldz, zd, ldd, n, m, 8);
+  dev_to_host(b, ldb, bd, ldd, n, n, 8);   // U in the upper triangle
+  return EIGX_OK;
+}
+
 }  // namespace
 
 int64_t solver_workspace_bytes(const Context& ctx, int n, int lda, int ldz, int mf, int mb) {
@@ -1060,6 +1139,32 @@ int eigx_gev(int n, double* a, int lda, double* b, int ldb, double* w, double* z
 }
 int eigx_gev_dev(int n, double* a, int lda, double* b, int ldb, double* w, double* z, int ldz) {
   return eigx_guard(g_ctx, [&] { return gev_dev(g_ctx, n, a, lda, b, ldb, w, z, ldz); });
+}
+
+// EXTENSION: eigenpairs il .. iu of A x = lambda B x by the Cholesky route (one GPU); see gev_range_dev
+int eigx_gev_range(int n, int il, int iu, double* a, int lda, double* b, int ldb, double* w, double* z, int ldz, char mode) {
+  return eigx_guard(g_ctx, [&] { return gev_range_host(g_ctx, n, il, iu, a, lda, b, ldb, w, z, ldz, mode); });
+}
+int eigx_gev_range_dev(int n, int il, int iu, double* a, int lda, double* b, int ldb, double* w, double* z, int ldz, char mode) {
+  return eigx_guard(g_ctx, [&] { return gev_range_dev(g_ctx, n, il, iu, a, lda, b, ldb, w, z, ldz, mode); });
+}
+// its reduction stage alone: upper(a) <- U^-T A U^-1 (all of a is written)
+int eigx_gev_reduce_dev(int n, double* a_dev, int lda, const double* u_dev, int ldu) {
+  if (!g_ctx.initialized) return EIGX_ERR_NOT_INITIALIZED;
+  if (n <= 0 || !a_dev || !u_dev || lda < n || ldu < n) return EIGX_ERR_BAD_ARG;
+  if (g_ctx.grid.nranks != 1) return EIGX_ERR_INTERNAL;
+  return eigx_guard(g_ctx, [&] {
+    EIGX_HIP_CHECK(hipSetDevice(g_ctx.device));
+    EIGX_HIP_CHECK(hipStreamSynchronize(nullptr));
+    const TriInv V = tri_inverses_dev(g_ctx, n, u_dev, ldu);
+    const int ldc = pad_ld(n);
+    double* c = g_ctx.pool.get_t<double>("gevr.c", (size_t)ldc * n);
+    gev_reduce_dev(g_ctx, n, a_dev, lda, u_dev, ldu, V, c, ldc);
+    EIGX_HIP_CHECK(hipMemcpy2DAsync(a_dev, (size_t)lda * 8, c, (size_t)ldc * 8, (size_t)n * 8, (size_t)n, hipMemcpyDeviceToDevice,
+                                    g_ctx.stream));
+    EIGX_HIP_CHECK(hipStreamSynchronize(g_ctx.stream));
+    return EIGX_OK;
+  });
 }
 
 int eigx_band_bisect_dev(int n, const double* d, const double* e, int lde, int band, double* w) {

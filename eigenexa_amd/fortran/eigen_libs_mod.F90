@@ -805,3 +805,30 @@ subroutine KMATH_EIGEN_HGEV(n, a, lda, b, ldb, w, z, ldz)
   integer(c_int) :: rc
   rc = eigx_hgev(int(n, c_int), a, int(lda, c_int), b, int(ldb, c_int), w, z, int(ldz, c_int))
 end subroutine KMATH_EIGEN_HGEV
+
+! KMATH_EIGEN_GEV_RANGE -- EXTENSION, not in the reference: eigenpairs il .. iu (1-based, inclusive) of A x = lambda B x by
+! the Cholesky route (B = U^T U, C = U^-T A U^-1, eigen_sx_range of C, Z = U^-1 Y) on one GPU.  w(1:iu-il+1) ascending,
+! z(:, 1:iu-il+1) with z^T B z = I; modes 'A' and 'N'.  Upper triangles of a, b significant; a is destroyed, b holds U in
+! its upper triangle.  External like KMATH_EIGEN_GEV; a caller that passes or omits `mode` needs an explicit interface.
+subroutine KMATH_EIGEN_GEV_RANGE(n, il, iu, a, lda, b, ldb, w, z, ldz, mode)
+  use, intrinsic :: iso_c_binding
+  implicit none
+  integer, intent(in) :: n, il, iu, lda, ldb, ldz
+  real(8), intent(inout) :: a(lda, *), b(ldb, *)
+  real(8), intent(inout) :: w(*), z(ldz, *)
+  character(*), intent(in), optional :: mode
+  interface
+    integer(c_int) function eigx_gev_range(n, il, iu, a, lda, b, ldb, w, z, ldz, mode) bind(C, name="eigx_gev_range")
+      import :: c_int, c_double, c_char
+      integer(c_int), value :: n, il, iu, lda, ldb, ldz
+      real(c_double), intent(inout) :: a(lda, *), b(ldb, *), w(*), z(ldz, *)
+      character(kind=c_char), value :: mode
+    end function
+  end interface
+  integer(c_int) :: rc
+  character(kind=c_char) :: md
+  md = 'A'
+  if (present(mode)) md = mode(1:1)
+  rc = eigx_gev_range(int(n, c_int), int(il, c_int), int(iu, c_int), a, int(lda, c_int), b, int(ldb, c_int), w, z, &
+                      int(ldz, c_int), md)
+end subroutine KMATH_EIGEN_GEV_RANGE

@@ -24,7 +24,8 @@
  * and, on top of them: eigx_solve_bc[_dev] (block-cyclic local blocks of a ScaLAPACK descriptor),
  * eigx_gev[_dev] (KMATH_EIGEN_GEV), eigx_h[_dev] (complex Hermitian eigen_h), eigx_hgev[_dev] (KMATH_EIGEN_HGEV, an
  * extension: complex Hermitian generalised problem), eigx_sx_range / eigx_s_range[_dev] (an extension: eigenpairs il .. iu
- * of the ascending spectrum, one GPU).
+ * of the ascending spectrum, one GPU), eigx_gev_range[_dev] (KMATH_EIGEN_GEV_RANGE, an extension: eigenpairs il .. iu of
+ * the generalised problem by the Cholesky route, one GPU).
  */
 #ifndef EIGENEXA_AMD_H
 #define EIGENEXA_AMD_H
@@ -197,7 +198,8 @@ int eigx_s_range_dev(int n, int il, int iu, double* a, int lda, double* w, doubl
                      char mode);
 /* the last range call: path 1 = subset path, 2 = fell back to the full D&C, 3 = full D&C by the size rule; m; cond = the
  * conditioning estimate max / min diag(L) of the acceptance test (0 when it did not run).  Any pointer may be NULL.  Only
- * the four solver entries (and eigx_sx / eigx_s routed by key 18) write this record; the stage entries do not. */
+ * the four solver entries, eigx_gev_range[_dev] (for their inner call on C) and eigx_sx / eigx_s routed by key 18 write
+ * this record; the stage entries do not. */
 int eigx_range_info(int* path, int* m, double* cond);
 /* stage seconds of the last range call: [0] bisection [1] inverse iteration [2] orthonormalisation + Rayleigh-Ritz (or
  * the fallback D&C) [3] back-transformation (tools/gpu_range_time.py) */
@@ -261,6 +263,36 @@ int eigx_gev_dev(int n, double* a_dev, int lda, double* b_dev, int ldb, double* 
  * 2-D cyclic blocks, nothing is gathered.  Inherits eigen_h's overflow above a matrix scale of about 1e77. */
 int eigx_hgev(int n, double* a, int lda, double* b, int ldb, double* w, double* z, int ldz);
 int eigx_hgev_dev(int n, double* a_dev, int lda, double* b_dev, int ldb, double* w_dev, double* z_dev, int ldz);
+
+/* KMATH_EIGEN_GEV_RANGE -- EXTENSION, not in the reference: eigenpairs il .. iu of the generalised symmetric-definite
+ * problem A x = lambda B x by the Cholesky route of LAPACK's dsygvd (csrc/tri.hip): B = U^T U ->
+ * C = U^-T A U^-1 -> the index-range solve of C on the eigen_sx route (eigx_sx_range_dev: scaling, size rule key 17,
+ * acceptance test, fallback to the full divide and conquer all stay in force) -> Z = U^-1 Y on the m columns.
+ * il = 1, iu = n is a full generalised solve.  eigx_gev keeps the reference's method and on-exit contract.
+ * One GPU only: with more than one rank the call prints one line and returns EIGX_ERR_BAD_ARG.
+ * 1 <= il <= iu <= n, m = iu - il + 1: w(1:m) = eigenvalues il .. iu of the ascending generalised spectrum, z(:, 1:m)
+ * the eigenvectors with z^T B z = I_m; nothing beyond m entries / columns of w, z is touched.  mode 'A' eigenpairs, 'N'
+ * eigenvalues only (z may be NULL, no back-substitution); anything else is EIGX_ERR_BAD_ARG.  Upper triangles of a, b
+ * significant (NaN in the strict lower triangles does not matter).  On exit a is destroyed and carries no statistics;
+ * b holds U in its upper triangle (B = U^T U), its strict lower triangle is unspecified.  The significant triangles of
+ * a AND b are scanned before anything is factored: a non-finite entry gives EIGX_ERR_NONFINITE and w(1:m) = NaN.  B not
+ * positive definite: EIGX_ERR_NOT_SPD and the message of eigx_gev.  Host form: any leading dimensions.  Device form:
+ * even leading dimensions, else EIGX_ERR_BAD_ARG (the rule of eigx_gev_dev); it waits on the default stream on entry.
+ * eigx_get_timers [0..4] = total, factorisation, forming C, the range solve, back-substitution (the layout of eigx_gev);
+ * eigx_range_info / eigx_range_timers report on the inner call.  B is NOT scaled: U carries the square root of B's
+ * scale and C its inverse, so a B near either end of the fp64 range overflows or underflows there (documented, not
+ * solved).  Workspace: pooled buffers named "gevr.*", one n x n matrix, panels of n x NB and the n x NB block inverses. */
+int eigx_gev_range(int n, int il, int iu, double* a, int lda, double* b, int ldb, double* w, double* z, int ldz, char mode);
+int eigx_gev_range_dev(int n, int il, int iu, double* a_dev, int lda, double* b_dev, int ldb, double* w_dev, double* z_dev,
+                       int ldz, char mode);
+/* Its stages (one GPU, device arrays, any leading dimension >= n, LAPACK uplo = 'U'; NB = eigx_tune key 20).
+ * eigx_chol_dev: B = U^T U, U in place in the upper triangle, nothing below the diagonal is read; EIGX_OK, or
+ * EIGX_ERR_NOT_SPD for a pivot that is not > 0 or not finite.  eigx_trsm_upper_dev: x(n, nrhs) <- op(U)^-1 x in place,
+ * trans 'N' or 'T', by block inversion (the inverses of U's NB-wide diagonal blocks, then two GEMMs per block row).
+ * eigx_gev_reduce_dev: upper(a) <- U^-T A U^-1 for the upper triangle of a on entry (all of a is overwritten). */
+int eigx_chol_dev(int n, double* b_dev, int ldb);
+int eigx_trsm_upper_dev(char trans, int n, int nrhs, const double* u_dev, int ldu, double* x_dev, int ldx);
+int eigx_gev_reduce_dev(int n, double* a_dev, int lda, const double* u_dev, int ldu);
 
 /* replaces eigen_bisect(d,e,w,n,mode) src/bisect.F:67-397 (band=1) / eigen_bisect2(d,e,f,w,n,mode)
  * src/bisect2.F:71-718 (band=2): all eigenvalues of the band matrix by Sturm counts, w_dev ascending.
@@ -332,7 +364,9 @@ int eigx_profile_read_kinds(double* out, int nkinds);
  * subset path was slower than the nvec = m route at every m, so it is not taken there unless the key is set); key 18 = 1: eigx_sx / eigx_s / _dev calls with mode 'A' and 0 < nvec < n are routed through the range path
  * as il = 1, iu = nvec, w(nvec+1:n) filled by bisection (default 0: results bit-identical to earlier versions);
  * key 19 = log10 of the acceptance bound on cond(L) (default 6; exists so that a test can force the fallback at a small
- * size, like keys 7-9; 0 .. 16); values outside the stated ranges of keys 17 - 19 are refused.  Returns the previous value, or
+ * size, like keys 7-9; 0 .. 16); values outside the stated ranges of keys 17 - 19 are refused.  key 20 = outer block
+ * width NB of the triangular stages of eigx_gev_range (csrc/tri.hip): a multiple of 64 from 64 to 1024 (default 256), other
+ * values are refused; like keys 7-9 it lets tests reach the multi-panel paths at small n.  Returns the previous value, or
  * -1 for an unknown key or a refused value.
  * Not part of the reference's interface. */
 int eigx_tune(int key, int value);
