@@ -384,13 +384,16 @@ __global__ __launch_bounds__(256) void secular_kernel(const MergeDev* __restrict
   double origin, lo, hi, tau;
   {
     const double gap = last ? rho : d[j + 1] - d[j];
-    const double mid = last ? d[K - 1] + 0.5 * rho : 0.5 * (d[j] + d[j + 1]);
+    // distances to the midpoint relative to the pole below the root, (d_i - d_j) - gap / 2 (as DLAED4 forms them): the
+    // rounded midpoint of a gap a few ulps wide leaves d_j - mid without a correct digit, fmid with the wrong sign and the
+    // root with a bracket that does not hold it
+    const double base = last ? d[K - 1] : d[j], half = 0.5 * gap;
     double c = 0.0;
     for (int i = sub; i < K; i += LPR)
-      if (i != jl && i != jr) c += z[i] * z[i] / (d[i] - mid);
+      if (i != jl && i != jr) c += z[i] * z[i] / ((d[i] - base) - half);
     c = group_sum<LPR>(c) + rhoinv;
     const double zl2 = z[jl] * z[jl], zr2 = z[jr] * z[jr];
-    const double fmid = c + zl2 / (d[jl] - mid) + zr2 / (d[jr] - mid);
+    const double fmid = c + zl2 / ((d[jl] - base) - half) + zr2 / ((d[jr] - base) - half);
     int org;
     if (last) { org = K - 1; if (fmid <= 0.0) { lo = 0.5 * gap; hi = gap; } else { lo = 0.0; hi = 0.5 * gap; } }
     else if (fmid > 0.0) { org = j; lo = 0.0; hi = 0.5 * gap; }

@@ -249,12 +249,14 @@ static void secular_root(int K, int j, const double* d, const double* z, double 
   double origin, lo, hi, tau;
   {
     const double gap = last ? rho : d[j + 1] - d[j];
-    const double mid = last ? d[K - 1] + 0.5 * rho : 0.5 * (d[j] + d[j + 1]);
-    /* f at the midpoint without the two kept poles, then with */
+    /* f at the midpoint without the two kept poles, then with.  The distances d_i - mid are formed relative to the pole
+     * below the root, (d_i - d_j) - gap/2 (as DLAED4 does): a rounded midpoint 0.5 (d_j + d_{j+1}) of a gap a few ulps wide
+     * gives d_j - mid, d_{j+1} - mid with O(1) relative error, fmid the wrong sign and the root a bracket without it */
+    const double base = last ? d[K - 1] : d[j], half = 0.5 * gap;
     double c = rhoinv;
     for (int i = 0; i < K; ++i)
-      if (i != jl && i != jr) c += z[i] * z[i] / (d[i] - mid);
-    const double fmid = c + z[jl] * z[jl] / (d[jl] - mid) + z[jr] * z[jr] / (d[jr] - mid);
+      if (i != jl && i != jr) c += z[i] * z[i] / ((d[i] - base) - half);
+    const double fmid = c + z[jl] * z[jl] / ((d[jl] - base) - half) + z[jr] * z[jr] / ((d[jr] - base) - half);
     int org;
     if (last) { org = K - 1; if (fmid <= 0.0) { lo = 0.5 * gap; hi = gap; } else { lo = 0.0; hi = 0.5 * gap; } }
     else if (fmid > 0.0) { org = j; lo = 0.0; hi = 0.5 * gap; }

@@ -125,6 +125,53 @@ procs, xp, yp = ee.eigen_get_procs()
 idn, xi, yi = ee.eigen_get_id()
 assert (xp, yp) == (dims or layout.grid_shape(world)) and idn == rank + 1
 px, py = xi - 1, yi - 1
+if route == "hard":
+    # the distributed D&C under deflation: dense symmetric tridiagonal / pentadiagonal matrices of tests/hard_band.py through
+    # the whole solve, judged column by column (E_r, E_o) on rank 0.  Bound: 16 x the worse of what the CPU oracle and LAPACK
+    # reach through the same whole solve (the reduction adds its own error to the D&C's)
+    sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+    import hard_band as hb
+
+    rows = np.arange(px, n, xp)
+    cols = np.arange(py, n, yp)
+    nx, ny = ee.eigen_get_matdims(n)
+    report, fails = [], []
+    for name, band in (("glued", 1), ("equal_d_tiny_e", 1), ("wilkinson", 2)):
+        d_, e_ = hb.families(n, band)[name]
+        A = hb.band_matrix(d_, e_, band)
+        rt = "sx" if band == 2 else "s"
+        a = np.zeros((nx, ny), order="F")
+        a[: len(rows), : len(cols)] = A[np.ix_(rows, cols)]
+        z = np.zeros((nx, ny), order="F")
+        w = np.zeros(n)
+        (ee.eigen_sx if rt == "sx" else ee.eigen_s)(n, n, a, nx, w, z, nx, m_forward=32, mode="A")
+        assert api.last_status() == 0, (name, api.last_status())
+        zl = np.zeros(((n + xp - 1) // xp, (n + yp - 1) // yp))
+        zl[: len(rows), : len(cols)] = z[: len(rows), : len(cols)]
+        blocks = [torch.zeros(zl.shape, dtype=torch.float64) for _ in range(world)]
+        dist.all_gather(blocks, torch.from_numpy(np.ascontiguousarray(zl)))
+        Z = layout.gather_cyclic([b.numpy() for b in blocks], n, n, dims=dims)
+        assert np.isfinite(w).all() and np.isfinite(Z).all() and (np.diff(w) >= 0).all(), name
+        if rank == 0:
+            from oracle import orc
+
+            er, eo = hb.dense_metrics(A, w, Z)
+            wo, Zo = orc.eigen(A, rt)[:2]
+            wl, Zl = np.linalg.eigh(A)
+            ref = [hb.dense_metrics(A, wo, Zo), hb.dense_metrics(A, wl, Zl)]
+            b_r = hb.BOUND_FACTOR * max(r_[0] for r_ in ref)
+            b_o = hb.BOUND_FACTOR * max(r_[1] for r_ in ref)
+            report.append(f"DC-HARD-MG world={world} dims={dims} {name} band={band} n={n}: E_r={er:.2f} (<{b_r:.1f}) "
+                          f"E_o={eo:.2f} (<{b_o:.1f}); oracle {ref[0][0]:.2f} {ref[0][1]:.2f}, LAPACK {ref[1][0]:.2f} {ref[1][1]:.2f}")
+            print(report[-1], flush=True)
+            if not (er < b_r and eo < b_o):
+                fails.append(report[-1])
+    ee.eigen_free()
+    dist.barrier()
+    dist.destroy_process_group()
+    assert not fails, fails      # after the last collective: the peers are not left waiting for this rank
+    print(f"OK rank {rank}/{world} n={n} hard: D&C under deflation on the process grid", flush=True)
+    sys.exit(0)
 A = layout.random_symmetric(n)
 if route.startswith("modes-"):
     # every mode of src/eigen_sx.F:200-240 and a partial eigenvector set on the process grid, against the CPU oracle run in
