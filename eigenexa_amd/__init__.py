@@ -32,6 +32,7 @@ from .api import (  # noqa: F401
     KMATH_EIGEN_GEV,
     KMATH_EIGEN_GEV_RANGE,
     KMATH_EIGEN_HGEV,
+    KMATH_EIGEN_HGEV_RANGE,
     eigen_NB_f,
     eigen_NB_b,
 )

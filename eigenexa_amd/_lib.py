@@ -89,6 +89,14 @@ SIGNATURES = {
     "eigx_chol_dev": (C.c_int, [C.c_int, C.c_void_p, C.c_int]),
     "eigx_trsm_upper_dev": (C.c_int, [C.c_char, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int]),
     "eigx_gev_reduce_dev": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int]),
+    # extension (not in the reference): the same for the complex Hermitian generalised problem (csrc/ztri.hip)
+    "eigx_hgev_range": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p,
+                                  C.c_void_p, C.c_int, C.c_char]),
+    "eigx_hgev_range_dev": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p,
+                                      C.c_void_p, C.c_int, C.c_char]),
+    "eigx_zchol_dev": (C.c_int, [C.c_int, C.c_void_p, C.c_int]),
+    "eigx_ztrsm_upper_dev": (C.c_int, [C.c_char, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int]),
+    "eigx_hgev_reduce_dev": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int]),
     "eigx_band_bisect_dev": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
     "eigx_trbak_dev": (C.c_int, [C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int,
                                  C.c_void_p, C.c_int, C.c_int, C.c_int]),

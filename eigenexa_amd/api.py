@@ -461,3 +461,59 @@ def KMATH_EIGEN_HGEV(n, a, lda, b, ldb, w, z, ldz):
     _state["last_status"] = rc
     if rc not in (0, -5, -7):
         print(f"Warning: KMATH_EIGEN_HGEV returned without computing (status {rc})", file=sys.stderr)
+
+
+def KMATH_EIGEN_HGEV_RANGE(n, il, iu, a, lda, b, ldb, w, z, ldz, mode="A"):
+    """EXTENSION, not in the reference: eigenpairs ``il .. iu`` (1-based, inclusive) of the complex Hermitian-definite
+    problem A x = lambda B x by the Cholesky route (B = U^H U, C = U^-H A U^-1, ``eigen_h`` of C with nvec = iu,
+    Z = U^-1 Y), one GPU.  ``a``, ``b``, ``z``: complex128, column-major (numpy, Fortran order) or GPU tensors holding the
+    column-major image (``a[j, i] = A(i, j)``), leading dimensions in complex elements; ``w`` float64.  ``w[:m]``
+    ascending, ``z[:, :m]`` with ``z^H B z = I``, ``m = iu - il + 1``; modes 'A' and 'N' (``z`` may be None).  Upper
+    triangles of ``a``, ``b`` significant; ``a`` is destroyed, ``b`` holds U in its upper triangle.  Status -7 if B is
+    not positive definite, -5 (``w[:m]`` = NaN) for a non-finite entry of either triangle."""
+    # the window and the mode are checked here, before the library is touched (status -2 = EIGX_ERR_BAD_ARG)
+    md = _char(mode, "A").upper()
+    try:
+        ok = 1 <= int(il) <= int(iu) <= int(n) and md in (b"A", b"N") and not (md == b"A" and z is None)
+    except (TypeError, ValueError):
+        ok = False
+    if not ok:
+        _state["last_status"] = -2
+        print(f"Warning: KMATH_EIGEN_HGEV_RANGE: invalid window / mode (n={n}, il={il}, iu={iu}, mode={mode!r})",
+              file=sys.stderr)
+        return
+    lib = _lib.load()
+    if not _state["initialized"]:
+        _state["last_status"] = -1
+        return
+    dev = _is_torch(a)
+
+    def cptr(x, name, real=False):
+        if x is None:
+            return None
+        if dev:
+            import torch
+
+            if not (_is_torch(x) and x.is_cuda):
+                raise ValueError("a, b, w, z must all be host arrays or all be device tensors")
+            if x.dtype != (torch.float64 if real else torch.complex128):
+                raise ValueError(f"{name}: {'float64' if real else 'complex128'} required")
+            return x.data_ptr()
+        if _is_torch(x):
+            raise ValueError("a, b, w, z must all be host arrays or all be device tensors")
+        if x.dtype != (np.float64 if real else np.complex128):
+            raise ValueError(f"{name}: {'float64' if real else 'complex128'} required")
+        if x.ndim == 2 and not x.flags.f_contiguous:
+            raise ValueError(f"{name}: Fortran (column-major) order required, as in the reference")
+        return x.ctypes.data
+
+    if dev:
+        import torch
+
+        torch.cuda.current_stream().synchronize()
+    pa, pb, pw, pz = cptr(a, "a"), cptr(b, "b"), cptr(w, "w", real=True), cptr(z, "z")
+    fn = lib.eigx_hgev_range_dev if dev else lib.eigx_hgev_range
+    rc = fn(int(n), int(il), int(iu), pa, int(lda), pb, int(ldb), pw, pz, int(ldz), md)
+    _state["last_status"] = rc
+    if rc not in (0, -5, -7):
+        print(f"Warning: KMATH_EIGEN_HGEV_RANGE returned without computing (status {rc})", file=sys.stderr)

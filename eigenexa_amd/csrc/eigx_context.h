@@ -182,6 +182,34 @@ void transpose_dev(hipStream_t st, int n, const double* in, int ldi, double* out
 int set_tri_nb(int v);
 int get_tri_nb();
 
+// ztri.hip (EXTENSION, one GPU): the complex siblings of the above on split planes (Re and Im as two real column-major
+// arrays of one leading dimension), pool buffers "hgevr.*", the same outer block width (key 20).  zchol_upper_dev:
+// B = U^H U in place, real positive diagonal, Im of B's diagonal not read and Im of U's written as 0 (synchronous; EIGX_OK
+// or EIGX_ERR_NOT_SPD).  ztri_inverses_dev: the inverses of U's diagonal blocks, block K at vr / vi + K nb^2, valid until
+// the next call.  ztrsm_upper_dev: X(n, nrhs) <- op(U)^-1 X, trans 'N' or 'C'; enqueued; upper_only as above (trans 'C').
+// hgev_reduce_dev: upper(C) = U^-H A U^-1 from the planes of the full Hermitian A (overwritten); enqueued.
+// zplanes: both planes of an ld x ncols matrix in ONE pool buffer `name`.
+struct ZTriInv { double* vr = nullptr; double* vi = nullptr; int nb = 0; };
+struct ZPlanes { double* r = nullptr; double* i = nullptr; };
+ZPlanes zplanes(Context& ctx, const char* name, int ld, int ncols);
+int zchol_upper_dev(Context& ctx, int n, double* Br, double* Bi, int ldb);
+ZTriInv ztri_inverses_dev(Context& ctx, int n, const double* Ur, const double* Ui, int ldu);
+void ztrsm_upper_dev(Context& ctx, char trans, int n, int nrhs, const double* Ur, const double* Ui, int ldu, double* Xr,
+                     double* Xi, int ldx, const ZTriInv& V, bool upper_only = false);
+void hgev_reduce_dev(Context& ctx, int n, double* Ar, double* Ai, int lda, const double* Ur, const double* Ui, int ldu,
+                     const ZTriInv& V, double* Cr, double* Ci, int ldc);
+void zconj_transpose_dev(hipStream_t st, int n, const double* inr, const double* ini, int ldi, double* outr, double* outi,
+                         int ldo);   // out = in^H (n x n)
+// hgev.hip: interleaved complex <-> planes (one GPU: Px = Py = 1, px = py = 0), shared with ztri.hip.  hg_expand_kernel:
+// upper triangle -> the full Hermitian matrix (grid: 32 x 32 tiles); hg_split_kernel: herm = 1 the upper triangle only, Im
+// of the diagonal := 0, w = optional column scaling; hg_join_kernel: upper = 1 only the entries on or above the diagonal.
+__global__ void hg_expand_kernel(const double* __restrict__ a, int lda, int n, double* __restrict__ Ar, double* __restrict__ Ai,
+                                 int ld);
+__global__ void hg_split_kernel(const double* __restrict__ x, int ldx, const double* __restrict__ w, int nr, int nc, int Px,
+                                int px, int Py, int py, int herm, double* __restrict__ Pr, double* __restrict__ Pi, int ld);
+__global__ void hg_join_kernel(const double* __restrict__ Pr, const double* __restrict__ Pi, int ld, int nr, int nc, int Px,
+                               int px, int Py, int py, int upper, double* __restrict__ x, int ldx);
+
 // trbak.hip: T factors of the back-transformation ahead of time on stream s, and Z(:, 0:nvec) <- H_n ... H_{1+band} Z
 void trbak_prepare_dev(Context& ctx, int n, double* A, int lda, const double* e, int lde, int mb, int band, hipStream_t s);
 void trbak_dev(Context& ctx, int n, int nvec, double* A, int lda, double* Z, int ldz, const double* e, int lde, int mb,

@@ -28,8 +28,7 @@
 
 namespace eigx {
 
-namespace {
-
+// The three plane kernels below are shared with ztri.hip (declared in eigx_context.h).
 // one GPU: interleaved upper triangle of a -> planes of the full Hermitian matrix (lower = conj(upper), Im of the diagonal
 // := 0).  One 32 x 32 tile of the upper block triangle per workgroup; the mirrored tile goes through LDS, so both writes
 // are coalesced.
@@ -82,20 +81,6 @@ __global__ void hg_split_kernel(const double* __restrict__ x, int ldx, const dou
   }
 }
 
-// several ranks: below the global diagonal A := conj(A^T), from the transposed planes (Xr, Xi) = (Ar^T, Ai^T)
-__global__ void hg_merge_kernel(double* __restrict__ Ar, double* __restrict__ Ai, const double* __restrict__ Xr,
-                                const double* __restrict__ Xi, int ld, int nr, int nc, int Px, int px, int Py, int py) {
-  for (int lc = blockIdx.y; lc < nc; lc += gridDim.y) {
-    const int gc = lc * Py + py;
-    for (int lr = blockIdx.x * blockDim.x + threadIdx.x; lr < nr; lr += gridDim.x * blockDim.x) {
-      if (lr * Px + px <= gc) continue;
-      const size_t o = (size_t)lr + (size_t)lc * ld;
-      Ar[o] = Xr[o];
-      Ai[o] = -Xi[o];
-    }
-  }
-}
-
 // planes -> interleaved local block x (nr x nc); upper: only the entries on or above the global diagonal
 __global__ void hg_join_kernel(const double* __restrict__ Pr, const double* __restrict__ Pi, int ld, int nr, int nc, int Px,
                                int px, int Py, int py, int upper, double* __restrict__ x, int ldx) {
@@ -106,6 +91,22 @@ __global__ void hg_join_kernel(const double* __restrict__ Pr, const double* __re
       const size_t o = (size_t)lr + (size_t)lc * ldx;
       x[2 * o] = Pr[(size_t)lr + (size_t)lc * ld];
       x[2 * o + 1] = Pi[(size_t)lr + (size_t)lc * ld];
+    }
+  }
+}
+
+namespace {
+
+// several ranks: below the global diagonal A := conj(A^T), from the transposed planes (Xr, Xi) = (Ar^T, Ai^T)
+__global__ void hg_merge_kernel(double* __restrict__ Ar, double* __restrict__ Ai, const double* __restrict__ Xr,
+                                const double* __restrict__ Xi, int ld, int nr, int nc, int Px, int px, int Py, int py) {
+  for (int lc = blockIdx.y; lc < nc; lc += gridDim.y) {
+    const int gc = lc * Py + py;
+    for (int lr = blockIdx.x * blockDim.x + threadIdx.x; lr < nr; lr += gridDim.x * blockDim.x) {
+      if (lr * Px + px <= gc) continue;
+      const size_t o = (size_t)lr + (size_t)lc * ld;
+      Ar[o] = Xr[o];
+      Ai[o] = -Xi[o];
     }
   }
 }
@@ -334,6 +335,101 @@ int hgev_host(Context& ctx, int n, double* a, int lda, double* b, int ldb, doubl
   return EIGX_OK;
 }
 
+// ---- KMATH_EIGEN_HGEV_RANGE: eigenpairs il .. iu of A x = lambda B x by the Cholesky route (EXTENSION, one GPU) ---------
+// B = U^H U (ztri.hip) -> C = U^-H A U^-1 -> eigen_h(C) with nvec = iu -> Z = U^-1 Y on the columns il .. iu: the complex
+// sibling of gev_range_dev (solver.hip).  4 (1/3 + 5/3 + m/n) n^3 real flops through the MFMA GEMM and ONE eigen_h where
+// hgev_dev spends 20 n^3 and two.  The inner solve is eigen_h itself, not a Hermitian subset path: its tridiagonal stage
+// is a few percent of it, so with il > 1 the columns 1 .. il - 1 of Y are computed and dropped, and the workspace holds
+// an n x iu complex Y.  B is not scaled (the limitation of gev_range_dev): U carries the square root of B's scale and C
+// its inverse; eigen_h scales C itself, but only once it has been formed.
+// Pool buffers: hgevr.u, hgevr.a, hgevr.cp (two planes of pad_ld(n) x n each), hgevr.c (C interleaved), hgevr.y (mode 'A':
+// Y, n x iu complex), hgevr.w (n) and the block inverses and panels of ztri.hip.
+int hgev_range_dev(Context& ctx, int n, int il, int iu, double* a, int lda, double* b, int ldb, double* w, double* z, int ldz,
+                   char mode) {
+  if (!ctx.initialized) return EIGX_ERR_NOT_INITIALIZED;
+  if (ctx.grid.nranks != 1) {
+    fprintf(stderr, "[eigx] index-range solves run on one GPU only (this grid has %d ranks)\n", ctx.grid.nranks);
+    return EIGX_ERR_BAD_ARG;
+  }
+  mode = upper_case(mode);
+  if (n <= 0 || il < 1 || iu > n || il > iu || (mode != 'A' && mode != 'N') || !a || !b || !w || lda < n || ldb < n ||
+      (mode == 'A' && (!z || ldz < n)))
+    return EIGX_ERR_BAD_ARG;
+  EIGX_HIP_CHECK(hipSetDevice(ctx.device));
+  EIGX_HIP_CHECK(hipStreamSynchronize(nullptr));   // the caller's default-stream work on the arguments
+  hipStream_t st = ctx.stream;
+  const int m = iu - il + 1;
+  const double t0 = now_s();
+  // both significant triangles are scanned before anything is factored; the scale factors are not used
+  double sigma = 1.0;
+  if (const int rc = eigen_scaling(ctx, a, lda, true, n, w, &sigma, m)) return rc;
+  if (const int rc = eigen_scaling(ctx, b, ldb, true, n, w, &sigma, m)) return rc;
+  const int ld = pad_ld(n);
+  const ZPlanes U = zplanes(ctx, "hgevr.u", ld, n);
+  const ZPlanes A = zplanes(ctx, "hgevr.a", ld, n);     // A, later the columns il .. iu of Y, later Z
+  const ZPlanes Cp = zplanes(ctx, "hgevr.cp", ld, n);
+  const dim3 cg = col_grid(n, n);
+  hipLaunchKernelGGL(hg_split_kernel, cg, dim3(256), 0, st, (const double*)b, ldb, (const double*)nullptr, n, n, 1, 0, 1, 0, 1,
+                     U.r, U.i, ld);
+  if (zchol_upper_dev(ctx, n, U.r, U.i, ld) != EIGX_OK) {
+    fprintf(stderr, "[eigx] Matrix B is not positive definite!\n");
+    return EIGX_ERR_NOT_SPD;
+  }
+  hipLaunchKernelGGL(hg_join_kernel, cg, dim3(256), 0, st, (const double*)U.r, (const double*)U.i, ld, n, n, 1, 0, 1, 0, 1, b, ldb);
+  const double t1 = now_s();
+  const ZTriInv V = ztri_inverses_dev(ctx, n, U.r, U.i, ld);   // once per factor: the three solves below share them
+  const int nt = ceil_div(n, 32);
+  hipLaunchKernelGGL(hg_expand_kernel, dim3(nt, nt), dim3(256), 0, st, (const double*)a, lda, n, A.r, A.i, ld);
+  hgev_reduce_dev(ctx, n, A.r, A.i, ld, U.r, U.i, ld, V, Cp.r, Cp.i, ld);
+  const int ldc = host_ld(n);
+  double* c = ctx.pool.get_t<double>("hgevr.c", (size_t)2 * ldc * n);
+  hipLaunchKernelGGL(hg_join_kernel, cg, dim3(256), 0, st, (const double*)Cp.r, (const double*)Cp.i, ld, n, n, 1, 0, 1, 0, 1, c, ldc);
+  EIGX_HIP_CHECK(hipStreamSynchronize(st));
+  const double t2 = now_s();
+  double* wn = ctx.pool.get_t<double>("hgevr.w", (size_t)n);
+  double* y = mode == 'A' ? ctx.pool.get_t<double>("hgevr.y", (size_t)2 * ldc * iu) : nullptr;
+  const int rc = herm_solve_dev(ctx, n, iu, c, ldc, wn, y, ldc, HG_MF, HG_MB, mode);    // C = Y diag(w) Y^H, the lowest iu
+  if (rc == EIGX_OK || rc == EIGX_ERR_NONFINITE)
+    EIGX_HIP_CHECK(hipMemcpyAsync(w, wn + (il - 1), (size_t)m * 8, hipMemcpyDeviceToDevice, st));
+  EIGX_HIP_CHECK(hipStreamSynchronize(st));
+  if (rc != EIGX_OK) return rc;
+  const double t3 = now_s();
+  if (mode == 'A') {
+    const dim3 cm = col_grid(n, m);
+    hipLaunchKernelGGL(hg_split_kernel, cm, dim3(256), 0, st, (const double*)(y + (size_t)2 * ldc * (il - 1)), ldc,
+                       (const double*)nullptr, n, m, 1, 0, 1, 0, 0, A.r, A.i, ld);
+    ztrsm_upper_dev(ctx, 'N', n, m, U.r, U.i, ld, A.r, A.i, ld, V);   // Z = U^-1 Y
+    hipLaunchKernelGGL(hg_join_kernel, cm, dim3(256), 0, st, (const double*)A.r, (const double*)A.i, ld, n, m, 1, 0, 1, 0, 0, z, ldz);
+    EIGX_HIP_CHECK(hipStreamSynchronize(st));
+  }
+  const double t4 = now_s();
+  ctx.timers[0] = t4 - t0; ctx.timers[1] = t1 - t0; ctx.timers[2] = t2 - t1; ctx.timers[3] = t3 - t2; ctx.timers[4] = t4 - t3;
+  return EIGX_OK;
+}
+
+int hgev_range_host(Context& ctx, int n, int il, int iu, double* a, int lda, double* b, int ldb, double* w, double* z, int ldz,
+                    char mode) {
+  if (!ctx.initialized) return EIGX_ERR_NOT_INITIALIZED;
+  if (ctx.grid.nranks != 1) return hgev_range_dev(ctx, n, il, iu, a, lda, b, ldb, w, z, ldz, mode);   // refuses
+  mode = upper_case(mode);
+  if (n <= 0 || il < 1 || iu > n || il > iu || (mode != 'A' && mode != 'N') || !a || !b || !w || lda < n || ldb < n ||
+      (mode == 'A' && (!z || ldz < n)))
+    return EIGX_ERR_BAD_ARG;
+  const int m = iu - il + 1;
+  EIGX_HIP_CHECK(hipSetDevice(ctx.device));
+  const int ldd = host_ld(n);
+  double* ad = (double*)host_to_dev(ctx, "host.ha", a, lda, n, n, 16);
+  double* bd = (double*)host_to_dev(ctx, "host.hb", b, ldb, n, n, 16);
+  double* zd = (double*)host_to_dev(ctx, "host.hz", nullptr, 0, n, mode == 'A' ? m : 1, 16);
+  double* wd = ctx.pool.get_t<double>("host.w", (size_t)m);
+  const int rc = hgev_range_dev(ctx, n, il, iu, ad, ldd, bd, ldd, wd, zd, ldd, mode);
+  if (rc == EIGX_OK || rc == EIGX_ERR_NONFINITE) EIGX_HIP_CHECK(hipMemcpy(w, wd, (size_t)m * 8, hipMemcpyDeviceToHost));
+  if (rc != EIGX_OK) return rc;
+  if (mode == 'A') dev_to_host(z, ldz, zd, ldd, n, m, 16);
+  dev_to_host(b, ldb, bd, ldd, n, n, 16);   // U in the upper triangle
+  return EIGX_OK;
+}
+
 }  // namespace eigx
 
 using namespace eigx;
@@ -345,6 +441,14 @@ int eigx_hgev(int n, double* a, int lda, double* b, int ldb, double* w, double* 
 }
 int eigx_hgev_dev(int n, double* a, int lda, double* b, int ldb, double* w, double* z, int ldz) {
   return eigx_guard(g_ctx, [&] { return hgev_dev(g_ctx, n, a, lda, b, ldb, w, z, ldz); });
+}
+
+// EXTENSION: eigenpairs il .. iu of the complex problem by the Cholesky route (one GPU); see hgev_range_dev
+int eigx_hgev_range(int n, int il, int iu, double* a, int lda, double* b, int ldb, double* w, double* z, int ldz, char mode) {
+  return eigx_guard(g_ctx, [&] { return hgev_range_host(g_ctx, n, il, iu, a, lda, b, ldb, w, z, ldz, mode); });
+}
+int eigx_hgev_range_dev(int n, int il, int iu, double* a, int lda, double* b, int ldb, double* w, double* z, int ldz, char mode) {
+  return eigx_guard(g_ctx, [&] { return hgev_range_dev(g_ctx, n, il, iu, a, lda, b, ldb, w, z, ldz, mode); });
 }
 
 }  // extern "C"

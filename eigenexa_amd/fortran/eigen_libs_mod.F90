@@ -832,3 +832,32 @@ subroutine KMATH_EIGEN_GEV_RANGE(n, il, iu, a, lda, b, ldb, w, z, ldz, mode)
   rc = eigx_gev_range(int(n, c_int), int(il, c_int), int(iu, c_int), a, int(lda, c_int), b, int(ldb, c_int), w, z, &
                       int(ldz, c_int), md)
 end subroutine KMATH_EIGEN_GEV_RANGE
+
+! KMATH_EIGEN_HGEV_RANGE -- EXTENSION, not in the reference: eigenpairs il .. iu (1-based, inclusive) of the complex
+! Hermitian-definite problem A x = lambda B x by the Cholesky route (B = U^H U, C = U^-H A U^-1, eigen_h of C with
+! nvec = iu, Z = U^-1 Y) on one GPU.  w(1:iu-il+1) ascending, z(:, 1:iu-il+1) with z^H B z = I; modes 'A' and 'N'.  Upper
+! triangles of a, b significant; a is destroyed, b holds U in its upper triangle.  External like KMATH_EIGEN_HGEV; a caller
+! that passes or omits `mode` needs an explicit interface.
+subroutine KMATH_EIGEN_HGEV_RANGE(n, il, iu, a, lda, b, ldb, w, z, ldz, mode)
+  use, intrinsic :: iso_c_binding
+  implicit none
+  integer, intent(in) :: n, il, iu, lda, ldb, ldz
+  complex(8), intent(inout) :: a(lda, *), b(ldb, *), z(ldz, *)
+  real(8), intent(inout) :: w(*)
+  character(*), intent(in), optional :: mode
+  interface
+    integer(c_int) function eigx_hgev_range(n, il, iu, a, lda, b, ldb, w, z, ldz, mode) bind(C, name="eigx_hgev_range")
+      import :: c_int, c_double, c_double_complex, c_char
+      integer(c_int), value :: n, il, iu, lda, ldb, ldz
+      complex(c_double_complex), intent(inout) :: a(lda, *), b(ldb, *), z(ldz, *)
+      real(c_double), intent(inout) :: w(*)
+      character(kind=c_char), value :: mode
+    end function
+  end interface
+  integer(c_int) :: rc
+  character(kind=c_char) :: md
+  md = 'A'
+  if (present(mode)) md = mode(1:1)
+  rc = eigx_hgev_range(int(n, c_int), int(il, c_int), int(iu, c_int), a, int(lda, c_int), b, int(ldb, c_int), w, z, &
+                       int(ldz, c_int), md)
+end subroutine KMATH_EIGEN_HGEV_RANGE

@@ -25,7 +25,8 @@
  * eigx_gev[_dev] (KMATH_EIGEN_GEV), eigx_h[_dev] (complex Hermitian eigen_h), eigx_hgev[_dev] (KMATH_EIGEN_HGEV, an
  * extension: complex Hermitian generalised problem), eigx_sx_range / eigx_s_range[_dev] (an extension: eigenpairs il .. iu
  * of the ascending spectrum, one GPU), eigx_gev_range[_dev] (KMATH_EIGEN_GEV_RANGE, an extension: eigenpairs il .. iu of
- * the generalised problem by the Cholesky route, one GPU).
+ * the generalised problem by the Cholesky route, one GPU), eigx_hgev_range[_dev] (KMATH_EIGEN_HGEV_RANGE, an extension: the
+ * same for the complex Hermitian generalised problem, one GPU).
  */
 #ifndef EIGENEXA_AMD_H
 #define EIGENEXA_AMD_H
@@ -293,6 +294,40 @@ int eigx_gev_range_dev(int n, int il, int iu, double* a_dev, int lda, double* b_
 int eigx_chol_dev(int n, double* b_dev, int ldb);
 int eigx_trsm_upper_dev(char trans, int n, int nrhs, const double* u_dev, int ldu, double* x_dev, int ldx);
 int eigx_gev_reduce_dev(int n, double* a_dev, int lda, const double* u_dev, int ldu);
+
+/* KMATH_EIGEN_HGEV_RANGE -- EXTENSION, not in the reference: eigenpairs il .. iu of the complex Hermitian-definite
+ * problem A x = lambda B x by the Cholesky route of LAPACK's zhegvd (csrc/ztri.hip): B = U^H U ->
+ * C = U^-H A U^-1 -> eigen_h of C with nvec = iu (it scales C itself) -> Z = U^-1 Y on the columns il .. iu.  The contract
+ * of eigx_gev_range over complex numbers, the storage of eigx_hgev: a, b, z complex(8) as interleaved (re, im) doubles,
+ * column-major, leading dimensions in COMPLEX elements.  il = 1, iu = n is a full solve at about half the cost of
+ * eigx_hgev, which keeps its method and on-exit contract.
+ * One GPU only: with more than one rank the call prints one line and returns EIGX_ERR_BAD_ARG.
+ * 1 <= il <= iu <= n, m = iu - il + 1: w(1:m) = eigenvalues il .. iu of the ascending generalised spectrum, z(:, 1:m)
+ * the eigenvectors with z^H B z = I_m; nothing beyond m entries / columns of w, z is touched.  mode 'A' eigenpairs, 'N'
+ * eigenvalues only (z may be NULL, no back-substitution); anything else is EIGX_ERR_BAD_ARG.  Upper triangles of a, b
+ * significant (NaN in the strict lower triangles and in Im of the diagonals does not matter).  On exit a is destroyed; b
+ * holds U in its upper triangle (B = U^H U, Im of U's diagonal = 0), its strict lower triangle is unspecified.  The
+ * significant triangles of a AND b are scanned before anything is factored: a non-finite entry gives EIGX_ERR_NONFINITE
+ * and w(1:m) = NaN.  B not positive definite: EIGX_ERR_NOT_SPD and the message of eigx_hgev.  Host form: any leading
+ * dimensions.  Device form: any leading dimensions >= n (as eigx_hgev_dev); it waits on the default stream on entry.
+ * eigx_get_timers [0..4] = total, factorisation, forming C, the inner eigen_h, back-substitution.  The inner solve is
+ * eigen_h, not a subset path: with il > 1 the columns 1 .. il - 1 are computed and dropped, the workspace holds an
+ * n x iu complex Y, and eigx_range_info / eigx_range_timers are not written.  B is NOT scaled (the limitation of
+ * eigx_gev_range).  Workspace: pooled buffers named "hgevr.*": three n x n complex matrices as split planes, C and Y
+ * interleaved, panels of n x NB and the n x NB block inverses. */
+int eigx_hgev_range(int n, int il, int iu, double* a, int lda, double* b, int ldb, double* w, double* z, int ldz, char mode);
+int eigx_hgev_range_dev(int n, int il, int iu, double* a_dev, int lda, double* b_dev, int ldb, double* w_dev, double* z_dev,
+                        int ldz, char mode);
+/* Its stages (one GPU, device arrays of interleaved complex(8), any leading dimension >= n in complex elements, LAPACK
+ * uplo = 'U'; NB = eigx_tune key 20, shared with the real stages).
+ * eigx_zchol_dev: B = U^H U, U in place in the upper triangle with a real positive diagonal (Im written as 0); nothing
+ * below the diagonal and no Im of the diagonal is read; EIGX_OK, or EIGX_ERR_NOT_SPD for a pivot that is not > 0 or not
+ * finite.  eigx_ztrsm_upper_dev: x(n, nrhs) <- op(U)^-1 x in place, trans 'N' or 'C' (conjugate transpose), by block
+ * inversion.  eigx_hgev_reduce_dev: upper(a) <- U^-H A U^-1 for the upper triangle of a on entry (the strict lower
+ * triangle of a is left as it was).  More than one rank: EIGX_ERR_INTERNAL. */
+int eigx_zchol_dev(int n, double* b_dev, int ldb);
+int eigx_ztrsm_upper_dev(char trans, int n, int nrhs, const double* u_dev, int ldu, double* x_dev, int ldx);
+int eigx_hgev_reduce_dev(int n, double* a_dev, int lda, const double* u_dev, int ldu);
 
 /* replaces eigen_bisect(d,e,w,n,mode) src/bisect.F:67-397 (band=1) / eigen_bisect2(d,e,f,w,n,mode)
  * src/bisect2.F:71-718 (band=2): all eigenvalues of the band matrix by Sturm counts, w_dev ascending.
