@@ -89,7 +89,8 @@ SIGNATURES = {
     "eigx_chol_dev": (C.c_int, [C.c_int, C.c_void_p, C.c_int]),
     "eigx_trsm_upper_dev": (C.c_int, [C.c_char, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int]),
     "eigx_gev_reduce_dev": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int]),
-    # extension (not in the reference): the same for the complex Hermitian generalised problem (csrc/ztri.hip)
+    # extension (not in the reference): the same for the complex Hermitian generalised problem (csrc/ztri.hip, on the
+    # split planes of csrc/zplanes.hip)
     "eigx_hgev_range": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p,
                                   C.c_void_p, C.c_int, C.c_char]),
     "eigx_hgev_range_dev": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p,

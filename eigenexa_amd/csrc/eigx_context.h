@@ -182,33 +182,46 @@ void transpose_dev(hipStream_t st, int n, const double* in, int ldi, double* out
 int set_tri_nb(int v);
 int get_tri_nb();
 
-// ztri.hip (EXTENSION, one GPU): the complex siblings of the above on split planes (Re and Im as two real column-major
-// arrays of one leading dimension), pool buffers "hgevr.*", the same outer block width (key 20).  zchol_upper_dev:
-// B = U^H U in place, real positive diagonal, Im of B's diagonal not read and Im of U's written as 0 (synchronous; EIGX_OK
-// or EIGX_ERR_NOT_SPD).  ztri_inverses_dev: the inverses of U's diagonal blocks, block K at vr / vi + K nb^2, valid until
-// the next call.  ztrsm_upper_dev: X(n, nrhs) <- op(U)^-1 X, trans 'N' or 'C'; enqueued; upper_only as above (trans 'C').
-// hgev_reduce_dev: upper(C) = U^-H A U^-1 from the planes of the full Hermitian A (overwritten); enqueued.
-// zplanes: both planes of an ld x ncols matrix in ONE pool buffer `name`.
-struct ZTriInv { double* vr = nullptr; double* vi = nullptr; int nb = 0; };
-struct ZPlanes { double* r = nullptr; double* i = nullptr; };
+// zplanes.hip: complex matrices as split planes (Re and Im as two real column-major arrays of one leading dimension), shared
+// by herm.hip, hgev.hip and ztri.hip.  A ZPlanes that is only read is passed like one that is written: the note behind
+// each declaration names the planes the routine writes.
+// zplanes: both planes of an ld x ncols matrix in ONE pool buffer `name`.  Conversions from / to interleaved complex(8)
+// (leading dimensions in complex elements), enqueued; x is a local block of nr x nc, with G that of the 2-D cyclic layout:
+// zexpand: the upper triangle of a -> the full Hermitian n x n matrix; zsplit: herm = the entries on or above the global
+// diagonal only, Im of the diagonal := 0, w = optional scaling of column c by w[global c]^(-1/2); zjoin: upper = only the
+// entries on or above the global diagonal; zconj_transpose: out = in^H (n x n).
+// zgemm_planes: C = alpha op(A) B + beta C, op = none ('N') or conjugate transpose ('C'), as four real products (dgemm_dev:
+// tri_mode, and the batch strides, the same for both planes of an operand).
+struct ZPlanes {
+  double* r = nullptr; double* i = nullptr;
+  ZPlanes at(size_t off) const { return {r + off, i + off}; }   // both planes from element `off` on
+};
+struct ZBatch { int batch = 1; long sA = 0, sB = 0, sC = 0; int batch2 = 1; long sA2 = 0, sB2 = 0, sC2 = 0; };
 ZPlanes zplanes(Context& ctx, const char* name, int ld, int ncols);
-int zchol_upper_dev(Context& ctx, int n, double* Br, double* Bi, int ldb);
-ZTriInv ztri_inverses_dev(Context& ctx, int n, const double* Ur, const double* Ui, int ldu);
-void ztrsm_upper_dev(Context& ctx, char trans, int n, int nrhs, const double* Ur, const double* Ui, int ldu, double* Xr,
-                     double* Xi, int ldx, const ZTriInv& V, bool upper_only = false);
-void hgev_reduce_dev(Context& ctx, int n, double* Ar, double* Ai, int lda, const double* Ur, const double* Ui, int ldu,
-                     const ZTriInv& V, double* Cr, double* Ci, int ldc);
-void zconj_transpose_dev(hipStream_t st, int n, const double* inr, const double* ini, int ldi, double* outr, double* outi,
-                         int ldo);   // out = in^H (n x n)
-// hgev.hip: interleaved complex <-> planes (one GPU: Px = Py = 1, px = py = 0), shared with ztri.hip.  hg_expand_kernel:
-// upper triangle -> the full Hermitian matrix (grid: 32 x 32 tiles); hg_split_kernel: herm = 1 the upper triangle only, Im
-// of the diagonal := 0, w = optional column scaling; hg_join_kernel: upper = 1 only the entries on or above the diagonal.
-__global__ void hg_expand_kernel(const double* __restrict__ a, int lda, int n, double* __restrict__ Ar, double* __restrict__ Ai,
-                                 int ld);
-__global__ void hg_split_kernel(const double* __restrict__ x, int ldx, const double* __restrict__ w, int nr, int nc, int Px,
-                                int px, int Py, int py, int herm, double* __restrict__ Pr, double* __restrict__ Pi, int ld);
-__global__ void hg_join_kernel(const double* __restrict__ Pr, const double* __restrict__ Pi, int ld, int nr, int nc, int Px,
-                               int px, int Py, int py, int upper, double* __restrict__ x, int ldx);
+// launch grid of a kernel that strides over an nr x nc block by columns: up to 8 workgroups of 256 along a column
+inline dim3 zcol_grid(int nr, int nc) { return dim3(ceil_div(nr, 256) < 8 ? ceil_div(nr, 256) : 8, nc < 65535 ? nc : 65535); }
+void zexpand(hipStream_t st, const double* a, int lda, int n, const ZPlanes& P, int ld);   // writes P
+void zsplit(hipStream_t st, const double* x, int ldx, int nr, int nc, bool herm, const ZPlanes& P, int ld,
+            const double* w = nullptr, const Grid& G = Grid());   // writes P
+void zjoin(hipStream_t st, const ZPlanes& P, int ld, int nr, int nc, bool upper, double* x, int ldx,
+           const Grid& G = Grid());   // writes x, reads P
+void zconj_transpose(hipStream_t st, int n, const ZPlanes& in, int ldi, const ZPlanes& out, int ldo);   // writes out
+void zgemm_planes(hipStream_t st, char opA, int M, int N, int K, double alpha, const ZPlanes& A, int lda, const ZPlanes& B, int ldb,
+                  double beta, const ZPlanes& C, int ldc, int tri_mode = 0, const ZBatch& zb = ZBatch());   // writes C
+
+// ztri.hip (EXTENSION, one GPU): the complex siblings of tri.hip's stages on split planes, pool buffers "hgevr.*", the same
+// outer block width (key 20).  zchol_upper_dev: B = U^H U in place, real positive diagonal, Im of B's diagonal not read and
+// Im of U's written as 0 (synchronous; EIGX_OK or EIGX_ERR_NOT_SPD).  ztri_inverses_dev: the inverses of U's diagonal
+// blocks, block K at v.at(K nb^2), valid until the next call.  ztrsm_upper_dev: X(n, nrhs) <- op(U)^-1 X, trans 'N' or
+// 'C'; enqueued; upper_only as above (trans 'C').  hgev_reduce_dev: upper(C) = U^-H A U^-1 from the planes of the full
+// Hermitian A (overwritten); enqueued.
+struct ZTriInv { ZPlanes v; int nb = 0; };
+int zchol_upper_dev(Context& ctx, int n, const ZPlanes& B, int ldb);   // writes B
+ZTriInv ztri_inverses_dev(Context& ctx, int n, const ZPlanes& U, int ldu);   // reads U
+void ztrsm_upper_dev(Context& ctx, char trans, int n, int nrhs, const ZPlanes& U, int ldu, const ZPlanes& X, int ldx,
+                     const ZTriInv& V, bool upper_only = false);   // writes X
+void hgev_reduce_dev(Context& ctx, int n, const ZPlanes& A, int lda, const ZPlanes& U, int ldu, const ZTriInv& V, const ZPlanes& C,
+                     int ldc);   // writes A and C
 
 // trbak.hip: T factors of the back-transformation ahead of time on stream s, and Z(:, 0:nvec) <- H_n ... H_{1+band} Z
 void trbak_prepare_dev(Context& ctx, int n, double* A, int lda, const double* e, int lde, int mb, int band, hipStream_t s);

@@ -104,18 +104,6 @@ __device__ __forceinline__ void hblock_sum(double (&v)[K], double* red /* 4*K */
   for (int q = 0; q < K; ++q) v[q] = (red[q] + red[K + q]) + (red[2 * K + q] + red[3 * K + q]);
 }
 
-// interleaved complex(8) upper triangle -> split planes of the FULL Hermitian matrix (lower := conj(upper), real diagonal)
-__global__ void h_split_kernel(const double* __restrict__ a, int lda, int n, double* __restrict__ Ar,
-                               double* __restrict__ Ai, int ld) {
-  const int j = blockIdx.y;
-  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i <= j; i += gridDim.x * blockDim.x) {
-    const double re = a[2 * ((size_t)i + (size_t)j * lda)];
-    const double im = (i == j) ? 0.0 : a[2 * ((size_t)i + (size_t)j * lda) + 1];
-    Ar[(size_t)i + (size_t)j * ld] = re; Ai[(size_t)i + (size_t)j * ld] = im;
-    if (i < j) { Ar[(size_t)j + (size_t)i * ld] = re; Ai[(size_t)j + (size_t)i * ld] = -im; }
-  }
-}
-
 __global__ void h_scale_kernel(double* __restrict__ a, int lda, int n, double s) {   // interleaved, upper triangle
   const int j = blockIdx.y;
   for (int i = blockIdx.x * blockDim.x + threadIdx.x; i <= j; i += gridDim.x * blockDim.x) {
@@ -669,44 +657,29 @@ __global__ void h_xstack_kernel(const double* __restrict__ Xr, const double* __r
 }
 
 // workspace of h_bt_block for up to nv eigenvector columns: Y = V^H Z stacked (YA | YB), its planes, X = T Y
-struct HBtWork { double *YA, *YB, *Yr, *Yi, *Xr, *Xi; };
+struct HBtWork { double *YA, *YB; ZPlanes Y, X; };
 HBtWork h_bt_work(Context& ctx, int nv) {
   HBtWork W;
   W.YA = ctx.pool.get_t<double>("h.YAB", (size_t)2 * 2 * HMB * nv);
   W.YB = W.YA + (size_t)2 * HMB * nv;
-  W.Yr = ctx.pool.get_t<double>("h.Yr", (size_t)HMB * nv);
-  W.Yi = ctx.pool.get_t<double>("h.Yi", (size_t)HMB * nv);
-  W.Xr = ctx.pool.get_t<double>("h.Xr", (size_t)HMB * nv);
-  W.Xi = ctx.pool.get_t<double>("h.Xi", (size_t)HMB * nv);
+  W.Y = {ctx.pool.get_t<double>("h.Yr", (size_t)HMB * nv), ctx.pool.get_t<double>("h.Yi", (size_t)HMB * nv)};
+  W.X = {ctx.pool.get_t<double>("h.Xr", (size_t)HMB * nv), ctx.pool.get_t<double>("h.Xi", (size_t)HMB * nv)};
   return W;
 }
 // one block of eigen_hrbakwyx on nvec columns of the planes Zr, Zi (ld ldzp, one buffer: V^H Z is batched over them):
-// Z -= V (T (V^H Z)) with the block's nb reflectors stacked as Vs = [Vr | Vi] (rows x 2nb, ld lds), T = Tr + i Ti (ld HMB)
-void h_bt_block(hipStream_t st, const HBtWork& W, const double* Vs, int lds, const double* Tr, const double* Ti, int nb,
-                int rows, int nvec, double* Zr, double* Zi, int ldzp) {
+// Z -= V (T (V^H Z)) with the block's nb reflectors stacked as Vs = [Vr | Vi] (rows x 2nb, ld lds), T on planes (ld HMB; read only)
+void h_bt_block(hipStream_t st, const HBtWork& W, const double* Vs, int lds, const ZPlanes& T, int nb, int rows, int nvec,
+                double* Zr, double* Zi, int ldzp) {
   // Y = V^H Z from YA = Vs^T Zr, YB = Vs^T Zi: one batched launch (256 tiles: the LDS-ring kernel; two launches of
   // 128 tiles each went to the 64 x 64 kernel)
   dgemm_dev(st, 'T', 'N', 2 * nb, nvec, rows, 1.0, Vs, lds, Zr, ldzp, 0.0, W.YA, 2 * HMB, 0, nullptr, nullptr, nullptr, 2, 0,
             (long)(Zi - Zr), (long)(W.YB - W.YA));
-  hipLaunchKernelGGL(h_ycombine_kernel, dim3(1, nvec), dim3(128), 0, st, W.YA, W.YB, nb, nvec, W.Yr, W.Yi);
-  // X = T Y : Xr = Tr Yr - Ti Yi ; Xi = Tr Yi + Ti Yr
-  dgemm_dev(st, 'N', 'N', nb, nvec, nb, 1.0, Tr, HMB, W.Yr, HMB, 0.0, W.Xr, HMB);
-  dgemm_dev(st, 'N', 'N', nb, nvec, nb, -1.0, Ti, HMB, W.Yi, HMB, 1.0, W.Xr, HMB);
-  dgemm_dev(st, 'N', 'N', nb, nvec, nb, 1.0, Tr, HMB, W.Yi, HMB, 0.0, W.Xi, HMB);
-  dgemm_dev(st, 'N', 'N', nb, nvec, nb, 1.0, Ti, HMB, W.Yr, HMB, 1.0, W.Xi, HMB);
+  hipLaunchKernelGGL(h_ycombine_kernel, dim3(1, nvec), dim3(128), 0, st, W.YA, W.YB, nb, nvec, W.Y.r, W.Y.i);
+  zgemm_planes(st, 'N', nb, nvec, nb, 1.0, T, HMB, W.Y, HMB, 0.0, W.X, HMB);   // X = T Y
   // Z -= V X : Zr -= Vs [Xr; -Xi] ; Zi -= Vs [Xi; Xr]   (K = 2nb)
-  hipLaunchKernelGGL(h_xstack_kernel, dim3(1, nvec), dim3(128), 0, st, W.Xr, W.Xi, nb, nvec, W.YA, W.YB);
+  hipLaunchKernelGGL(h_xstack_kernel, dim3(1, nvec), dim3(128), 0, st, W.X.r, W.X.i, nb, nvec, W.YA, W.YB);
   dgemm_dev(st, 'N', 'N', rows, nvec, 2 * nb, -1.0, Vs, lds, W.YA, 2 * HMB, 1.0, Zr, ldzp);
   dgemm_dev(st, 'N', 'N', rows, nvec, 2 * nb, -1.0, Vs, lds, W.YB, 2 * HMB, 1.0, Zi, ldzp);
-}
-
-__global__ void h_join_kernel(const double* __restrict__ Zr, const double* __restrict__ Zi, int ldzp, int n, int nvec,
-                              double* __restrict__ z, int ldz) {
-  const int c = blockIdx.y;
-  for (int r = blockIdx.x * blockDim.x + threadIdx.x; r < n; r += gridDim.x * blockDim.x) {
-    z[2 * ((size_t)r + (size_t)c * ldz)] = Zr[(size_t)r + (size_t)c * ldzp];
-    z[2 * ((size_t)r + (size_t)c * ldz) + 1] = Zi[(size_t)r + (size_t)c * ldzp];
-  }
 }
 
 // z(c0 + j, j) = 1 for j < cn: the identity on the eigenvector columns [c0, c0 + cn) (mode 'S')
@@ -862,7 +835,7 @@ static int herm_solve_full(SolveFrame& F, int n, int nvec, double* a, int lda, d
   H.Ar = ctx.pool.get_t<double>("h.Ar", (size_t)ld * (n + HMB));   // HMB columns of slack: the batched Gram products of phase A
   H.Ai = ctx.pool.get_t<double>("h.Ai", (size_t)ld * (n + HMB) + H_PLANE_SKEW) + H_PLANE_SKEW;
   const HWork ws = h_workspace(ctx, n, m, H);
-  hipLaunchKernelGGL(h_split_kernel, dim3(8, n), dim3(256), 0, st, a, lda, n, H.Ar, H.Ai, ld);
+  zexpand(st, a, lda, n, ZPlanes{H.Ar, H.Ai}, ld);
   HColumns C = h_start_reduction(st, H, ws, n, m);
 
   // ---- eigen_hrd: Hermitian -> real tridiagonal ---------------------------------------------------------------------
@@ -927,14 +900,13 @@ static int herm_solve_full(SolveFrame& F, int n, int nvec, double* a, int lda, d
       const int j0 = 1 + b * bw;
       const int nb = (j0 + bw <= n) ? bw : n - j0;
       const int rows = j0 + nb - 1;
-      const double* Tr = Tall + (size_t)b * 2 * HMB * HMB;
-      const double* Ti = Tr + (size_t)HMB * HMB;
+      double* Tr = Tall + (size_t)b * 2 * HMB * HMB;
       hipLaunchKernelGGL(h_stack_v_kernel, dim3(8, 2 * nb), dim3(256), 0, st, H.Ar + (size_t)j0 * ld, H.Ai + (size_t)j0 * ld,
                          ld, rows, nb, Vs, lds);
-      h_bt_block(st, W, Vs, lds, Tr, Ti, nb, rows, nvec, Zr, Zi, ldzp);
+      h_bt_block(st, W, Vs, lds, ZPlanes{Tr, Tr + (size_t)HMB * HMB}, nb, rows, nvec, Zr, Zi, ldzp);
     }
   }
-  if (want_vec) hipLaunchKernelGGL(h_join_kernel, dim3(8, nvec), dim3(256), 0, st, Zr, Zi, ldzp, n, nvec, z, ldz);
+  if (want_vec) zjoin(st, ZPlanes{Zr, Zi}, ldzp, n, nvec, false, z, ldz);
   return F.finish(w, n, ctx.timers[11], want_vec ? nvec : 0, n);
 }
 
@@ -1021,15 +993,6 @@ __global__ void hs_zero_below_kernel(HArgs H, int n, int nlc) {
   if (j >= n) return;
   for (int r = j + blockIdx.x * blockDim.x + threadIdx.x; r < n; r += gridDim.x * blockDim.x) {
     H.Ar[(size_t)lc * H.ld + r] = 0.0; H.Ai[(size_t)lc * H.ld + r] = 0.0;
-  }
-}
-__global__ void hs_join_cyclic_kernel(const double* __restrict__ zr, const double* __restrict__ zi, int ldt, int nr, int nzc,
-                                      double* __restrict__ z, int ldz) {
-  const int lj = blockIdx.y;
-  if (lj >= nzc) return;
-  for (int li = blockIdx.x * blockDim.x + threadIdx.x; li < nr; li += gridDim.x * blockDim.x) {
-    z[2 * ((size_t)lj * ldz + li)] = zr[(size_t)lj * ldt + li];
-    z[2 * ((size_t)lj * ldz + li) + 1] = zi[(size_t)lj * ldt + li];
   }
 }
 }  // namespace
@@ -1200,10 +1163,9 @@ static int herm_solve_sharded(SolveFrame& F, int n, int nvec, double* a, int lda
         const int j0 = blk_j0(b), nb = blk_j1(b) - j0;
         if (nb <= 0) continue;
         const int rows = j0 + nb - 1;
-        const double* Vs = brecv + (size_t)q * SB;
-        const double* Tr = Vs + (size_t)lds * 2 * HMB;
-        const double* Ti = Tr + (size_t)HMB * HMB;
-        h_bt_block(st, W, Vs, lds, Tr, Ti, nb, rows, cn, Zr, Zi, ldzp);
+        double* Vs = brecv + (size_t)q * SB;
+        double* Tr = Vs + (size_t)lds * 2 * HMB;
+        h_bt_block(st, W, Vs, lds, ZPlanes{Tr, Tr + (size_t)HMB * HMB}, nb, rows, cn, Zr, Zi, ldzp);
       }
     }
   }
@@ -1215,9 +1177,7 @@ static int herm_solve_sharded(SolveFrame& F, int n, int nvec, double* a, int lda
     double* ti_ = ctx.pool.get_t<double>("hs.zi", (size_t)ldt * (nloc_c > 0 ? nloc_c : 1));
     cols_to_cyclic_dev(ctx, n, nvec, 1, zc, c0, cn, Zr, ldzp, tr_, ldt, st);
     cols_to_cyclic_dev(ctx, n, nvec, 1, zc, c0, cn, Zi, ldzp, ti_, ldt, st);
-    if (nzc > 0 && nloc_r > 0)
-      hipLaunchKernelGGL(hs_join_cyclic_kernel, dim3(ceil_div(nloc_r, 256), nzc), dim3(256), 0, st, (const double*)tr_,
-                         (const double*)ti_, ldt, nloc_r, nzc, z, ldz);
+    zjoin(st, ZPlanes{tr_, ti_}, ldt, nloc_r, nzc, false, z, ldz);
   }
   // statistics a(1,1), a(2,1) on the owner of the first column
   return F.finish(w, n, ctx.timers[11], want_vec ? nvec : 0, (G.px == 0 && G.py == 0 && nloc_c > 0) ? nloc_r : 0);

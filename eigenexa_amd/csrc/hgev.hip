@@ -11,8 +11,9 @@
 // w = NaN (a is scanned before B's solve).  A is never scaled here, so eigen_h's overflow above a matrix scale of about
 // 1e77 is inherited.
 //
-// The three complex products are real fp64 MFMA GEMMs (dgemm_dev) on split planes, as in herm.hip:
-//   one GPU: four real products per complex product with beta accumulation (Tr = Ar Fr - Ai Fi, Ti = Ar Fi + Ai Fr).
+// The three complex products are real fp64 MFMA GEMMs (dgemm_dev) on split planes, as in herm.hip; the planes, their
+// conversions from and to the interleaved arrays and the one-GPU product are those of zplanes.hip:
+//   one GPU: four real products per complex product with beta accumulation (zgemm_planes: Tr = Ar Fr - Ai Fi, Ti = Ar Fi + Ai Fr).
 //            Stacking K to 2n instead would need two more n^2 planes for the same flops; the extra pass over C that
 //            the four-product form costs is ~1 ms at N = 8192 against ~45 ms of MFMA work per complex product.
 //            C = F^H T computes only the tiles that meet the upper triangle (tri_mode 1): eigen_h reads nothing else.
@@ -27,73 +28,6 @@
 #include <string>
 
 namespace eigx {
-
-// The three plane kernels below are shared with ztri.hip (declared in eigx_context.h).
-// one GPU: interleaved upper triangle of a -> planes of the full Hermitian matrix (lower = conj(upper), Im of the diagonal
-// := 0).  One 32 x 32 tile of the upper block triangle per workgroup; the mirrored tile goes through LDS, so both writes
-// are coalesced.
-__global__ __launch_bounds__(256) void hg_expand_kernel(const double* __restrict__ a, int lda, int n, double* __restrict__ Ar,
-                                                        double* __restrict__ Ai, int ld) {
-  __shared__ double sr[32][33], si[32][33];
-  const int ti = blockIdx.x, tj = blockIdx.y;   // tile row, tile column
-  if (ti > tj) return;
-  const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
-  const int i = ti * 32 + tx;
-  for (int c = ty; c < 32; c += 8) {
-    const int j = tj * 32 + c;
-    double re = 0.0, im = 0.0;
-    if (i <= j && j < n) {
-      const size_t o = (size_t)i + (size_t)j * lda;
-      re = a[2 * o];
-      im = (i == j) ? 0.0 : a[2 * o + 1];
-      Ar[(size_t)i + (size_t)j * ld] = re;
-      Ai[(size_t)i + (size_t)j * ld] = im;
-    }
-    sr[c][tx] = re; si[c][tx] = im;   // element (ti*32 + tx, tj*32 + c)
-  }
-  __syncthreads();
-  for (int c = ty; c < 32; c += 8) {
-    const int r = tj * 32 + tx, col = ti * 32 + c;   // (r, col) = conj of (col, r) = sr[tx][c]
-    if (r < n && col < r) {
-      Ar[(size_t)r + (size_t)col * ld] = sr[tx][c];
-      Ai[(size_t)r + (size_t)col * ld] = -si[tx][c];
-    }
-  }
-}
-
-// interleaved local block x (nr x nc) -> planes, column lc scaled by w[global column]^(-1/2) when w is given (F from U in
-// one pass).  herm: x holds the upper triangle of a Hermitian matrix on the 2-D cyclic blocks -- entries below the global
-// diagonal are not read (the planes keep what they hold there), Im of the diagonal := 0.
-__global__ void hg_split_kernel(const double* __restrict__ x, int ldx, const double* __restrict__ w, int nr, int nc, int Px,
-                                int px, int Py, int py, int herm, double* __restrict__ Pr, double* __restrict__ Pi, int ld) {
-  for (int lc = blockIdx.y; lc < nc; lc += gridDim.y) {
-    const int gc = lc * Py + py;
-    const double s = w ? 1.0 / sqrt(w[gc]) : 1.0;
-    for (int lr = blockIdx.x * blockDim.x + threadIdx.x; lr < nr; lr += gridDim.x * blockDim.x) {
-      const int gr = lr * Px + px;
-      if (herm && gr > gc) continue;
-      const size_t o = (size_t)lr + (size_t)lc * ldx;
-      const double re = x[2 * o];
-      const double im = (herm && gr == gc) ? 0.0 : x[2 * o + 1];
-      Pr[(size_t)lr + (size_t)lc * ld] = re * s;
-      Pi[(size_t)lr + (size_t)lc * ld] = im * s;
-    }
-  }
-}
-
-// planes -> interleaved local block x (nr x nc); upper: only the entries on or above the global diagonal
-__global__ void hg_join_kernel(const double* __restrict__ Pr, const double* __restrict__ Pi, int ld, int nr, int nc, int Px,
-                               int px, int Py, int py, int upper, double* __restrict__ x, int ldx) {
-  for (int lc = blockIdx.y; lc < nc; lc += gridDim.y) {
-    const int gc = lc * Py + py;
-    for (int lr = blockIdx.x * blockDim.x + threadIdx.x; lr < nr; lr += gridDim.x * blockDim.x) {
-      if (upper && lr * Px + px > gc) continue;
-      const size_t o = (size_t)lr + (size_t)lc * ldx;
-      x[2 * o] = Pr[(size_t)lr + (size_t)lc * ld];
-      x[2 * o + 1] = Pi[(size_t)lr + (size_t)lc * ld];
-    }
-  }
-}
 
 namespace {
 
@@ -127,12 +61,10 @@ __global__ void hg_unpack_b_kernel(const double* __restrict__ recv, int Px, int 
   }
 }
 
-inline dim3 col_grid(int nr, int nc) { return dim3(ceil_div(nr, 256) < 8 ? ceil_div(nr, 256) : 8, nc < 65535 ? nc : 65535); }
-
 // C = X B on the 2-D cyclic blocks (all n x n, complete matrices), complex on split planes, X = Xr + i sa Xi (sa = -1:
 // the conjugate of the stored planes).  tri: only the tiles of C that meet the upper triangle (tri_mode 2).  Synchronous.
-int zsumma(Context& ctx, int n, const double* Xr, const double* Xi, int ldx, double sa, const double* Br, const double* Bi,
-           int ldb, double* Cr, double* Ci, int ldc, bool tri) {
+int zsumma(Context& ctx, int n, const ZPlanes& X, int ldx, double sa, const ZPlanes& B, int ldb, const ZPlanes& C, int ldc,
+           bool tri) {
   const Grid& G = ctx.grid;
   hipStream_t st = ctx.stream;
   const int nr = local_count(n, G.Px, G.px), nc = local_count(n, G.Py, G.py);
@@ -152,20 +84,20 @@ int zsumma(Context& ctx, int n, const double* Xr, const double* Xi, int ldx, dou
   double* B1 = ctx.pool.get_t<double>("hgev.pb", (size_t)4 * kb * ncp);
   double* B2 = B1 + (size_t)2 * kb * ncp;
   for (int k0 = 0; k0 < n; k0 += kb) {
-    hipLaunchKernelGGL(mm_pack_a_kernel, dim3(ceil_div(nrp, 256), kbl_y), dim3(256), 0, st, Xr, ldx, nr, nc, k0 / G.Py, nrp, sendA);
-    hipLaunchKernelGGL(mm_pack_a_kernel, dim3(ceil_div(nrp, 256), kbl_y), dim3(256), 0, st, Xi, ldx, nr, nc, k0 / G.Py, nrp,
+    hipLaunchKernelGGL(mm_pack_a_kernel, dim3(ceil_div(nrp, 256), kbl_y), dim3(256), 0, st, X.r, ldx, nr, nc, k0 / G.Py, nrp, sendA);
+    hipLaunchKernelGGL(mm_pack_a_kernel, dim3(ceil_div(nrp, 256), kbl_y), dim3(256), 0, st, X.i, ldx, nr, nc, k0 / G.Py, nrp,
                        sendA + (size_t)nrp * kbl_y);
     comm_allgather(ctx, COMM_Y, sendA, Ap, (size_t)2 * nrp * kbl_y, st);     // Ap(:, q 2kbl_y + pl kbl_y + c)
-    hipLaunchKernelGGL(mm_pack_b_kernel, dim3(ceil_div(kbl_x, 256), ncp), dim3(256), 0, st, Br, ldb, nr, nc, k0 / G.Px, kbl_x, sendB);
-    hipLaunchKernelGGL(mm_pack_b_kernel, dim3(ceil_div(kbl_x, 256), ncp), dim3(256), 0, st, Bi, ldb, nr, nc, k0 / G.Px, kbl_x,
+    hipLaunchKernelGGL(mm_pack_b_kernel, dim3(ceil_div(kbl_x, 256), ncp), dim3(256), 0, st, B.r, ldb, nr, nc, k0 / G.Px, kbl_x, sendB);
+    hipLaunchKernelGGL(mm_pack_b_kernel, dim3(ceil_div(kbl_x, 256), ncp), dim3(256), 0, st, B.i, ldb, nr, nc, k0 / G.Px, kbl_x,
                        sendB + (size_t)kbl_x * ncp);
     comm_allgather(ctx, COMM_X, sendB, recvB, (size_t)2 * kbl_x * ncp, st);
     hipLaunchKernelGGL(hg_unpack_b_kernel, dim3(ceil_div(kbl_x, 256), ncp, G.Px), dim3(256), 0, st, (const double*)recvB, G.Px,
                        G.Py, kbl_x, kbl_y, ncp, kb, sa, B1, B2);
     const double beta = k0 == 0 ? 0.0 : 1.0;
     if (nr > 0 && nc > 0) {
-      dgemm_dev(st, 'N', 'N', nr, nc, 2 * kb, 1.0, Ap, nrp, B1, 2 * kb, beta, Cr, ldc, tri ? 2 : 0, tri ? &G : nullptr);
-      dgemm_dev(st, 'N', 'N', nr, nc, 2 * kb, 1.0, Ap, nrp, B2, 2 * kb, beta, Ci, ldc, tri ? 2 : 0, tri ? &G : nullptr);
+      dgemm_dev(st, 'N', 'N', nr, nc, 2 * kb, 1.0, Ap, nrp, B1, 2 * kb, beta, C.r, ldc, tri ? 2 : 0, tri ? &G : nullptr);
+      dgemm_dev(st, 'N', 'N', nr, nc, 2 * kb, 1.0, Ap, nrp, B2, 2 * kb, beta, C.i, ldc, tri ? 2 : 0, tri ? &G : nullptr);
     }
   }
   EIGX_HIP_CHECK(hipStreamSynchronize(st));
@@ -199,58 +131,40 @@ int hgev_dev_mg(Context& ctx, int n, double* a, int lda, double* b, int ldb, dou
   if (rc != EIGX_OK) return rc;
   const int ldt = ((nr > 2 ? nr : 2) + 1) & ~1;
   const size_t pl = (size_t)ldt * (nc > 0 ? nc : 1);
-  double* Ar = ctx.pool.get_t<double>("hgev.planes", 8 * pl);
-  double* Ai = Ar + pl;
-  double* Xr = Ai + pl;   // A^T, later C
-  double* Xi = Xr + pl;
-  double* Fr = Xi + pl;
-  double* Fi = Fr + pl;
-  double* Tr = Fi + pl;   // A F, later Z
-  double* Ti = Tr + pl;
-  const bool mine = nr > 0 && nc > 0;
-  const dim3 cg = col_grid(nr, nc);
-  if (mine)
-    hipLaunchKernelGGL(hg_split_kernel, cg, dim3(256), 0, st, (const double*)a, lda, (const double*)nullptr, nr, nc, G.Px, G.px,
-                       G.Py, G.py, 1, Ar, Ai, ldt);
-  dist_transpose(ctx, n, Ar, ldt, Xr, ldt, st, "hgev");
-  dist_transpose(ctx, n, Ai, ldt, Xi, ldt, st, "hgev");
-  if (mine)
-    hipLaunchKernelGGL(hg_merge_kernel, cg, dim3(256), 0, st, Ar, Ai, (const double*)Xr, (const double*)Xi, ldt, nr, nc, G.Px,
-                       G.px, G.Py, G.py);
+  double* planes = ctx.pool.get_t<double>("hgev.planes", 8 * pl);
+  const ZPlanes A = {planes, planes + pl};
+  const ZPlanes X = A.at(2 * pl);   // A^T, later C
+  const ZPlanes F = A.at(4 * pl);
+  const ZPlanes T = A.at(6 * pl);   // A F, later Z
+  zsplit(st, a, lda, nr, nc, true, A, ldt, nullptr, G);
+  dist_transpose(ctx, n, A.r, ldt, X.r, ldt, st, "hgev");
+  dist_transpose(ctx, n, A.i, ldt, X.i, ldt, st, "hgev");
+  if (nr > 0 && nc > 0)
+    hipLaunchKernelGGL(hg_merge_kernel, zcol_grid(nr, nc), dim3(256), 0, st, A.r, A.i, X.r, X.i, ldt, nr, nc, G.Px, G.px, G.Py, G.py);
   EIGX_HIP_CHECK(hipStreamSynchronize(st));
   if (comm_failed(ctx)) return EIGX_ERR_INTERNAL;
   rc = herm_solve_dev(ctx, n, n, b, ldb, w, z, ldz, HG_MF, HG_MB, 'X');                   // B = U diag(mu) U^H
   if (rc != EIGX_OK) return rc;
   const double t1 = now_s();
   if (!b_is_positive_definite(ctx, w)) return EIGX_ERR_NOT_SPD;
-  if (mine) {
-    hipLaunchKernelGGL(hg_split_kernel, cg, dim3(256), 0, st, (const double*)z, ldz, (const double*)w, nr, nc, G.Px, G.px, G.Py,
-                       G.py, 0, Fr, Fi, ldt);                                                // F = U diag(mu)^-1/2
-    hipLaunchKernelGGL(hg_join_kernel, cg, dim3(256), 0, st, (const double*)Fr, (const double*)Fi, ldt, nr, nc, G.Px, G.px, G.Py,
-                       G.py, 0, b, ldb);
-  }
-  rc = zsumma(ctx, n, Ar, Ai, ldt, 1.0, Fr, Fi, ldt, Tr, Ti, ldt, false);                  // T = A F
+  zsplit(st, z, ldz, nr, nc, false, F, ldt, w, G);                                          // F = U diag(mu)^-1/2
+  zjoin(st, F, ldt, nr, nc, false, b, ldb, G);
+  rc = zsumma(ctx, n, A, ldt, 1.0, F, ldt, T, ldt, false);                                  // T = A F
   if (rc != EIGX_OK) return rc;
-  dist_transpose(ctx, n, Fr, ldt, Ar, ldt, st, "hgev");                                     // F^T planes (A is done)
-  dist_transpose(ctx, n, Fi, ldt, Ai, ldt, st, "hgev");
-  rc = zsumma(ctx, n, Ar, Ai, ldt, -1.0, Tr, Ti, ldt, Xr, Xi, ldt, true);                  // C = F^H T, upper tiles
+  dist_transpose(ctx, n, F.r, ldt, A.r, ldt, st, "hgev");                                   // F^T planes (A is done)
+  dist_transpose(ctx, n, F.i, ldt, A.i, ldt, st, "hgev");
+  rc = zsumma(ctx, n, A, ldt, -1.0, T, ldt, X, ldt, true);                                  // C = F^H T, upper tiles
   if (rc != EIGX_OK) return rc;
-  if (mine)
-    hipLaunchKernelGGL(hg_join_kernel, cg, dim3(256), 0, st, (const double*)Xr, (const double*)Xi, ldt, nr, nc, G.Px, G.px, G.Py,
-                       G.py, 1, z, ldz);
+  zjoin(st, X, ldt, nr, nc, true, z, ldz, G);
   EIGX_HIP_CHECK(hipStreamSynchronize(st));
   const double t2 = now_s();
   rc = herm_solve_dev(ctx, n, n, z, ldz, w, a, lda, HG_MF, HG_MB, 'X');                   // C = Y diag(w) Y^H, Y in a
   if (rc != EIGX_OK) return rc;
   const double t3 = now_s();
-  if (mine)
-    hipLaunchKernelGGL(hg_split_kernel, cg, dim3(256), 0, st, (const double*)a, lda, (const double*)nullptr, nr, nc, G.Px, G.px,
-                       G.Py, G.py, 0, Ar, Ai, ldt);
-  rc = zsumma(ctx, n, Fr, Fi, ldt, 1.0, Ar, Ai, ldt, Tr, Ti, ldt, false);                  // Z = F Y
+  zsplit(st, a, lda, nr, nc, false, A, ldt, nullptr, G);
+  rc = zsumma(ctx, n, F, ldt, 1.0, A, ldt, T, ldt, false);                                  // Z = F Y
   if (rc != EIGX_OK) return rc;
-  if (mine)
-    hipLaunchKernelGGL(hg_join_kernel, cg, dim3(256), 0, st, (const double*)Tr, (const double*)Ti, ldt, nr, nc, G.Px, G.px, G.Py,
-                       G.py, 0, z, ldz);
+  zjoin(st, T, ldt, nr, nc, false, z, ldz, G);
   EIGX_HIP_CHECK(hipStreamSynchronize(st));
   const double t4 = now_s();
   ctx.timers[0] = t4 - t0; ctx.timers[1] = t1 - t0; ctx.timers[2] = t2 - t1; ctx.timers[3] = t3 - t2; ctx.timers[4] = t4 - t3;
@@ -272,43 +186,27 @@ int hgev_dev(Context& ctx, int n, double* a, int lda, double* b, int ldb, double
   if (rc != EIGX_OK) return rc;
   const int ld = pad_ld(n);
   const size_t pl = (size_t)ld * n;
-  double* Ar = ctx.pool.get_t<double>("hgev.ar", pl);   // A, later C, later Z
-  double* Ai = ctx.pool.get_t<double>("hgev.ai", pl);
-  double* Fr = ctx.pool.get_t<double>("hgev.fr", pl);
-  double* Fi = ctx.pool.get_t<double>("hgev.fi", pl);
-  double* Tr = ctx.pool.get_t<double>("hgev.tr", pl);   // A F, later Y
-  double* Ti = ctx.pool.get_t<double>("hgev.ti", pl);
-  const int nt = ceil_div(n, 32);
-  hipLaunchKernelGGL(hg_expand_kernel, dim3(nt, nt), dim3(256), 0, st, (const double*)a, lda, n, Ar, Ai, ld);
+  const ZPlanes A = {ctx.pool.get_t<double>("hgev.ar", pl), ctx.pool.get_t<double>("hgev.ai", pl)};   // A, later C, later Z
+  const ZPlanes F = {ctx.pool.get_t<double>("hgev.fr", pl), ctx.pool.get_t<double>("hgev.fi", pl)};
+  const ZPlanes T = {ctx.pool.get_t<double>("hgev.tr", pl), ctx.pool.get_t<double>("hgev.ti", pl)};   // A F, later Y
+  zexpand(st, a, lda, n, A, ld);
   rc = herm_solve_dev(ctx, n, n, b, ldb, w, z, ldz, HG_MF, HG_MB, 'X');                   // B = U diag(mu) U^H
   if (rc != EIGX_OK) return rc;
   const double t1 = now_s();
   if (!b_is_positive_definite(ctx, w)) return EIGX_ERR_NOT_SPD;
-  const dim3 cg = col_grid(n, n);
-  hipLaunchKernelGGL(hg_split_kernel, cg, dim3(256), 0, st, (const double*)z, ldz, (const double*)w, n, n, 1, 0, 1, 0, 0, Fr, Fi,
-                     ld);                                                                    // F = U diag(mu)^-1/2
-  hipLaunchKernelGGL(hg_join_kernel, cg, dim3(256), 0, st, (const double*)Fr, (const double*)Fi, ld, n, n, 1, 0, 1, 0, 0, b, ldb);
-  dgemm_dev(st, 'N', 'N', n, n, n, 1.0, Ar, ld, Fr, ld, 0.0, Tr, ld);                       // Tr = Ar Fr - Ai Fi
-  dgemm_dev(st, 'N', 'N', n, n, n, -1.0, Ai, ld, Fi, ld, 1.0, Tr, ld);
-  dgemm_dev(st, 'N', 'N', n, n, n, 1.0, Ar, ld, Fi, ld, 0.0, Ti, ld);                       // Ti = Ar Fi + Ai Fr
-  dgemm_dev(st, 'N', 'N', n, n, n, 1.0, Ai, ld, Fr, ld, 1.0, Ti, ld);
-  dgemm_dev(st, 'T', 'N', n, n, n, 1.0, Fr, ld, Tr, ld, 0.0, Ar, ld, 1);                    // Cr = Fr^T Tr + Fi^T Ti
-  dgemm_dev(st, 'T', 'N', n, n, n, 1.0, Fi, ld, Ti, ld, 1.0, Ar, ld, 1);
-  dgemm_dev(st, 'T', 'N', n, n, n, 1.0, Fr, ld, Ti, ld, 0.0, Ai, ld, 1);                    // Ci = Fr^T Ti - Fi^T Tr
-  dgemm_dev(st, 'T', 'N', n, n, n, -1.0, Fi, ld, Tr, ld, 1.0, Ai, ld, 1);
-  hipLaunchKernelGGL(hg_join_kernel, cg, dim3(256), 0, st, (const double*)Ar, (const double*)Ai, ld, n, n, 1, 0, 1, 0, 1, z, ldz);
+  zsplit(st, z, ldz, n, n, false, F, ld, w);                                                // F = U diag(mu)^-1/2
+  zjoin(st, F, ld, n, n, false, b, ldb);
+  zgemm_planes(st, 'N', n, n, n, 1.0, A, ld, F, ld, 0.0, T, ld);                            // T = A F
+  zgemm_planes(st, 'C', n, n, n, 1.0, F, ld, T, ld, 0.0, A, ld, 1);                         // C = F^H T, upper tiles
+  zjoin(st, A, ld, n, n, true, z, ldz);
   EIGX_HIP_CHECK(hipStreamSynchronize(st));
   const double t2 = now_s();
   rc = herm_solve_dev(ctx, n, n, z, ldz, w, a, lda, HG_MF, HG_MB, 'X');                   // C = Y diag(w) Y^H, Y in a
   if (rc != EIGX_OK) return rc;
   const double t3 = now_s();
-  hipLaunchKernelGGL(hg_split_kernel, cg, dim3(256), 0, st, (const double*)a, lda, (const double*)nullptr, n, n, 1, 0, 1, 0, 0, Tr,
-                     Ti, ld);
-  dgemm_dev(st, 'N', 'N', n, n, n, 1.0, Fr, ld, Tr, ld, 0.0, Ar, ld);                       // Zr = Fr Yr - Fi Yi
-  dgemm_dev(st, 'N', 'N', n, n, n, -1.0, Fi, ld, Ti, ld, 1.0, Ar, ld);
-  dgemm_dev(st, 'N', 'N', n, n, n, 1.0, Fr, ld, Ti, ld, 0.0, Ai, ld);                       // Zi = Fr Yi + Fi Yr
-  dgemm_dev(st, 'N', 'N', n, n, n, 1.0, Fi, ld, Tr, ld, 1.0, Ai, ld);
-  hipLaunchKernelGGL(hg_join_kernel, cg, dim3(256), 0, st, (const double*)Ar, (const double*)Ai, ld, n, n, 1, 0, 1, 0, 0, z, ldz);
+  zsplit(st, a, lda, n, n, false, T, ld);
+  zgemm_planes(st, 'N', n, n, n, 1.0, F, ld, T, ld, 0.0, A, ld);                            // Z = F Y
+  zjoin(st, A, ld, n, n, false, z, ldz);
   EIGX_HIP_CHECK(hipStreamSynchronize(st));
   const double t4 = now_s();
   ctx.timers[0] = t4 - t0; ctx.timers[1] = t1 - t0; ctx.timers[2] = t2 - t1; ctx.timers[3] = t3 - t2; ctx.timers[4] = t4 - t3;
@@ -368,22 +266,19 @@ int hgev_range_dev(Context& ctx, int n, int il, int iu, double* a, int lda, doub
   const ZPlanes U = zplanes(ctx, "hgevr.u", ld, n);
   const ZPlanes A = zplanes(ctx, "hgevr.a", ld, n);     // A, later the columns il .. iu of Y, later Z
   const ZPlanes Cp = zplanes(ctx, "hgevr.cp", ld, n);
-  const dim3 cg = col_grid(n, n);
-  hipLaunchKernelGGL(hg_split_kernel, cg, dim3(256), 0, st, (const double*)b, ldb, (const double*)nullptr, n, n, 1, 0, 1, 0, 1,
-                     U.r, U.i, ld);
-  if (zchol_upper_dev(ctx, n, U.r, U.i, ld) != EIGX_OK) {
+  zsplit(st, b, ldb, n, n, true, U, ld);
+  if (zchol_upper_dev(ctx, n, U, ld) != EIGX_OK) {
     fprintf(stderr, "[eigx] Matrix B is not positive definite!\n");
     return EIGX_ERR_NOT_SPD;
   }
-  hipLaunchKernelGGL(hg_join_kernel, cg, dim3(256), 0, st, (const double*)U.r, (const double*)U.i, ld, n, n, 1, 0, 1, 0, 1, b, ldb);
+  zjoin(st, U, ld, n, n, true, b, ldb);
   const double t1 = now_s();
-  const ZTriInv V = ztri_inverses_dev(ctx, n, U.r, U.i, ld);   // once per factor: the three solves below share them
-  const int nt = ceil_div(n, 32);
-  hipLaunchKernelGGL(hg_expand_kernel, dim3(nt, nt), dim3(256), 0, st, (const double*)a, lda, n, A.r, A.i, ld);
-  hgev_reduce_dev(ctx, n, A.r, A.i, ld, U.r, U.i, ld, V, Cp.r, Cp.i, ld);
+  const ZTriInv V = ztri_inverses_dev(ctx, n, U, ld);   // once per factor: the three solves below share them
+  zexpand(st, a, lda, n, A, ld);
+  hgev_reduce_dev(ctx, n, A, ld, U, ld, V, Cp, ld);
   const int ldc = host_ld(n);
   double* c = ctx.pool.get_t<double>("hgevr.c", (size_t)2 * ldc * n);
-  hipLaunchKernelGGL(hg_join_kernel, cg, dim3(256), 0, st, (const double*)Cp.r, (const double*)Cp.i, ld, n, n, 1, 0, 1, 0, 1, c, ldc);
+  zjoin(st, Cp, ld, n, n, true, c, ldc);
   EIGX_HIP_CHECK(hipStreamSynchronize(st));
   const double t2 = now_s();
   double* wn = ctx.pool.get_t<double>("hgevr.w", (size_t)n);
@@ -395,11 +290,9 @@ int hgev_range_dev(Context& ctx, int n, int il, int iu, double* a, int lda, doub
   if (rc != EIGX_OK) return rc;
   const double t3 = now_s();
   if (mode == 'A') {
-    const dim3 cm = col_grid(n, m);
-    hipLaunchKernelGGL(hg_split_kernel, cm, dim3(256), 0, st, (const double*)(y + (size_t)2 * ldc * (il - 1)), ldc,
-                       (const double*)nullptr, n, m, 1, 0, 1, 0, 0, A.r, A.i, ld);
-    ztrsm_upper_dev(ctx, 'N', n, m, U.r, U.i, ld, A.r, A.i, ld, V);   // Z = U^-1 Y
-    hipLaunchKernelGGL(hg_join_kernel, cm, dim3(256), 0, st, (const double*)A.r, (const double*)A.i, ld, n, m, 1, 0, 1, 0, 0, z, ldz);
+    zsplit(st, y + (size_t)2 * ldc * (il - 1), ldc, n, m, false, A, ld);
+    ztrsm_upper_dev(ctx, 'N', n, m, U, ld, A, ld, V);   // Z = U^-1 Y
+    zjoin(st, A, ld, n, m, false, z, ldz);
     EIGX_HIP_CHECK(hipStreamSynchronize(st));
   }
   const double t4 = now_s();

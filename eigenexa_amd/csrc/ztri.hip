@@ -1,16 +1,17 @@
 // ztri.hip -- complex triangular stages of the Cholesky-route Hermitian generalised solver (EXTENSION, one GPU; LAPACK
 // uplo = 'U').  The complex siblings of tri.hip, on split planes (Re and Im of a matrix as two real column-major arrays
-// of one leading dimension), as hgev.hip and herm.hip work:
+// of one leading dimension, ZPlanes), as hgev.hip and herm.hip work:
 //   zchol_upper_dev    : B = U^H U, U in place in the upper triangle, real positive diagonal (role of zpotrf)
 //   ztri_inverses_dev  : the inverses of the NB-wide diagonal blocks of U (pool buffer hgevr.inv)
 //   ztrsm_upper_dev    : X <- op(U)^-1 X by block inversion, op = none ('N') or conjugate transpose ('C') (role of ztrsm)
 //   hgev_reduce_dev    : upper(C) = U^-H A U^-1 (role of zhegst, itype 1) by two solves with U^H and a conjugate transpose
 // NB is the outer block width, eigx_tune key 20, shared with tri.hip.  The structure is that of tri.hip step for step;
-// everything of O(n^3) is a complex product on the planes, which zgemm_planes runs as FOUR real fp64 MFMA GEMMs with beta
-// accumulation (Cr = Ar Br - Ai Bi, Ci = Ar Bi + Ai Br; a conjugate-transposed left operand flips the sign of Ai), the
-// form hgev.hip uses.  Stacking K to [Ur; Ui] instead would need the row panel of every step packed twice (rows are the K
-// index of a transposed operand, so the two planes of a panel are not contiguous in K) to save two of the four passes
-// over C; with K = NB = 256 a pass over C is 16 bytes per 512 flops of a product, far below what the GEMM is bound by.
+// everything of O(n^3) is a complex product on the planes, which zgemm_planes (zplanes.hip) runs as FOUR real fp64 MFMA
+// GEMMs with beta accumulation (Cr = Ar Br - Ai Bi, Ci = Ar Bi + Ai Br; a conjugate-transposed left operand flips the sign
+// of Ai).  The planes, their conversions and the conjugate transpose come from zplanes.hip as well.  Stacking K to
+// [Ur; Ui] instead would need the row panel of every step packed twice (rows are the K index of a transposed operand, so
+// the two planes of a panel are not contiguous in K) to save two of the four passes over C; with K = NB = 256 a pass over
+// C is 16 bytes per 512 flops of a product, far below what the GEMM is bound by.
 // Nothing below the diagonal of B / U is read; what the kernels write there is unspecified.  Im of B's diagonal is not
 // read; Im of U's diagonal is written as 0.
 #include "eigx_context.h"
@@ -221,26 +222,6 @@ __global__ __launch_bounds__(TB) void ztri_inv_diag_kernel(const double* __restr
     }
 }
 
-// out = in^H on planes (n x n)
-__global__ __launch_bounds__(256) void zconj_transpose_kernel(const double* __restrict__ inr, const double* __restrict__ ini,
-                                                              int ldi, double* __restrict__ outr, double* __restrict__ outi,
-                                                              int ldo, int n) {
-  __shared__ double Tr[32][33], Ti[32][33];
-  const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
-  const int r0 = blockIdx.x * 32, c0 = blockIdx.y * 32;
-  for (int c = ty; c < 32; c += 8)
-    if (r0 + tx < n && c0 + c < n) {
-      Tr[c][tx] = inr[(size_t)(c0 + c) * ldi + r0 + tx];
-      Ti[c][tx] = ini[(size_t)(c0 + c) * ldi + r0 + tx];
-    }
-  __syncthreads();
-  for (int c = ty; c < 32; c += 8)
-    if (c0 + tx < n && r0 + c < n) {
-      outr[(size_t)(r0 + c) * ldo + c0 + tx] = Tr[tx][c];
-      outi[(size_t)(r0 + c) * ldo + c0 + tx] = -Ti[tx][c];
-    }
-}
-
 // the four kernels with dynamic LDS above 64 KiB ask for it once
 void zlds_attributes() {
   static bool done = false;
@@ -252,35 +233,9 @@ void zlds_attributes() {
   done = true;
 }
 
-// batch strides of a complex product: the same for both planes of an operand
-struct ZBatch { int batch = 1; long sA = 0, sB = 0, sC = 0; int batch2 = 1; long sA2 = 0, sB2 = 0, sC2 = 0; };
-
-// C = alpha op(A) B + beta C on planes, op = none ('N') or conjugate transpose ('C'): four real products
-void zgemm_planes(hipStream_t st, char opA, int M, int N, int K, double alpha, const double* Ar, const double* Ai, int lda,
-                  const double* Br, const double* Bi, int ldb, double beta, double* Cr, double* Ci, int ldc, int tri_mode = 0,
-                  const ZBatch& zb = ZBatch()) {
-  if (M <= 0 || N <= 0 || K <= 0) return;
-  const char t = (opA == 'C') ? 'T' : 'N';
-  const double sa = (opA == 'C') ? -1.0 : 1.0;   // sign of Ai under op
-  auto one = [&](double al, const double* A, const double* B, double be, double* C) {
-    dgemm_dev(st, t, 'N', M, N, K, al, A, lda, B, ldb, be, C, ldc, tri_mode, nullptr, nullptr, nullptr, zb.batch, zb.sA, zb.sB,
-              zb.sC, zb.batch2, zb.sA2, zb.sB2, zb.sC2);
-  };
-  one(alpha, Ar, Br, beta, Cr);            // Cr = op(Ar) Br - sa op(Ai) Bi
-  one(-sa * alpha, Ai, Bi, 1.0, Cr);
-  one(alpha, Ar, Bi, beta, Ci);            // Ci = op(Ar) Bi + sa op(Ai) Br
-  one(sa * alpha, Ai, Br, 1.0, Ci);
-}
-
 }  // namespace
 
-void zconj_transpose_dev(hipStream_t st, int n, const double* inr, const double* ini, int ldi, double* outr, double* outi,
-                         int ldo) {
-  const int t = ceil_div(n, 32);
-  hipLaunchKernelGGL(zconj_transpose_kernel, dim3(t, t), dim3(256), 0, st, inr, ini, ldi, outr, outi, ldo, n);
-}
-
-int zchol_upper_dev(Context& ctx, int n, double* Br, double* Bi, int ldb) {
+int zchol_upper_dev(Context& ctx, int n, const ZPlanes& B, int ldb) {
   hipStream_t st = ctx.stream;
   const int NB = get_tri_nb();
   zlds_attributes();
@@ -291,19 +246,19 @@ int zchol_upper_dev(Context& ctx, int n, double* Br, double* Bi, int ldb) {
     const int p1 = std::min(p0 + NB, n);
     for (int j0 = p0; j0 < p1; j0 += TB) {
       const int nb = std::min(TB, n - j0), j1 = j0 + nb;
-      hipLaunchKernelGGL(zchol_diag_upper_kernel, dim3(1), dim3(2 * TB), ZDIAG_SHM, st, Br, Bi, ldb, j0, nb, stat);
+      hipLaunchKernelGGL(zchol_diag_upper_kernel, dim3(1), dim3(2 * TB), ZDIAG_SHM, st, B.r, B.i, ldb, j0, nb, stat);
       if (j1 >= n) break;
-      hipLaunchKernelGGL(zchol_inv_block_kernel, dim3(1), dim3(TB), ZDIAG_SHM, st, (const double*)Br, (const double*)Bi, ldb, j0, nb, Vt);
-      hipLaunchKernelGGL(zchol_row_panel_kernel, dim3(ceil_div(n - j1, TB)), dim3(256), ZROW_SHM, st, Br, Bi, ldb, j0, nb, j1,
+      hipLaunchKernelGGL(zchol_inv_block_kernel, dim3(1), dim3(TB), ZDIAG_SHM, st, (const double*)B.r, (const double*)B.i, ldb, j0, nb, Vt);
+      hipLaunchKernelGGL(zchol_row_panel_kernel, dim3(ceil_div(n - j1, TB)), dim3(256), ZROW_SHM, st, B.r, B.i, ldb, j0, nb, j1,
                          n - j1, (const double*)Vt);
       // the panel's remaining rows, all columns to the right: B(j1:p1, j1:n) -= U(j0:j1, j1:p1)^H U(j0:j1, j1:n)
-      const size_t ou = (size_t)j1 * ldb + j0, oc = (size_t)j1 * ldb + j1;
-      if (j1 < p1) zgemm_planes(st, 'C', p1 - j1, n - j1, nb, -1.0, Br + ou, Bi + ou, ldb, Br + ou, Bi + ou, ldb, 1.0, Br + oc, Bi + oc, ldb);
+      const ZPlanes U12 = B.at((size_t)j1 * ldb + j0);
+      if (j1 < p1) zgemm_planes(st, 'C', p1 - j1, n - j1, nb, -1.0, U12, ldb, U12, ldb, 1.0, B.at((size_t)j1 * ldb + j1), ldb);
     }
     if (p1 < n) {
       // trailing update of the outer panel, tiles of the upper triangle only: B22 -= U12^H U12
-      const size_t ou = (size_t)p1 * ldb + p0, oc = (size_t)p1 * ldb + p1;
-      zgemm_planes(st, 'C', n - p1, n - p1, p1 - p0, -1.0, Br + ou, Bi + ou, ldb, Br + ou, Bi + ou, ldb, 1.0, Br + oc, Bi + oc, ldb, 1);
+      const ZPlanes U12 = B.at((size_t)p1 * ldb + p0);
+      zgemm_planes(st, 'C', n - p1, n - p1, p1 - p0, -1.0, U12, ldb, U12, ldb, 1.0, B.at((size_t)p1 * ldb + p1), ldb, 1);
     }
   }
   int bad = 0;
@@ -312,7 +267,7 @@ int zchol_upper_dev(Context& ctx, int n, double* Br, double* Bi, int ldb) {
   return bad ? EIGX_ERR_NOT_SPD : EIGX_OK;
 }
 
-ZTriInv ztri_inverses_dev(Context& ctx, int n, const double* Ur, const double* Ui, int ldu) {
+ZTriInv ztri_inverses_dev(Context& ctx, int n, const ZPlanes& U, int ldu) {
   hipStream_t st = ctx.stream;
   const int NB = get_tri_nb();
   zlds_attributes();
@@ -320,14 +275,16 @@ ZTriInv ztri_inverses_dev(Context& ctx, int n, const double* Ur, const double* U
   const size_t vp = (size_t)nblk * NB * NB;
   ZTriInv V;
   V.nb = NB;
-  V.vr = ctx.pool.get_t<double>("hgevr.inv", 2 * vp);
-  V.vi = V.vr + vp;
+  V.v.r = ctx.pool.get_t<double>("hgevr.inv", 2 * vp);
+  V.v.i = V.v.r + vp;
   // U12 V22 of one level: at most n / (2 w) blocks of w x w, w < NB; two planes
   const size_t tp = (size_t)n * NB + (size_t)NB * NB;
-  double* Tr = ctx.pool.get_t<double>("hgevr.invt", 2 * tp);
-  double* Ti = Tr + tp;
-  EIGX_HIP_CHECK(hipMemsetAsync(V.vr, 0, 2 * vp * sizeof(double), st));
-  hipLaunchKernelGGL(ztri_inv_diag_kernel, dim3(ceil_div(n, TB)), dim3(TB), ZDIAG_SHM, st, Ur, Ui, ldu, n, NB, V.vr, vp);
+  ZPlanes T;
+  T.r = ctx.pool.get_t<double>("hgevr.invt", 2 * tp);
+  T.i = T.r + tp;
+  EIGX_HIP_CHECK(hipMemsetAsync(V.v.r, 0, 2 * vp * sizeof(double), st));
+  hipLaunchKernelGGL(ztri_inv_diag_kernel, dim3(ceil_div(n, TB)), dim3(TB), ZDIAG_SHM, st, (const double*)U.r, (const double*)U.i,
+                     ldu, n, NB, V.v.r, vp);
   // `batch` pairs (left block of width w at local offset o + 2 w q, right block of width wr behind it) in each of `batch2`
   // outer blocks from K0 on: V12 = -V11 (U12 V22)
   auto pairs = [&](int K0, int o, int w, int wr, int batch, int batch2) {
@@ -338,9 +295,9 @@ ZTriInv ztri_inverses_dev(Context& ctx, int n, const double* Ur, const double* U
     const size_t oV11 = ob + o + (size_t)o * NB, oV22 = ob + (o + w) + (size_t)(o + w) * NB, oV12 = ob + o + (size_t)(o + w) * NB;
     const long sU = 2L * w * (ldu + 1), sV = 2L * w * (NB + 1), sT = (long)w * w;
     const long sU2 = (long)NB * (ldu + 1), sV2 = (long)NB * NB, sT2 = sT * batch;
-    zgemm_planes(st, 'N', w, wr, wr, 1.0, Ur + oU12, Ui + oU12, ldu, V.vr + oV22, V.vi + oV22, NB, 0.0, Tr, Ti, w, 0,
+    zgemm_planes(st, 'N', w, wr, wr, 1.0, U.at(oU12), ldu, V.v.at(oV22), NB, 0.0, T, w, 0,
                  ZBatch{batch, sU, sV, sT, batch2, sU2, sV2, sT2});
-    zgemm_planes(st, 'N', w, wr, w, -1.0, V.vr + oV11, V.vi + oV11, NB, Tr, Ti, w, 0.0, V.vr + oV12, V.vi + oV12, NB, 0,
+    zgemm_planes(st, 'N', w, wr, w, -1.0, V.v.at(oV11), NB, T, w, 0.0, V.v.at(oV12), NB, 0,
                  ZBatch{batch, sV, sT, sV, batch2, sV2, sT2, sV2});
   };
   for (int w = TB; w < NB; w *= 2) {
@@ -354,74 +311,44 @@ ZTriInv ztri_inverses_dev(Context& ctx, int n, const double* Ur, const double* U
   return V;
 }
 
-void ztrsm_upper_dev(Context& ctx, char trans, int n, int nrhs, const double* Ur, const double* Ui, int ldu, double* Xr,
-                     double* Xi, int ldx, const ZTriInv& V, bool upper_only) {
+void ztrsm_upper_dev(Context& ctx, char trans, int n, int nrhs, const ZPlanes& U, int ldu, const ZPlanes& X, int ldx,
+                     const ZTriInv& V, bool upper_only) {
   if (nrhs <= 0) return;
   if (trans != 'C' || nrhs != n) upper_only = false;
   hipStream_t st = ctx.stream;
   const int NB = V.nb, nblk = ceil_div(n, NB);
-  double* tr = ctx.pool.get_t<double>("hgevr.xk", (size_t)2 * NB * nrhs);
-  double* ti = tr + (size_t)NB * nrhs;
+  ZPlanes t;
+  t.r = ctx.pool.get_t<double>("hgevr.xk", (size_t)2 * NB * nrhs);
+  t.i = t.r + (size_t)NB * nrhs;
   for (int q = 0; q < nblk; ++q) {
     const int K = (trans == 'C') ? q : nblk - 1 - q;           // U^H is lower triangular: forwards; U: backwards
     const int k0 = K * NB, w = std::min(NB, n - k0), k1 = k0 + w;
     // upper_only (trans 'C', X square): block row K of the result is wanted from column k0 on, and the rows below it want
     // still fewer columns, so the columns before k0 drop out of this and every later step (2/3 of the flops remain)
     const int c0 = upper_only ? k0 : 0, nc = nrhs - c0;
-    double* Xcr = Xr + (size_t)c0 * ldx;
-    double* Xci = Xi + (size_t)c0 * ldx;
-    const size_t ov = (size_t)K * NB * NB;
-    zgemm_planes(st, trans, w, nc, w, 1.0, V.vr + ov, V.vi + ov, NB, Xcr + k0, Xci + k0, ldx, 0.0, tr, ti, NB);
-    EIGX_HIP_CHECK(hipMemcpy2DAsync(Xcr + k0, (size_t)ldx * 8, tr, (size_t)NB * 8, (size_t)w * 8, (size_t)nc,
+    const ZPlanes Xc = X.at((size_t)c0 * ldx);
+    zgemm_planes(st, trans, w, nc, w, 1.0, V.v.at((size_t)K * NB * NB), NB, Xc.at(k0), ldx, 0.0, t, NB);
+    EIGX_HIP_CHECK(hipMemcpy2DAsync(Xc.r + k0, (size_t)ldx * 8, t.r, (size_t)NB * 8, (size_t)w * 8, (size_t)nc,
                                     hipMemcpyDeviceToDevice, st));
-    EIGX_HIP_CHECK(hipMemcpy2DAsync(Xci + k0, (size_t)ldx * 8, ti, (size_t)NB * 8, (size_t)w * 8, (size_t)nc,
+    EIGX_HIP_CHECK(hipMemcpy2DAsync(Xc.i + k0, (size_t)ldx * 8, t.i, (size_t)NB * 8, (size_t)w * 8, (size_t)nc,
                                     hipMemcpyDeviceToDevice, st));
-    if (trans == 'C') {
-      const size_t ou = (size_t)k1 * ldu + k0;
-      zgemm_planes(st, 'C', n - k1, nc, w, -1.0, Ur + ou, Ui + ou, ldu, tr, ti, NB, 1.0, Xcr + k1, Xci + k1, ldx);
-    } else {
-      const size_t ou = (size_t)k0 * ldu;
-      zgemm_planes(st, 'N', k0, nc, w, -1.0, Ur + ou, Ui + ou, ldu, tr, ti, NB, 1.0, Xcr, Xci, ldx);
-    }
+    if (trans == 'C') zgemm_planes(st, 'C', n - k1, nc, w, -1.0, U.at((size_t)k1 * ldu + k0), ldu, t, NB, 1.0, Xc.at(k1), ldx);
+    else zgemm_planes(st, 'N', k0, nc, w, -1.0, U.at((size_t)k0 * ldu), ldu, t, NB, 1.0, Xc, ldx);
   }
 }
 
 // upper(C) = U^-H A U^-1 (below the diagonal C is unspecified); the planes of A hold the full Hermitian matrix and are
 // overwritten.  4 x 5/3 n^3 real flops: A <- U^-H A, C = A^H, C <- U^-H C on the block columns that reach the upper triangle.
-void hgev_reduce_dev(Context& ctx, int n, double* Ar, double* Ai, int lda, const double* Ur, const double* Ui, int ldu,
-                     const ZTriInv& V, double* Cr, double* Ci, int ldc) {
-  ztrsm_upper_dev(ctx, 'C', n, n, Ur, Ui, ldu, Ar, Ai, lda, V);
-  zconj_transpose_dev(ctx.stream, n, Ar, Ai, lda, Cr, Ci, ldc);
-  ztrsm_upper_dev(ctx, 'C', n, n, Ur, Ui, ldu, Cr, Ci, ldc, V, true);   // eigen_h reads the upper triangle only
-}
-
-ZPlanes zplanes(Context& ctx, const char* name, int ld, int ncols) {
-  const size_t pl = (size_t)ld * (ncols > 0 ? ncols : 1);
-  ZPlanes P;
-  P.r = ctx.pool.get_t<double>(name, 2 * pl);
-  P.i = P.r + pl;
-  return P;
+void hgev_reduce_dev(Context& ctx, int n, const ZPlanes& A, int lda, const ZPlanes& U, int ldu, const ZTriInv& V, const ZPlanes& C,
+                     int ldc) {
+  ztrsm_upper_dev(ctx, 'C', n, n, U, ldu, A, lda, V);
+  zconj_transpose(ctx.stream, n, A, lda, C, ldc);
+  ztrsm_upper_dev(ctx, 'C', n, n, U, ldu, C, ldc, V, true);   // eigen_h reads the upper triangle only
 }
 
 }  // namespace eigx
 
 using namespace eigx;
-
-namespace {
-
-inline dim3 zcol_grid(int nr, int nc) { return dim3(ceil_div(nr, 256) < 8 ? ceil_div(nr, 256) : 8, nc < 65535 ? nc : 65535); }
-
-// interleaved (ld in complex elements) -> planes; herm: the upper triangle only, Im of the diagonal := 0
-void zsplit(hipStream_t st, const double* x, int ldx, int nr, int nc, bool herm, const ZPlanes& P, int ld) {
-  hipLaunchKernelGGL(hg_split_kernel, zcol_grid(nr, nc), dim3(256), 0, st, x, ldx, (const double*)nullptr, nr, nc, 1, 0, 1, 0,
-                     herm ? 1 : 0, P.r, P.i, ld);
-}
-void zjoin(hipStream_t st, const ZPlanes& P, int ld, int nr, int nc, bool upper, double* x, int ldx) {
-  hipLaunchKernelGGL(hg_join_kernel, zcol_grid(nr, nc), dim3(256), 0, st, (const double*)P.r, (const double*)P.i, ld, nr, nc, 1, 0,
-                     1, 0, upper ? 1 : 0, x, ldx);
-}
-
-}  // namespace
 
 extern "C" {
 
@@ -436,7 +363,7 @@ int eigx_zchol_dev(int n, double* b_dev, int ldb) {
     const int ld = pad_ld(n);
     const ZPlanes U = zplanes(g_ctx, "hgevr.u", ld, n);
     zsplit(st, b_dev, ldb, n, n, true, U, ld);
-    const int rc = zchol_upper_dev(g_ctx, n, U.r, U.i, ld);
+    const int rc = zchol_upper_dev(g_ctx, n, U, ld);
     zjoin(st, U, ld, n, n, true, b_dev, ldb);
     EIGX_HIP_CHECK(hipStreamSynchronize(st));
     return rc;
@@ -458,8 +385,8 @@ int eigx_ztrsm_upper_dev(char trans, int n, int nrhs, const double* u_dev, int l
     const ZPlanes X = zplanes(g_ctx, "hgevr.a", ld, nrhs);
     zsplit(st, u_dev, ldu, n, n, true, U, ld);
     zsplit(st, x_dev, ldx, n, nrhs, false, X, ld);
-    const ZTriInv V = ztri_inverses_dev(g_ctx, n, U.r, U.i, ld);
-    ztrsm_upper_dev(g_ctx, trans, n, nrhs, U.r, U.i, ld, X.r, X.i, ld, V, false);
+    const ZTriInv V = ztri_inverses_dev(g_ctx, n, U, ld);
+    ztrsm_upper_dev(g_ctx, trans, n, nrhs, U, ld, X, ld, V, false);
     zjoin(st, X, ld, n, nrhs, false, x_dev, ldx);
     EIGX_HIP_CHECK(hipStreamSynchronize(st));
     return EIGX_OK;
@@ -475,14 +402,14 @@ int eigx_hgev_reduce_dev(int n, double* a_dev, int lda, const double* u_dev, int
     EIGX_HIP_CHECK(hipSetDevice(g_ctx.device));
     EIGX_HIP_CHECK(hipStreamSynchronize(nullptr));
     hipStream_t st = g_ctx.stream;
-    const int ld = pad_ld(n), nt = ceil_div(n, 32);
+    const int ld = pad_ld(n);
     const ZPlanes U = zplanes(g_ctx, "hgevr.u", ld, n);
     const ZPlanes A = zplanes(g_ctx, "hgevr.a", ld, n);
     const ZPlanes Cp = zplanes(g_ctx, "hgevr.cp", ld, n);
     zsplit(st, u_dev, ldu, n, n, true, U, ld);
-    hipLaunchKernelGGL(hg_expand_kernel, dim3(nt, nt), dim3(256), 0, st, (const double*)a_dev, lda, n, A.r, A.i, ld);
-    const ZTriInv V = ztri_inverses_dev(g_ctx, n, U.r, U.i, ld);
-    hgev_reduce_dev(g_ctx, n, A.r, A.i, ld, U.r, U.i, ld, V, Cp.r, Cp.i, ld);
+    zexpand(st, a_dev, lda, n, A, ld);
+    const ZTriInv V = ztri_inverses_dev(g_ctx, n, U, ld);
+    hgev_reduce_dev(g_ctx, n, A, ld, U, ld, V, Cp, ld);
     zjoin(st, Cp, ld, n, n, true, a_dev, lda);
     EIGX_HIP_CHECK(hipStreamSynchronize(st));
     return EIGX_OK;

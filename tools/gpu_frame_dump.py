@@ -4,7 +4,9 @@ usage: [EIGX_LIB=other/libeigenexa_amd.so] gpu_frame_dump.py OUTDIR [--quick]
 Runs a fixed list of seeded calls of eigen_sx / eigen_s, the index-range solves and eigen_h (device and host entry
 points; every mode, panel widths, nvec < n, odd leading dimensions, scaled and non-finite inputs) and writes for each
 call  NNN_label.{rc,w,z,flops}.npy : the returned status, w, z (the columns the call owns) and a(1,1) (the flop count;
-the seconds in a(2,1) differ from run to run and are left out).  An array above 8 MiB is stored as its SHA-256.
+the seconds in a(2,1) differ from run to run and are left out).  Then the complex generalised solvers eigx_hgev_dev and
+eigx_hgev_range_dev and their stages (Cholesky, triangular solves, reduction; eigx_tune key 20 = 64 and the default):
+the status, w, z and the arrays a / b as the call leaves them.  An array above 8 MiB is stored as its SHA-256.
 The library is deterministic, so two builds that compute the same leave directories that `cmp` finds equal:
     for f in A/*; do cmp $f B/$(basename $f); done
 Run each build in a fresh process.  --quick leaves out n >= 2048."""
@@ -147,5 +149,62 @@ for n in (1, 2, 3, 200, 1000) + (() if quick else (2048,)):
                 herm_dev(f"h_n{n}_{mode}_mf{mf}_v{nvec}", A, nvec, mode, mf)
 herm_dev("h_big", herm(200) * 1e120, 200, "A", 48)
 herm_dev("h_tiny", herm(200) * 1e-120, 200, "X", 48)
+
+# ---- the complex generalised solvers and their stages (split planes: zplanes.hip) ----------------------------------------
+def pencil(n):
+    g = np.random.default_rng(3000 + n)
+    X = g.standard_normal((n, n)) + 1j * g.standard_normal((n, n))
+    B = X @ X.conj().T / n + np.eye(n)
+    return herm(n), (B + B.conj().T) / 2
+
+
+def cdev(M, ld):
+    """t[j, i] = M(i, j) with leading dimension ld (complex elements), the padding zero"""
+    t = torch.zeros(M.shape[1], ld, dtype=torch.complex128, device=dev)
+    t[:, :M.shape[0]] = torch.from_numpy(np.ascontiguousarray(M.T)).to(dev)
+    return t
+
+
+def hgev_dev(label, n, il=None, iu=None, mode="A"):
+    A, B = pencil(n)
+    ld = n + 2
+    a, b = cdev(A, ld), cdev(B, ld)
+    m = n if il is None else iu - il + 1
+    z = torch.zeros(m, ld, dtype=torch.complex128, device=dev)
+    w = torch.zeros(m, dtype=torch.float64, device=dev)
+    if il is None:
+        rc = lib.eigx_hgev_dev(n, a.data_ptr(), ld, b.data_ptr(), ld, w.data_ptr(), z.data_ptr(), ld)
+    else:
+        rc = lib.eigx_hgev_range_dev(n, il, iu, a.data_ptr(), ld, b.data_ptr(), ld, w.data_ptr(), z.data_ptr(), ld,
+                                     mode.encode())
+    torch.cuda.synchronize()
+    save(label, rc=np.int64(rc), w=w.cpu().numpy(), z=z.cpu().numpy(), a=a.cpu().numpy(), b=b.cpu().numpy())
+
+
+for n in (5, 130, 517):
+    hgev_dev(f"hgev_n{n}", n)
+for n in (130, 517):
+    for il, iu in ((1, n), (n // 3, n // 3 + 39)):
+        for mode in "AN":
+            hgev_dev(f"hgevr_n{n}_{il}_{iu}_{mode}", n, il, iu, mode)
+nb_default = lib.eigx_tune(20, 64)
+for nb in (64, nb_default):
+    lib.eigx_tune(20, nb)
+    for n in (65, 517):
+        A, B = pencil(n)
+        ld = n + 2
+        b = cdev(B, ld)
+        rc = lib.eigx_zchol_dev(n, b.data_ptr(), ld)
+        torch.cuda.synchronize()
+        save(f"zchol_n{n}_nb{nb}", rc=np.int64(rc), b=b.cpu().numpy())
+        for trans in "NC":
+            x = cdev(A[:, :n // 2 + 1], ld)
+            rc = lib.eigx_ztrsm_upper_dev(trans.encode(), n, n // 2 + 1, b.data_ptr(), ld, x.data_ptr(), ld)
+            torch.cuda.synchronize()
+            save(f"ztrsm_n{n}_nb{nb}_{trans}", rc=np.int64(rc), z=x.cpu().numpy())
+        a = cdev(A, ld)
+        rc = lib.eigx_hgev_reduce_dev(n, a.data_ptr(), ld, b.data_ptr(), ld)
+        torch.cuda.synchronize()
+        save(f"hgev_reduce_n{n}_nb{nb}", rc=np.int64(rc), a=a.cpu().numpy())
 lib.eigx_free()
 print(f"DUMPED {count[0]} calls into {out}", flush=True)
