@@ -25,12 +25,16 @@ from .api import (  # noqa: F401
     eigen_h,
     eigen_sx_range,
     eigen_s_range,
+    eigen_sx_range_v,
+    eigen_s_range_v,
+    band_count,
     range_info,
     eigen_sx_bc,
     eigen_s_bc,
     numroc,
     KMATH_EIGEN_GEV,
     KMATH_EIGEN_GEV_RANGE,
+    KMATH_EIGEN_GEV_RANGE_V,
     KMATH_EIGEN_HGEV,
     KMATH_EIGEN_HGEV_RANGE,
     eigen_NB_f,

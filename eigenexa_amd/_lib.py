@@ -75,6 +75,20 @@ SIGNATURES = {
                                 C.c_int, C.c_int, C.c_char]),
     "eigx_s_range_dev": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int,
                                 C.c_int, C.c_int, C.c_char]),
+    # extension: the same by value window (vl <= lambda < vu); m and il come back through host int pointers
+    "eigx_sx_range_v": (C.c_int, [C.c_int, C.c_double, C.c_double, C.c_int, _c_int_p, _c_int_p, C.c_void_p, C.c_int,
+                                  C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_char]),
+    "eigx_s_range_v": (C.c_int, [C.c_int, C.c_double, C.c_double, C.c_int, _c_int_p, _c_int_p, C.c_void_p, C.c_int,
+                                 C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_char]),
+    "eigx_sx_range_v_dev": (C.c_int, [C.c_int, C.c_double, C.c_double, C.c_int, _c_int_p, _c_int_p, C.c_void_p, C.c_int,
+                                      C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_char]),
+    "eigx_s_range_v_dev": (C.c_int, [C.c_int, C.c_double, C.c_double, C.c_int, _c_int_p, _c_int_p, C.c_void_p, C.c_int,
+                                     C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_char]),
+    "eigx_gev_range_v": (C.c_int, [C.c_int, C.c_double, C.c_double, C.c_int, _c_int_p, _c_int_p, C.c_void_p, C.c_int,
+                                   C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_char]),
+    "eigx_gev_range_v_dev": (C.c_int, [C.c_int, C.c_double, C.c_double, C.c_int, _c_int_p, _c_int_p, C.c_void_p, C.c_int,
+                                       C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_char]),
+    "eigx_band_count_dev": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "eigx_band_bisect_range_dev": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
                                              C.c_void_p]),
     "eigx_band_eigvec_dev": (C.c_int, [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p,

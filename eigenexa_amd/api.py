@@ -296,6 +296,95 @@ def eigen_s_range(n, il, iu, a, lda, w, z, ldz, m_forward=None, m_backward=None,
     _solve_range("s", n, il, iu, a, lda, w, z, ldz, m_forward, m_backward, mode)
 
 
+def _value_window(name, n, vl, vu, w, z, mode, mmax):
+    """checks of the value-window wrappers, made before the library is touched: (mode byte, mmax) or None (status -2)"""
+    md = _char(mode, "A").upper()
+    try:
+        ok = int(n) > 0 and float(vl) < float(vu) and md in (b"A", b"N", b"C")   # a NaN bound fails the comparison
+        if ok and md != b"C":
+            if mmax is None:
+                mmax = int(w.numel() if _is_torch(w) else w.size)
+                if md == b"A" and z is not None and z.ndim == 2:
+                    # columns of z: a torch tensor holds the column-major image, z[j, i] = Z(i, j)
+                    mmax = min(mmax, int(z.shape[0] if _is_torch(z) else z.shape[1]))
+            ok = int(mmax) >= 1 and w is not None and not (md == b"A" and z is None)
+    except (TypeError, ValueError, AttributeError):
+        ok = False
+    if not ok:
+        _state["last_status"] = -2
+        print(f"Warning: {name}: invalid window / mode (n={n}, vl={vl}, vu={vu}, mmax={mmax}, mode={mode!r})", file=sys.stderr)
+        return None
+    return md, (0 if md == b"C" else int(mmax))
+
+
+def _finish_value_call(name, rc, m, il, quiet):
+    _state["last_status"] = rc
+    if rc not in quiet:
+        print(f"Warning: {name} returned without computing (status {rc})", file=sys.stderr)
+    return (m.value, il.value) if rc in (0, -9) else None
+
+
+def _solve_range_v(which, n, vl, vu, a, lda, w, z, ldz, m_forward, m_backward, mode, mmax):
+    chk = _value_window(f"eigen_{which}_range_v", n, vl, vu, w, z, mode, mmax)
+    if chk is None:
+        return None
+    md, mmax = chk
+    lib = _lib.load()
+    if not _state["initialized"]:
+        _state["last_status"] = -1
+        return None
+    dev = _is_torch(a)
+    if dev:
+        import torch
+
+        torch.cuda.current_stream().synchronize()
+    pa, pw, pz = _ptr(a, "a", dev), _ptr(w, "w", dev), _ptr(z, "z", dev)
+    mf = eigen_NB_f if m_forward is None else int(m_forward)
+    mb = eigen_NB_b if m_backward is None else int(m_backward)
+    fn = getattr(lib, f"eigx_{which}_range_v" + ("_dev" if dev else ""))
+    m, il = C.c_int(0), C.c_int(0)
+    rc = fn(int(n), float(vl), float(vu), mmax, C.byref(m), C.byref(il), pa, int(lda), pw, pz, int(ldz), mf, mb, md)
+    return _finish_value_call(f"eigen_{which}_range_v", rc, m, il, (0, -5, -9))
+
+
+def eigen_sx_range_v(n, vl, vu, a, lda, w, z, ldz, m_forward=None, m_backward=None, mode="A", mmax=None):
+    """EXTENSION (not in the reference; LAPACK's range = 'V'): the eigenpairs with ``vl <= lambda < vu`` by the
+    pentadiagonal route, one GPU.  Returns ``(m, il)``: ``m`` eigenvalues lie in the window, the first is number ``il``
+    (1-based) of the ascending spectrum; ``w[:m]``, ``z[:, :m]`` as from ``eigen_sx_range(n, il, il + m - 1, ...)``, bit for
+    bit.  The interval is half-open; an eigenvalue within rounding of an end point may fall on either side, as in LAPACK;
+    ``-inf`` / ``inf`` are allowed.  ``mmax`` = room in ``w`` / ``z`` (default: the entries of ``w``, further limited by the
+    columns of a 2-D ``z``): with ``m > mmax`` the status is -9, ``w`` and ``z`` are untouched and ``(m, il)`` is returned
+    for a retry by index; ``m = 0`` is status 0 with ``w``, ``z`` untouched.  Modes 'A', 'N' (``z`` may be None) and 'C'
+    (count only: ``w``, ``z`` may be None).  Returns None when nothing was resolved (any other status)."""
+    return _solve_range_v("sx", n, vl, vu, a, lda, w, z, ldz, m_forward, m_backward, mode, mmax)
+
+
+def eigen_s_range_v(n, vl, vu, a, lda, w, z, ldz, m_forward=None, m_backward=None, mode="A", mmax=None):
+    """EXTENSION: ``eigen_sx_range_v`` by the tridiagonal route."""
+    return _solve_range_v("s", n, vl, vu, a, lda, w, z, ldz, m_forward, m_backward, mode, mmax)
+
+
+def band_count(d, e, band, x):
+    """EXTENSION, stage entry: ``cnt[p]`` = number of eigenvalues of the symmetric band matrix below ``x[p]``.  ``d`` (n),
+    ``e`` (shape (2, lde) or flat with 2 lde entries, lde >= n, as ``eigx_band_reduce_dev`` writes it for either band) and
+    ``x`` are float64 torch tensors on the GPU; returns an int32 tensor of ``x.numel()`` counts (-1 for a NaN point)."""
+    import torch
+
+    lib = _lib.load()
+    n = int(d.numel())
+    lde = int(e.shape[-1]) if e.ndim == 2 else int(e.numel()) // 2
+    for t, name in ((d, "d"), (e, "e"), (x, "x")):
+        if not (_is_torch(t) and t.is_cuda and t.dtype == torch.float64 and t.is_contiguous()):
+            raise ValueError(f"{name}: contiguous float64 GPU tensor required")
+    if lde < n:
+        raise ValueError("e: two rows of at least n entries required")
+    cnt = torch.empty(x.numel(), dtype=torch.int32, device=x.device)
+    torch.cuda.current_stream().synchronize()
+    _lib.check(lib.eigx_band_count_dev(n, d.data_ptr(), e.data_ptr(), lde, int(band), int(x.numel()), x.data_ptr(),
+                                       cnt.data_ptr()), "eigx_band_count_dev")
+    return cnt.reshape(x.shape)
+
+
 def range_info():
     """What the last range call did: ``path`` (1 subset path, 2 fell back to the full divide and conquer, 3 full divide
     and conquer by the size rule), ``m`` and ``cond`` (the conditioning estimate of the acceptance test)."""
@@ -419,6 +508,31 @@ def KMATH_EIGEN_GEV_RANGE(n, il, iu, a, lda, b, ldb, w, z, ldz, mode="A"):
     _state["last_status"] = rc
     if rc not in (0, -5, -7):
         print(f"Warning: KMATH_EIGEN_GEV_RANGE returned without computing (status {rc})", file=sys.stderr)
+
+
+def KMATH_EIGEN_GEV_RANGE_V(n, vl, vu, a, lda, b, ldb, w, z, ldz, mode="A", mmax=None):
+    """EXTENSION, not in the reference: the eigenpairs of A x = lambda B x with ``vl <= lambda < vu`` by the Cholesky route
+    of ``KMATH_EIGEN_GEV_RANGE``, one GPU.  Window, ``mmax``, modes, statuses and the returned ``(m, il)`` as for
+    ``eigen_sx_range_v``; ``z[:, :m]`` with ``z^T B z = I``.  ``a`` is destroyed and ``b`` holds U on status 0; on status -9
+    host arrays are left as they were passed.  Status -7 if B is not positive definite."""
+    chk = _value_window("KMATH_EIGEN_GEV_RANGE_V", n, vl, vu, w, z, mode, mmax)
+    if chk is None:
+        return None
+    md, mmax = chk
+    lib = _lib.load()
+    if not _state["initialized"]:
+        _state["last_status"] = -1
+        return None
+    dev = _is_torch(a)
+    if dev:
+        import torch
+
+        torch.cuda.current_stream().synchronize()
+    pa, pb, pw, pz = _ptr(a, "a", dev), _ptr(b, "b", dev), _ptr(w, "w", dev), _ptr(z, "z", dev)
+    fn = lib.eigx_gev_range_v_dev if dev else lib.eigx_gev_range_v
+    m, il = C.c_int(0), C.c_int(0)
+    rc = fn(int(n), float(vl), float(vu), mmax, C.byref(m), C.byref(il), pa, int(lda), pb, int(ldb), pw, pz, int(ldz), md)
+    return _finish_value_call("KMATH_EIGEN_GEV_RANGE_V", rc, m, il, (0, -5, -7, -9))
 
 
 def KMATH_EIGEN_HGEV(n, a, lda, b, ldb, w, z, ldz):

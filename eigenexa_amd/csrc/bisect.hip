@@ -18,6 +18,7 @@
 // matrix rows).  The invariant count(lb) <= k < count(ub) is kept by construction, so the result brackets the
 // k-th eigenvalue even where rounding makes the pivoted count non-monotone.
 #include "eigx_context.h"
+#include "../../include/eigenexa_amd.h"
 #include <algorithm>
 #include <cfloat>
 #include <vector>
@@ -270,6 +271,23 @@ __global__ void bis_final_kernel(BisArgs a, double* w) {
   if (k < a.m) w[k] = 0.5 * (a.lb[k] + a.ub[k]);
 }
 
+// counts at caller-given points: cnt[p] = number of eigenvalues below x[p], one thread per point.  The ends are decided
+// before the recurrence, as the multi-section assumes them for its first brackets (count = 0 at the lower Gershgorin
+// bound and below, n at the upper one and above), so +-Inf and huge values never enter dd - x; NaN gives -1.  Such a
+// lane, and a lane past npts, still walks the matrix (sturm_count synchronises the workgroup) at a point of the interval.
+template <int BAND>
+__global__ __launch_bounds__(256) void bis_count_kernel(BisArgs a, int npts, const double* __restrict__ x, int* __restrict__ cnt) {
+  __shared__ double sd[BS_TILE], se1[BS_TILE], se2[BS_TILE];
+  const long t = (long)blockIdx.x * 256 + threadIdx.x;
+  const long tc = t < npts ? t : npts - 1;
+  const double lo = a.scal[0], hi = a.scal[1], pivmin = a.scal[2];
+  const double xp = x[tc];
+  const bool inside = xp > lo && xp < hi;   // false for NaN
+  int c = sturm_count<BAND>(a, inside ? xp : lo, pivmin, sd, se1, se2);
+  if (!inside) c = (xp <= lo) ? 0 : (xp >= hi ? a.n : -1);
+  if (t < npts) cnt[t] = c;
+}
+
 int g_bis_threads = 65536;   // target number of concurrent Sturm sweeps n*S (eigx_tune key 1)
 
 }  // namespace
@@ -324,9 +342,42 @@ void band_bisect_range_dev(Context& ctx, int n, int il, int iu, const double* d,
   EIGX_HIP_CHECK(hipGetLastError());
 }
 
+// cnt[p] = number of eigenvalues of the band matrix below x[p], p < npts (device arrays): the Sturm count and the pivmin
+// of the multi-section above, so a window resolved by these counts agrees by construction with the brackets
+// band_bisect_range_dev builds for it (count(lb) <= k < count(ub)).  Enqueued; the caller copies cnt back.
+void band_count_dev(Context& ctx, int n, const double* d, const double* e, int lde, int band, int npts, const double* x,
+                    int* cnt) {
+  if (n <= 0 || npts <= 0) return;
+  hipStream_t st = ctx.stream;
+  BisArgs a;
+  a.n = n; a.lde = lde; a.band = band; a.d = d; a.e = e;
+  a.m = 0; a.k0 = 0; a.S = 1; a.lb = a.ub = nullptr; a.cnt = nullptr;
+  a.scal = ctx.pool.get_t<double>("bis.scal", 8);
+  const int gb = (npts + 255) / 256;
+  hipLaunchKernelGGL(bis_bounds_kernel, dim3(1), dim3(256), 0, st, a);
+  if (band == 1) hipLaunchKernelGGL(bis_count_kernel<1>, dim3(gb), dim3(256), 0, st, a, npts, x, cnt);
+  else hipLaunchKernelGGL(bis_count_kernel<2>, dim3(gb), dim3(256), 0, st, a, npts, x, cnt);
+}
+
 // all n eigenvalues: the window [1, n] of the same code
 void band_bisect_dev(Context& ctx, int n, const double* d, const double* e, int lde, int band, double* w) {
   band_bisect_range_dev(ctx, n, 1, n, d, e, lde, band, w);
 }
 
 }  // namespace eigx
+
+using namespace eigx;
+
+extern "C" int eigx_band_count_dev(int n, const double* d, const double* e, int lde, int band, int npts, const double* x,
+                                   int* cnt) {
+  if (!g_ctx.initialized) return EIGX_ERR_NOT_INITIALIZED;
+  if (n <= 0 || npts <= 0 || lde < n || (band != 1 && band != 2) || !d || !e || !x || !cnt) return EIGX_ERR_BAD_ARG;
+  if (g_ctx.grid.nranks != 1) return EIGX_ERR_BAD_ARG;
+  return eigx_guard(g_ctx, [&] {
+    EIGX_HIP_CHECK(hipStreamSynchronize(nullptr));
+    band_count_dev(g_ctx, n, d, e, lde, band, npts, x, cnt);
+    EIGX_HIP_CHECK(hipStreamSynchronize(g_ctx.stream));
+    EIGX_HIP_CHECK(hipGetLastError());
+    return EIGX_OK;
+  });
+}

@@ -152,6 +152,29 @@ void band_bisect_dev(Context& ctx, int n, const double* d, const double* e, int 
 void band_bisect_range_dev(Context& ctx, int n, int il, int iu, const double* d, const double* e, int lde, int band,
                            double* w);
 
+// bisect.hip (EXTENSION): cnt[p] = number of eigenvalues of the band matrix below x[p] for npts caller-given points (device
+// arrays), by the Sturm count and pivmin of the multi-section; 0 at or below the lower Gershgorin bound (-Inf included), n
+// at or above the upper one, -1 for NaN.  Enqueued on ctx.stream.
+void band_count_dev(Context& ctx, int n, const double* d, const double* e, int lde, int band, int npts, const double* x,
+                    int* cnt);
+
+// The window of a range solve (solver.hip: range_solve_dev, gev_range_dev and their host forms).  By index: eigenpairs
+// il .. iu (1-based, inclusive).  By value: those with vl <= lambda < vu, resolved into il .. iu by two Sturm counts after
+// the band reduction; at most mmax of them are returned, and *m_out / *il_out (host) receive their number and the index
+// of the first.  m() = the entries of w / columns of z the caller provides.
+struct RangeWindow {
+  bool by_value = false;
+  int il = 0, iu = 0;
+  double vl = 0.0, vu = 0.0;
+  int mmax = 0;
+  int* m_out = nullptr; int* il_out = nullptr;
+  static RangeWindow index(int il_, int iu_) { RangeWindow r; r.il = il_; r.iu = iu_; return r; }
+  static RangeWindow value(double vl_, double vu_, int mmax_, int* m_, int* il_) {
+    RangeWindow r; r.by_value = true; r.vl = vl_; r.vu = vu_; r.mmax = mmax_; r.m_out = m_; r.il_out = il_; return r;
+  }
+  int m() const { return by_value ? mmax : iu - il + 1; }
+};
+
 // subset.hip (EXTENSION, one GPU): eigenvectors of the band matrix for m chosen eigenvalues by inverse iteration, CholQR2
 // and Rayleigh-Ritz; w_out = Ritz values (ascending), z(ldz, m) orthonormal.  EIGX_OK, or > 0: the acceptance test refused
 // the result (1 Cholesky breakdown, 2 cond(L) above 10^key19); cond_out, stage_s[2] (seconds of the inverse

@@ -278,7 +278,8 @@ int eigen_scaling(Context& ctx, const double* a, int lda, bool cplx, int n, doub
   if (G.nranks > 1 && comm_failed(ctx)) return EIGX_ERR_INTERNAL;
   const double anrm = hp[0], bad = hp[1];
   if (bad != 0.0) {  // NaN/Inf in the input (on any rank): w(:) = NaN on every rank (src/eigen_sx.F:151-155, src/eigen_h.F:147-150)
-    hipLaunchKernelGGL(fill_vec_kernel, dim3((nw + 255) / 256), dim3(256), 0, st, w, nw, std::numeric_limits<double>::quiet_NaN());
+    if (nw > 0)   // (a count-only value-window call has no w)
+      hipLaunchKernelGGL(fill_vec_kernel, dim3((nw + 255) / 256), dim3(256), 0, st, w, nw, std::numeric_limits<double>::quiet_NaN());
     EIGX_HIP_CHECK(hipStreamSynchronize(st));
     ctx.errinfo = -1;
     return EIGX_ERR_NONFINITE;
@@ -388,7 +389,7 @@ int SolveFrame::scale(double* a, int lda, double* w, int nw) {
 int SolveFrame::finish(double* w, int nw, double f_mid, int bt_cols, int stat_rows) {
   const bool peers = ctx.grid.nranks > 1;
   hipStream_t st = ctx.stream;
-  if (sigma != 1.0 && sigma != 0.0)
+  if (sigma != 1.0 && sigma != 0.0 && nw > 0)
     hipLaunchKernelGGL(scale_vec_kernel, dim3((nw + 255) / 256), dim3(256), 0, st, w, nw, 1.0 / sigma);
   stage_trace(ctx.grid.rank, "exit redistribution enqueued");
   EIGX_HIP_CHECK(hipStreamSynchronize(st));
@@ -421,7 +422,54 @@ __global__ void copy_vec_kernel(const double* __restrict__ src, double* __restri
   if (i < n) dst[i] = src[i];
 }
 
-// ---- index-range solve: eigenpairs il .. iu (1-based, inclusive) of the ascending spectrum, one GPU ---------------------
+// what both entry points of the range solves require of their arguments (mode in upper case).  By value: vl < vu (a NaN
+// fails it), room for at least one eigenpair unless only the count is asked for (mode 'C', value form only: w and z are
+// not used), and somewhere to put m and il.
+static bool range_args_ok(int n, const RangeWindow& W, const double* a, int lda, const double* w, const double* z, int ldz,
+                          char mode) {
+  if (n <= 0 || !a || lda < n) return false;
+  if (W.by_value) {
+    if (!(W.vl < W.vu) || !W.m_out || !W.il_out || (mode != 'A' && mode != 'N' && mode != 'C')) return false;
+    if (mode == 'C') return true;
+    if (W.mmax < 1 || !w) return false;
+  } else {
+    if (W.il < 1 || W.iu > n || W.il > W.iu || (mode != 'A' && mode != 'N') || !w) return false;
+  }
+  return mode == 'N' || (z && ldz >= n);
+}
+// entries of w that a range call may write (NaN on a non-finite input), eigenvector columns it may ask room for
+static int range_w_cap(const RangeWindow& W, char mode) { return (W.by_value && mode == 'C') ? 0 : W.m(); }
+static int range_z_cap(int n, const RangeWindow& W, char mode) { return std::max(1, std::min(n, range_w_cap(W, mode))); }
+
+// ---- value window -> index window (EXTENSION) ------------------------------------------------------------------------------
+// The eigenvalues with vl <= lambda < vu of the matrix whose band form (d, e) is sigma times the caller's: il = count(sigma vl)
+// + 1, iu = count(sigma vu), count(x) = eigenvalues below x by band_count_dev.  The pentadiagonal count is not strictly
+// monotone in floating point: iu < il - 1 is an empty window like iu = il - 1.  An infinite bound needs no count.  One
+// launch, one 8-byte copy back, one stream synchronisation.
+static void resolve_value_window(Context& ctx, int n, const double* d, const double* e, int lde, int band, double sigma,
+                                 RangeWindow& W) {
+  const bool lo_inf = std::isinf(W.vl), hi_inf = std::isinf(W.vu);   // vl < vu: only vl = -Inf, vu = +Inf can be
+  int c[2] = {0, n};
+  if (!lo_inf || !hi_inf) {
+    hipStream_t st = ctx.stream;
+    double* xd = ctx.pool.get_t<double>("bis.vx", 2);
+    int* cd = ctx.pool.get_t<int>("bis.vcnt", 2);
+    const double x[2] = {sigma * W.vl, sigma * W.vu};
+    EIGX_HIP_CHECK(hipMemcpyAsync(xd, x, sizeof(x), hipMemcpyHostToDevice, st));
+    band_count_dev(ctx, n, d, e, lde, band, 2, xd, cd);
+    int h[2] = {0, n};
+    EIGX_HIP_CHECK(hipMemcpyAsync(h, cd, sizeof(h), hipMemcpyDeviceToHost, st));
+    EIGX_HIP_CHECK(hipStreamSynchronize(st));
+    if (!lo_inf) c[0] = h[0];
+    if (!hi_inf) c[1] = h[1];
+  }
+  W.il = c[0] + 1;
+  W.iu = std::max(c[1], c[0]);
+  *W.m_out = W.iu - W.il + 1;
+  *W.il_out = W.il;
+}
+
+// ---- range solve: eigenpairs il .. iu (1-based, inclusive) of the ascending spectrum, one GPU ---------------------------
 // EXTENSION, not in the reference (whose nvec only trims the back-transformation, src/eigen_sx.F:200-240).
 //   scaling -> band reduction (as solve_dev) -> Sturm multi-section on the index window -> band_eigvec_dev (inverse
 //   iteration + CholQR2 + Rayleigh-Ritz, subset.hip) -> back-transformation of the m columns.
@@ -429,13 +477,11 @@ __global__ void copy_vec_kernel(const double* __restrict__ src, double* __restri
 // il .. iu copied out) serves windows beyond the size rule (eigx_tune key 17; path 3) and results that the acceptance
 // test of band_eigvec_dev refused (path 2).  w(1:m), z(:, 1:m); fill_rest (the opt-in route of eigx_sx / eigx_s, il = 1):
 // w(m+1:n) is filled by bisection as well, so that w holds all n eigenvalues like the reference's.
-// what both entry points of the index-range solves require of their arguments (mode in upper case)
-static bool range_args_ok(int n, int il, int iu, const double* a, int lda, const double* w, const double* z, int ldz, char mode) {
-  if (n <= 0 || il < 1 || iu > n || il > iu || (mode != 'A' && mode != 'N') || !a || !w || lda < n) return false;
-  return mode == 'N' || (z && ldz >= n);
-}
-
-int range_solve_dev(Context& ctx, int n, int il, int iu, double* a, int lda, double* w, double* z, int ldz, int mf, int mb,
+// A window by value (W.by_value) becomes an index window right after the reduction (resolve_value_window); what is sized
+// before that is sized by W.mmax.  *W.m_out, *W.il_out are set whenever the window was resolved: m = 0 returns EIGX_OK
+// and m > mmax EIGX_ERR_WINDOW, both without touching w or z and without an eigenvector stage; mode 'C' (value form
+// only) stops there in every case.  From then on a value call runs the code of the index call il .. iu.
+int range_solve_dev(Context& ctx, int n, RangeWindow W, double* a, int lda, double* w, double* z, int ldz, int mf, int mb,
                     char mode, int band, bool fill_rest) {
   if (ctx.initialized && ctx.grid.nranks != 1) {
     fprintf(stderr, "[eigx] index-range solves run on one GPU only (this grid has %d ranks)\n", ctx.grid.nranks);
@@ -443,20 +489,22 @@ int range_solve_dev(Context& ctx, int n, int il, int iu, double* a, int lda, dou
   }
   mode = upper_case(mode);
   SolveFrame F(ctx, n, false);
-  if (const int rc = F.begin(range_args_ok(n, il, iu, a, lda, w, z, ldz, mode))) return rc;
+  if (const int rc = F.begin(range_args_ok(n, W, a, lda, w, z, ldz, mode))) return rc;
   const bool want_vec = mode == 'A';
-  const int m = iu - il + 1;
   if (mf <= 0) mf = 128;
   if (mb <= 0) mb = 128;
   hipStream_t st = ctx.stream;
   RangeInfo& info = range_info();
-  info.path = 0; info.m = m; info.cond = 0.0;
+  info.path = 0; info.m = W.by_value ? 0 : W.m(); info.cond = 0.0;
   for (int q = 0; q < 4; ++q) info.t[q] = 0.0;
-  const int nw = fill_rest ? n : m;   // entries of w that belong to this call
+  const int wcap = range_w_cap(W, mode);
 
-  if (const int rc = F.stage_inputs(a, lda, z, ldz, want_vec, m, 1)) return rc;
+  if (const int rc = F.stage_inputs(a, lda, z, ldz, want_vec, W.by_value ? range_z_cap(n, W, mode) : W.m(), 1)) return rc;
   double* wn = ctx.pool.get_t<double>("sub.wfull", (size_t)n);   // all n eigenvalues, where the full D&C serves the window
-  if (const int rc = F.scale(a, lda, w, nw)) return rc;
+  if (const int rc = F.scale(a, lda, w, fill_rest ? n : wcap)) {
+    if (W.by_value) *W.m_out = 0;
+    return rc;
+  }
 
   // ---- forward reduction ---------------------------------------------------------------------------------------------
   const int lde = (n + 3) / 4 * 4;
@@ -466,6 +514,20 @@ int range_solve_dev(Context& ctx, int n, int il, int iu, double* a, int lda, dou
   band_reduce_dev(ctx, n, a, lda, d, e, lde, mf, band);
   EIGX_HIP_CHECK(hipStreamSynchronize(st));
   const double t2 = F.t2 = now_s();
+
+  if (W.by_value) {
+    resolve_value_window(ctx, n, d, e, lde, band, F.sigma, W);
+    const int mv = *W.m_out;
+    info.m = mv;
+    if (mode != 'C' && mv > W.mmax) return EIGX_ERR_WINDOW;
+    if (mode == 'C' || mv == 0) {   // nothing to compute: the statistics of the reduction alone
+      F.t3 = now_s();
+      info.t[0] = F.t3 - t2;
+      return F.finish(w, 0, 0.0, 0, n);
+    }
+  }
+  const int il = W.il, iu = W.iu, m = iu - il + 1;
+  const int nw = fill_rest ? n : m;   // entries of w that belong to this call
 
   // ---- eigenvalues il .. iu, then their eigenvectors -------------------------------------------------------------------
   if (!want_vec) {
@@ -519,22 +581,25 @@ int range_solve_dev(Context& ctx, int n, int il, int iu, double* a, int lda, dou
   return rc;
 }
 
-int range_solve_host(Context& ctx, int n, int il, int iu, double* a, int lda, double* w, double* z, int ldz, int mf, int mb,
+// Host arrays.  By value: nothing is copied back into w or z on EIGX_ERR_WINDOW and on m = 0 (a non-finite input fills
+// w(1:mmax) with NaN); a gets its a(1:3,1) statistics whenever the call returns EIGX_OK.
+int range_solve_host(Context& ctx, int n, RangeWindow W, double* a, int lda, double* w, double* z, int ldz, int mf, int mb,
                      char mode, int band) {
   if (!ctx.initialized) return EIGX_ERR_NOT_INITIALIZED;
-  if (ctx.grid.nranks != 1) return range_solve_dev(ctx, n, il, iu, a, lda, w, z, ldz, mf, mb, mode, band, false);   // refuses
+  if (ctx.grid.nranks != 1) return range_solve_dev(ctx, n, W, a, lda, w, z, ldz, mf, mb, mode, band, false);   // refuses
   mode = upper_case(mode);
-  if (!range_args_ok(n, il, iu, a, lda, w, z, ldz, mode)) return EIGX_ERR_BAD_ARG;
-  const int m = iu - il + 1;
+  if (!range_args_ok(n, W, a, lda, w, z, ldz, mode)) return EIGX_ERR_BAD_ARG;
+  const int wcap = range_w_cap(W, mode);
   EIGX_HIP_CHECK(hipSetDevice(ctx.device));
   const int ldd = host_ld(n);
   double* ad = (double*)host_to_dev(ctx, "host.a", a, lda, n, n, 8);
-  double* zd = (double*)host_to_dev(ctx, "host.z", nullptr, 0, n, mode == 'A' ? m : 1, 8);
-  double* wd = ctx.pool.get_t<double>("host.w", (size_t)m);
-  const int rc = range_solve_dev(ctx, n, il, iu, ad, ldd, wd, zd, ldd, mf, mb, mode, band, false);
-  if (rc == EIGX_OK || rc == EIGX_ERR_NONFINITE) EIGX_HIP_CHECK(hipMemcpy(w, wd, (size_t)m * 8, hipMemcpyDeviceToHost));
+  double* zd = (double*)host_to_dev(ctx, "host.z", nullptr, 0, n, mode == 'A' ? range_z_cap(n, W, mode) : 1, 8);
+  double* wd = ctx.pool.get_t<double>("host.w", (size_t)std::max(wcap, 1));
+  const int rc = range_solve_dev(ctx, n, W, ad, ldd, wd, zd, ldd, mf, mb, mode, band, false);
+  const int m = (W.by_value && rc == EIGX_OK) ? (mode == 'C' ? 0 : *W.m_out) : wcap;   // entries that were written
+  if ((rc == EIGX_OK || rc == EIGX_ERR_NONFINITE) && m > 0) EIGX_HIP_CHECK(hipMemcpy(w, wd, (size_t)m * 8, hipMemcpyDeviceToHost));
   if (rc != EIGX_OK) return rc;
-  if (mode == 'A') dev_to_host(z, ldz, zd, ldd, n, m, 8);
+  if (mode == 'A' && m > 0) dev_to_host(z, ldz, zd, ldd, n, m, 8);
   dev_to_host(a, lda, ad, ldd, std::min(n, 3), 1, 8);
   return EIGX_OK;
 }
@@ -553,7 +618,7 @@ int solve_dev(Context& ctx, int n, int nvec, double* a, int lda, double* w, doub
   const bool want_vec = rq.want_vec;
   // opt-in (eigx_tune key 18, default off): the lowest nvec < n eigenpairs by the index-range path (EXTENSION)
   if (get_range_knob(18) == 1 && P == 1 && nb == 1 && mode == 'A' && nvec > 0 && nvec < n)
-    return range_solve_dev(ctx, n, 1, nvec, a, lda, w, z, ldz, mf, mb, 'A', band, true);
+    return range_solve_dev(ctx, n, RangeWindow::index(1, nvec), a, lda, w, z, ldz, mf, mb, 'A', band, true);
   SolveFrame F(ctx, n, false);
   if (const int rc = F.begin(nb >= 1 && a && w && lda >= ld_min && (!want_vec || (z && ldz >= ld_min)))) return rc;
   if (mf <= 0) mf = 128;
@@ -953,7 +1018,9 @@ void gev_reduce_dev(Context& ctx, int n, double* a, int lda, const double* u, in
   trsm_upper_dev(ctx, 'T', n, n, u, ldu, c, ldc, V, true);   // the solvers read the upper triangle only
 }
 
-int gev_range_dev(Context& ctx, int n, int il, int iu, double* a, int lda, double* b, int ldb, double* w, double* z, int ldz,
+// W by value: the window goes to range_solve_dev on C as it is (B is not scaled, so the eigenvalues of C are the
+// generalised ones; range_solve_dev applies its own sigma of C), m is read back for the back-substitution.
+int gev_range_dev(Context& ctx, int n, RangeWindow W, double* a, int lda, double* b, int ldb, double* w, double* z, int ldz,
                   char mode) {
   if (!ctx.initialized) return EIGX_ERR_NOT_INITIALIZED;
   if (ctx.grid.nranks != 1) {
@@ -961,17 +1028,21 @@ int gev_range_dev(Context& ctx, int n, int il, int iu, double* a, int lda, doubl
     return EIGX_ERR_BAD_ARG;
   }
   mode = upper_case(mode);
-  if (!range_args_ok(n, il, iu, a, lda, w, z, ldz, mode) || !b || ldb < n || ((lda | ldb) & 1) || (mode == 'A' && (ldz & 1)))
+  if (!range_args_ok(n, W, a, lda, w, z, ldz, mode) || !b || ldb < n || ((lda | ldb) & 1) || (mode == 'A' && (ldz & 1)))
     return EIGX_ERR_BAD_ARG;
   EIGX_HIP_CHECK(hipSetDevice(ctx.device));
   EIGX_HIP_CHECK(hipStreamSynchronize(nullptr));
   hipStream_t st = ctx.stream;
-  const int m = iu - il + 1;
+  const int wcap = range_w_cap(W, mode);
   const double t0 = now_s();
   // both significant triangles are scanned before anything is factored; the scale factors are not used
   double sigma = 1.0;
-  if (const int rc = eigen_scaling(ctx, a, lda, false, n, w, &sigma, m)) return rc;
-  if (const int rc = eigen_scaling(ctx, b, ldb, false, n, w, &sigma, m)) return rc;
+  int rc = eigen_scaling(ctx, a, lda, false, n, w, &sigma, wcap);
+  if (rc == EIGX_OK) rc = eigen_scaling(ctx, b, ldb, false, n, w, &sigma, wcap);
+  if (rc != EIGX_OK) {
+    if (W.by_value) *W.m_out = 0;
+    return rc;
+  }
   if (chol_upper_dev(ctx, n, b, ldb) != EIGX_OK) {
     fprintf(stderr, "[eigx] Matrix B is not positive definite!\n");
     return EIGX_ERR_NOT_SPD;
@@ -983,10 +1054,11 @@ int gev_range_dev(Context& ctx, int n, int il, int iu, double* a, int lda, doubl
   gev_reduce_dev(ctx, n, a, lda, b, ldb, V, c, ldc);
   EIGX_HIP_CHECK(hipStreamSynchronize(st));
   const double t2 = now_s();
-  const int rc = range_solve_dev(ctx, n, il, iu, c, ldc, w, z, ldz, 128, 128, mode, 2, false);
+  rc = range_solve_dev(ctx, n, W, c, ldc, w, z, ldz, 128, 128, mode, 2, false);
   if (rc != EIGX_OK) return rc;
+  const int m = W.by_value ? *W.m_out : W.m();
   const double t3 = now_s();
-  if (mode == 'A') {
+  if (mode == 'A' && m > 0) {
     trsm_upper_dev(ctx, 'N', n, m, b, ldb, z, ldz, V);   // Z = U^-1 Y
     EIGX_HIP_CHECK(hipStreamSynchronize(st));
   }
@@ -995,24 +1067,25 @@ int gev_range_dev(Context& ctx, int n, int il, int iu, double* a, int lda, doubl
   return EIGX_OK;
 }
 
-int gev_range_host(Context& ctx, int n, int il, int iu, double* a, int lda, double* b, int ldb, double* w, double* z, int ldz,
+int gev_range_host(Context& ctx, int n, RangeWindow W, double* a, int lda, double* b, int ldb, double* w, double* z, int ldz,
                    char mode) {
   if (!ctx.initialized) return EIGX_ERR_NOT_INITIALIZED;
-  if (ctx.grid.nranks != 1) return gev_range_dev(ctx, n, il, iu, a, lda, b, ldb, w, z, ldz, mode);   // refuses
+  if (ctx.grid.nranks != 1) return gev_range_dev(ctx, n, W, a, lda, b, ldb, w, z, ldz, mode);   // refuses
   mode = upper_case(mode);
-  if (!range_args_ok(n, il, iu, a, lda, w, z, ldz, mode) || !b || ldb < n) return EIGX_ERR_BAD_ARG;
-  const int m = iu - il + 1;
+  if (!range_args_ok(n, W, a, lda, w, z, ldz, mode) || !b || ldb < n) return EIGX_ERR_BAD_ARG;
+  const int wcap = range_w_cap(W, mode);
   EIGX_HIP_CHECK(hipSetDevice(ctx.device));
   const int ldd = host_ld(n);
   double* ad = (double*)host_to_dev(ctx, "host.a", a, lda, n, n, 8);
   double* bd = (double*)host_to_dev(ctx, "host.b", b, ldb, n, n, 8);
-  double* zd = (double*)host_to_dev(ctx, "host.z", nullptr, 0, n, mode == 'A' ? m : 1, 8);
-  double* wd = ctx.pool.get_t<double>("host.w", (size_t)m);
-  const int rc = gev_range_dev(ctx, n, il, iu, ad, ldd, bd, ldd, wd, zd, ldd, mode);
-  if (rc == EIGX_OK || rc == EIGX_ERR_NONFINITE) EIGX_HIP_CHECK(hipMemcpy(w, wd, (size_t)m * 8, hipMemcpyDeviceToHost));
-  if (rc != EIGX_OK) return rc;
-  if (mode == 'A') dev_to_host(z, ldz, zd, ldd, n, m, 8);
+  double* zd = (double*)host_to_dev(ctx, "host.z", nullptr, 0, n, mode == 'A' ? range_z_cap(n, W, mode) : 1, 8);
+  double* wd = ctx.pool.get_t<double>("host.w", (size_t)std::max(wcap, 1));
+  const int rc = gev_range_dev(ctx, n, W, ad, ldd, bd, ldd, wd, zd, ldd, mode);
+  const int m = (W.by_value && rc == EIGX_OK) ? (mode == 'C' ? 0 : *W.m_out) : wcap;   // entries that were written
+  if ((rc == EIGX_OK || rc == EIGX_ERR_NONFINITE) && m > 0) EIGX_HIP_CHECK(hipMemcpy(w, wd, (size_t)m * 8, hipMemcpyDeviceToHost));
+  if (rc != EIGX_OK) return rc;            // (EIGX_ERR_WINDOW: a and b are as the caller passed them, ready for the retry by index)
   dev_to_host(b, ldb, bd, ldd, n, n, 8);   // U in the upper triangle
+  if (mode == 'A' && m > 0) dev_to_host(z, ldz, zd, ldd, n, m, 8);
   return EIGX_OK;
 }
 
@@ -1077,16 +1150,41 @@ int eigx_s(int n, int nvec, double* a, int lda, double* w, double* z, int ldz, i
 }
 // EXTENSION: eigenpairs il .. iu of the ascending spectrum (one GPU); see range_solve_dev
 int eigx_sx_range(int n, int il, int iu, double* a, int lda, double* w, double* z, int ldz, int mf, int mb, char mode) {
-  return eigx_guard(g_ctx, [&] { return range_solve_host(g_ctx, n, il, iu, a, lda, w, z, ldz, mf, mb, mode, 2); });
+  return eigx_guard(g_ctx, [&] { return range_solve_host(g_ctx, n, RangeWindow::index(il, iu), a, lda, w, z, ldz, mf, mb, mode, 2); });
 }
 int eigx_s_range(int n, int il, int iu, double* a, int lda, double* w, double* z, int ldz, int mf, int mb, char mode) {
-  return eigx_guard(g_ctx, [&] { return range_solve_host(g_ctx, n, il, iu, a, lda, w, z, ldz, mf, mb, mode, 1); });
+  return eigx_guard(g_ctx, [&] { return range_solve_host(g_ctx, n, RangeWindow::index(il, iu), a, lda, w, z, ldz, mf, mb, mode, 1); });
 }
 int eigx_sx_range_dev(int n, int il, int iu, double* a, int lda, double* w, double* z, int ldz, int mf, int mb, char mode) {
-  return eigx_guard(g_ctx, [&] { return range_solve_dev(g_ctx, n, il, iu, a, lda, w, z, ldz, mf, mb, mode, 2, false); });
+  return eigx_guard(g_ctx, [&] { return range_solve_dev(g_ctx, n, RangeWindow::index(il, iu), a, lda, w, z, ldz, mf, mb, mode, 2, false); });
 }
 int eigx_s_range_dev(int n, int il, int iu, double* a, int lda, double* w, double* z, int ldz, int mf, int mb, char mode) {
-  return eigx_guard(g_ctx, [&] { return range_solve_dev(g_ctx, n, il, iu, a, lda, w, z, ldz, mf, mb, mode, 1, false); });
+  return eigx_guard(g_ctx, [&] { return range_solve_dev(g_ctx, n, RangeWindow::index(il, iu), a, lda, w, z, ldz, mf, mb, mode, 1, false); });
+}
+// EXTENSION: the eigenpairs with vl <= lambda < vu (one GPU); see range_solve_dev.  m, il: host pointers in both forms
+int eigx_sx_range_v(int n, double vl, double vu, int mmax, int* m, int* il, double* a, int lda, double* w, double* z, int ldz,
+                    int mf, int mb, char mode) {
+  return eigx_guard(g_ctx, [&] {
+    return range_solve_host(g_ctx, n, RangeWindow::value(vl, vu, mmax, m, il), a, lda, w, z, ldz, mf, mb, mode, 2);
+  });
+}
+int eigx_s_range_v(int n, double vl, double vu, int mmax, int* m, int* il, double* a, int lda, double* w, double* z, int ldz,
+                   int mf, int mb, char mode) {
+  return eigx_guard(g_ctx, [&] {
+    return range_solve_host(g_ctx, n, RangeWindow::value(vl, vu, mmax, m, il), a, lda, w, z, ldz, mf, mb, mode, 1);
+  });
+}
+int eigx_sx_range_v_dev(int n, double vl, double vu, int mmax, int* m, int* il, double* a, int lda, double* w, double* z,
+                        int ldz, int mf, int mb, char mode) {
+  return eigx_guard(g_ctx, [&] {
+    return range_solve_dev(g_ctx, n, RangeWindow::value(vl, vu, mmax, m, il), a, lda, w, z, ldz, mf, mb, mode, 2, false);
+  });
+}
+int eigx_s_range_v_dev(int n, double vl, double vu, int mmax, int* m, int* il, double* a, int lda, double* w, double* z,
+                       int ldz, int mf, int mb, char mode) {
+  return eigx_guard(g_ctx, [&] {
+    return range_solve_dev(g_ctx, n, RangeWindow::value(vl, vu, mmax, m, il), a, lda, w, z, ldz, mf, mb, mode, 1, false);
+  });
 }
 int eigx_sx_dev(int n, int nvec, double* a, int lda, double* w, double* z, int ldz, int mf, int mb, char mode) {
   return eigx_guard(g_ctx, [&] { return solve_dev(g_ctx, n, nvec, a, lda, w, z, ldz, mf, mb, mode, 2, 1); });
@@ -1143,10 +1241,23 @@ int eigx_gev_dev(int n, double* a, int lda, double* b, int ldb, double* w, doubl
 
 // EXTENSION: eigenpairs il .. iu of A x = lambda B x by the Cholesky route (one GPU); see gev_range_dev
 int eigx_gev_range(int n, int il, int iu, double* a, int lda, double* b, int ldb, double* w, double* z, int ldz, char mode) {
-  return eigx_guard(g_ctx, [&] { return gev_range_host(g_ctx, n, il, iu, a, lda, b, ldb, w, z, ldz, mode); });
+  return eigx_guard(g_ctx, [&] { return gev_range_host(g_ctx, n, RangeWindow::index(il, iu), a, lda, b, ldb, w, z, ldz, mode); });
 }
 int eigx_gev_range_dev(int n, int il, int iu, double* a, int lda, double* b, int ldb, double* w, double* z, int ldz, char mode) {
-  return eigx_guard(g_ctx, [&] { return gev_range_dev(g_ctx, n, il, iu, a, lda, b, ldb, w, z, ldz, mode); });
+  return eigx_guard(g_ctx, [&] { return gev_range_dev(g_ctx, n, RangeWindow::index(il, iu), a, lda, b, ldb, w, z, ldz, mode); });
+}
+// the same for the eigenpairs with vl <= lambda < vu
+int eigx_gev_range_v(int n, double vl, double vu, int mmax, int* m, int* il, double* a, int lda, double* b, int ldb, double* w,
+                     double* z, int ldz, char mode) {
+  return eigx_guard(g_ctx, [&] {
+    return gev_range_host(g_ctx, n, RangeWindow::value(vl, vu, mmax, m, il), a, lda, b, ldb, w, z, ldz, mode);
+  });
+}
+int eigx_gev_range_v_dev(int n, double vl, double vu, int mmax, int* m, int* il, double* a, int lda, double* b, int ldb,
+                         double* w, double* z, int ldz, char mode) {
+  return eigx_guard(g_ctx, [&] {
+    return gev_range_dev(g_ctx, n, RangeWindow::value(vl, vu, mmax, m, il), a, lda, b, ldb, w, z, ldz, mode);
+  });
 }
 // its reduction stage alone: upper(a) <- U^-T A U^-1 (all of a is written)
 int eigx_gev_reduce_dev(int n, double* a_dev, int lda, const double* u_dev, int ldu) {

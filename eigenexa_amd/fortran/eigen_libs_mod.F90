@@ -32,6 +32,7 @@ module eigen_libs_mod
   public :: eigen_sx_bc, eigen_s_bc   ! ScaLAPACK block-cyclic local blocks in and out (no pdgemr2d step)
   public :: eigen_h                   ! complex Hermitian solver (src/eigen_h.F)
   public :: eigen_sx_range, eigen_s_range   ! EXTENSION: eigenpairs il .. iu of the ascending spectrum (one GPU)
+  public :: eigen_sx_range_v, eigen_s_range_v   ! EXTENSION: the eigenpairs with vl <= lambda < vu (one GPU)
 
   interface
     integer(c_int) function eigx_init(device) bind(C, name="eigx_init")
@@ -126,6 +127,27 @@ module eigen_libs_mod
       integer(c_int), value :: n, il, iu, lda, ldz, mf, mb
       real(c_double), intent(inout) :: a(lda, *)
       real(c_double), intent(out) :: w(*), z(ldz, *)
+      character(kind=c_char), value :: mode
+    end function
+    ! EXTENSION (not in the reference): the eigenpairs with vl <= lambda < vu, one GPU
+    integer(c_int) function eigx_sx_range_v(n, vl, vu, mmax, m, il, a, lda, w, z, ldz, mf, mb, mode) &
+        bind(C, name="eigx_sx_range_v")
+      import :: c_int, c_double, c_char
+      integer(c_int), value :: n, mmax, lda, ldz, mf, mb
+      real(c_double), value :: vl, vu
+      integer(c_int), intent(out) :: m, il
+      real(c_double), intent(inout) :: a(lda, *)
+      real(c_double), intent(inout) :: w(*), z(ldz, *)
+      character(kind=c_char), value :: mode
+    end function
+    integer(c_int) function eigx_s_range_v(n, vl, vu, mmax, m, il, a, lda, w, z, ldz, mf, mb, mode) &
+        bind(C, name="eigx_s_range_v")
+      import :: c_int, c_double, c_char
+      integer(c_int), value :: n, mmax, lda, ldz, mf, mb
+      real(c_double), value :: vl, vu
+      integer(c_int), intent(out) :: m, il
+      real(c_double), intent(inout) :: a(lda, *)
+      real(c_double), intent(inout) :: w(*), z(ldz, *)
       character(kind=c_char), value :: mode
     end function
     integer(c_int) function eigx_s(n, nvec, a, lda, w, z, ldz, mf, mb, mode) bind(C, name="eigx_s")
@@ -626,6 +648,55 @@ contains
     rc = eigx_s_range(n, il, iu, a, lda, w, z, ldz, mf, mb, md)
   end subroutine eigen_s_range
 
+  !> eigen_sx_range_v(n, vl, vu, mmax, m, il, a, lda, w, z, ldz, m_forward, m_backward, mode) -- EXTENSION, not in the
+  !> reference (LAPACK's range = 'V'): the eigenpairs with vl <= lambda < vu by the pentadiagonal route on one GPU.  On
+  !> return m eigenvalues lie in the window and the first is number il of the ascending spectrum; w(1:m), z(:, 1:m) as from
+  !> eigen_sx_range(n, il, il + m - 1, ...).  mmax = room in w / z: with m > mmax (status EIGX_ERR_WINDOW inside) m and il
+  !> are set and w, z, a are untouched, so the caller can retry by index; m = 0 leaves w, z untouched.  Modes 'A', 'N' and
+  !> 'C' (count only).  m = -1 when nothing was resolved (bad arguments, no eigen_init, non-finite input).
+  subroutine eigen_sx_range_v(n, vl, vu, mmax, m, il, a, lda, w, z, ldz, m_forward, m_backward, mode)
+    integer, intent(in) :: n, mmax, lda, ldz
+    real(8), intent(in) :: vl, vu
+    integer, intent(out) :: m, il
+    real(8), intent(inout) :: a(lda, *)
+    real(8), intent(inout) :: w(*), z(ldz, *)
+    integer, intent(in), optional :: m_forward, m_backward
+    character(*), intent(in), optional :: mode
+    integer :: mf, mb, rc
+    integer(c_int) :: mc, ilc
+    character(kind=c_char) :: md
+    mf = eigen_NB_f; mb = eigen_NB_b; md = 'A'
+    if (present(m_forward)) mf = m_forward
+    if (present(m_backward)) mb = m_backward
+    if (present(mode)) md = mode(1:1)
+    mc = 0; ilc = 0
+    rc = eigx_sx_range_v(n, vl, vu, mmax, mc, ilc, a, lda, w, z, ldz, mf, mb, md)
+    m = mc; il = ilc
+    if (rc /= 0 .and. rc /= -9) m = -1
+  end subroutine eigen_sx_range_v
+
+  !> eigen_s_range_v: the same by the tridiagonal route (EXTENSION)
+  subroutine eigen_s_range_v(n, vl, vu, mmax, m, il, a, lda, w, z, ldz, m_forward, m_backward, mode)
+    integer, intent(in) :: n, mmax, lda, ldz
+    real(8), intent(in) :: vl, vu
+    integer, intent(out) :: m, il
+    real(8), intent(inout) :: a(lda, *)
+    real(8), intent(inout) :: w(*), z(ldz, *)
+    integer, intent(in), optional :: m_forward, m_backward
+    character(*), intent(in), optional :: mode
+    integer :: mf, mb, rc
+    integer(c_int) :: mc, ilc
+    character(kind=c_char) :: md
+    mf = eigen_NB_f; mb = eigen_NB_b; md = 'A'
+    if (present(m_forward)) mf = m_forward
+    if (present(m_backward)) mb = m_backward
+    if (present(mode)) md = mode(1:1)
+    mc = 0; ilc = 0
+    rc = eigx_s_range_v(n, vl, vu, mmax, mc, ilc, a, lda, w, z, ldz, mf, mb, md)
+    m = mc; il = ilc
+    if (rc /= 0 .and. rc /= -9) m = -1
+  end subroutine eigen_s_range_v
+
   !> The reference's per-stage report of a TIMER_PRINT=1 build (src/eigen_sx.F:167-174, :225-232, :252-258, format 10000 at
   !> :304; src/eigen_FS.F likewise): one line per stage on rank 1 -- name, n, seconds, flops of the reference's model, GFLOPS.
   !> Here a run-time switch: EIGX_TIMER_PRINT=1 in the environment.
@@ -832,6 +903,41 @@ subroutine KMATH_EIGEN_GEV_RANGE(n, il, iu, a, lda, b, ldb, w, z, ldz, mode)
   rc = eigx_gev_range(int(n, c_int), int(il, c_int), int(iu, c_int), a, int(lda, c_int), b, int(ldb, c_int), w, z, &
                       int(ldz, c_int), md)
 end subroutine KMATH_EIGEN_GEV_RANGE
+
+! KMATH_EIGEN_GEV_RANGE_V -- EXTENSION, not in the reference: the eigenpairs of A x = lambda B x with vl <= lambda < vu by the
+! Cholesky route of KMATH_EIGEN_GEV_RANGE on one GPU.  m, il, mmax and the modes ('A', 'N', 'C') as for eigen_sx_range_v of
+! module eigen_libs_mod: w(1:m) ascending, z(:, 1:m) with z^T B z = I; m > mmax sets m and il and leaves a, b, w, z as they
+! were; m = -1 when nothing was resolved.  External like KMATH_EIGEN_GEV_RANGE.
+subroutine KMATH_EIGEN_GEV_RANGE_V(n, vl, vu, mmax, m, il, a, lda, b, ldb, w, z, ldz, mode)
+  use, intrinsic :: iso_c_binding
+  implicit none
+  integer, intent(in) :: n, mmax, lda, ldb, ldz
+  real(8), intent(in) :: vl, vu
+  integer, intent(out) :: m, il
+  real(8), intent(inout) :: a(lda, *), b(ldb, *)
+  real(8), intent(inout) :: w(*), z(ldz, *)
+  character(*), intent(in), optional :: mode
+  interface
+    integer(c_int) function eigx_gev_range_v(n, vl, vu, mmax, m, il, a, lda, b, ldb, w, z, ldz, mode) &
+        bind(C, name="eigx_gev_range_v")
+      import :: c_int, c_double, c_char
+      integer(c_int), value :: n, mmax, lda, ldb, ldz
+      real(c_double), value :: vl, vu
+      integer(c_int), intent(out) :: m, il
+      real(c_double), intent(inout) :: a(lda, *), b(ldb, *), w(*), z(ldz, *)
+      character(kind=c_char), value :: mode
+    end function
+  end interface
+  integer(c_int) :: rc, mc, ilc
+  character(kind=c_char) :: md
+  md = 'A'
+  if (present(mode)) md = mode(1:1)
+  mc = 0; ilc = 0
+  rc = eigx_gev_range_v(int(n, c_int), real(vl, c_double), real(vu, c_double), int(mmax, c_int), mc, ilc, a, int(lda, c_int), &
+                        b, int(ldb, c_int), w, z, int(ldz, c_int), md)
+  m = mc; il = ilc
+  if (rc /= 0 .and. rc /= -9) m = -1
+end subroutine KMATH_EIGEN_GEV_RANGE_V
 
 ! KMATH_EIGEN_HGEV_RANGE -- EXTENSION, not in the reference: eigenpairs il .. iu (1-based, inclusive) of the complex
 ! Hermitian-definite problem A x = lambda B x by the Cholesky route (B = U^H U, C = U^-H A U^-1, eigen_h of C with

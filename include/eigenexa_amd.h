@@ -26,7 +26,9 @@
  * extension: complex Hermitian generalised problem), eigx_sx_range / eigx_s_range[_dev] (an extension: eigenpairs il .. iu
  * of the ascending spectrum, one GPU), eigx_gev_range[_dev] (KMATH_EIGEN_GEV_RANGE, an extension: eigenpairs il .. iu of
  * the generalised problem by the Cholesky route, one GPU), eigx_hgev_range[_dev] (KMATH_EIGEN_HGEV_RANGE, an extension: the
- * same for the complex Hermitian generalised problem, one GPU).
+ * same for the complex Hermitian generalised problem, one GPU), eigx_sx_range_v / eigx_s_range_v / eigx_gev_range_v[_dev] (an
+ * extension: the eigenpairs with vl <= lambda < vu of the real solvers, LAPACK's range = 'V', one GPU) and the stage entry
+ * eigx_band_count_dev (Sturm counts of a band matrix at caller-given points).
  */
 #ifndef EIGENEXA_AMD_H
 #define EIGENEXA_AMD_H
@@ -46,6 +48,7 @@ extern "C" {
 #define EIGX_ERR_INTERNAL (-6)
 #define EIGX_ERR_NOT_SPD (-7)
 #define EIGX_ERR_NO_MEMORY (-8)   /* a workspace allocation failed; on several ranks the others return EIGX_ERR_INTERNAL at once */
+#define EIGX_ERR_WINDOW (-9)      /* a value window holds more eigenvalues than the caller gave room for (mmax); *m, *il are set */
 
 /* ---- life cycle -------------------------------------------------------------------------- */
 
@@ -199,12 +202,46 @@ int eigx_s_range_dev(int n, int il, int iu, double* a, int lda, double* w, doubl
                      char mode);
 /* the last range call: path 1 = subset path, 2 = fell back to the full D&C, 3 = full D&C by the size rule; m; cond = the
  * conditioning estimate max / min diag(L) of the acceptance test (0 when it did not run).  Any pointer may be NULL.  Only
- * the four solver entries, eigx_gev_range[_dev] (for their inner call on C) and eigx_sx / eigx_s routed by key 18 write
- * this record; the stage entries do not. */
+ * the four solver entries, their value-window forms (path 0: the window was empty, did not fit, or only the count was asked
+ * for), eigx_gev_range[_v][_dev] (for their inner call on C) and eigx_sx / eigx_s routed by key 18 write this record; the
+ * stage entries do not. */
 int eigx_range_info(int* path, int* m, double* cond);
 /* stage seconds of the last range call: [0] bisection [1] inverse iteration [2] orthonormalisation + Rayleigh-Ritz (or
  * the fallback D&C) [3] back-transformation (tools/gpu_range_time.py) */
 int eigx_range_timers(double* out4);
+
+/* Value-window solves -- EXTENSION, not in the reference (LAPACK callers know this as range = 'V', vl, vu): the eigenpairs
+ * with vl <= lambda < vu, without knowing their indices.  The contract of the index-range entries above with these changes.
+ * One GPU only (the same printed line and EIGX_ERR_BAD_ARG on several ranks).
+ * Window: half-open, as the library's Sturm count (eigenvalues below x) defines it; an eigenvalue within rounding of an
+ * end point may fall on either side, as in LAPACK.  vl = -Inf and vu = +Inf are allowed and cost no count.  After the band
+ * reduction (once: no second reduction as with a mode-'N' solve followed by an index call) two counts at sigma vl,
+ * sigma vu (sigma = the scale factor of eigen_scaling; a matrix of scale 1e120 works) give il = count(vl) + 1,
+ * iu = count(vu), m = max(0, iu - il + 1); the counts use the Sturm sequence and pivmin of the multi-section, so the window
+ * agrees with the brackets the multi-section then builds for il .. iu.  From there the call runs the code of the index
+ * call il .. iu: size rule (key 17), acceptance test (key 19), fallback, eigx_range_info, eigx_range_timers and a(1:3,1)
+ * stay in force, and w, z are bit-identical to that call's.
+ * mmax = room in w (entries) and z (columns); *m and *il (host pointers in the host AND the device forms) receive the
+ * number of eigenvalues in the window and the 1-based index of the first.  On return w(1:m), z(:, 1:m); nothing beyond m
+ * entries / columns is touched.
+ *   m = 0:      EIGX_OK, *m = 0, *il = count(vl) + 1; w, z untouched, no eigenvector stage, no back-transformation;
+ *               eigx_range_info: path 0, m 0; a(1:3,1) is written.
+ *   m > mmax:   EIGX_ERR_WINDOW, *m and *il set, w, z untouched, the rest of the solve does not run; the caller retries
+ *               through the index entries with il .. il + m - 1 (host forms: a is untouched; device forms: a is destroyed,
+ *               as in every other case).
+ *   mode 'C':   count only (value form only): *m, *il as above and return; w, z may be NULL, mmax is ignored; the cost is
+ *               one reduction; a(1:3,1) is written.  Modes 'A' and 'N' as for the index entries.
+ * EIGX_ERR_BAD_ARG unless vl < vu (a NaN bound fails it), mmax >= 1 (not for mode 'C'), m and il non-NULL, and the rest as
+ * for the index entries with mmax in the place of iu - il + 1.  NaN / Inf in the upper triangle: EIGX_ERR_NONFINITE,
+ * w(1:mmax) = NaN, *m = 0. */
+int eigx_sx_range_v(int n, double vl, double vu, int mmax, int* m, int* il, double* a, int lda, double* w, double* z, int ldz,
+                    int m_forward, int m_backward, char mode);
+int eigx_s_range_v(int n, double vl, double vu, int mmax, int* m, int* il, double* a, int lda, double* w, double* z, int ldz,
+                   int m_forward, int m_backward, char mode);
+int eigx_sx_range_v_dev(int n, double vl, double vu, int mmax, int* m, int* il, double* a, int lda, double* w, double* z,
+                        int ldz, int m_forward, int m_backward, char mode);
+int eigx_s_range_v_dev(int n, double vl, double vu, int mmax, int* m, int* il, double* a, int lda, double* w, double* z,
+                       int ldz, int m_forward, int m_backward, char mode);
 
 /* ScaLAPACK interop without a redistribution step.  The reference asks block-cyclic callers to
  * convert with pdgemr2d into its cyclic layout first (manual 3.4; benchmark/ev_test.f:68-84 does the reverse for the
@@ -286,6 +323,17 @@ int eigx_hgev_dev(int n, double* a_dev, int lda, double* b_dev, int ldb, double*
 int eigx_gev_range(int n, int il, int iu, double* a, int lda, double* b, int ldb, double* w, double* z, int ldz, char mode);
 int eigx_gev_range_dev(int n, int il, int iu, double* a_dev, int lda, double* b_dev, int ldb, double* w_dev, double* z_dev,
                        int ldz, char mode);
+/* KMATH_EIGEN_GEV_RANGE_V -- EXTENSION: the eigenpairs of A x = lambda B x with vl <= lambda < vu; eigx_gev_range with the
+ * window protocol of eigx_sx_range_v (vl, vu, mmax, *m, *il, mode 'C', m = 0, EIGX_ERR_WINDOW, statuses).  B is factored and
+ * C formed as in eigx_gev_range, the value window goes to the range solve of C (B is not scaled, so C's eigenvalues are the
+ * generalised ones), and the back-substitution runs on the m columns found -- not at all for m = 0, modes 'N' and 'C'.
+ * b holds U on exit whenever the call returns EIGX_OK; on EIGX_ERR_WINDOW the host form leaves a and b as they were
+ * passed, the device form has destroyed a and holds U in b.  eigx_get_timers [0..4] as for eigx_gev_range.  The complex
+ * solver eigx_hgev_range has no value form (its inner solve has no index window to resolve into). */
+int eigx_gev_range_v(int n, double vl, double vu, int mmax, int* m, int* il, double* a, int lda, double* b, int ldb, double* w,
+                     double* z, int ldz, char mode);
+int eigx_gev_range_v_dev(int n, double vl, double vu, int mmax, int* m, int* il, double* a_dev, int lda, double* b_dev,
+                         int ldb, double* w_dev, double* z_dev, int ldz, char mode);
 /* Its stages (one GPU, device arrays, any leading dimension >= n, LAPACK uplo = 'U'; NB = eigx_tune key 20).
  * eigx_chol_dev: B = U^T U, U in place in the upper triangle, nothing below the diagonal is read; EIGX_OK, or
  * EIGX_ERR_NOT_SPD for a pivot that is not > 0 or not finite.  eigx_trsm_upper_dev: x(n, nrhs) <- op(U)^-1 x in place,
@@ -338,6 +386,13 @@ int eigx_band_bisect_dev(int n, const double* d_dev, const double* e_dev, int ld
  * multi-section on an index window, w_dev[0 .. iu - il] ascending. */
 int eigx_band_bisect_range_dev(int n, int il, int iu, const double* d_dev, const double* e_dev, int lde, int band,
                                double* w_dev);
+/* EXTENSION: cnt_dev[p] = number of eigenvalues of the band matrix below x_dev[p], p < npts, by the Sturm count and the
+ * pivmin of the multi-section (a window resolved by these counts agrees with the brackets of eigx_band_bisect_range_dev).
+ * 0 for a point at or below the lower Gershgorin bound (-Inf included), n at or above the upper one (+Inf included), -1
+ * for NaN.  One thread per point: npts = 2 resolves a value window, thousands give a density-of-states histogram straight
+ * after a reduction.  One GPU; returns after cnt_dev is complete. */
+int eigx_band_count_dev(int n, const double* d_dev, const double* e_dev, int lde, int band, int npts, const double* x_dev,
+                        int* cnt_dev);
 /* EXTENSION, the counterpart of eigx_band_dc_dev for a chosen set: m approximate eigenvalues w_sel_dev of the band matrix
  * (d, e(lde, 2), band 1 or 2) -> Ritz values w_out_dev[m] (ascending) and an orthonormal n x m eigenvector basis
  * z_dev(ldz, m).  One GPU.  Returns EIGX_OK, or a positive value when its acceptance test refused the result (1: a Cholesky
