@@ -1,5 +1,5 @@
 // api.hip -- C-ABI entry points (include/eigenexa_amd.h): life cycle, queries, memory helpers.
-// The solver entry points live in solver.hip.
+// The solver entry points live in solver.hip, gev.hip, hgev.hip and herm.hip.
 #include "eigx_context.h"
 #include "eigx_comm.h"
 #include "../../include/eigenexa_amd.h"

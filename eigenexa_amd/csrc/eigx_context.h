@@ -158,7 +158,8 @@ void band_bisect_range_dev(Context& ctx, int n, int il, int iu, const double* d,
 void band_count_dev(Context& ctx, int n, const double* d, const double* e, int lde, int band, int npts, const double* x,
                     int* cnt);
 
-// The window of a range solve (solver.hip: range_solve_dev, gev_range_dev and their host forms).  By index: eigenpairs
+// The window of a range solve (range_solve_dev in solver.hip, gev_range_dev in gev.hip, hgev_range_dev in hgev.hip and their
+// host forms; the complex solver takes index windows only).  By index: eigenpairs
 // il .. iu (1-based, inclusive).  By value: those with vl <= lambda < vu, resolved into il .. iu by two Sturm counts after
 // the band reduction; at most mmax of them are returned, and *m_out / *il_out (host) receive their number and the index
 // of the first.  m() = the entries of w / columns of z the caller provides.
@@ -174,6 +175,16 @@ struct RangeWindow {
   }
   int m() const { return by_value ? mmax : iu - il + 1; }
 };
+// entries of w that a range call may write (NaN on a non-finite input), eigenvector columns it may ask room for
+inline int range_w_cap(const RangeWindow& W, char mode) { return (W.by_value && mode == 'C') ? 0 : W.m(); }
+inline int range_z_cap(int n, const RangeWindow& W, char mode) { const int c = range_w_cap(W, mode); return c < 1 ? 1 : (c < n ? c : n); }
+// solver.hip (see there): the argument check of every range entry, the refusal of a grid of several ranks
+// (EIGX_ERR_BAD_ARG), and the drivers of eigen_sx (band 2) / eigen_s (band 1) and of their range solve on device arrays
+bool range_args_ok(int n, const RangeWindow& W, const double* a, int lda, const double* w, const double* z, int ldz, char mode);
+int refuse_several_ranks(const Context& ctx);
+int solve_dev(Context& ctx, int n, int nvec, double* a, int lda, double* w, double* z, int ldz, int mf, int mb, char mode, int band, int nb);
+int range_solve_dev(Context& ctx, int n, RangeWindow W, double* a, int lda, double* w, double* z, int ldz, int mf, int mb,
+                    char mode, int band, bool fill_rest);
 
 // subset.hip (EXTENSION, one GPU): eigenvectors of the band matrix for m chosen eigenvalues by inverse iteration, CholQR2
 // and Rayleigh-Ritz; w_out = Ritz values (ascending), z(ldz, m) orthonormal.  EIGX_OK, or > 0: the acceptance test refused
@@ -251,16 +262,18 @@ void trbak_prepare_dev(Context& ctx, int n, double* A, int lda, const double* e,
 void trbak_dev(Context& ctx, int n, int nvec, double* A, int lda, double* Z, int ldz, const double* e, int lde, int mb,
                int band);
 
-// solver.hip
-// eigenvector column blocks -> the callers' 2-D (block-)cyclic blocks (one all-to-all); see solver.hip
+// redist.hip: eigenvector column blocks -> the callers' 2-D (block-)cyclic blocks, and a block-cyclic caller's a -> the
+// cyclic layout (synchronous; EIGX_OK or EIGX_ERR_INTERNAL); one all-to-all each
 void cols_to_cyclic_dev(Context& ctx, int n, int nvec, int nb, int zc, int zc0, int zcnt, const double* zcols, int ldz,
                         double* z_user, int ldz_user, hipStream_t st);
+int bc_to_cyclic(Context& ctx, const double* a, int lda, int n, int nb, double* out, int ldo, hipStream_t st);
+// solver.hip
 int64_t solver_workspace_bytes(const Context& ctx, int n, int lda, int ldz, int mf, int mb);
 // eigen_scaling of every solver (src/eigen_scaling.F:86-150): max |a| and a non-finite flag over the upper triangle of
 // this rank's 2-D cyclic block of an n x n matrix (real, or interleaved complex with lda in complex elements: max of
 // |Re|, |Im|, Im of the diagonal not read), combined over the ranks.  NaN / Inf anywhere: w(1:nw) = NaN (nw < 0: all n;
 // an index-range solve's w may hold fewer), errinfo = -1, EIGX_ERR_NONFINITE.  Otherwise *sigma = the factor to scale
-// the matrix by (1 = none).
+// the matrix by (1 = none; sigma == nullptr: only the scan is wanted).
 int eigen_scaling(Context& ctx, const double* a, int lda, bool cplx, int n, double* w, double* sigma, int nw = -1);
 
 // The frame of a whole solve: what eigen_sx / eigen_s (solve_dev), the index-range solves (range_solve_dev) and the two
@@ -299,13 +312,43 @@ struct SolveFrame {
 inline int host_ld(int nr) { return pad_ld(nr + 2); }
 void* host_to_dev(Context& ctx, const char* name, const void* h, int ld, int nr, int nc, int esz);
 void dev_to_host(void* h, int ld, const void* d, int ldd, int nr, int nc, int esz);
+// Host form of a solve on a local block of nr rows: a (nc columns), b (the same; b_h == nullptr: none), z (zcols columns,
+// allocated only) and w (nw entries) in the pool buffers host.a / host.b / host.z (esz 8) or host.ha / host.hb / host.hz
+// (esz 16, interleaved complex) and host.w, leading dimension ldd.  What comes back, and when, is each driver's contract:
+// w_back copies cnt entries of w, back ncols columns (of nrows rows, default nr) of a device block.
+struct HostStage {
+  const int esz, nr, ldd;
+  double* a = nullptr; double* b = nullptr; double* z = nullptr; double* w = nullptr;
+  HostStage(Context& c, int esz_, int nr_, int nc, const void* a_h, int lda, const void* b_h, int ldb, int zcols, int nw);
+  void w_back(double* w_h, int cnt) const { if (cnt > 0) EIGX_HIP_CHECK(hipMemcpy(w_h, w, (size_t)cnt * 8, hipMemcpyDeviceToHost)); }
+  void back(void* h, int ld, const double* d, int ncols, int nrows = -1) const {
+    dev_to_host(h, ld, d, ldd, nrows < 0 ? nr : nrows, ncols, esz);
+  }
+};
+// gev.hip: the frame of the six generalised device drivers (gev.hip, hgev.hip).  A driver tests `initialized` and the number
+// of ranks itself, then: begin (EIGX_ERR_BAD_ARG, or device set, the caller's default stream drained, t[0] taken) -> mark
+// at the end of each of its first three stages -> finish (end of the last; timers[0] = total, [1 .. 4] = stages; EIGX_OK).
+struct GevFrame {
+  Context& ctx;
+  double t[5] = {0.0, 0.0, 0.0, 0.0, 0.0}; int k = 0;
+  explicit GevFrame(Context& c) : ctx(c) {}
+  int begin(bool args_ok);
+  void mark() { if (k < 4) t[++k] = now_s(); }
+  int finish();
+};
+// B's smallest eigenvalue w(1) > 0 (read back synchronously), else report_not_spd: the message (rank 0), EIGX_ERR_NOT_SPD
+bool b_is_positive_definite(const Context& ctx, const double* w);
+int report_not_spd(const Context& ctx);
 // Building blocks of the multi-rank KMATH_EIGEN_GEV, shared with the complex generalised solver (hgev.hip):
 // z = a^T on the 2-D cyclic blocks of n x n matrices (exchange buffers in the pool as `tag`.tsend / `tag`.trecv), and the
-// SUMMA panel packing of a's columns lc0 .. lc0 + kbl - 1 (out[c * nrp + r]) and of b's rows lr0 .. lr0 + kbl - 1
-// (out[j * kbl + rr])
+// SUMMA panel plan: L = lcm(Px, Py), kb = the panel width (kb_want rounded up to a multiple of 2 L), kbl_x / kbl_y = its
+// share per process row / column, nrp / ncp = the padded local extents.  summa_pack_a: a's columns lc0 .. lc0 + kbl_y - 1
+// (out[c * nrp + r]); summa_pack_b: b's rows lr0 .. lr0 + kbl_x - 1 (out[j * kbl_x + rr]); both enqueued on st.
 void dist_transpose(Context& ctx, int n, const double* a, int lda, double* z, int ldz, hipStream_t st, const char* tag = "gev");
-__global__ void mm_pack_a_kernel(const double* __restrict__ a, int lda, int nr, int nc, int lc0, int nrp, double* __restrict__ out);
-__global__ void mm_pack_b_kernel(const double* __restrict__ b, int ldb, int nr, int nc, int lr0, int kbl, double* __restrict__ out);
+struct SummaPlan { int L, kb, kbl_x, kbl_y, nrp, ncp; };
+SummaPlan summa_plan(const Grid& G, int n, int kb_want);
+void summa_pack_a(hipStream_t st, const SummaPlan& p, const double* a, int lda, int nr, int nc, int lc0, double* out);
+void summa_pack_b(hipStream_t st, const SummaPlan& p, const double* b, int ldb, int nr, int nc, int lr0, double* out);
 
 // herm.hip: eigen_h on device arrays (interleaved complex; one GPU, or this rank's 2-D cyclic blocks)
 int herm_solve_dev(Context& ctx, int n, int nvec, double* a, int lda, double* w, double* z, int ldz, int mf, int mb,

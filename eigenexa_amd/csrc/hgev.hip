@@ -2,7 +2,7 @@
 //
 // EXTENSION: the reference has no complex generalised solver.  This one follows the reference's method for the real case
 // (KMATH_EIGEN_GEV_1, src/KMATH_EIGEN_GEV_1.F:57-139: two eigensolves and three products) over complex numbers, with the
-// same argument list and on-exit contract as KMATH_EIGEN_GEV (solver.hip gev_dev / gev_dev_mg):
+// same argument list and on-exit contract as KMATH_EIGEN_GEV (gev.hip gev_dev / gev_dev_mg):
 //   eigen_h(B, 'X'):  B = U diag(mu) U^H          (mu_min <= 0: "Matrix B is not positive definite!", EIGX_ERR_NOT_SPD)
 //   F = U diag(mu)^-1/2 ;  C = F^H (A F) ;  eigen_h(C, 'X'):  C = Y diag(w) Y^H ;  Z = F Y       (Z^H B Z = I)
 // On exit a holds Y, b holds F, w is ascending, z = F Y; timers [0..4] = total, eigen_h(B), forming C, eigen_h(C), Z = F Y.
@@ -68,15 +68,10 @@ int zsumma(Context& ctx, int n, const ZPlanes& X, int ldx, double sa, const ZPla
   const Grid& G = ctx.grid;
   hipStream_t st = ctx.stream;
   const int nr = local_count(n, G.Px, G.px), nc = local_count(n, G.Py, G.py);
-  int g = G.Px, h = G.Py;
-  while (h) { const int t = g % h; g = h; h = t; }
-  const int L = G.Px / g * G.Py;
-  const int unit = 2 * L;                        // panels start at multiples of Px and Py; even widths
   // panel width about n / 16 between 64 and 512: both planes travel, and the panels stay within ~2 n^2/P + 1 MiB
   const int kb_want = (n < 64) ? n : (n / 16 < 64 ? 64 : (n / 16 > 512 ? 512 : n / 16));
-  const int kb = unit * ceil_div(kb_want, unit);
-  const int kbl_x = kb / G.Px, kbl_y = kb / G.Py;
-  const int nrp = ((nr > 2 ? nr : 2) + 1) & ~1, ncp = nc > 1 ? nc : 1;
+  const SummaPlan p = summa_plan(G, n, kb_want);
+  const int kb = p.kb, kbl_x = p.kbl_x, kbl_y = p.kbl_y, nrp = p.nrp, ncp = p.ncp;
   double* sendA = ctx.pool.get_t<double>("hgev.sa", (size_t)2 * nrp * kbl_y);
   double* Ap = ctx.pool.get_t<double>("hgev.pa", (size_t)2 * nrp * kb);
   double* sendB = ctx.pool.get_t<double>("hgev.sb", (size_t)2 * kbl_x * ncp);
@@ -84,13 +79,11 @@ int zsumma(Context& ctx, int n, const ZPlanes& X, int ldx, double sa, const ZPla
   double* B1 = ctx.pool.get_t<double>("hgev.pb", (size_t)4 * kb * ncp);
   double* B2 = B1 + (size_t)2 * kb * ncp;
   for (int k0 = 0; k0 < n; k0 += kb) {
-    hipLaunchKernelGGL(mm_pack_a_kernel, dim3(ceil_div(nrp, 256), kbl_y), dim3(256), 0, st, X.r, ldx, nr, nc, k0 / G.Py, nrp, sendA);
-    hipLaunchKernelGGL(mm_pack_a_kernel, dim3(ceil_div(nrp, 256), kbl_y), dim3(256), 0, st, X.i, ldx, nr, nc, k0 / G.Py, nrp,
-                       sendA + (size_t)nrp * kbl_y);
+    summa_pack_a(st, p, X.r, ldx, nr, nc, k0 / G.Py, sendA);
+    summa_pack_a(st, p, X.i, ldx, nr, nc, k0 / G.Py, sendA + (size_t)nrp * kbl_y);
     comm_allgather(ctx, COMM_Y, sendA, Ap, (size_t)2 * nrp * kbl_y, st);     // Ap(:, q 2kbl_y + pl kbl_y + c)
-    hipLaunchKernelGGL(mm_pack_b_kernel, dim3(ceil_div(kbl_x, 256), ncp), dim3(256), 0, st, B.r, ldb, nr, nc, k0 / G.Px, kbl_x, sendB);
-    hipLaunchKernelGGL(mm_pack_b_kernel, dim3(ceil_div(kbl_x, 256), ncp), dim3(256), 0, st, B.i, ldb, nr, nc, k0 / G.Px, kbl_x,
-                       sendB + (size_t)kbl_x * ncp);
+    summa_pack_b(st, p, B.r, ldb, nr, nc, k0 / G.Px, sendB);
+    summa_pack_b(st, p, B.i, ldb, nr, nc, k0 / G.Px, sendB + (size_t)kbl_x * ncp);
     comm_allgather(ctx, COMM_X, sendB, recvB, (size_t)2 * kbl_x * ncp, st);
     hipLaunchKernelGGL(hg_unpack_b_kernel, dim3(ceil_div(kbl_x, 256), ncp, G.Px), dim3(256), 0, st, (const double*)recvB, G.Px,
                        G.Py, kbl_x, kbl_y, ncp, kb, sa, B1, B2);
@@ -104,15 +97,6 @@ int zsumma(Context& ctx, int n, const ZPlanes& X, int ldx, double sa, const ZPla
   return comm_failed(ctx) ? EIGX_ERR_INTERNAL : EIGX_OK;
 }
 
-bool b_is_positive_definite(const Context& ctx, const double* w) {
-  double wmin = 0.0;
-  EIGX_HIP_CHECK(hipMemcpy(&wmin, w, 8, hipMemcpyDeviceToHost));
-  if (wmin > 0.0) return true;
-  // w is replicated bit for bit on several ranks: every rank takes the same way out
-  if (ctx.grid.rank == 0) fprintf(stderr, "[eigx] Matrix B is not positive definite!\n");   // src/KMATH_EIGEN_GEV_1.F:75-80
-  return false;
-}
-
 // eigen_h's default panel widths (eigen_NB_f, eigen_NB_b)
 constexpr int HG_MF = 48, HG_MB = 128;
 
@@ -121,13 +105,10 @@ int hgev_dev_mg(Context& ctx, int n, double* a, int lda, double* b, int ldb, dou
   const Grid G = ctx.grid;
   const int nr = local_count(n, G.Px, G.px), nc = local_count(n, G.Py, G.py);
   const int lmin = nr > 1 ? nr : 1;
-  if (n <= 0 || !a || !b || !w || !z || lda < lmin || ldb < lmin || ldz < lmin) return EIGX_ERR_BAD_ARG;
-  EIGX_HIP_CHECK(hipSetDevice(ctx.device));
-  EIGX_HIP_CHECK(hipStreamSynchronize(nullptr));   // the caller's default-stream work on the arguments (see SolveFrame::begin)
+  GevFrame Fr(ctx);
+  if (const int rc0 = Fr.begin(n > 0 && a && b && w && z && lda >= lmin && ldb >= lmin && ldz >= lmin)) return rc0;
   hipStream_t st = ctx.stream;
-  const double t0 = now_s();
-  double sigma = 1.0;
-  int rc = eigen_scaling(ctx, a, lda, true, n, w, &sigma);   // NaN / Inf in A: eigen_h's status, before B's solve
+  int rc = eigen_scaling(ctx, a, lda, true, n, w, nullptr);   // NaN / Inf in A: eigen_h's status, before B's solve
   if (rc != EIGX_OK) return rc;
   const int ldt = ((nr > 2 ? nr : 2) + 1) & ~1;
   const size_t pl = (size_t)ldt * (nc > 0 ? nc : 1);
@@ -145,7 +126,7 @@ int hgev_dev_mg(Context& ctx, int n, double* a, int lda, double* b, int ldb, dou
   if (comm_failed(ctx)) return EIGX_ERR_INTERNAL;
   rc = herm_solve_dev(ctx, n, n, b, ldb, w, z, ldz, HG_MF, HG_MB, 'X');                   // B = U diag(mu) U^H
   if (rc != EIGX_OK) return rc;
-  const double t1 = now_s();
+  Fr.mark();
   if (!b_is_positive_definite(ctx, w)) return EIGX_ERR_NOT_SPD;
   zsplit(st, z, ldz, nr, nc, false, F, ldt, w, G);                                          // F = U diag(mu)^-1/2
   zjoin(st, F, ldt, nr, nc, false, b, ldb, G);
@@ -157,18 +138,16 @@ int hgev_dev_mg(Context& ctx, int n, double* a, int lda, double* b, int ldb, dou
   if (rc != EIGX_OK) return rc;
   zjoin(st, X, ldt, nr, nc, true, z, ldz, G);
   EIGX_HIP_CHECK(hipStreamSynchronize(st));
-  const double t2 = now_s();
+  Fr.mark();
   rc = herm_solve_dev(ctx, n, n, z, ldz, w, a, lda, HG_MF, HG_MB, 'X');                   // C = Y diag(w) Y^H, Y in a
   if (rc != EIGX_OK) return rc;
-  const double t3 = now_s();
+  Fr.mark();
   zsplit(st, a, lda, nr, nc, false, A, ldt, nullptr, G);
   rc = zsumma(ctx, n, F, ldt, 1.0, A, ldt, T, ldt, false);                                  // Z = F Y
   if (rc != EIGX_OK) return rc;
   zjoin(st, T, ldt, nr, nc, false, z, ldz, G);
   EIGX_HIP_CHECK(hipStreamSynchronize(st));
-  const double t4 = now_s();
-  ctx.timers[0] = t4 - t0; ctx.timers[1] = t1 - t0; ctx.timers[2] = t2 - t1; ctx.timers[3] = t3 - t2; ctx.timers[4] = t4 - t3;
-  return EIGX_OK;
+  return Fr.finish();
 }
 
 }  // namespace
@@ -176,13 +155,10 @@ int hgev_dev_mg(Context& ctx, int n, double* a, int lda, double* b, int ldb, dou
 int hgev_dev(Context& ctx, int n, double* a, int lda, double* b, int ldb, double* w, double* z, int ldz) {
   if (!ctx.initialized) return EIGX_ERR_NOT_INITIALIZED;
   if (ctx.grid.nranks != 1) return hgev_dev_mg(ctx, n, a, lda, b, ldb, w, z, ldz);
-  if (n <= 0 || !a || !b || !w || !z || lda < n || ldb < n || ldz < n) return EIGX_ERR_BAD_ARG;
-  EIGX_HIP_CHECK(hipSetDevice(ctx.device));
-  EIGX_HIP_CHECK(hipStreamSynchronize(nullptr));   // the caller's default-stream work on the arguments (see SolveFrame::begin)
+  GevFrame Fr(ctx);
+  if (const int rc0 = Fr.begin(n > 0 && a && b && w && z && lda >= n && ldb >= n && ldz >= n)) return rc0;
   hipStream_t st = ctx.stream;
-  const double t0 = now_s();
-  double sigma = 1.0;
-  int rc = eigen_scaling(ctx, a, lda, true, n, w, &sigma);   // NaN / Inf in A: eigen_h's status, before B's solve
+  int rc = eigen_scaling(ctx, a, lda, true, n, w, nullptr);   // NaN / Inf in A: eigen_h's status, before B's solve
   if (rc != EIGX_OK) return rc;
   const int ld = pad_ld(n);
   const size_t pl = (size_t)ld * n;
@@ -192,7 +168,7 @@ int hgev_dev(Context& ctx, int n, double* a, int lda, double* b, int ldb, double
   zexpand(st, a, lda, n, A, ld);
   rc = herm_solve_dev(ctx, n, n, b, ldb, w, z, ldz, HG_MF, HG_MB, 'X');                   // B = U diag(mu) U^H
   if (rc != EIGX_OK) return rc;
-  const double t1 = now_s();
+  Fr.mark();
   if (!b_is_positive_definite(ctx, w)) return EIGX_ERR_NOT_SPD;
   zsplit(st, z, ldz, n, n, false, F, ld, w);                                                // F = U diag(mu)^-1/2
   zjoin(st, F, ld, n, n, false, b, ldb);
@@ -200,17 +176,15 @@ int hgev_dev(Context& ctx, int n, double* a, int lda, double* b, int ldb, double
   zgemm_planes(st, 'C', n, n, n, 1.0, F, ld, T, ld, 0.0, A, ld, 1);                         // C = F^H T, upper tiles
   zjoin(st, A, ld, n, n, true, z, ldz);
   EIGX_HIP_CHECK(hipStreamSynchronize(st));
-  const double t2 = now_s();
+  Fr.mark();
   rc = herm_solve_dev(ctx, n, n, z, ldz, w, a, lda, HG_MF, HG_MB, 'X');                   // C = Y diag(w) Y^H, Y in a
   if (rc != EIGX_OK) return rc;
-  const double t3 = now_s();
+  Fr.mark();
   zsplit(st, a, lda, n, n, false, T, ld);
   zgemm_planes(st, 'N', n, n, n, 1.0, F, ld, T, ld, 0.0, A, ld);                            // Z = F Y
   zjoin(st, A, ld, n, n, false, z, ldz);
   EIGX_HIP_CHECK(hipStreamSynchronize(st));
-  const double t4 = now_s();
-  ctx.timers[0] = t4 - t0; ctx.timers[1] = t1 - t0; ctx.timers[2] = t2 - t1; ctx.timers[3] = t3 - t2; ctx.timers[4] = t4 - t3;
-  return EIGX_OK;
+  return Fr.finish();
 }
 
 int hgev_host(Context& ctx, int n, double* a, int lda, double* b, int ldb, double* w, double* z, int ldz) {
@@ -218,61 +192,46 @@ int hgev_host(Context& ctx, int n, double* a, int lda, double* b, int ldb, doubl
   // host arrays: the rank's 2-D cyclic blocks a(lda, *), b(ldb, *), z(ldz, *), interleaved complex (one rank: the whole matrices)
   const int nr = local_count(n, ctx.grid.Px, ctx.grid.px), nc = local_count(n, ctx.grid.Py, ctx.grid.py);
   if (n <= 0 || !a || !b || !w || !z || lda < nr || ldb < nr || ldz < nr) return EIGX_ERR_BAD_ARG;
-  EIGX_HIP_CHECK(hipSetDevice(ctx.device));
-  const int ldd = host_ld(nr);
-  double* ad = (double*)host_to_dev(ctx, "host.ha", a, lda, nr, nc, 16);
-  double* bd = (double*)host_to_dev(ctx, "host.hb", b, ldb, nr, nc, 16);
-  double* zd = (double*)host_to_dev(ctx, "host.hz", nullptr, 0, nr, nc, 16);
-  double* wd = ctx.pool.get_t<double>("host.w", (size_t)n);
-  const int rc = hgev_dev(ctx, n, ad, ldd, bd, ldd, wd, zd, ldd);
-  EIGX_HIP_CHECK(hipMemcpy(w, wd, (size_t)n * 8, hipMemcpyDeviceToHost));   // NaN for a non-finite input, as eigen_h
+  const HostStage S(ctx, 16, nr, nc, a, lda, b, ldb, nc, n);
+  const int rc = hgev_dev(ctx, n, S.a, S.ldd, S.b, S.ldd, S.w, S.z, S.ldd);
+  S.w_back(w, n);   // in every case (gev_host: on EIGX_OK only): NaN for a non-finite input, as eigen_h
   if (rc != EIGX_OK) return rc;
-  dev_to_host(z, ldz, zd, ldd, nr, nc, 16);
-  dev_to_host(a, lda, ad, ldd, nr, nc, 16);
-  dev_to_host(b, ldb, bd, ldd, nr, nc, 16);
+  S.back(z, ldz, S.z, nc);
+  S.back(a, lda, S.a, nc);   // Y
+  S.back(b, ldb, S.b, nc);   // F
   return EIGX_OK;
 }
 
 // ---- KMATH_EIGEN_HGEV_RANGE: eigenpairs il .. iu of A x = lambda B x by the Cholesky route (EXTENSION, one GPU) ---------
 // B = U^H U (ztri.hip) -> C = U^-H A U^-1 -> eigen_h(C) with nvec = iu -> Z = U^-1 Y on the columns il .. iu: the complex
-// sibling of gev_range_dev (solver.hip).  4 (1/3 + 5/3 + m/n) n^3 real flops through the MFMA GEMM and ONE eigen_h where
+// sibling of gev_range_dev (gev.hip).  4 (1/3 + 5/3 + m/n) n^3 real flops through the MFMA GEMM and ONE eigen_h where
 // hgev_dev spends 20 n^3 and two.  The inner solve is eigen_h itself, not a Hermitian subset path: its tridiagonal stage
 // is a few percent of it, so with il > 1 the columns 1 .. il - 1 of Y are computed and dropped, and the workspace holds
 // an n x iu complex Y.  B is not scaled (the limitation of gev_range_dev): U carries the square root of B's scale and C
 // its inverse; eigen_h scales C itself, but only once it has been formed.
 // Pool buffers: hgevr.u, hgevr.a, hgevr.cp (two planes of pad_ld(n) x n each), hgevr.c (C interleaved), hgevr.y (mode 'A':
 // Y, n x iu complex), hgevr.w (n) and the block inverses and panels of ztri.hip.
-int hgev_range_dev(Context& ctx, int n, int il, int iu, double* a, int lda, double* b, int ldb, double* w, double* z, int ldz,
-                   char mode) {
+// W is an index window: the C entries build no other (a value form would need the window resolved inside eigen_h).
+int hgev_range_dev(Context& ctx, int n, const RangeWindow& W, double* a, int lda, double* b, int ldb, double* w, double* z,
+                   int ldz, char mode) {
   if (!ctx.initialized) return EIGX_ERR_NOT_INITIALIZED;
-  if (ctx.grid.nranks != 1) {
-    fprintf(stderr, "[eigx] index-range solves run on one GPU only (this grid has %d ranks)\n", ctx.grid.nranks);
-    return EIGX_ERR_BAD_ARG;
-  }
+  if (ctx.grid.nranks != 1) return refuse_several_ranks(ctx);
   mode = upper_case(mode);
-  if (n <= 0 || il < 1 || iu > n || il > iu || (mode != 'A' && mode != 'N') || !a || !b || !w || lda < n || ldb < n ||
-      (mode == 'A' && (!z || ldz < n)))
-    return EIGX_ERR_BAD_ARG;
-  EIGX_HIP_CHECK(hipSetDevice(ctx.device));
-  EIGX_HIP_CHECK(hipStreamSynchronize(nullptr));   // the caller's default-stream work on the arguments
+  GevFrame Fr(ctx);
+  if (const int rc0 = Fr.begin(range_args_ok(n, W, a, lda, w, z, ldz, mode) && b && ldb >= n)) return rc0;
   hipStream_t st = ctx.stream;
-  const int m = iu - il + 1;
-  const double t0 = now_s();
-  // both significant triangles are scanned before anything is factored; the scale factors are not used
-  double sigma = 1.0;
-  if (const int rc = eigen_scaling(ctx, a, lda, true, n, w, &sigma, m)) return rc;
-  if (const int rc = eigen_scaling(ctx, b, ldb, true, n, w, &sigma, m)) return rc;
+  const int il = W.il, iu = W.iu, m = W.m();
+  // both significant triangles are scanned before anything is factored
+  if (const int rc = eigen_scaling(ctx, a, lda, true, n, w, nullptr, m)) return rc;
+  if (const int rc = eigen_scaling(ctx, b, ldb, true, n, w, nullptr, m)) return rc;
   const int ld = pad_ld(n);
   const ZPlanes U = zplanes(ctx, "hgevr.u", ld, n);
   const ZPlanes A = zplanes(ctx, "hgevr.a", ld, n);     // A, later the columns il .. iu of Y, later Z
   const ZPlanes Cp = zplanes(ctx, "hgevr.cp", ld, n);
   zsplit(st, b, ldb, n, n, true, U, ld);
-  if (zchol_upper_dev(ctx, n, U, ld) != EIGX_OK) {
-    fprintf(stderr, "[eigx] Matrix B is not positive definite!\n");
-    return EIGX_ERR_NOT_SPD;
-  }
+  if (zchol_upper_dev(ctx, n, U, ld) != EIGX_OK) return report_not_spd(ctx);
   zjoin(st, U, ld, n, n, true, b, ldb);
-  const double t1 = now_s();
+  Fr.mark();
   const ZTriInv V = ztri_inverses_dev(ctx, n, U, ld);   // once per factor: the three solves below share them
   zexpand(st, a, lda, n, A, ld);
   hgev_reduce_dev(ctx, n, A, ld, U, ld, V, Cp, ld);
@@ -280,7 +239,7 @@ int hgev_range_dev(Context& ctx, int n, int il, int iu, double* a, int lda, doub
   double* c = ctx.pool.get_t<double>("hgevr.c", (size_t)2 * ldc * n);
   zjoin(st, Cp, ld, n, n, true, c, ldc);
   EIGX_HIP_CHECK(hipStreamSynchronize(st));
-  const double t2 = now_s();
+  Fr.mark();
   double* wn = ctx.pool.get_t<double>("hgevr.w", (size_t)n);
   double* y = mode == 'A' ? ctx.pool.get_t<double>("hgevr.y", (size_t)2 * ldc * iu) : nullptr;
   const int rc = herm_solve_dev(ctx, n, iu, c, ldc, wn, y, ldc, HG_MF, HG_MB, mode);    // C = Y diag(w) Y^H, the lowest iu
@@ -288,38 +247,29 @@ int hgev_range_dev(Context& ctx, int n, int il, int iu, double* a, int lda, doub
     EIGX_HIP_CHECK(hipMemcpyAsync(w, wn + (il - 1), (size_t)m * 8, hipMemcpyDeviceToDevice, st));
   EIGX_HIP_CHECK(hipStreamSynchronize(st));
   if (rc != EIGX_OK) return rc;
-  const double t3 = now_s();
+  Fr.mark();
   if (mode == 'A') {
     zsplit(st, y + (size_t)2 * ldc * (il - 1), ldc, n, m, false, A, ld);
     ztrsm_upper_dev(ctx, 'N', n, m, U, ld, A, ld, V);   // Z = U^-1 Y
     zjoin(st, A, ld, n, m, false, z, ldz);
     EIGX_HIP_CHECK(hipStreamSynchronize(st));
   }
-  const double t4 = now_s();
-  ctx.timers[0] = t4 - t0; ctx.timers[1] = t1 - t0; ctx.timers[2] = t2 - t1; ctx.timers[3] = t3 - t2; ctx.timers[4] = t4 - t3;
-  return EIGX_OK;
+  return Fr.finish();
 }
 
-int hgev_range_host(Context& ctx, int n, int il, int iu, double* a, int lda, double* b, int ldb, double* w, double* z, int ldz,
-                    char mode) {
+int hgev_range_host(Context& ctx, int n, const RangeWindow& W, double* a, int lda, double* b, int ldb, double* w, double* z,
+                    int ldz, char mode) {
   if (!ctx.initialized) return EIGX_ERR_NOT_INITIALIZED;
-  if (ctx.grid.nranks != 1) return hgev_range_dev(ctx, n, il, iu, a, lda, b, ldb, w, z, ldz, mode);   // refuses
+  if (ctx.grid.nranks != 1) return hgev_range_dev(ctx, n, W, a, lda, b, ldb, w, z, ldz, mode);   // refuses
   mode = upper_case(mode);
-  if (n <= 0 || il < 1 || iu > n || il > iu || (mode != 'A' && mode != 'N') || !a || !b || !w || lda < n || ldb < n ||
-      (mode == 'A' && (!z || ldz < n)))
-    return EIGX_ERR_BAD_ARG;
-  const int m = iu - il + 1;
-  EIGX_HIP_CHECK(hipSetDevice(ctx.device));
-  const int ldd = host_ld(n);
-  double* ad = (double*)host_to_dev(ctx, "host.ha", a, lda, n, n, 16);
-  double* bd = (double*)host_to_dev(ctx, "host.hb", b, ldb, n, n, 16);
-  double* zd = (double*)host_to_dev(ctx, "host.hz", nullptr, 0, n, mode == 'A' ? m : 1, 16);
-  double* wd = ctx.pool.get_t<double>("host.w", (size_t)m);
-  const int rc = hgev_range_dev(ctx, n, il, iu, ad, ldd, bd, ldd, wd, zd, ldd, mode);
-  if (rc == EIGX_OK || rc == EIGX_ERR_NONFINITE) EIGX_HIP_CHECK(hipMemcpy(w, wd, (size_t)m * 8, hipMemcpyDeviceToHost));
+  if (!range_args_ok(n, W, a, lda, w, z, ldz, mode) || !b || ldb < n) return EIGX_ERR_BAD_ARG;
+  const int m = W.m();
+  const HostStage S(ctx, 16, n, n, a, lda, b, ldb, mode == 'A' ? m : 1, m);
+  const int rc = hgev_range_dev(ctx, n, W, S.a, S.ldd, S.b, S.ldd, S.w, S.z, S.ldd, mode);
+  if (rc == EIGX_OK || rc == EIGX_ERR_NONFINITE) S.w_back(w, m);
   if (rc != EIGX_OK) return rc;
-  if (mode == 'A') dev_to_host(z, ldz, zd, ldd, n, m, 16);
-  dev_to_host(b, ldb, bd, ldd, n, n, 16);   // U in the upper triangle
+  if (mode == 'A') S.back(z, ldz, S.z, m);
+  S.back(b, ldb, S.b, n);   // U in the upper triangle; a is not returned
   return EIGX_OK;
 }
 
@@ -338,10 +288,10 @@ int eigx_hgev_dev(int n, double* a, int lda, double* b, int ldb, double* w, doub
 
 // EXTENSION: eigenpairs il .. iu of the complex problem by the Cholesky route (one GPU); see hgev_range_dev
 int eigx_hgev_range(int n, int il, int iu, double* a, int lda, double* b, int ldb, double* w, double* z, int ldz, char mode) {
-  return eigx_guard(g_ctx, [&] { return hgev_range_host(g_ctx, n, il, iu, a, lda, b, ldb, w, z, ldz, mode); });
+  return eigx_guard(g_ctx, [&] { return hgev_range_host(g_ctx, n, RangeWindow::index(il, iu), a, lda, b, ldb, w, z, ldz, mode); });
 }
 int eigx_hgev_range_dev(int n, int il, int iu, double* a, int lda, double* b, int ldb, double* w, double* z, int ldz, char mode) {
-  return eigx_guard(g_ctx, [&] { return hgev_range_dev(g_ctx, n, il, iu, a, lda, b, ldb, w, z, ldz, mode); });
+  return eigx_guard(g_ctx, [&] { return hgev_range_dev(g_ctx, n, RangeWindow::index(il, iu), a, lda, b, ldb, w, z, ldz, mode); });
 }
 
 }  // extern "C"

@@ -1,4 +1,6 @@
-// solver.hip -- drivers: eigx_sx (pentadiagonal route) and eigx_s (tridiagonal route).
+// solver.hip -- eigen_scaling, the solve frame and host staging (eigx_context.h), and the drivers of the standard problem:
+// eigx_sx (pentadiagonal route), eigx_s (tridiagonal route) and their range solves, with their C entries.  The layout
+// redistributions are in redist.hip, the generalised solvers in gev.hip (real) and hgev.hip (complex).
 //
 // Replaces eigen_sx (src/eigen_sx.F:30-308) and eigen_s -> eigen_FS / eigen_s0
 // (src/eigen_libs.F:150-202, src/eigen_FS.F:29-300, src/eigen_s.F:30-307):
@@ -10,8 +12,6 @@
 #include <algorithm>
 #include <cfloat>
 #include <limits>
-#include <vector>
-#include <cstring>
 
 namespace eigx {
 
@@ -72,8 +72,6 @@ __global__ void absmax_final_kernel(const double* __restrict__ part, int nb, dou
   }
 }
 
-// local index l of process p (of P) -> global index, blocks of nb (nb = 1: cyclic, l*P + p)
-__device__ __forceinline__ int bc_l2g(int l, int nb, int P, int p) { return ((l / nb) * P + p) * nb + l % nb; }
 
 // z(:, j) = e_j for the first gridDim.y columns (modes 'S', 'C': eigen_identity, src/eigen_sx.F:214)
 __global__ void identity_kernel(double* __restrict__ z, int ldz, int n, int c0) {
@@ -82,172 +80,7 @@ __global__ void identity_kernel(double* __restrict__ z, int ldz, int n, int c0) 
   for (int r = blockIdx.x * blockDim.x + threadIdx.x; r < n; r += gridDim.x * blockDim.x) col[r] = (r == c0 + j) ? 1.0 : 0.0;
 }
 
-__device__ __host__ __forceinline__ int bc_owner(int g, int nb, int P) { return (g / nb) % P; }
-__device__ __host__ __forceinline__ int bc_g2l(int g, int nb, int P) { return ((g / nb) / P) * nb + g % nb; }
-// number of indices g < n that process p owns (NUMROC), usable on the device
-__device__ __host__ __forceinline__ int bc_count(int n, int nb, int p, int P) {
-  const int nblocks = n / nb;
-  int cnt = (nblocks / P) * nb;
-  const int extra = nblocks % P;
-  if (p < extra) cnt += nb;
-  else if (p == extra) cnt += n % nb;
-  return cnt;
-}
-
-// Eigenvector column block of this rank (columns [c0, c0 + cnt), all n rows) -> pieces for the all-to-all that deals
-// the matrix into the callers' 2-D (block-)cyclic blocks: the piece for rank (qx, qy) holds the rows that qx owns of
-// those of my columns that qy owns: send[rank][ljr * nrmax + li]   (src/dc_redist1.F / dc_redist2.F play this role
-// in the reference, between its D&C layout and the API layout)
-__global__ void pack_z_pieces_kernel(const double* __restrict__ Z, int ldz, int n, int c0, int cnt, int nb, int Px, int Py,
-                                     int row_major, int nrmax, size_t piece, double* __restrict__ send) {
-  const int cl = blockIdx.y, qx = blockIdx.z;
-  if (cl >= cnt) return;
-  const int c = c0 + cl;
-  const int qy = bc_owner(c, nb, Py);
-  const int ljr = bc_g2l(c, nb, Py) - bc_count(c0, nb, qy, Py);
-  const int dst = row_major ? qx * Py + qy : qx + qy * Px;
-  const int nr = bc_count(n, nb, qx, Px);
-  double* out = send + (size_t)dst * piece + (size_t)ljr * nrmax;
-  const double* col = Z + (size_t)cl * ldz;
-  for (int li = blockIdx.x * blockDim.x + threadIdx.x; li < nr; li += gridDim.x * blockDim.x)
-    out[li] = col[bc_l2g(li, nb, Px, qx)];
-}
-// z_user(li, lj) for my local columns that lie in source rank q's column range [q*zc, min((q+1)*zc, nvec))
-__global__ void unpack_z_pieces_kernel(const double* __restrict__ recv, size_t piece, int nrmax, int nvec, int zc, int nb,
-                                       int py, int Py, int nr, double* __restrict__ z, int ldz) {
-  const int q = blockIdx.z;
-  const int g0 = q * zc < nvec ? q * zc : nvec, g1 = (q + 1) * zc < nvec ? (q + 1) * zc : nvec;
-  const int l0 = bc_count(g0, nb, py, Py), l1 = bc_count(g1, nb, py, Py);
-  const int ljr = blockIdx.y;
-  if (ljr >= l1 - l0) return;
-  const double* src = recv + (size_t)q * piece + (size_t)ljr * nrmax;
-  double* col = z + (size_t)(l0 + ljr) * ldz;
-  for (int li = blockIdx.x * blockDim.x + threadIdx.x; li < nr; li += gridDim.x * blockDim.x)
-    col[li] = __hip_atomic_load(src + li, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-}
-
-// ---- block-cyclic (nb x nb blocks, a ScaLAPACK descriptor's layout) -> cyclic, as one all-to-all ---------------------
-// The element a rank holds at local (li, lj) is global (gi, gj) = (l2g(li), l2g(lj)); in the cyclic layout it belongs to
-// rank (gi mod Px, gj mod Py) at local (gi div Px, gj div Py).  The piece for a destination is addressed by the RANK of
-// the row / column among the sender's rows / columns that go to that destination: rrank[li], crank[lj] (host tables,
-// O(n / P) integers); the receiver holds, for each of its cyclic rows / columns, the sender's grid coordinate and that
-// rank (srcx / posr, srcy / posc).  This is what pdgemr2d does for the reference's callers (manual 3.4).
-__global__ void bc_pack_kernel(const double* __restrict__ a, int lda, int nr, int nc, int nb, int Px, int px, int Py, int py,
-                               int row_major, const int* __restrict__ rrank, const int* __restrict__ crank, int nrp,
-                               size_t piece, double* __restrict__ send) {
-  const int lj = blockIdx.y;
-  if (lj >= nc) return;
-  const int gj = bc_l2g(lj, nb, Py, py);
-  const int qy = gj % Py;
-  const int pc = crank[lj];
-  for (int li = blockIdx.x * blockDim.x + threadIdx.x; li < nr; li += gridDim.x * blockDim.x) {
-    const int gi = bc_l2g(li, nb, Px, px);
-    const int qx = gi % Px;
-    const int dst = row_major ? qx * Py + qy : qx + qy * Px;
-    send[(size_t)dst * piece + (size_t)pc * nrp + rrank[li]] = a[(size_t)lj * lda + li];
-  }
-}
-__global__ void bc_unpack_kernel(const double* __restrict__ recv, size_t piece, int nrp, int clr, int clc, int Px, int Py,
-                                 int row_major, const int* __restrict__ srcx, const int* __restrict__ posr,
-                                 const int* __restrict__ srcy, const int* __restrict__ posc, double* __restrict__ out, int ldo) {
-  const int lj = blockIdx.y;
-  if (lj >= clc) return;
-  const int sy = srcy[lj], pc = posc[lj];
-  for (int li = blockIdx.x * blockDim.x + threadIdx.x; li < clr; li += gridDim.x * blockDim.x) {
-    const int sx = srcx[li];
-    const int src = row_major ? sx * Py + sy : sx + sy * Px;
-    out[(size_t)lj * ldo + li] = __hip_atomic_load(recv + (size_t)src * piece + (size_t)pc * nrp + posr[li], __ATOMIC_RELAXED,
-                                                   __HIP_MEMORY_SCOPE_SYSTEM);
-  }
-}
-
-// one dimension of the index tables: n indices dealt in blocks of nb to P processes (me = p) -> cyclic over the same P
-static void bc_tables_1d(int n, int nb, int P, int p, std::vector<int>& rank_of_local, std::vector<int>& src_of_cyc,
-                         std::vector<int>& pos_of_cyc, int& max_piece) {
-  const int nl = numroc(n, nb, p, P);
-  rank_of_local.assign(nl > 0 ? nl : 1, 0);
-  std::vector<int> cnt(P, 0);
-  for (int l = 0; l < nl; ++l) {                       // my block-cyclic indices in ascending local order
-    const int g = ((l / nb) * P + p) * nb + l % nb;
-    rank_of_local[l] = cnt[g % P]++;
-  }
-  // what I receive as cyclic owner p: my cyclic index c is global g = c*P + p, held by block-cyclic process (g/nb) % P
-  // at the rank it has among THAT process's indices going to me
-  const int nc = local_count(n, P, p);
-  src_of_cyc.assign(nc > 0 ? nc : 1, 0);
-  pos_of_cyc.assign(nc > 0 ? nc : 1, 0);
-  std::vector<int> seen(P, 0);
-  for (int c = 0; c < nc; ++c) {                       // ascending global order = ascending local order on every sender
-    const int g = c * P + p;
-    const int s = (g / nb) % P;
-    src_of_cyc[c] = s;
-    pos_of_cyc[c] = seen[s]++;
-  }
-  max_piece = 0;
-  for (int q = 0; q < P; ++q) { if (cnt[q] > max_piece) max_piece = cnt[q]; if (seen[q] > max_piece) max_piece = seen[q]; }
-}
-
-static int bc_to_cyclic(Context& ctx, const double* a, int lda, int n, int nb, double* out, int ldo, hipStream_t st) {
-  const Grid& G = ctx.grid;
-  const int P = G.nranks;
-  std::vector<int> rrank, srcx, posr, crank, srcy, posc;
-  int mr = 0, mc = 0;
-  bc_tables_1d(n, nb, G.Px, G.px, rrank, srcx, posr, mr);
-  bc_tables_1d(n, nb, G.Py, G.py, crank, srcy, posc, mc);
-  // the piece extents must agree on every rank: an upper bound that depends on (n, nb, grid) only
-  // (every block of a sender starts at the same residue mod P, so one destination can get ceil(nb/P) rows of EVERY block)
-  const int nrp = (numroc(n, nb, 0, G.Px) / nb + 1) * ceil_div(nb, G.Px), ncp = (numroc(n, nb, 0, G.Py) / nb + 1) * ceil_div(nb, G.Py);
-  if (mr > nrp || mc > ncp) {   // cannot happen (see the bound above); refuse rather than write past a piece
-    fprintf(stderr, "[eigx] internal: block-cyclic piece bound violated (%d > %d or %d > %d)\n", mr, nrp, mc, ncp);
-    return EIGX_ERR_INTERNAL;
-  }
-  const size_t piece = (size_t)nrp * ncp;
-  const int nr = numroc(n, nb, G.px, G.Px), nc = numroc(n, nb, G.py, G.Py);
-  const int clr = local_count(n, G.Px, G.px), clc = local_count(n, G.Py, G.py);
-  const size_t nt = rrank.size() + srcx.size() + posr.size() + crank.size() + srcy.size() + posc.size();
-  int* tab = ctx.pool.get_t<int>("mg.bctab", nt);
-  int* htab = (int*)ctx.pool.get_host("mg.bctab", nt * sizeof(int));
-  size_t o = 0;
-  auto put = [&](const std::vector<int>& v) { int* d = tab + o; memcpy(htab + o, v.data(), v.size() * sizeof(int)); o += v.size(); return d; };
-  const int* d_rrank = put(rrank); const int* d_srcx = put(srcx); const int* d_posr = put(posr);
-  const int* d_crank = put(crank); const int* d_srcy = put(srcy); const int* d_posc = put(posc);
-  EIGX_HIP_CHECK(hipMemcpyAsync(tab, htab, nt * sizeof(int), hipMemcpyHostToDevice, st));
-  double* sendb = ctx.pool.get_t<double>("mg.xsend", piece * P);
-  double* recvb = ctx.pool.get_t<double>("mg.xrecv", piece * P);
-  if (nr > 0 && nc > 0)
-    hipLaunchKernelGGL(bc_pack_kernel, dim3(8, nc), dim3(256), 0, st, a, lda, nr, nc, nb, G.Px, G.px, G.Py, G.py, G.row_major,
-                       d_rrank, d_crank, nrp, piece, sendb);
-  comm_exchange_big(ctx, COMM_WORLD, sendb, piece, recvb, piece, st);
-  if (clr > 0 && clc > 0)
-    hipLaunchKernelGGL(bc_unpack_kernel, dim3(8, clc), dim3(256), 0, st, (const double*)recvb, piece, nrp, clr, clc, G.Px,
-                       G.Py, G.row_major, d_srcx, d_posr, d_srcy, d_posc, out, ldo);
-  EIGX_HIP_CHECK(hipStreamSynchronize(st));   // the pinned table staging buffer is reused by the next call
-  return EIGX_OK;
-}
-
 }  // namespace
-
-// Eigenvector column blocks (rank r holds columns [r zc, r zc + zc) of the first nvec, all n rows: zcols(ldz, zcnt) are
-// mine, starting at global column zc0) -> the callers' 2-D (block-)cyclic blocks: one all-to-all of
-// (rows of qx) x (my columns of qy) pieces.  Enqueued on st.  (eigen_h's split planes go through it one plane at a time.)
-void cols_to_cyclic_dev(Context& ctx, int n, int nvec, int nb, int zc, int zc0, int zcnt, const double* zcols, int ldz,
-                        double* z_user, int ldz_user, hipStream_t st) {
-  const Grid& G = ctx.grid;
-  const int P = G.nranks;
-  const int nloc_r = numroc(n, nb, G.px, G.Px);
-  const int nrmax = numroc(n, nb, 0, G.Px);
-  const int ncmax = (zc / (nb * G.Py) + 2) * nb;
-  const size_t piece = (size_t)nrmax * ncmax;
-  double* sendb = ctx.pool.get_t<double>("mg.xsend", piece * P);
-  double* recvb = ctx.pool.get_t<double>("mg.xrecv", piece * P);
-  if (zcnt > 0)
-    hipLaunchKernelGGL(pack_z_pieces_kernel, dim3(8, zcnt, G.Px), dim3(256), 0, st, zcols, ldz, n, zc0, zcnt, nb, G.Px,
-                       G.Py, G.row_major, nrmax, piece, sendb);
-  comm_exchange_big(ctx, COMM_WORLD, sendb, piece, recvb, piece, st);
-  if (nloc_r > 0)
-    hipLaunchKernelGGL(unpack_z_pieces_kernel, dim3(8, ncmax, P), dim3(256), 0, st, (const double*)recvb, piece, nrmax,
-                       nvec, zc, nb, G.py, G.Py, nloc_r, z_user, ldz_user);
-}
 
 __global__ void fill_kernel(double* p, size_t n, double v) {
   for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) p[i] = v;
@@ -288,6 +121,7 @@ int eigen_scaling(Context& ctx, const double* a, int lda, bool cplx, int n, doub
   // to RMIN/RMAX ~ 1e-146/1e+146.  This implementation forms reflector quantities that are cubic in the
   // matrix scale (u^T A u with un-normalised u), so its safe range is narrower and the target is O(1):
   // outside [1e-90, 1e90] the matrix is scaled by the exact power of two nearest to 1/max|a|.
+  if (!sigma) return EIGX_OK;   // the caller only wanted the scan
   *sigma = 1.0;
   if (anrm > 0.0 && (anrm < 1e-90 || anrm > 1e90)) {
     int ex = 0;
@@ -308,6 +142,16 @@ void* host_to_dev(Context& ctx, const char* name, const void* h, int ld, int nr,
 void dev_to_host(void* h, int ld, const void* d, int ldd, int nr, int nc, int esz) {
   if (nr > 0 && nc > 0)
     EIGX_HIP_CHECK(hipMemcpy2D(h, (size_t)ld * esz, d, (size_t)ldd * esz, (size_t)nr * esz, (size_t)nc, hipMemcpyDeviceToHost));
+}
+
+HostStage::HostStage(Context& ctx, int esz_, int nr_, int nc, const void* a_h, int lda, const void* b_h, int ldb, int zcols, int nw)
+    : esz(esz_), nr(nr_), ldd(host_ld(nr_)) {
+  EIGX_HIP_CHECK(hipSetDevice(ctx.device));
+  const bool cx = esz == 16;
+  a = (double*)host_to_dev(ctx, cx ? "host.ha" : "host.a", a_h, lda, nr, nc, esz);
+  if (b_h) b = (double*)host_to_dev(ctx, cx ? "host.hb" : "host.b", b_h, ldb, nr, nc, esz);
+  z = (double*)host_to_dev(ctx, cx ? "host.hz" : "host.z", nullptr, 0, nr, zcols, esz);
+  w = ctx.pool.get_t<double>("host.w", (size_t)nw);
 }
 
 // ---- the solve frame (eigx_context.h) ---------------------------------------------------------------------------------
@@ -422,25 +266,6 @@ __global__ void copy_vec_kernel(const double* __restrict__ src, double* __restri
   if (i < n) dst[i] = src[i];
 }
 
-// what both entry points of the range solves require of their arguments (mode in upper case).  By value: vl < vu (a NaN
-// fails it), room for at least one eigenpair unless only the count is asked for (mode 'C', value form only: w and z are
-// not used), and somewhere to put m and il.
-static bool range_args_ok(int n, const RangeWindow& W, const double* a, int lda, const double* w, const double* z, int ldz,
-                          char mode) {
-  if (n <= 0 || !a || lda < n) return false;
-  if (W.by_value) {
-    if (!(W.vl < W.vu) || !W.m_out || !W.il_out || (mode != 'A' && mode != 'N' && mode != 'C')) return false;
-    if (mode == 'C') return true;
-    if (W.mmax < 1 || !w) return false;
-  } else {
-    if (W.il < 1 || W.iu > n || W.il > W.iu || (mode != 'A' && mode != 'N') || !w) return false;
-  }
-  return mode == 'N' || (z && ldz >= n);
-}
-// entries of w that a range call may write (NaN on a non-finite input), eigenvector columns it may ask room for
-static int range_w_cap(const RangeWindow& W, char mode) { return (W.by_value && mode == 'C') ? 0 : W.m(); }
-static int range_z_cap(int n, const RangeWindow& W, char mode) { return std::max(1, std::min(n, range_w_cap(W, mode))); }
-
 // ---- value window -> index window (EXTENSION) ------------------------------------------------------------------------------
 // The eigenvalues with vl <= lambda < vu of the matrix whose band form (d, e) is sigma times the caller's: il = count(sigma vl)
 // + 1, iu = count(sigma vu), count(x) = eigenvalues below x by band_count_dev.  The pentadiagonal count is not strictly
@@ -469,6 +294,27 @@ static void resolve_value_window(Context& ctx, int n, const double* d, const dou
   *W.il_out = W.il;
 }
 
+}  // namespace
+
+// what both entry points of the range solves require of their arguments (mode in upper case).  By value: vl < vu (a NaN
+// fails it), room for at least one eigenpair unless only the count is asked for (mode 'C', value form only: w and z are
+// not used), and somewhere to put m and il.
+bool range_args_ok(int n, const RangeWindow& W, const double* a, int lda, const double* w, const double* z, int ldz, char mode) {
+  if (n <= 0 || !a || lda < n) return false;
+  if (W.by_value) {
+    if (!(W.vl < W.vu) || !W.m_out || !W.il_out || (mode != 'A' && mode != 'N' && mode != 'C')) return false;
+    if (mode == 'C') return true;
+    if (W.mmax < 1 || !w) return false;
+  } else {
+    if (W.il < 1 || W.iu > n || W.il > W.iu || (mode != 'A' && mode != 'N') || !w) return false;
+  }
+  return mode == 'N' || (z && ldz >= n);
+}
+int refuse_several_ranks(const Context& ctx) {
+  fprintf(stderr, "[eigx] index-range solves run on one GPU only (this grid has %d ranks)\n", ctx.grid.nranks);
+  return EIGX_ERR_BAD_ARG;
+}
+
 // ---- range solve: eigenpairs il .. iu (1-based, inclusive) of the ascending spectrum, one GPU ---------------------------
 // EXTENSION, not in the reference (whose nvec only trims the back-transformation, src/eigen_sx.F:200-240).
 //   scaling -> band reduction (as solve_dev) -> Sturm multi-section on the index window -> band_eigvec_dev (inverse
@@ -483,10 +329,7 @@ static void resolve_value_window(Context& ctx, int n, const double* d, const dou
 // only) stops there in every case.  From then on a value call runs the code of the index call il .. iu.
 int range_solve_dev(Context& ctx, int n, RangeWindow W, double* a, int lda, double* w, double* z, int ldz, int mf, int mb,
                     char mode, int band, bool fill_rest) {
-  if (ctx.initialized && ctx.grid.nranks != 1) {
-    fprintf(stderr, "[eigx] index-range solves run on one GPU only (this grid has %d ranks)\n", ctx.grid.nranks);
-    return EIGX_ERR_BAD_ARG;
-  }
+  if (ctx.initialized && ctx.grid.nranks != 1) return refuse_several_ranks(ctx);
   mode = upper_case(mode);
   SolveFrame F(ctx, n, false);
   if (const int rc = F.begin(range_args_ok(n, W, a, lda, w, z, ldz, mode))) return rc;
@@ -583,24 +426,20 @@ int range_solve_dev(Context& ctx, int n, RangeWindow W, double* a, int lda, doub
 
 // Host arrays.  By value: nothing is copied back into w or z on EIGX_ERR_WINDOW and on m = 0 (a non-finite input fills
 // w(1:mmax) with NaN); a gets its a(1:3,1) statistics whenever the call returns EIGX_OK.
-int range_solve_host(Context& ctx, int n, RangeWindow W, double* a, int lda, double* w, double* z, int ldz, int mf, int mb,
+static int range_solve_host(Context& ctx, int n, RangeWindow W, double* a, int lda, double* w, double* z, int ldz, int mf, int mb,
                      char mode, int band) {
   if (!ctx.initialized) return EIGX_ERR_NOT_INITIALIZED;
   if (ctx.grid.nranks != 1) return range_solve_dev(ctx, n, W, a, lda, w, z, ldz, mf, mb, mode, band, false);   // refuses
   mode = upper_case(mode);
   if (!range_args_ok(n, W, a, lda, w, z, ldz, mode)) return EIGX_ERR_BAD_ARG;
   const int wcap = range_w_cap(W, mode);
-  EIGX_HIP_CHECK(hipSetDevice(ctx.device));
-  const int ldd = host_ld(n);
-  double* ad = (double*)host_to_dev(ctx, "host.a", a, lda, n, n, 8);
-  double* zd = (double*)host_to_dev(ctx, "host.z", nullptr, 0, n, mode == 'A' ? range_z_cap(n, W, mode) : 1, 8);
-  double* wd = ctx.pool.get_t<double>("host.w", (size_t)std::max(wcap, 1));
-  const int rc = range_solve_dev(ctx, n, W, ad, ldd, wd, zd, ldd, mf, mb, mode, band, false);
+  const HostStage S(ctx, 8, n, n, a, lda, nullptr, 0, mode == 'A' ? range_z_cap(n, W, mode) : 1, std::max(wcap, 1));
+  const int rc = range_solve_dev(ctx, n, W, S.a, S.ldd, S.w, S.z, S.ldd, mf, mb, mode, band, false);
   const int m = (W.by_value && rc == EIGX_OK) ? (mode == 'C' ? 0 : *W.m_out) : wcap;   // entries that were written
-  if ((rc == EIGX_OK || rc == EIGX_ERR_NONFINITE) && m > 0) EIGX_HIP_CHECK(hipMemcpy(w, wd, (size_t)m * 8, hipMemcpyDeviceToHost));
+  if (rc == EIGX_OK || rc == EIGX_ERR_NONFINITE) S.w_back(w, m);
   if (rc != EIGX_OK) return rc;
-  if (mode == 'A' && m > 0) dev_to_host(z, ldz, zd, ldd, n, m, 8);
-  dev_to_host(a, lda, ad, ldd, std::min(n, 3), 1, 8);
+  if (mode == 'A') S.back(z, ldz, S.z, m);
+  S.back(a, lda, S.a, 1, std::min(n, 3));
   return EIGX_OK;
 }
 
@@ -684,412 +523,21 @@ int solve_dev(Context& ctx, int n, int nvec, double* a, int lda, double* w, doub
   return F.finish(w, n, ctx.timers[11], do_bt ? nvec : 0, nloc_c > 0 ? nloc_r : 0);
 }
 
-int solve_host(Context& ctx, int n, int nvec, double* a, int lda, double* w, double* z, int ldz, int mf, int mb,
+static int solve_host(Context& ctx, int n, int nvec, double* a, int lda, double* w, double* z, int ldz, int mf, int mb,
                char mode, int band, int nb) {
   if (!ctx.initialized) return EIGX_ERR_NOT_INITIALIZED;
   if (nb < 1) return EIGX_ERR_BAD_ARG;
   const int nr = numroc(n, nb, ctx.grid.px, ctx.grid.Px), nc = numroc(n, nb, ctx.grid.py, ctx.grid.Py);
   if (n <= 0 || !a || !w || lda < nr) return EIGX_ERR_BAD_ARG;
-  EIGX_HIP_CHECK(hipSetDevice(ctx.device));
-  const int ldd = host_ld(nr);
-  double* ad = (double*)host_to_dev(ctx, "host.a", a, lda, nr, nc, 8);
-  double* zd = (double*)host_to_dev(ctx, "host.z", nullptr, 0, nr, nc, 8);
-  double* wd = ctx.pool.get_t<double>("host.w", (size_t)n);
-  const int rc = solve_dev(ctx, n, nvec, ad, ldd, wd, zd, ldd, mf, mb, mode, band, nb);
-  EIGX_HIP_CHECK(hipMemcpy(w, wd, (size_t)n * 8, hipMemcpyDeviceToHost));
+  const HostStage S(ctx, 8, nr, nc, a, lda, nullptr, 0, nc, n);
+  const int rc = solve_dev(ctx, n, nvec, S.a, S.ldd, S.w, S.z, S.ldd, mf, mb, mode, band, nb);
+  S.w_back(w, n);
   if (rc != EIGX_OK) return rc;
   const SolveRequest rq = normalize_request(n, nvec, mode);
-  if (z && rq.want_vec) dev_to_host(z, ldz, zd, ldd, nr, numroc(rq.nvec, nb, ctx.grid.py, ctx.grid.Py), 8);
-  dev_to_host(a, lda, ad, ldd, nc > 0 ? std::min(nr, 3) : 0, 1, 8);   // `a` is destroyed by contract: only the statistics
+  if (z && rq.want_vec) S.back(z, ldz, S.z, numroc(rq.nvec, nb, ctx.grid.py, ctx.grid.Py));
+  S.back(a, lda, S.a, 1, nc > 0 ? std::min(nr, 3) : 0);   // `a` is destroyed by contract: only the statistics
   return EIGX_OK;
 }
-
-// ---- KMATH_EIGEN_GEV: generalised symmetric-definite problem A x = lambda B x -----------------------------
-// lower triangle := upper triangle (the GEMMs below need the full symmetric A; trpos_utol of the reference,
-// src/KMATH_EIGEN_GEV_misc.F:140-173)
-__global__ void symmetrize_kernel(double* __restrict__ a, int lda, int n) {
-  const int j = blockIdx.y;
-  for (int i = j + 1 + blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x)
-    a[(size_t)j * lda + i] = a[(size_t)i * lda + j];
-}
-
-// b(:, j) = z(:, j) * w(j)^(-1/2)   (diag_mult, src/KMATH_EIGEN_GEV_misc.F:49-104)
-__global__ void scale_cols_rsqrt_kernel(const double* __restrict__ z, int ldz, const double* __restrict__ w,
-                                        double* __restrict__ b, int ldb, int n) {
-  const int j = blockIdx.y;
-  const double s = 1.0 / sqrt(w[j]);
-  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x)
-    b[(size_t)j * ldb + i] = z[(size_t)j * ldz + i] * s;
-}
-
-
-}  // namespace
-
-// ---- multi-rank KMATH_EIGEN_GEV on the 2-D cyclic blocks -------------------------------------------------------------
-// (outside the anonymous namespace: hgev.hip builds the complex generalised solver from the same transpose and packing
-// kernels; declared in eigx_context.h)
-// Two building blocks, both O(n^2 / P) memory per rank:
-//   dist_transpose : Z = A^T.  Element A(j, i) lives on rank (j % Px, i % Py) and goes to rank (i % Px, j % Py): on a
-//                    non-square grid that is a genuine all-to-all.  The rows i that rank (px, .) receives from a source in
-//                    process column sy are the i = i0 + t L (L = lcm(Px, Py), i0 by the Chinese remainder theorem, none
-//                    if px != sy mod gcd); likewise the columns j = j0 + u L: a piece is the (t, u) rectangle, piece
-//                    [u][t].  (role of PDTRAN + trpos_utol, src/KMATH_EIGEN_GEV_1.F:57-58)
-//   dist_gemm_nn   : C = A B (SUMMA): for every panel of kb global indices k the ranks of a process ROW allgather their
-//                    columns of A(:, k-panel), the ranks of a process COLUMN their rows of B(k-panel, :), and the local
-//                    fp64 MFMA GEMM accumulates the panel product.  (role of the three PDGEMMs, :100-139)
-struct TrPeers { int i0[EIGX_MAXP], j0[EIGX_MAXP]; };   // per peer (world rank order): first row / column of the piece, -1 = empty
-// pack: piece for destination d, element [u][t] = A(j0 + u L, i0 + t L) of my block (row j, column i)
-__global__ void tr_pack_kernel(const double* __restrict__ a, int lda, int n, int Px, int Py, int L, TrPeers tp, int nimax,
-                               int u0, int ucw, double* __restrict__ send) {
-  const int d = blockIdx.z;
-  const int i0 = tp.i0[d], j0 = tp.j0[d];
-  for (int uu = blockIdx.y; uu < ucw; uu += gridDim.y) {
-    const int u = u0 + uu;
-    double* dst = send + ((size_t)d * ucw + uu) * nimax;
-    for (int t = blockIdx.x * blockDim.x + threadIdx.x; t < nimax; t += gridDim.x * blockDim.x) {
-      double v = 0.0;
-      if (i0 >= 0 && j0 >= 0) {
-        const int i = i0 + t * L, j = j0 + u * L;   // I hold row j (local j / Px), column i (local i / Py)
-        if (i < n && j < n) v = a[(size_t)(i / Py) * lda + j / Px];
-      }
-      dst[t] = v;
-    }
-  }
-}
-// unpack: Z(i, j) = piece from source s at [u][t]; I hold row i (local i / Px), column j (local j / Py)
-__global__ void tr_unpack_kernel(const double* __restrict__ recv, int n, int Px, int Py, int L, TrPeers tp, int nimax,
-                                 int u0, int ucw, double* __restrict__ z, int ldz) {
-  const int sidx = blockIdx.z;
-  const int i0 = tp.i0[sidx], j0 = tp.j0[sidx];
-  if (i0 < 0 || j0 < 0) return;
-  for (int uu = blockIdx.y; uu < ucw; uu += gridDim.y) {
-    const int u = u0 + uu;
-    const double* src = recv + ((size_t)sidx * ucw + uu) * nimax;
-    const int j = j0 + u * L;
-    if (j >= n) return;
-    for (int t = blockIdx.x * blockDim.x + threadIdx.x; t < nimax; t += gridDim.x * blockDim.x) {
-      const int i = i0 + t * L;
-      if (i < n) z[(size_t)(j / Py) * ldz + i / Px] = __hip_atomic_load(src + t, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-    }
-  }
-}
-static int crt_small(int a, int A_, int b, int B_, int L) {   // smallest x < L with x % A_ == a and x % B_ == b, -1 if none
-  for (int x = 0; x < L; ++x)
-    if (x % A_ == a && x % B_ == b) return x;
-  return -1;
-}
-static int gcd_int(int a, int b) { while (b) { const int t = a % b; a = b; b = t; } return a; }
-// the pieces rank (px, py) exchanges with rank (qx, qy) in Z = A^T (pure arithmetic; eigx_transpose_plan exposes it to the
-// CPU tests, which assemble A^T from the pieces for every grid)
-static void transpose_plan(int Px, int Py, int px, int py, int qx, int qy, int* send_i0, int* send_j0, int* recv_i0,
-                           int* recv_j0, int* step) {
-  const int L = Px / gcd_int(Px, Py) * Py;
-  // to (qx, qy): its rows i (i % Px == qx) among my columns (i % Py == py); its columns j (j % Py == qy) among my rows
-  *send_i0 = crt_small(qx, Px, py, Py, L);
-  *send_j0 = crt_small(px, Px, qy, Py, L);
-  // from (qx, qy): my rows i (i % Px == px) among its columns (i % Py == qy); my columns j (j % Py == py) among its rows
-  *recv_i0 = crt_small(px, Px, qy, Py, L);
-  *recv_j0 = crt_small(qx, Px, py, Py, L);
-  *step = L;
-}
-
-// z(ldz, nc) = (a(lda, nc))^T on the cyclic blocks (both n x n); enqueued on st.  The all-to-all's pieces are uniform, and
-// only gcd(Px, Py)^-2 of the rank pairs exchange anything, so the exchange runs in rounds over the pieces' columns u that
-// keep the send + receive buffers (pool entries `tag`.tsend / `tag`.trecv) at about one local block each.
-void dist_transpose(Context& ctx, int n, const double* a, int lda, double* z, int ldz, hipStream_t st, const char* tag) {
-  const Grid& G = ctx.grid;
-  const int g = gcd_int(G.Px, G.Py);
-  const int P = G.nranks, L = G.Px / g * G.Py;
-  const int nimax = ceil_div(n, L);
-  const int ucw = ceil_div(nimax, g * g);                      // piece columns per round
-  const size_t count = (size_t)nimax * ucw;
-  double* sendb = ctx.pool.get_t<double>(std::string(tag) + ".tsend", count * P);
-  double* recvb = ctx.pool.get_t<double>(std::string(tag) + ".trecv", count * P);
-  TrPeers to, from;
-  for (int q = 0; q < P; ++q) {
-    const int qx = G.row_major ? q / G.Py : q % G.Px, qy = G.row_major ? q % G.Py : q / G.Px;
-    int step_;
-    transpose_plan(G.Px, G.Py, G.px, G.py, qx, qy, &to.i0[q], &to.j0[q], &from.i0[q], &from.j0[q], &step_);
-  }
-  const int gy = ucw < 32768 ? ucw : 32768;
-  for (int u0 = 0; u0 < nimax; u0 += ucw) {
-    hipLaunchKernelGGL(tr_pack_kernel, dim3(ceil_div(nimax, 256), gy, P), dim3(256), 0, st, a, lda, n, G.Px, G.Py, L, to, nimax, u0,
-                       ucw, sendb);
-    comm_exchange_big(ctx, COMM_WORLD, sendb, count, recvb, count, st);
-    hipLaunchKernelGGL(tr_unpack_kernel, dim3(ceil_div(nimax, 256), gy, P), dim3(256), 0, st, (const double*)recvb, n, G.Px, G.Py, L,
-                       from, nimax, u0, ucw, z, ldz);
-  }
-}
-
-// a(i, j) for i > j (global indices) from t = a^T: the full symmetric matrix out of its upper triangle
-__global__ void sym_merge_kernel(double* __restrict__ a, int lda, const double* __restrict__ t, int ldt, int nr, int Px, int px,
-                                 int Py, int py) {
-  const int lc = blockIdx.y, gj = lc * Py + py;
-  for (int lr = blockIdx.x * blockDim.x + threadIdx.x; lr < nr; lr += gridDim.x * blockDim.x)
-    if (lr * Px + px > gj) a[(size_t)lc * lda + lr] = t[(size_t)lc * ldt + lr];
-}
-// b(:, lc) = z(:, lc) * w(global column)^(-1/2) on the local block   (diag_mult, src/KMATH_EIGEN_GEV_misc.F:49-104)
-__global__ void scale_cols_rsqrt_cyclic_kernel(const double* __restrict__ z, int ldz, const double* __restrict__ w,
-                                               double* __restrict__ b, int ldb, int nr, int Py, int py) {
-  const int lc = blockIdx.y;
-  const double sc = 1.0 / sqrt(w[lc * Py + py]);
-  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < nr; i += gridDim.x * blockDim.x)
-    b[(size_t)lc * ldb + i] = z[(size_t)lc * ldz + i] * sc;
-}
-// SUMMA panels.  A side: my columns lc0 .. lc0 + kbl - 1 of the panel, rows padded to nrp: out[c * nrp + r]
-__global__ void mm_pack_a_kernel(const double* __restrict__ a, int lda, int nr, int nc, int lc0, int nrp, double* __restrict__ out) {
-  const int c = blockIdx.y, lc = lc0 + c;
-  for (int r = blockIdx.x * blockDim.x + threadIdx.x; r < nrp; r += gridDim.x * blockDim.x)
-    out[(size_t)c * nrp + r] = (r < nr && lc < nc) ? a[(size_t)lc * lda + r] : 0.0;
-}
-// B side: my rows lr0 .. lr0 + kbl - 1 of the panel for every local column j: out[j * kbl + rr]
-__global__ void mm_pack_b_kernel(const double* __restrict__ b, int ldb, int nr, int nc, int lr0, int kbl, double* __restrict__ out) {
-  const int j = blockIdx.y;
-  for (int rr = blockIdx.x * blockDim.x + threadIdx.x; rr < kbl; rr += gridDim.x * blockDim.x)
-    out[(size_t)j * kbl + rr] = (j < nc && lr0 + rr < nr) ? b[(size_t)j * ldb + lr0 + rr] : 0.0;
-}
-// gathered B rows [q'][j][rr] (k = k0 + rr Px + q') -> panel matrix Bp(pos, j) in the k order of the gathered A columns:
-// k - k0 = c Py + q  ->  pos = q kbl_y + c
-__global__ void mm_unpack_b_kernel(const double* __restrict__ recv, int Px, int Py, int kbl_x, int kbl_y, int ncp, int kb,
-                                   double* __restrict__ Bp) {
-  const int j = blockIdx.y, q = blockIdx.z;
-  for (int rr = blockIdx.x * blockDim.x + threadIdx.x; rr < kbl_x; rr += gridDim.x * blockDim.x) {
-    const int dk = rr * Px + q;
-    Bp[(size_t)j * kb + (size_t)(dk % Py) * kbl_y + dk / Py] = recv[((size_t)q * ncp + j) * kbl_x + rr];
-  }
-}
-
-namespace {
-
-// C(ldc, nc) = A B on the cyclic blocks (all n x n, A and B complete -- not triangles); synchronous
-static int dist_gemm_nn(Context& ctx, int n, const double* A, int lda, const double* B, int ldb, double* C, int ldc) {
-  const Grid& G = ctx.grid;
-  hipStream_t st = ctx.stream;
-  const int nr = local_count(n, G.Px, G.px), nc = local_count(n, G.Py, G.py);
-  const int L = G.Px / gcd_int(G.Px, G.Py) * G.Py;
-  const int unit = 2 * L;                                    // panels start at multiples of Px and Py; even widths
-  // panel width: about n / 8 between 128 and 1024 (the panels are O(n kb / sqrt(P)) of workspace)
-  const int kb_want = (n / 8 < 128) ? (n < 128 ? n : 128) : (n / 8 > 1024 ? 1024 : n / 8);
-  const int kb = unit * ceil_div(kb_want, unit);
-  const int kbl_x = kb / G.Px, kbl_y = kb / G.Py;
-  const int nrp = ((nr > 2 ? nr : 2) + 1) & ~1, ncp = nc > 1 ? nc : 1;
-  double* sendA = ctx.pool.get_t<double>("gev.sa", (size_t)nrp * kbl_y);
-  double* Ap = ctx.pool.get_t<double>("gev.pa", (size_t)nrp * kb);
-  double* sendB = ctx.pool.get_t<double>("gev.sb", (size_t)kbl_x * ncp);
-  double* recvB = ctx.pool.get_t<double>("gev.rb", (size_t)kb * ncp);
-  double* Bp = ctx.pool.get_t<double>("gev.pb", (size_t)kb * ncp);
-  for (int k0 = 0; k0 < n; k0 += kb) {
-    hipLaunchKernelGGL(mm_pack_a_kernel, dim3(ceil_div(nrp, 256), kbl_y), dim3(256), 0, st, A, lda, nr, nc, k0 / G.Py, nrp, sendA);
-    comm_allgather(ctx, COMM_Y, sendA, Ap, (size_t)nrp * kbl_y, st);          // Ap(:, q kbl_y + c) = A(my rows, k0 + c Py + q)
-    hipLaunchKernelGGL(mm_pack_b_kernel, dim3(ceil_div(kbl_x, 256), ncp), dim3(256), 0, st, B, ldb, nr, nc, k0 / G.Px, kbl_x, sendB);
-    comm_allgather(ctx, COMM_X, sendB, recvB, (size_t)kbl_x * ncp, st);
-    hipLaunchKernelGGL(mm_unpack_b_kernel, dim3(ceil_div(kbl_x, 256), ncp, G.Px), dim3(256), 0, st, (const double*)recvB, G.Px, G.Py,
-                       kbl_x, kbl_y, ncp, kb, Bp);
-    if (nr > 0 && nc > 0) dgemm_dev(st, 'N', 'N', nr, nc, kb, 1.0, Ap, nrp, Bp, kb, k0 == 0 ? 0.0 : 1.0, C, ldc);
-  }
-  EIGX_HIP_CHECK(hipStreamSynchronize(st));
-  return comm_failed(ctx) ? EIGX_ERR_INTERNAL : EIGX_OK;
-}
-
-// Same sequence as KMATH_EIGEN_GEV_1 (src/KMATH_EIGEN_GEV_1.F:57-139): eigen_s(B, 'X') -> B^(-1/2) := Z_B W_B^(-1/2);
-// A' = B^(-1/2)^T A B^(-1/2) by two GEMMs; eigen_s(A', 'X') -> w, Y; Z = B^(-1/2) Y (B-orthonormal).  On entry only
-// the upper triangles of a and b are significant; a, b are destroyed (a holds Y, b holds B^(-1/2) on exit, as in
-// the reference).  One GPU; all three products run on the fp64 MFMA GEMM.
-int gev_dev(Context& ctx, int n, double* a, int lda, double* b, int ldb, double* w, double* z, int ldz);
-
-// Several ranks: the same sequence on the 2-D cyclic blocks, nothing gathered -- two distributed eigen_s solves, the
-// symmetrisation of A and the transposed factor by dist_transpose, three SUMMA products with local MFMA GEMMs
-// (round 4; the first version gathered A and B on every rank).
-static int gev_dev_mg(Context& ctx, int n, double* a, int lda, double* b, int ldb, double* w, double* z, int ldz) {
-  const Grid G = ctx.grid;
-  const int nr = local_count(n, G.Px, G.px), nc = local_count(n, G.Py, G.py);
-  if (n <= 0 || !a || !b || !w || !z || lda < (nr > 1 ? nr : 1) || ldb < (nr > 1 ? nr : 1) || ldz < (nr > 1 ? nr : 1))
-    return EIGX_ERR_BAD_ARG;
-  EIGX_HIP_CHECK(hipSetDevice(ctx.device));
-  EIGX_HIP_CHECK(hipStreamSynchronize(nullptr));
-  hipStream_t st = ctx.stream;
-  const double t0 = now_s();
-  const int ldt = pad_ld((nr > 2 ? nr : 2));
-  const int ncd = nc > 0 ? nc : 1;
-  double* tb = ctx.pool.get_t<double>("gev.t", (size_t)ldt * ncd);    // A^T, later (B^(-1/2))^T
-  double* cb = ctx.pool.get_t<double>("gev.c", (size_t)ldt * ncd);    // C = A B^(-1/2)
-  dist_transpose(ctx, n, a, lda, tb, ldt, st);
-  if (nr > 0 && nc > 0)
-    hipLaunchKernelGGL(sym_merge_kernel, dim3(ceil_div(nr, 256), nc), dim3(256), 0, st, a, lda, (const double*)tb, ldt, nr, G.Px, G.px,
-                       G.Py, G.py);
-  EIGX_HIP_CHECK(hipStreamSynchronize(st));
-  if (comm_failed(ctx)) return EIGX_ERR_INTERNAL;
-  int rc = solve_dev(ctx, n, n, b, ldb, w, z, ldz, 128, 128, 'X', 1, 1);      // B = Z_B W_B Z_B^T
-  if (rc != EIGX_OK) return rc;
-  const double t1 = now_s();
-  double wmin = 0.0;
-  EIGX_HIP_CHECK(hipMemcpy(&wmin, w, 8, hipMemcpyDeviceToHost));
-  if (!(wmin > 0.0)) {   // w is replicated bit for bit: every rank takes the same way out
-    if (G.rank == 0) fprintf(stderr, "[eigx] Matrix B is not positive definite!\n");            // src/KMATH_EIGEN_GEV_1.F:75-80
-    return EIGX_ERR_NOT_SPD;
-  }
-  if (nr > 0 && nc > 0)
-    hipLaunchKernelGGL(scale_cols_rsqrt_cyclic_kernel, dim3(ceil_div(nr, 256), nc), dim3(256), 0, st, (const double*)z, ldz,
-                       (const double*)w, b, ldb, nr, G.Py, G.py);
-  rc = dist_gemm_nn(ctx, n, a, lda, b, ldb, cb, ldt);                          // C  = A B^(-1/2)
-  if (rc != EIGX_OK) return rc;
-  dist_transpose(ctx, n, b, ldb, tb, ldt, st);                                 // (B^(-1/2))^T
-  rc = dist_gemm_nn(ctx, n, tb, ldt, cb, ldt, z, ldz);                         // A' = B^(-1/2)^T C
-  if (rc != EIGX_OK) return rc;
-  const double t2 = now_s();
-  rc = solve_dev(ctx, n, n, z, ldz, w, a, lda, 128, 128, 'X', 1, 1);            // A' = Y W Y^T, Y in a
-  if (rc != EIGX_OK) return rc;
-  const double t3 = now_s();
-  rc = dist_gemm_nn(ctx, n, b, ldb, a, lda, z, ldz);                           // Z = B^(-1/2) Y
-  if (rc != EIGX_OK) return rc;
-  const double t4 = now_s();
-  ctx.timers[0] = t4 - t0; ctx.timers[1] = t1 - t0; ctx.timers[2] = t2 - t1; ctx.timers[3] = t3 - t2; ctx.timers[4] = t4 - t3;
-  return EIGX_OK;
-}
-
-int gev_dev(Context& ctx, int n, double* a, int lda, double* b, int ldb, double* w, double* z, int ldz) {
-  if (!ctx.initialized) return EIGX_ERR_NOT_INITIALIZED;
-  if (ctx.grid.nranks != 1) return gev_dev_mg(ctx, n, a, lda, b, ldb, w, z, ldz);
-  if (n <= 0 || !a || !b || !w || !z || lda < n || ldb < n || ldz < n || ((lda | ldb | ldz) & 1)) return EIGX_ERR_BAD_ARG;
-  EIGX_HIP_CHECK(hipSetDevice(ctx.device));
-  EIGX_HIP_CHECK(hipStreamSynchronize(nullptr));
-  hipStream_t st = ctx.stream;
-  const double t0 = now_s();
-  hipLaunchKernelGGL(symmetrize_kernel, dim3(8, n), dim3(256), 0, st, a, lda, n);
-  int rc = solve_dev(ctx, n, n, b, ldb, w, z, ldz, 128, 128, 'X', 1, 1);      // B = Z_B W_B Z_B^T
-  if (rc != EIGX_OK) return rc;
-  const double t1 = now_s();
-  double wmin = 0.0;
-  EIGX_HIP_CHECK(hipMemcpy(&wmin, w, 8, hipMemcpyDeviceToHost));
-  if (!(wmin > 0.0)) {
-    fprintf(stderr, "[eigx] Matrix B is not positive definite!\n");            // src/KMATH_EIGEN_GEV_1.F:75-80
-    return EIGX_ERR_NOT_SPD;
-  }
-  hipLaunchKernelGGL(scale_cols_rsqrt_kernel, dim3(8, n), dim3(256), 0, st, z, ldz, w, b, ldb, n);
-  const int ldc = pad_ld(n);
-  double* c = ctx.pool.get_t<double>("gev.c", (size_t)ldc * n);
-  dgemm_dev(st, 'N', 'N', n, n, n, 1.0, a, lda, b, ldb, 0.0, c, ldc);          // C  = A B^(-1/2)
-  dgemm_dev(st, 'T', 'N', n, n, n, 1.0, b, ldb, c, ldc, 0.0, z, ldz);          // A' = B^(-1/2)^T C
-  EIGX_HIP_CHECK(hipStreamSynchronize(st));
-  const double t2 = now_s();
-  rc = solve_dev(ctx, n, n, z, ldz, w, a, lda, 128, 128, 'X', 1, 1);            // A' = Y W Y^T, Y in a
-  if (rc != EIGX_OK) return rc;
-  const double t3 = now_s();
-  dgemm_dev(st, 'N', 'N', n, n, n, 1.0, b, ldb, a, lda, 0.0, z, ldz);          // Z = B^(-1/2) Y
-  EIGX_HIP_CHECK(hipStreamSynchronize(st));
-  const double t4 = now_s();
-  ctx.timers[0] = t4 - t0; ctx.timers[1] = t1 - t0; ctx.timers[2] = t2 - t1; ctx.timers[3] = t3 - t2; ctx.timers[4] = t4 - t3;
-  return EIGX_OK;
-}
-
-int gev_host(Context& ctx, int n, double* a, int lda, double* b, int ldb, double* w, double* z, int ldz) {
-  if (!ctx.initialized) return EIGX_ERR_NOT_INITIALIZED;
-  // host arrays: the rank's 2-D cyclic blocks a(lda, *), b(ldb, *), z(ldz, *) (one rank: the whole matrices)
-  const int nr = local_count(n, ctx.grid.Px, ctx.grid.px), nc = local_count(n, ctx.grid.Py, ctx.grid.py);
-  if (n <= 0 || !a || !b || !w || !z || lda < nr || ldb < nr || ldz < nr) return EIGX_ERR_BAD_ARG;
-  EIGX_HIP_CHECK(hipSetDevice(ctx.device));
-  const int ldd = host_ld(nr);
-  double* ad = (double*)host_to_dev(ctx, "host.a", a, lda, nr, nc, 8);
-  double* bd = (double*)host_to_dev(ctx, "host.b", b, ldb, nr, nc, 8);
-  double* zd = (double*)host_to_dev(ctx, "host.z", nullptr, 0, nr, nc, 8);
-  double* wd = ctx.pool.get_t<double>("host.w", (size_t)n);
-  const int rc = gev_dev(ctx, n, ad, ldd, bd, ldd, wd, zd, ldd);
-  if (rc != EIGX_OK) return rc;
-  EIGX_HIP_CHECK(hipMemcpy(w, wd, (size_t)n * 8, hipMemcpyDeviceToHost));
-  dev_to_host(z, ldz, zd, ldd, nr, nc, 8);
-  dev_to_host(a, lda, ad, ldd, nr, nc, 8);
-  dev_to_host(b, ldb, bd, ldd, nr, nc, 8);
-  return EIGX_OK;
-}
-
-// ---- KMATH_EIGEN_GEV_RANGE: eigenpairs il .. iu of A x = lambda B x by the Cholesky route (EXTENSION, one GPU) ----------
-// B = U^T U (tri.hip) -> C = U^-T A U^-1 -> range_solve_dev(C, il, iu) on the eigen_sx route -> Z = U^-1 Y on the m
-// columns.  n^3 / 3 + 2 n^3 + n^2 m flops through the MFMA GEMM where KMATH_EIGEN_GEV spends a whole eigen_s of B and
-// 6 n^3.  B is not scaled: U carries sqrt of B's scale, C its inverse, and a B near the ends of the fp64 range
-// overflows there (range_solve_dev scales C itself, but only once it has been formed).
-
-// upper(c) = U^-T A U^-1 (below the diagonal c is unspecified); a is overwritten.  a: upper triangle significant.
-// 5/3 n^3 flops: a <- U^-T sym(a), c = a^T, c <- U^-T c on the block columns that reach the upper triangle.
-void gev_reduce_dev(Context& ctx, int n, double* a, int lda, const double* u, int ldu, const TriInv& V, double* c, int ldc) {
-  hipStream_t st = ctx.stream;
-  hipLaunchKernelGGL(symmetrize_kernel, dim3(8, n), dim3(256), 0, st, a, lda, n);
-  trsm_upper_dev(ctx, 'T', n, n, u, ldu, a, lda, V);
-  transpose_dev(st, n, a, lda, c, ldc);
-  trsm_upper_dev(ctx, 'T', n, n, u, ldu, c, ldc, V, true);   // the solvers read the upper triangle only
-}
-
-// W by value: the window goes to range_solve_dev on C as it is (B is not scaled, so the eigenvalues of C are the
-// generalised ones; range_solve_dev applies its own sigma of C), m is read back for the back-substitution.
-int gev_range_dev(Context& ctx, int n, RangeWindow W, double* a, int lda, double* b, int ldb, double* w, double* z, int ldz,
-                  char mode) {
-  if (!ctx.initialized) return EIGX_ERR_NOT_INITIALIZED;
-  if (ctx.grid.nranks != 1) {
-    fprintf(stderr, "[eigx] index-range solves run on one GPU only (this grid has %d ranks)\n", ctx.grid.nranks);
-    return EIGX_ERR_BAD_ARG;
-  }
-  mode = upper_case(mode);
-  if (!range_args_ok(n, W, a, lda, w, z, ldz, mode) || !b || ldb < n || ((lda | ldb) & 1) || (mode == 'A' && (ldz & 1)))
-    return EIGX_ERR_BAD_ARG;
-  EIGX_HIP_CHECK(hipSetDevice(ctx.device));
-  EIGX_HIP_CHECK(hipStreamSynchronize(nullptr));
-  hipStream_t st = ctx.stream;
-  const int wcap = range_w_cap(W, mode);
-  const double t0 = now_s();
-  // both significant triangles are scanned before anything is factored; the scale factors are not used
-  double sigma = 1.0;
-  int rc = eigen_scaling(ctx, a, lda, false, n, w, &sigma, wcap);
-  if (rc == EIGX_OK) rc = eigen_scaling(ctx, b, ldb, false, n, w, &sigma, wcap);
-  if (rc != EIGX_OK) {
-    if (W.by_value) *W.m_out = 0;
-    return rc;
-  }
-  if (chol_upper_dev(ctx, n, b, ldb) != EIGX_OK) {
-    fprintf(stderr, "[eigx] Matrix B is not positive definite!\n");
-    return EIGX_ERR_NOT_SPD;
-  }
-  const double t1 = now_s();
-  const TriInv V = tri_inverses_dev(ctx, n, b, ldb);   // once per factor: the three solves below share them
-  const int ldc = pad_ld(n);
-  double* c = ctx.pool.get_t<double>("gevr.c", (size_t)ldc * n);
-  gev_reduce_dev(ctx, n, a, lda, b, ldb, V, c, ldc);
-  EIGX_HIP_CHECK(hipStreamSynchronize(st));
-  const double t2 = now_s();
-  rc = range_solve_dev(ctx, n, W, c, ldc, w, z, ldz, 128, 128, mode, 2, false);
-  if (rc != EIGX_OK) return rc;
-  const int m = W.by_value ? *W.m_out : W.m();
-  const double t3 = now_s();
-  if (mode == 'A' && m > 0) {
-    trsm_upper_dev(ctx, 'N', n, m, b, ldb, z, ldz, V);   // Z = U^-1 Y
-    EIGX_HIP_CHECK(hipStreamSynchronize(st));
-  }
-  const double t4 = now_s();
-  ctx.timers[0] = t4 - t0; ctx.timers[1] = t1 - t0; ctx.timers[2] = t2 - t1; ctx.timers[3] = t3 - t2; ctx.timers[4] = t4 - t3;
-  return EIGX_OK;
-}
-
-int gev_range_host(Context& ctx, int n, RangeWindow W, double* a, int lda, double* b, int ldb, double* w, double* z, int ldz,
-                   char mode) {
-  if (!ctx.initialized) return EIGX_ERR_NOT_INITIALIZED;
-  if (ctx.grid.nranks != 1) return gev_range_dev(ctx, n, W, a, lda, b, ldb, w, z, ldz, mode);   // refuses
-  mode = upper_case(mode);
-  if (!range_args_ok(n, W, a, lda, w, z, ldz, mode) || !b || ldb < n) return EIGX_ERR_BAD_ARG;
-  const int wcap = range_w_cap(W, mode);
-  EIGX_HIP_CHECK(hipSetDevice(ctx.device));
-  const int ldd = host_ld(n);
-  double* ad = (double*)host_to_dev(ctx, "host.a", a, lda, n, n, 8);
-  double* bd = (double*)host_to_dev(ctx, "host.b", b, ldb, n, n, 8);
-  double* zd = (double*)host_to_dev(ctx, "host.z", nullptr, 0, n, mode == 'A' ? range_z_cap(n, W, mode) : 1, 8);
-  double* wd = ctx.pool.get_t<double>("host.w", (size_t)std::max(wcap, 1));
-  const int rc = gev_range_dev(ctx, n, W, ad, ldd, bd, ldd, wd, zd, ldd, mode);
-  const int m = (W.by_value && rc == EIGX_OK) ? (mode == 'C' ? 0 : *W.m_out) : wcap;   // entries that were written
-  if ((rc == EIGX_OK || rc == EIGX_ERR_NONFINITE) && m > 0) EIGX_HIP_CHECK(hipMemcpy(w, wd, (size_t)m * 8, hipMemcpyDeviceToHost));
-  if (rc != EIGX_OK) return rc;            // (EIGX_ERR_WINDOW: a and b are as the caller passed them, ready for the retry by index)
-  dev_to_host(b, ldb, bd, ldd, n, n, 8);   // U in the upper triangle
-  if (mode == 'A' && m > 0) dev_to_host(z, ldz, zd, ldd, n, m, 8);
-  return EIGX_OK;
-}
-
-}  // namespace
 
 int64_t solver_workspace_bytes(const Context& ctx, int n, int lda, int ldz, int mf, int mb) {
   (void)lda; (void)ldz;
@@ -1126,21 +574,11 @@ int64_t solver_workspace_bytes(const Context& ctx, int n, int lda, int ldz, int 
   return 8 * w;
 }
 
-
-
 }  // namespace eigx
 
 using namespace eigx;
 
 extern "C" {
-
-int eigx_transpose_plan(int Px, int Py, int px, int py, int qx, int qy, int* send_i0, int* send_j0, int* recv_i0,
-                        int* recv_j0, int* step) {
-  if (Px < 1 || Py < 1 || px < 0 || px >= Px || py < 0 || py >= Py || qx < 0 || qx >= Px || qy < 0 || qy >= Py || !send_i0 ||
-      !send_j0 || !recv_i0 || !recv_j0 || !step) return EIGX_ERR_BAD_ARG;
-  transpose_plan(Px, Py, px, py, qx, qy, send_i0, send_j0, recv_i0, recv_j0, step);
-  return EIGX_OK;
-}
 
 int eigx_sx(int n, int nvec, double* a, int lda, double* w, double* z, int ldz, int mf, int mb, char mode) {
   return eigx_guard(g_ctx, [&] { return solve_host(g_ctx, n, nvec, a, lda, w, z, ldz, mf, mb, mode, 2, 1); });
@@ -1230,52 +668,6 @@ int eigx_band_dc_dev(int n, int nvec, const double* d, const double* e, int lde,
   EIGX_HIP_CHECK(hipStreamSynchronize(nullptr));
   band_dc_dev(g_ctx, n, nvec, d, e, lde, band, w, z, ldz);
   return EIGX_OK;
-}
-
-int eigx_gev(int n, double* a, int lda, double* b, int ldb, double* w, double* z, int ldz) {
-  return eigx_guard(g_ctx, [&] { return gev_host(g_ctx, n, a, lda, b, ldb, w, z, ldz); });
-}
-int eigx_gev_dev(int n, double* a, int lda, double* b, int ldb, double* w, double* z, int ldz) {
-  return eigx_guard(g_ctx, [&] { return gev_dev(g_ctx, n, a, lda, b, ldb, w, z, ldz); });
-}
-
-// EXTENSION: eigenpairs il .. iu of A x = lambda B x by the Cholesky route (one GPU); see gev_range_dev
-int eigx_gev_range(int n, int il, int iu, double* a, int lda, double* b, int ldb, double* w, double* z, int ldz, char mode) {
-  return eigx_guard(g_ctx, [&] { return gev_range_host(g_ctx, n, RangeWindow::index(il, iu), a, lda, b, ldb, w, z, ldz, mode); });
-}
-int eigx_gev_range_dev(int n, int il, int iu, double* a, int lda, double* b, int ldb, double* w, double* z, int ldz, char mode) {
-  return eigx_guard(g_ctx, [&] { return gev_range_dev(g_ctx, n, RangeWindow::index(il, iu), a, lda, b, ldb, w, z, ldz, mode); });
-}
-// the same for the eigenpairs with vl <= lambda < vu
-int eigx_gev_range_v(int n, double vl, double vu, int mmax, int* m, int* il, double* a, int lda, double* b, int ldb, double* w,
-                     double* z, int ldz, char mode) {
-  return eigx_guard(g_ctx, [&] {
-    return gev_range_host(g_ctx, n, RangeWindow::value(vl, vu, mmax, m, il), a, lda, b, ldb, w, z, ldz, mode);
-  });
-}
-int eigx_gev_range_v_dev(int n, double vl, double vu, int mmax, int* m, int* il, double* a, int lda, double* b, int ldb,
-                         double* w, double* z, int ldz, char mode) {
-  return eigx_guard(g_ctx, [&] {
-    return gev_range_dev(g_ctx, n, RangeWindow::value(vl, vu, mmax, m, il), a, lda, b, ldb, w, z, ldz, mode);
-  });
-}
-// its reduction stage alone: upper(a) <- U^-T A U^-1 (all of a is written)
-int eigx_gev_reduce_dev(int n, double* a_dev, int lda, const double* u_dev, int ldu) {
-  if (!g_ctx.initialized) return EIGX_ERR_NOT_INITIALIZED;
-  if (n <= 0 || !a_dev || !u_dev || lda < n || ldu < n) return EIGX_ERR_BAD_ARG;
-  if (g_ctx.grid.nranks != 1) return EIGX_ERR_INTERNAL;
-  return eigx_guard(g_ctx, [&] {
-    EIGX_HIP_CHECK(hipSetDevice(g_ctx.device));
-    EIGX_HIP_CHECK(hipStreamSynchronize(nullptr));
-    const TriInv V = tri_inverses_dev(g_ctx, n, u_dev, ldu);
-    const int ldc = pad_ld(n);
-    double* c = g_ctx.pool.get_t<double>("gevr.c", (size_t)ldc * n);
-    gev_reduce_dev(g_ctx, n, a_dev, lda, u_dev, ldu, V, c, ldc);
-    EIGX_HIP_CHECK(hipMemcpy2DAsync(a_dev, (size_t)lda * 8, c, (size_t)ldc * 8, (size_t)n * 8, (size_t)n, hipMemcpyDeviceToDevice,
-                                    g_ctx.stream));
-    EIGX_HIP_CHECK(hipStreamSynchronize(g_ctx.stream));
-    return EIGX_OK;
-  });
 }
 
 int eigx_band_bisect_dev(int n, const double* d, const double* e, int lde, int band, double* w) {

@@ -6,7 +6,10 @@ points; every mode, panel widths, nvec < n, odd leading dimensions, scaled and n
 call  NNN_label.{rc,w,z,flops}.npy : the returned status, w, z (the columns the call owns) and a(1,1) (the flop count;
 the seconds in a(2,1) differ from run to run and are left out).  Then the complex generalised solvers eigx_hgev_dev and
 eigx_hgev_range_dev and their stages (Cholesky, triangular solves, reduction; eigx_tune key 20 = 64 and the default):
-the status, w, z and the arrays a / b as the call leaves them.  An array above 8 MiB is stored as its SHA-256.
+the status, w, z and the arrays a / b as the call leaves them.  Then the real generalised solvers eigx_gev[_range][_dev],
+the value-window solves (m and il as well), the host forms of all four generalised solvers and their statuses (non-finite
+A or B, B not positive definite, a bad window, ldb < n) from sentinel-filled w and z.  An array above 8 MiB is stored as
+its SHA-256.
 The library is deterministic, so two builds that compute the same leave directories that `cmp` finds equal:
     for f in A/*; do cmp $f B/$(basename $f); done
 Run each build in a fresh process.  --quick leaves out n >= 2048."""
@@ -206,5 +209,149 @@ for nb in (64, nb_default):
         rc = lib.eigx_hgev_reduce_dev(n, a.data_ptr(), ld, b.data_ptr(), ld)
         torch.cuda.synchronize()
         save(f"hgev_reduce_n{n}_nb{nb}", rc=np.int64(rc), a=a.cpu().numpy())
+
+# ---- the real generalised solvers (gev.hip), the value-window solves, and the host forms of all four ---------------------
+SENT = 12345.678   # w and z start from it where "not written" is to show in the dump
+
+
+def rpencil(n):
+    X = np.random.default_rng(4000 + n).standard_normal((n, n))
+    B = X @ X.T / n + np.eye(n)
+    return sym(n), (B + B.T) / 2
+
+
+def rdev(M, ld, ncols=None, fill=0.0):
+    """t[j, i] = M(i, j) with leading dimension ld, the padding `fill` (M None: all `fill`)"""
+    t = torch.full((ncols if M is None else M.shape[1], ld), fill, dtype=torch.float64, device=dev)
+    if M is not None:
+        t[:, :M.shape[0]] = torch.from_numpy(np.ascontiguousarray(M.T)).to(dev)
+    return t
+
+
+def gen_eigs(A, B):
+    L = np.linalg.cholesky(B)
+    Y = np.linalg.solve(L, A)
+    return np.linalg.eigvalsh(np.linalg.solve(L, Y.T).T)
+
+
+def mid(lam, k):
+    """between the eigenvalues k and k + 1 (1-based); k = 0 / n: below / above all"""
+    if k == 0:
+        return lam[0] - 1.0
+    return lam[-1] + 1.0 if k == len(lam) else 0.5 * (lam[k - 1] + lam[k])
+
+
+def gen_dev(label, fn, A, B, win=None, mode="A", ld=None, ldb=None, cplx=False, fill=0.0):
+    """One device call of a generalised solver: win None (eigx_gev_dev / eigx_hgev_dev), (il, iu), or (vl, vu, mmax)"""
+    n = A.shape[0]
+    ld = ld or n + (n & 1)
+    mk = cdev if cplx else rdev
+    a, b = mk(A, ld), mk(B, ld)
+    cap = n if win is None else (win[2] if len(win) == 3 else max(win[1] - win[0] + 1, 1))
+    z = torch.full((max(cap, 1), ld), fill, dtype=torch.complex128 if cplx else torch.float64, device=dev)
+    w = torch.full((max(cap, 1),), fill, dtype=torch.float64, device=dev)
+    extra = {}
+    pa, pb, pw, pz = a.data_ptr(), b.data_ptr(), w.data_ptr(), z.data_ptr()
+    if win is None:
+        rc = fn(n, pa, ld, pb, ldb or ld, pw, pz, ld)
+    elif len(win) == 2:
+        rc = fn(n, win[0], win[1], pa, ld, pb, ldb or ld, pw, pz, ld, mode.encode())
+    else:
+        m, il = C.c_int(-1), C.c_int(-1)
+        rc = fn(n, win[0], win[1], win[2], C.byref(m), C.byref(il), pa, ld, pb, ldb or ld, pw, pz, ld, mode.encode())
+        extra = dict(m=np.int64(m.value), il=np.int64(il.value))
+    torch.cuda.synchronize()
+    if win is None and rc == -7:
+        b[0, 1] = 0.0   # B not positive definite: b is what eigen_s / eigen_h of B left, its b(2,1) the seconds of that solve
+    save(label, rc=np.int64(rc), w=w.cpu().numpy(), z=z.cpu().numpy(), a=a.cpu().numpy(), b=b.cpu().numpy(), **extra)
+
+
+def gen_host(label, fn, A, B, win=None, mode="A", ldb=None, fill=0.0):
+    """The same through a host entry point (Fortran-ordered arrays; complex by A's dtype)"""
+    n = A.shape[0]
+    a, b = np.asfortranarray(A.copy()), np.asfortranarray(B.copy())
+    cap = n if win is None else (win[2] if len(win) == 3 else max(win[1] - win[0] + 1, 1))
+    z = np.full((n, max(cap, 1)), fill, dtype=A.dtype, order="F")
+    w = np.full(max(cap, 1), fill)
+    extra = {}
+    pa, pb, pw, pz = a.ctypes.data, b.ctypes.data, w.ctypes.data, z.ctypes.data
+    if win is None:
+        rc = fn(n, pa, n, pb, ldb or n, pw, pz, n)
+    elif len(win) == 2:
+        rc = fn(n, win[0], win[1], pa, n, pb, ldb or n, pw, pz, n, mode.encode())
+    else:
+        m, il = C.c_int(-1), C.c_int(-1)
+        rc = fn(n, win[0], win[1], win[2], C.byref(m), C.byref(il), pa, n, pb, ldb or n, pw, pz, n, mode.encode())
+        extra = dict(m=np.int64(m.value), il=np.int64(il.value))
+    save(label, rc=np.int64(rc), w=w, z=z, a=a, b=b, **extra)
+
+
+for n in (5, 130, 517):
+    gen_dev(f"gev_n{n}", lib.eigx_gev_dev, *rpencil(n))
+gen_host("gev_host_n130", lib.eigx_gev, *rpencil(130))
+n = 517
+A, B = rpencil(n)
+for pct in (100, 0):
+    lib.eigx_tune(17, pct)
+    for il, iu in ((1, n), (n // 3, n // 3 + 39)):
+        for mode in "AN":
+            gen_dev(f"gevr_pct{pct}_{il}_{iu}_{mode}", lib.eigx_gev_range_dev, A, B, (il, iu), mode)
+lib.eigx_tune(17, -1)
+gen_host("gevr_host", lib.eigx_gev_range, A, B, (n // 3, n // 3 + 39))
+
+# by value: vl, vu midway between neighbouring eigenvalues, so that no count depends on rounding
+k0 = n // 3
+for name, fn, lam in (("sxrv", lib.eigx_sx_range_v_dev, np.linalg.eigvalsh(A)), ("srv", lib.eigx_s_range_v_dev, np.linalg.eigvalsh(A)),
+                      ("gevrv", lib.eigx_gev_range_v_dev, gen_eigs(A, B))):
+    gap = lam[k0] - lam[k0 - 1]
+    cases = (("w40", mid(lam, k0), mid(lam, k0 + 40), 64, "A"), ("empty", lam[k0 - 1] + 0.25 * gap, lam[k0 - 1] + 0.75 * gap, 64, "A"),
+             ("small", mid(lam, k0), mid(lam, k0 + 40), 10, "A"), ("count", mid(lam, k0), mid(lam, k0 + 40), 0, "C"),
+             ("all", -np.inf, np.inf, n, "A"), ("w40N", mid(lam, k0), mid(lam, k0 + 40), 64, "N"))
+    for cname, vl, vu, mmax, mode in cases:
+        if name == "gevrv":
+            gen_dev(f"{name}_{cname}", fn, A, B, (vl, vu, mmax), mode, fill=SENT)
+        else:
+            a = rdev(A, n + 1)
+            z = torch.full((max(mmax, 1), n + 1), SENT, dtype=torch.float64, device=dev)
+            w = torch.full((max(mmax, 1),), SENT, dtype=torch.float64, device=dev)
+            m, il = C.c_int(-1), C.c_int(-1)
+            rc = fn(n, vl, vu, mmax, C.byref(m), C.byref(il), a.data_ptr(), n + 1, w.data_ptr(), z.data_ptr(), n + 1, 128, 128,
+                    mode.encode())
+            torch.cuda.synchronize()
+            save(f"{name}_{cname}", rc=np.int64(rc), w=w.cpu().numpy(), z=z.cpu().numpy(), flops=a[0, 0].item(),
+                 m=np.int64(m.value), il=np.int64(il.value))
+lam = np.linalg.eigvalsh(A)
+a = np.asfortranarray(A.copy())
+z = np.full((n, 64), SENT, order="F")
+w = np.full(64, SENT)
+m, il = C.c_int(-1), C.c_int(-1)
+rc = lib.eigx_sx_range_v(n, mid(lam, k0), mid(lam, k0 + 40), 64, C.byref(m), C.byref(il), a.ctypes.data, n, w.ctypes.data,
+                         z.ctypes.data, n, 128, 128, b"A")
+save("sxrv_host", rc=np.int64(rc), w=w, z=z, flops=a[0, 0], m=np.int64(m.value), il=np.int64(il.value))
+lam = gen_eigs(A, B)
+gen_host("gevrv_host", lib.eigx_gev_range_v, A, B, (mid(lam, k0), mid(lam, k0 + 40), 64), fill=SENT)
+
+n = 130
+gen_host("hgev_host_n130", lib.eigx_hgev, *pencil(n))
+gen_host("hgevr_host_n130", lib.eigx_hgev_range, *pencil(n), (n // 3, n // 3 + 39))
+
+# statuses of the four generalised solvers, device and host form: w and z start from the sentinel
+n = 65
+for fam, cplx, pen in (("gev", False, rpencil(n)), ("hgev", True, pencil(n))):
+    A, B = pen
+    nanA, nanB, indef = A.copy(), B.copy(), B.copy()
+    nanA[3, 9] = nanA[9, 3] = np.nan
+    nanB[3, 9] = nanB[9, 3] = np.nan
+    indef[7, 7] = -1.0
+    full, rng = getattr(lib, f"eigx_{fam}"), getattr(lib, f"eigx_{fam}_range")
+    full_d, rng_d = getattr(lib, f"eigx_{fam}_dev"), getattr(lib, f"eigx_{fam}_range_dev")
+    for cname, Ax, Bx, win, ldb in (("nanA", nanA, B, (5, 20), None), ("nanB", A, nanB, (5, 20), None),
+                                    ("notspd", A, indef, (5, 20), None), ("badwin", A, B, (20, 5), None),
+                                    ("ldb", A, B, (5, 20), n - 1)):
+        if cname != "badwin":
+            gen_dev(f"st_{fam}_dev_{cname}", full_d, Ax, Bx, None, cplx=cplx, ldb=ldb, fill=SENT)
+            gen_host(f"st_{fam}_host_{cname}", full, Ax, Bx, None, ldb=ldb, fill=SENT)
+        gen_dev(f"st_{fam}r_dev_{cname}", rng_d, Ax, Bx, win, cplx=cplx, ldb=ldb, fill=SENT)
+        gen_host(f"st_{fam}r_host_{cname}", rng, Ax, Bx, win, ldb=ldb, fill=SENT)
 lib.eigx_free()
 print(f"DUMPED {count[0]} calls into {out}", flush=True)
