@@ -23,6 +23,8 @@ from .api import (  # noqa: F401
     eigen_sx,
     eigen_s,
     eigen_h,
+    eigen_h_range,
+    eigen_h_range_v,
     eigen_sx_range,
     eigen_s_range,
     eigen_sx_range_v,
@@ -37,6 +39,7 @@ from .api import (  # noqa: F401
     KMATH_EIGEN_GEV_RANGE_V,
     KMATH_EIGEN_HGEV,
     KMATH_EIGEN_HGEV_RANGE,
+    KMATH_EIGEN_HGEV_RANGE_V,
     eigen_NB_f,
     eigen_NB_b,
 )

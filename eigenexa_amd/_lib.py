@@ -109,6 +109,19 @@ SIGNATURES = {
                                   C.c_void_p, C.c_int, C.c_char]),
     "eigx_hgev_range_dev": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p,
                                       C.c_void_p, C.c_int, C.c_char]),
+    # extension: index and value windows of eigen_h, the value window of the complex generalised problem
+    "eigx_h_range": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int,
+                               C.c_int, C.c_int, C.c_char]),
+    "eigx_h_range_dev": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int,
+                                   C.c_int, C.c_int, C.c_char]),
+    "eigx_h_range_v": (C.c_int, [C.c_int, C.c_double, C.c_double, C.c_int, _c_int_p, _c_int_p, C.c_void_p, C.c_int,
+                                 C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_char]),
+    "eigx_h_range_v_dev": (C.c_int, [C.c_int, C.c_double, C.c_double, C.c_int, _c_int_p, _c_int_p, C.c_void_p, C.c_int,
+                                     C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_char]),
+    "eigx_hgev_range_v": (C.c_int, [C.c_int, C.c_double, C.c_double, C.c_int, _c_int_p, _c_int_p, C.c_void_p, C.c_int,
+                                    C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_char]),
+    "eigx_hgev_range_v_dev": (C.c_int, [C.c_int, C.c_double, C.c_double, C.c_int, _c_int_p, _c_int_p, C.c_void_p, C.c_int,
+                                        C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_char]),
     "eigx_zchol_dev": (C.c_int, [C.c_int, C.c_void_p, C.c_int]),
     "eigx_ztrsm_upper_dev": (C.c_int, [C.c_char, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int]),
     "eigx_hgev_reduce_dev": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int]),

@@ -631,3 +631,113 @@ def KMATH_EIGEN_HGEV_RANGE(n, il, iu, a, lda, b, ldb, w, z, ldz, mode="A"):
     _state["last_status"] = rc
     if rc not in (0, -5, -7):
         print(f"Warning: KMATH_EIGEN_HGEV_RANGE returned without computing (status {rc})", file=sys.stderr)
+
+
+def _cptr(x, name, dev, real=False):
+    """address of a complex128 (``real``: float64) array of the complex range wrappers; all host or all device"""
+    if x is None:
+        return None
+    if dev:
+        import torch
+
+        if not (_is_torch(x) and x.is_cuda):
+            raise ValueError("a, b, w, z must all be host arrays or all be device tensors")
+        if x.dtype != (torch.float64 if real else torch.complex128):
+            raise ValueError(f"{name}: {'float64' if real else 'complex128'} required")
+        return x.data_ptr()
+    if _is_torch(x):
+        raise ValueError("a, b, w, z must all be host arrays or all be device tensors")
+    if x.dtype != (np.float64 if real else np.complex128):
+        raise ValueError(f"{name}: {'float64' if real else 'complex128'} required")
+    if x.ndim == 2 and not x.flags.f_contiguous:
+        raise ValueError(f"{name}: Fortran (column-major) order required, as in the reference")
+    return x.ctypes.data
+
+
+def _complex_call_begins(a):
+    """library, device flag -- or None when eigen_init has not been called (status -1)"""
+    lib = _lib.load()
+    if not _state["initialized"]:
+        _state["last_status"] = -1
+        return None
+    dev = _is_torch(a)
+    if dev:
+        import torch
+
+        torch.cuda.current_stream().synchronize()
+    return lib, dev
+
+
+def eigen_h_range(n, il, iu, a, lda, w, z, ldz, m_forward=None, m_backward=None, mode="A"):
+    """EXTENSION (not in the reference): eigenpairs ``il .. iu`` (1-based, inclusive) of the ascending spectrum of a complex
+    Hermitian matrix, one GPU.  Arrays as for ``eigen_h`` (``a``, ``z`` complex128, ``w`` float64); ``w[:m]``, ``z[:, :m]``
+    with ``m = iu - il + 1``; modes 'A' and 'N' (``z`` may be None).  After eigen_h's reduction the work and the memory
+    scale with ``m`` (multi-section on the window, inverse iteration, CholQR2 + Rayleigh-Ritz on the real tridiagonal
+    matrix, back-transformation of ``m`` columns); ``range_info()`` tells whether that path or the full divide and conquer
+    produced the result."""
+    # the window and the mode are checked here, before the library is touched (status -2 = EIGX_ERR_BAD_ARG)
+    md = _char(mode, "A").upper()
+    try:
+        ok = 1 <= int(il) <= int(iu) <= int(n) and md in (b"A", b"N") and not (md == b"A" and z is None)
+    except (TypeError, ValueError):
+        ok = False
+    if not ok:
+        _state["last_status"] = -2
+        print(f"Warning: eigen_h_range: invalid window / mode (n={n}, il={il}, iu={iu}, mode={mode!r})", file=sys.stderr)
+        return
+    began = _complex_call_begins(a)
+    if began is None:
+        return
+    lib, dev = began
+    mf = eigen_NB_f if m_forward is None else int(m_forward)
+    mb = eigen_NB_b if m_backward is None else int(m_backward)
+    fn = lib.eigx_h_range_dev if dev else lib.eigx_h_range
+    rc = fn(int(n), int(il), int(iu), _cptr(a, "a", dev), int(lda), _cptr(w, "w", dev, real=True), _cptr(z, "z", dev),
+            int(ldz), mf, mb, md)
+    _state["last_status"] = rc
+    if rc not in (0, -5):
+        print(f"Warning: eigen_h_range returned without computing (status {rc})", file=sys.stderr)
+
+
+def eigen_h_range_v(n, vl, vu, a, lda, w, z, ldz, m_forward=None, m_backward=None, mode="A", mmax=None):
+    """EXTENSION (not in the reference; LAPACK's range = 'V'): the eigenpairs of a complex Hermitian matrix with
+    ``vl <= lambda < vu``, one GPU, at the cost of ONE reduction.  Arrays as for ``eigen_h``; window, ``mmax``, modes
+    ('A', 'N', 'C'), statuses and the returned ``(m, il)`` as for ``eigen_sx_range_v``; ``w[:m]``, ``z[:, :m]`` as from
+    ``eigen_h_range(n, il, il + m - 1, ...)``, bit for bit.  Returns None when nothing was resolved."""
+    chk = _value_window("eigen_h_range_v", n, vl, vu, w, z, mode, mmax)
+    if chk is None:
+        return None
+    md, mmax = chk
+    began = _complex_call_begins(a)
+    if began is None:
+        return None
+    lib, dev = began
+    mf = eigen_NB_f if m_forward is None else int(m_forward)
+    mb = eigen_NB_b if m_backward is None else int(m_backward)
+    fn = lib.eigx_h_range_v_dev if dev else lib.eigx_h_range_v
+    m, il = C.c_int(0), C.c_int(0)
+    rc = fn(int(n), float(vl), float(vu), mmax, C.byref(m), C.byref(il), _cptr(a, "a", dev), int(lda),
+            _cptr(w, "w", dev, real=True), _cptr(z, "z", dev), int(ldz), mf, mb, md)
+    return _finish_value_call("eigen_h_range_v", rc, m, il, (0, -5, -9))
+
+
+def KMATH_EIGEN_HGEV_RANGE_V(n, vl, vu, a, lda, b, ldb, w, z, ldz, mode="A", mmax=None):
+    """EXTENSION, not in the reference: the eigenpairs of the complex Hermitian-definite problem A x = lambda B x with
+    ``vl <= lambda < vu`` by the Cholesky route of ``KMATH_EIGEN_HGEV_RANGE`` with ``eigen_h_range_v`` as the inner solve,
+    one GPU.  Arrays as for ``KMATH_EIGEN_HGEV_RANGE``; window, ``mmax``, modes, statuses and the returned ``(m, il)`` as
+    for ``eigen_sx_range_v``; ``z[:, :m]`` with ``z^H B z = I``.  ``a`` is destroyed and ``b`` holds U on status 0; on
+    status -9 host arrays are left as they were passed.  Status -7 if B is not positive definite.  Agrees with
+    ``KMATH_EIGEN_HGEV_RANGE`` on the resolved window to rounding, not bit for bit (the inner routes differ)."""
+    chk = _value_window("KMATH_EIGEN_HGEV_RANGE_V", n, vl, vu, w, z, mode, mmax)
+    if chk is None:
+        return None
+    md, mmax = chk
+    began = _complex_call_begins(a)
+    if began is None:
+        return None
+    lib, dev = began
+    fn = lib.eigx_hgev_range_v_dev if dev else lib.eigx_hgev_range_v
+    m, il = C.c_int(0), C.c_int(0)
+    rc = fn(int(n), float(vl), float(vu), mmax, C.byref(m), C.byref(il), _cptr(a, "a", dev), int(lda), _cptr(b, "b", dev),
+            int(ldb), _cptr(w, "w", dev, real=True), _cptr(z, "z", dev), int(ldz), md)
+    return _finish_value_call("KMATH_EIGEN_HGEV_RANGE_V", rc, m, il, (0, -5, -7, -9))

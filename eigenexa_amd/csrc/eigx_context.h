@@ -159,7 +159,7 @@ void band_count_dev(Context& ctx, int n, const double* d, const double* e, int l
                     int* cnt);
 
 // The window of a range solve (range_solve_dev in solver.hip, gev_range_dev in gev.hip, hgev_range_dev in hgev.hip and their
-// host forms; the complex solver takes index windows only).  By index: eigenpairs
+// host forms, herm_range_dev in herm.hip).  By index: eigenpairs
 // il .. iu (1-based, inclusive).  By value: those with vl <= lambda < vu, resolved into il .. iu by two Sturm counts after
 // the band reduction; at most mmax of them are returned, and *m_out / *il_out (host) receive their number and the index
 // of the first.  m() = the entries of w / columns of z the caller provides.
@@ -182,6 +182,9 @@ inline int range_z_cap(int n, const RangeWindow& W, char mode) { const int c = r
 // (EIGX_ERR_BAD_ARG), and the drivers of eigen_sx (band 2) / eigen_s (band 1) and of their range solve on device arrays
 bool range_args_ok(int n, const RangeWindow& W, const double* a, int lda, const double* w, const double* z, int ldz, char mode);
 int refuse_several_ranks(const Context& ctx);
+// value window -> index window right after a reduction to the band form (d, e) = sigma times the caller's matrix: W.il,
+// W.iu, *W.m_out, *W.il_out (range_solve_dev, herm_range_dev)
+void resolve_value_window(Context& ctx, int n, const double* d, const double* e, int lde, int band, double sigma, RangeWindow& W);
 int solve_dev(Context& ctx, int n, int nvec, double* a, int lda, double* w, double* z, int ldz, int mf, int mb, char mode, int band, int nb);
 int range_solve_dev(Context& ctx, int n, RangeWindow W, double* a, int lda, double* w, double* z, int ldz, int mf, int mb,
                     char mode, int band, bool fill_rest);
@@ -350,8 +353,11 @@ SummaPlan summa_plan(const Grid& G, int n, int kb_want);
 void summa_pack_a(hipStream_t st, const SummaPlan& p, const double* a, int lda, int nr, int nc, int lc0, double* out);
 void summa_pack_b(hipStream_t st, const SummaPlan& p, const double* b, int ldb, int nr, int nc, int lr0, double* out);
 
-// herm.hip: eigen_h on device arrays (interleaved complex; one GPU, or this rank's 2-D cyclic blocks)
+// herm.hip: eigen_h on device arrays (interleaved complex; one GPU, or this rank's 2-D cyclic blocks), and its range solve
+// (EXTENSION, one GPU): modes 'A', 'N' and, by value, 'C'
 int herm_solve_dev(Context& ctx, int n, int nvec, double* a, int lda, double* w, double* z, int ldz, int mf, int mb,
+                   char mode);
+int herm_range_dev(Context& ctx, int n, RangeWindow W, double* a, int lda, double* w, double* z, int ldz, int mf, int mb,
                    char mode);
 
 }  // namespace eigx

@@ -817,14 +817,15 @@ HPlanes h_tridiagonal_stage(Context& ctx, int n, int nvec, char mode, bool want_
 }
 }  // namespace
 
-// One GPU.  a, z: device, interleaved complex(8), leading dimensions in complex elements; the request is checked and
-// cleaned up, the frame begun (herm_solve_dev)
-static int herm_solve_full(SolveFrame& F, int n, int nvec, double* a, int lda, double* w, double* z, int ldz, int m, int mb,
-                           char mode, bool want_vec) {
+// One GPU, what herm_solve_full and herm_range_dev share.  h_reduce_full: eigen_scaling_h (a non-finite input fills
+// w(1:nw) with NaN), the planes of A, eigen_hrd, and with want_t phase A of the back-transformation (the T factors of all
+// blocks); drained, F.t1 and F.t2 marked.  h_back_transform: phase B on ncols columns of the planes Zr | Zi.
+struct HReduced { HArgs H; int ld, lde, bw, nblk; double* Tall; };
+static int h_reduce_full(SolveFrame& F, int n, double* a, int lda, double* w, int nw, int m, int mb, bool want_t, HReduced& R) {
   Context& ctx = F.ctx;
   hipStream_t st = ctx.stream;
   // ---- eigen_scaling_h -------------------------------------------------------------------------------------------
-  if (const int rc = F.scale(a, lda, w, n)) return rc;
+  if (const int rc = F.scale(a, lda, w, nw)) return rc;
   if (F.sigma != 1.0) hipLaunchKernelGGL(h_scale_kernel, dim3(8, n), dim3(256), 0, st, a, lda, n, F.sigma);
 
   // ---- workspace -----------------------------------------------------------------------------------------------------
@@ -866,10 +867,9 @@ static int herm_solve_full(SolveFrame& F, int n, int nvec, double* a, int lda, d
   // (a per-block single-workgroup kernel on the critical path cost 37 of 149 ms at N=8192).
   int bw = mb <= 0 ? HMB : mb;
   if (bw > HMB) bw = HMB;
-  const int lds = ld;
   const int nblk = n > 1 ? ceil_div(n - 1, bw) : 1;
   double* Tall = nullptr;
-  if (want_vec && n > 1) {
+  if (want_t && n > 1) {
     double* Gall = ctx.pool.get_t<double>("h.Gall", (size_t)nblk * 4 * HMB * HMB);
     Tall = ctx.pool.get_t<double>("h.Tall", (size_t)nblk * 2 * HMB * HMB);
     const size_t shm = h_tinv_shm();
@@ -887,26 +887,42 @@ static int herm_solve_full(SolveFrame& F, int n, int nvec, double* a, int lda, d
   EIGX_HIP_CHECK(hipStreamSynchronize(st));
   F.t2 = now_s();
 
+  R.H = H; R.ld = ld; R.lde = ws.lde; R.bw = bw; R.nblk = nblk; R.Tall = Tall;
+  return EIGX_OK;
+}
+static void h_back_transform(Context& ctx, const HReduced& R, int n, int ncols, double* Zr, double* Zi, int ldzp) {
+  hipStream_t st = ctx.stream;
+  const HArgs& H = R.H;
+  const int ld = R.ld, lds = R.ld, bw = R.bw;
+  const HBtWork W = h_bt_work(ctx, ncols);
+  double* Vs = ctx.pool.get_t<double>("h.Vs", (size_t)lds * 2 * HMB);
+  // phase B: apply the blocks in ascending order
+  for (int b = 0; b < R.nblk; ++b) {
+    const int j0 = 1 + b * bw;
+    const int nb = (j0 + bw <= n) ? bw : n - j0;
+    const int rows = j0 + nb - 1;
+    double* Tr = R.Tall + (size_t)b * 2 * HMB * HMB;
+    hipLaunchKernelGGL(h_stack_v_kernel, dim3(8, 2 * nb), dim3(256), 0, st, H.Ar + (size_t)j0 * ld, H.Ai + (size_t)j0 * ld,
+                       ld, rows, nb, Vs, lds);
+    h_bt_block(st, W, Vs, lds, ZPlanes{Tr, Tr + (size_t)HMB * HMB}, nb, rows, ncols, Zr, Zi, ldzp);
+  }
+}
+
+// One GPU.  a, z: device, interleaved complex(8), leading dimensions in complex elements; the request is checked and
+// cleaned up, the frame begun (herm_solve_dev)
+static int herm_solve_full(SolveFrame& F, int n, int nvec, double* a, int lda, double* w, double* z, int ldz, int m, int mb,
+                           char mode, bool want_vec) {
+  Context& ctx = F.ctx;
+  HReduced R;
+  if (const int rc = h_reduce_full(F, n, a, lda, w, n, m, mb, want_vec, R)) return rc;
+
   // ---- real tridiagonal eigenproblem (dc2 / bisect) --------------------------------------------------------------------
-  const auto [Zr, Zi, ldzp] = h_tridiagonal_stage(ctx, n, nvec, mode, want_vec, H.d, H.e, ws.lde, w, 0, nvec, nvec, n, "h.Zri");
+  const auto [Zr, Zi, ldzp] = h_tridiagonal_stage(ctx, n, nvec, mode, want_vec, R.H.d, R.H.e, R.lde, w, 0, nvec, nvec, n, "h.Zri");
   F.t3 = now_s();
 
   // ---- eigen_hrbakwyx: z = H_{n-1}^H ... H_1^H y in blocks of HMB reflectors -------------------------------------------
-  if (want_vec && n > 1) {
-    const HBtWork W = h_bt_work(ctx, nvec);
-    double* Vs = ctx.pool.get_t<double>("h.Vs", (size_t)lds * 2 * HMB);
-    // phase B: apply the blocks in ascending order
-    for (int b = 0; b < nblk; ++b) {
-      const int j0 = 1 + b * bw;
-      const int nb = (j0 + bw <= n) ? bw : n - j0;
-      const int rows = j0 + nb - 1;
-      double* Tr = Tall + (size_t)b * 2 * HMB * HMB;
-      hipLaunchKernelGGL(h_stack_v_kernel, dim3(8, 2 * nb), dim3(256), 0, st, H.Ar + (size_t)j0 * ld, H.Ai + (size_t)j0 * ld,
-                         ld, rows, nb, Vs, lds);
-      h_bt_block(st, W, Vs, lds, ZPlanes{Tr, Tr + (size_t)HMB * HMB}, nb, rows, nvec, Zr, Zi, ldzp);
-    }
-  }
-  if (want_vec) zjoin(st, ZPlanes{Zr, Zi}, ldzp, n, nvec, false, z, ldz);
+  if (want_vec && n > 1) h_back_transform(ctx, R, n, nvec, Zr, Zi, ldzp);
+  if (want_vec) zjoin(ctx.stream, ZPlanes{Zr, Zi}, ldzp, n, nvec, false, z, ldz);
   return F.finish(w, n, ctx.timers[11], want_vec ? nvec : 0, n);
 }
 
@@ -1219,6 +1235,124 @@ int herm_solve_host(Context& ctx, int n, int nvec, double* a, int lda, double* w
   return EIGX_OK;
 }
 
+// ---- eigen_h range solve: eigenpairs il .. iu of the ascending spectrum, or those with vl <= lambda < vu (one GPU) ----------
+// EXTENSION, not in the reference: the Hermitian sibling of range_solve_dev (solver.hip) with band = 1.
+//   h_reduce_full (scaling, eigen_hrd, with mode 'A' the T factors) -> a value window resolved on (h.d, h.e) by two Sturm
+//   counts (resolve_value_window: the protocol of range_solve_dev word for word) -> multi-section on the index window ->
+//   band_eigvec_dev straight into the real plane Zr of m columns (path 1), or band_dc_dev with nvec = iu into planes of iu
+//   columns, of which the window is the pointer offset (il - 1) ldzp into both (path 3 by the size rule of key 17, path 2
+//   after a refusal by the acceptance test of key 19) -> Zi = 0 on the m columns -> phase B on the m columns -> z.
+// Modes 'A', 'N' and, by value, 'C' (the count alone).  w(1:m), z(:, 1:m); a is destroyed and gets its two statistics.
+int herm_range_dev(Context& ctx, int n, RangeWindow W, double* a, int lda, double* w, double* z, int ldz, int mf, int mb,
+                   char mode) {
+  if (ctx.initialized && ctx.grid.nranks != 1) return refuse_several_ranks(ctx);
+  mode = upper_case(mode);
+  SolveFrame F(ctx, n, true);
+  if (const int rc = F.begin(range_args_ok(n, W, a, lda, w, z, ldz, mode))) return rc;
+  F.a_user = a;
+  const bool want_vec = mode == 'A';
+  hipStream_t st = ctx.stream;
+  RangeInfo& info = range_info();
+  info.path = 0; info.m = W.by_value ? 0 : W.m(); info.cond = 0.0;
+  for (int q = 0; q < 4; ++q) info.t[q] = 0.0;
+  HReduced R;
+  if (const int rc = h_reduce_full(F, n, a, lda, w, range_w_cap(W, mode), std::min(std::min(mf <= 0 ? 48 : mf, HM), n), mb, want_vec, R)) {
+    if (W.by_value) *W.m_out = 0;
+    return rc;
+  }
+  const double* d = R.H.d;
+  const double* e = R.H.e;
+  const int lde = R.lde;
+  const double t2 = F.t2;
+
+  if (W.by_value) {
+    resolve_value_window(ctx, n, d, e, lde, 1, F.sigma, W);
+    const int mv = *W.m_out;
+    info.m = mv;
+    if (mode != 'C' && mv > W.mmax) return EIGX_ERR_WINDOW;
+    if (mode == 'C' || mv == 0) {   // nothing to compute: the statistics of the reduction alone
+      F.t3 = now_s();
+      info.t[0] = F.t3 - t2;
+      return F.finish(w, 0, 0.0, 0, n);
+    }
+  }
+  const int il = W.il, iu = W.iu, m = iu - il + 1;
+
+  // ---- eigenvalues il .. iu, then their eigenvectors as the real plane Zr -------------------------------------------------
+  double* Zr = nullptr;
+  double* Zi = nullptr;
+  const int ldzp = pad_ld(n + 2);
+  if (!want_vec) {
+    band_bisect_range_dev(ctx, n, il, iu, d, e, lde, 1, w);
+    info.path = 1;
+    info.t[0] = now_s() - t2;
+  } else {
+    // both planes in one buffer, the imaginary one H_PLANE_SKEW off, as h_tridiagonal_stage lays them out
+    auto planes = [&](int zcap) {
+      const size_t zplane = (size_t)ldzp * (zcap + 1) + H_PLANE_SKEW;
+      Zr = ctx.pool.get_t<double>("h.Zri", 2 * zplane);
+      Zi = Zr + zplane;
+    };
+    int path = range_takes_subset(n, m) ? 1 : 3;
+    if (path == 1) {
+      double* wsel = ctx.pool.get_t<double>("sub.wsel", (size_t)m);
+      band_bisect_range_dev(ctx, n, il, iu, d, e, lde, 1, wsel);
+      const double tb = now_s();
+      info.t[0] = tb - t2;
+      double cond = 0.0;
+      double ts[2] = {0.0, 0.0};
+      planes(m);
+      const int rc_ev = band_eigvec_dev(ctx, n, m, d, e, lde, 1, wsel, w, Zr, ldzp, &cond, ts);
+      if (rc_ev < 0) return rc_ev;
+      info.cond = cond; info.t[1] = ts[0]; info.t[2] = ts[1];
+      if (rc_ev > 0) path = 2;   // refused by the acceptance test
+    }
+    if (path != 1) {
+      // the full divide and conquer for the lowest iu pairs; the window is columns il .. iu of both planes where they lie
+      const double tf = now_s();
+      double* wn = ctx.pool.get_t<double>("h.wfull", (size_t)n);
+      planes(iu);
+      band_dc_dev(ctx, n, iu, d, e, lde, 1, wn, Zr, ldzp);
+      EIGX_HIP_CHECK(hipMemcpyAsync(w, wn + (il - 1), (size_t)m * 8, hipMemcpyDeviceToDevice, st));
+      Zr += (size_t)(il - 1) * ldzp;
+      Zi += (size_t)(il - 1) * ldzp;
+      EIGX_HIP_CHECK(hipStreamSynchronize(st));
+      info.t[2] += now_s() - tf;
+    }
+    info.path = path;
+    hipLaunchKernelGGL(fill_kernel, dim3(1024), dim3(256), 0, st, Zi, (size_t)ldzp * m, 0.0);
+  }
+  F.t3 = now_s();
+
+  // ---- eigen_hrbakwyx on the m columns of the window ---------------------------------------------------------------------
+  if (want_vec && n > 1) h_back_transform(ctx, R, n, m, Zr, Zi, ldzp);
+  if (want_vec) zjoin(st, ZPlanes{Zr, Zi}, ldzp, n, m, false, z, ldz);
+  const double f_mid = want_vec ? (info.path == 1 ? 6.0 * (double)n * m * m : ctx.timers[11]) : 0.0;
+  int rc = F.finish(w, m, f_mid, want_vec ? m : 0, n);
+  info.t[3] = ctx.timers[3];
+  if (rc == EIGX_OK) EIGX_HIP_CHECK(hipGetLastError());
+  return rc;
+}
+
+// Host arrays, as range_solve_host: by value nothing is copied back into w or z on EIGX_ERR_WINDOW and on m = 0 (a
+// non-finite input fills w(1:mmax) with NaN); a gets its a(1:2,1) statistics whenever the call returns EIGX_OK.
+int herm_range_host(Context& ctx, int n, RangeWindow W, double* a, int lda, double* w, double* z, int ldz, int mf, int mb,
+                    char mode) {
+  if (!ctx.initialized) return EIGX_ERR_NOT_INITIALIZED;
+  if (ctx.grid.nranks != 1) return herm_range_dev(ctx, n, W, a, lda, w, z, ldz, mf, mb, mode);   // refuses
+  mode = upper_case(mode);
+  if (!range_args_ok(n, W, a, lda, w, z, ldz, mode)) return EIGX_ERR_BAD_ARG;
+  const int wcap = range_w_cap(W, mode);
+  const HostStage S(ctx, 16, n, n, a, lda, nullptr, 0, mode == 'A' ? range_z_cap(n, W, mode) : 1, std::max(wcap, 1));
+  const int rc = herm_range_dev(ctx, n, W, S.a, S.ldd, S.w, S.z, S.ldd, mf, mb, mode);
+  const int m = (W.by_value && rc == EIGX_OK) ? (mode == 'C' ? 0 : *W.m_out) : wcap;   // entries that were written
+  if (rc == EIGX_OK || rc == EIGX_ERR_NONFINITE) S.w_back(w, m);
+  if (rc != EIGX_OK) return rc;
+  if (mode == 'A') S.back(z, ldz, S.z, m);
+  S.back(a, lda, S.a, 1, std::min(n, 2));   // statistics only: a is destroyed
+  return EIGX_OK;
+}
+
 }  // namespace eigx
 
 using namespace eigx;
@@ -1230,6 +1364,27 @@ int eigx_h(int n, int nvec, double* a, int lda, double* w, double* z, int ldz, i
 }
 int eigx_h_dev(int n, int nvec, double* a, int lda, double* w, double* z, int ldz, int mf, int mb, char mode) {
   return eigx_guard(g_ctx, [&] { return herm_solve_dev(g_ctx, n, nvec, a, lda, w, z, ldz, mf, mb, mode); });
+}
+
+// EXTENSION: eigenpairs il .. iu of a Hermitian matrix, or those with vl <= lambda < vu (one GPU); see
+// herm_range_dev.  m, il: host pointers in both forms
+int eigx_h_range(int n, int il, int iu, double* a, int lda, double* w, double* z, int ldz, int mf, int mb, char mode) {
+  return eigx_guard(g_ctx, [&] { return herm_range_host(g_ctx, n, RangeWindow::index(il, iu), a, lda, w, z, ldz, mf, mb, mode); });
+}
+int eigx_h_range_dev(int n, int il, int iu, double* a, int lda, double* w, double* z, int ldz, int mf, int mb, char mode) {
+  return eigx_guard(g_ctx, [&] { return herm_range_dev(g_ctx, n, RangeWindow::index(il, iu), a, lda, w, z, ldz, mf, mb, mode); });
+}
+int eigx_h_range_v(int n, double vl, double vu, int mmax, int* m, int* il, double* a, int lda, double* w, double* z, int ldz,
+                   int mf, int mb, char mode) {
+  return eigx_guard(g_ctx, [&] {
+    return herm_range_host(g_ctx, n, RangeWindow::value(vl, vu, mmax, m, il), a, lda, w, z, ldz, mf, mb, mode);
+  });
+}
+int eigx_h_range_v_dev(int n, double vl, double vu, int mmax, int* m, int* il, double* a, int lda, double* w, double* z,
+                       int ldz, int mf, int mb, char mode) {
+  return eigx_guard(g_ctx, [&] {
+    return herm_range_dev(g_ctx, n, RangeWindow::value(vl, vu, mmax, m, il), a, lda, w, z, ldz, mf, mb, mode);
+  });
 }
 
 }

@@ -25,6 +25,7 @@
 #include "eigx_context.h"
 #include "eigx_comm.h"
 #include "../../include/eigenexa_amd.h"
+#include <algorithm>
 #include <string>
 
 namespace eigx {
@@ -202,16 +203,18 @@ int hgev_host(Context& ctx, int n, double* a, int lda, double* b, int ldb, doubl
   return EIGX_OK;
 }
 
-// ---- KMATH_EIGEN_HGEV_RANGE: eigenpairs il .. iu of A x = lambda B x by the Cholesky route (EXTENSION, one GPU) ---------
-// B = U^H U (ztri.hip) -> C = U^-H A U^-1 -> eigen_h(C) with nvec = iu -> Z = U^-1 Y on the columns il .. iu: the complex
+// ---- KMATH_EIGEN_HGEV_RANGE[_V]: eigenpairs il .. iu of A x = lambda B x, or those with vl <= lambda < vu, by the Cholesky
+// route (EXTENSION, one GPU) ------------------------------------------------------------------------------------------------
+// B = U^H U (ztri.hip) -> C = U^-H A U^-1 -> the inner solve of C -> Z = U^-1 Y on the window's columns: the complex
 // sibling of gev_range_dev (gev.hip).  4 (1/3 + 5/3 + m/n) n^3 real flops through the MFMA GEMM and ONE eigen_h where
-// hgev_dev spends 20 n^3 and two.  The inner solve is eigen_h itself, not a Hermitian subset path: its tridiagonal stage
-// is a few percent of it, so with il > 1 the columns 1 .. il - 1 of Y are computed and dropped, and the workspace holds
-// an n x iu complex Y.  B is not scaled (the limitation of gev_range_dev): U carries the square root of B's scale and C
-// its inverse; eigen_h scales C itself, but only once it has been formed.
+// hgev_dev spends 20 n^3 and two.  B is not scaled (the limitation of gev_range_dev): U carries the square root of B's scale
+// and C its inverse; eigen_h scales C itself, but only once it has been formed.
+// By index, the inner solve is eigen_h itself with nvec = iu: with il > 1 the columns 1 .. il - 1 of Y are computed and
+// dropped, and the workspace holds an n x iu complex Y.  By value, it is herm_range_dev (herm.hip) with the same window on
+// C: B is not scaled, so the bounds need no transformation (DESIGN 8e "Generalised"); m is read back and Z = U^-1 Y runs on
+// m columns (not at all for m = 0, 'N' and 'C'); Y holds min(mmax, n) columns.  b holds U whenever the call returns EIGX_OK.
 // Pool buffers: hgevr.u, hgevr.a, hgevr.cp (two planes of pad_ld(n) x n each), hgevr.c (C interleaved), hgevr.y (mode 'A':
-// Y, n x iu complex), hgevr.w (n) and the block inverses and panels of ztri.hip.
-// W is an index window: the C entries build no other (a value form would need the window resolved inside eigen_h).
+// Y), hgevr.w (n, by index) and the block inverses and panels of ztri.hip.
 int hgev_range_dev(Context& ctx, int n, const RangeWindow& W, double* a, int lda, double* b, int ldb, double* w, double* z,
                    int ldz, char mode) {
   if (!ctx.initialized) return EIGX_ERR_NOT_INITIALIZED;
@@ -220,13 +223,17 @@ int hgev_range_dev(Context& ctx, int n, const RangeWindow& W, double* a, int lda
   GevFrame Fr(ctx);
   if (const int rc0 = Fr.begin(range_args_ok(n, W, a, lda, w, z, ldz, mode) && b && ldb >= n)) return rc0;
   hipStream_t st = ctx.stream;
-  const int il = W.il, iu = W.iu, m = W.m();
+  const int wcap = range_w_cap(W, mode);
   // both significant triangles are scanned before anything is factored
-  if (const int rc = eigen_scaling(ctx, a, lda, true, n, w, nullptr, m)) return rc;
-  if (const int rc = eigen_scaling(ctx, b, ldb, true, n, w, nullptr, m)) return rc;
+  int rc = eigen_scaling(ctx, a, lda, true, n, w, nullptr, wcap);
+  if (rc == EIGX_OK) rc = eigen_scaling(ctx, b, ldb, true, n, w, nullptr, wcap);
+  if (rc != EIGX_OK) {
+    if (W.by_value) *W.m_out = 0;
+    return rc;
+  }
   const int ld = pad_ld(n);
   const ZPlanes U = zplanes(ctx, "hgevr.u", ld, n);
-  const ZPlanes A = zplanes(ctx, "hgevr.a", ld, n);     // A, later the columns il .. iu of Y, later Z
+  const ZPlanes A = zplanes(ctx, "hgevr.a", ld, n);     // A, later the window's columns of Y, later Z
   const ZPlanes Cp = zplanes(ctx, "hgevr.cp", ld, n);
   zsplit(st, b, ldb, n, n, true, U, ld);
   if (zchol_upper_dev(ctx, n, U, ld) != EIGX_OK) return report_not_spd(ctx);
@@ -240,16 +247,28 @@ int hgev_range_dev(Context& ctx, int n, const RangeWindow& W, double* a, int lda
   zjoin(st, Cp, ld, n, n, true, c, ldc);
   EIGX_HIP_CHECK(hipStreamSynchronize(st));
   Fr.mark();
-  double* wn = ctx.pool.get_t<double>("hgevr.w", (size_t)n);
-  double* y = mode == 'A' ? ctx.pool.get_t<double>("hgevr.y", (size_t)2 * ldc * iu) : nullptr;
-  const int rc = herm_solve_dev(ctx, n, iu, c, ldc, wn, y, ldc, HG_MF, HG_MB, mode);    // C = Y diag(w) Y^H, the lowest iu
-  if (rc == EIGX_OK || rc == EIGX_ERR_NONFINITE)
-    EIGX_HIP_CHECK(hipMemcpyAsync(w, wn + (il - 1), (size_t)m * 8, hipMemcpyDeviceToDevice, st));
-  EIGX_HIP_CHECK(hipStreamSynchronize(st));
-  if (rc != EIGX_OK) return rc;
+  int m = W.m();
+  const double* ywin = nullptr;   // the window's columns of Y
+  if (W.by_value) {
+    double* y = mode == 'A' ? ctx.pool.get_t<double>("hgevr.y", (size_t)2 * ldc * range_z_cap(n, W, mode)) : nullptr;
+    rc = herm_range_dev(ctx, n, W, c, ldc, w, y, ldc, HG_MF, HG_MB, mode);   // the pairs of C with vl <= lambda < vu
+    if (rc != EIGX_OK) return rc;
+    m = mode == 'C' ? 0 : *W.m_out;
+    ywin = y;
+  } else {
+    const int il = W.il, iu = W.iu;
+    double* wn = ctx.pool.get_t<double>("hgevr.w", (size_t)n);
+    double* y = mode == 'A' ? ctx.pool.get_t<double>("hgevr.y", (size_t)2 * ldc * iu) : nullptr;
+    rc = herm_solve_dev(ctx, n, iu, c, ldc, wn, y, ldc, HG_MF, HG_MB, mode);    // C = Y diag(w) Y^H, the lowest iu
+    if (rc == EIGX_OK || rc == EIGX_ERR_NONFINITE)
+      EIGX_HIP_CHECK(hipMemcpyAsync(w, wn + (il - 1), (size_t)m * 8, hipMemcpyDeviceToDevice, st));
+    EIGX_HIP_CHECK(hipStreamSynchronize(st));
+    if (rc != EIGX_OK) return rc;
+    ywin = y + (size_t)2 * ldc * (il - 1);
+  }
   Fr.mark();
-  if (mode == 'A') {
-    zsplit(st, y + (size_t)2 * ldc * (il - 1), ldc, n, m, false, A, ld);
+  if (mode == 'A' && m > 0) {
+    zsplit(st, ywin, ldc, n, m, false, A, ld);
     ztrsm_upper_dev(ctx, 'N', n, m, U, ld, A, ld, V);   // Z = U^-1 Y
     zjoin(st, A, ld, n, m, false, z, ldz);
     EIGX_HIP_CHECK(hipStreamSynchronize(st));
@@ -263,12 +282,13 @@ int hgev_range_host(Context& ctx, int n, const RangeWindow& W, double* a, int ld
   if (ctx.grid.nranks != 1) return hgev_range_dev(ctx, n, W, a, lda, b, ldb, w, z, ldz, mode);   // refuses
   mode = upper_case(mode);
   if (!range_args_ok(n, W, a, lda, w, z, ldz, mode) || !b || ldb < n) return EIGX_ERR_BAD_ARG;
-  const int m = W.m();
-  const HostStage S(ctx, 16, n, n, a, lda, b, ldb, mode == 'A' ? m : 1, m);
+  const int wcap = range_w_cap(W, mode);
+  const HostStage S(ctx, 16, n, n, a, lda, b, ldb, mode == 'A' ? range_z_cap(n, W, mode) : 1, std::max(wcap, 1));
   const int rc = hgev_range_dev(ctx, n, W, S.a, S.ldd, S.b, S.ldd, S.w, S.z, S.ldd, mode);
+  const int m = (W.by_value && rc == EIGX_OK) ? (mode == 'C' ? 0 : *W.m_out) : wcap;   // entries that were written
   if (rc == EIGX_OK || rc == EIGX_ERR_NONFINITE) S.w_back(w, m);
-  if (rc != EIGX_OK) return rc;
-  if (mode == 'A') S.back(z, ldz, S.z, m);
+  if (rc != EIGX_OK) return rc;   // (EIGX_ERR_WINDOW: a and b are as the caller passed them, ready for the retry by index)
+  if (mode == 'A') S.back(z, ldz, S.z, m);   // (m = 0: nothing)
   S.back(b, ldb, S.b, n);   // U in the upper triangle; a is not returned
   return EIGX_OK;
 }
@@ -292,6 +312,19 @@ int eigx_hgev_range(int n, int il, int iu, double* a, int lda, double* b, int ld
 }
 int eigx_hgev_range_dev(int n, int il, int iu, double* a, int lda, double* b, int ldb, double* w, double* z, int ldz, char mode) {
   return eigx_guard(g_ctx, [&] { return hgev_range_dev(g_ctx, n, RangeWindow::index(il, iu), a, lda, b, ldb, w, z, ldz, mode); });
+}
+// EXTENSION: the eigenpairs with vl <= lambda < vu of the complex problem; m, il: host pointers in both forms
+int eigx_hgev_range_v(int n, double vl, double vu, int mmax, int* m, int* il, double* a, int lda, double* b, int ldb, double* w,
+                      double* z, int ldz, char mode) {
+  return eigx_guard(g_ctx, [&] {
+    return hgev_range_host(g_ctx, n, RangeWindow::value(vl, vu, mmax, m, il), a, lda, b, ldb, w, z, ldz, mode);
+  });
+}
+int eigx_hgev_range_v_dev(int n, double vl, double vu, int mmax, int* m, int* il, double* a, int lda, double* b, int ldb,
+                          double* w, double* z, int ldz, char mode) {
+  return eigx_guard(g_ctx, [&] {
+    return hgev_range_dev(g_ctx, n, RangeWindow::value(vl, vu, mmax, m, il), a, lda, b, ldb, w, z, ldz, mode);
+  });
 }
 
 }  // extern "C"

@@ -266,13 +266,15 @@ __global__ void copy_vec_kernel(const double* __restrict__ src, double* __restri
   if (i < n) dst[i] = src[i];
 }
 
+}  // namespace
+
 // ---- value window -> index window (EXTENSION) ------------------------------------------------------------------------------
 // The eigenvalues with vl <= lambda < vu of the matrix whose band form (d, e) is sigma times the caller's: il = count(sigma vl)
 // + 1, iu = count(sigma vu), count(x) = eigenvalues below x by band_count_dev.  The pentadiagonal count is not strictly
 // monotone in floating point: iu < il - 1 is an empty window like iu = il - 1.  An infinite bound needs no count.  One
 // launch, one 8-byte copy back, one stream synchronisation.
-static void resolve_value_window(Context& ctx, int n, const double* d, const double* e, int lde, int band, double sigma,
-                                 RangeWindow& W) {
+void resolve_value_window(Context& ctx, int n, const double* d, const double* e, int lde, int band, double sigma,
+                          RangeWindow& W) {
   const bool lo_inf = std::isinf(W.vl), hi_inf = std::isinf(W.vu);   // vl < vu: only vl = -Inf, vu = +Inf can be
   int c[2] = {0, n};
   if (!lo_inf || !hi_inf) {
@@ -293,8 +295,6 @@ static void resolve_value_window(Context& ctx, int n, const double* d, const dou
   *W.m_out = W.iu - W.il + 1;
   *W.il_out = W.il;
 }
-
-}  // namespace
 
 // what both entry points of the range solves require of their arguments (mode in upper case).  By value: vl < vu (a NaN
 // fails it), room for at least one eigenpair unless only the count is asked for (mode 'C', value form only: w and z are

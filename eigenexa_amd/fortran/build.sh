@@ -14,6 +14,10 @@ $FC -cpp -O2 -c "$HERE/eigen_libs_mod.F90" -o eigen_libs_mod.o
 $FC -cpp -O2 -c "$HERE/example_frank.F90" -o example_frank.o
 $FC -o example_frank example_frank.o eigen_libs_mod.o -L"$HERE/../lib" -leigenexa_amd -Wl,-rpath,"$HERE/../lib"
 echo "built $OUT/example_frank"
+# the caller of the Hermitian range entries (tests/test_h_range.py runs it on the GPU)
+$FC -cpp -O2 -c "$ROOT/tests/fortran/h_range_caller.F90" -o h_range_caller.o
+$FC -o h_range_caller h_range_caller.o eigen_libs_mod.o -L"$HERE/../lib" -leigenexa_amd -Wl,-rpath,"$HERE/../lib"
+echo "built $OUT/h_range_caller"
 MPI_INC=${MPI_INC:-/opt/conda/include}
 MPI_LIB=${MPI_LIB:-/opt/conda/lib}
 if [ -f "$MPI_INC/mpif.h" ] && ls "$MPI_LIB"/libmpifort.so* >/dev/null 2>&1; then

@@ -33,6 +33,7 @@ module eigen_libs_mod
   public :: eigen_h                   ! complex Hermitian solver (src/eigen_h.F)
   public :: eigen_sx_range, eigen_s_range   ! EXTENSION: eigenpairs il .. iu of the ascending spectrum (one GPU)
   public :: eigen_sx_range_v, eigen_s_range_v   ! EXTENSION: the eigenpairs with vl <= lambda < vu (one GPU)
+  public :: eigen_h_range, eigen_h_range_v   ! EXTENSION: both kinds of window for the complex Hermitian solver (one GPU)
 
   interface
     integer(c_int) function eigx_init(device) bind(C, name="eigx_init")
@@ -160,6 +161,24 @@ module eigen_libs_mod
     integer(c_int) function eigx_h(n, nvec, a, lda, w, z, ldz, mf, mb, mode) bind(C, name="eigx_h")
       import :: c_int, c_double, c_double_complex, c_char
       integer(c_int), value :: n, nvec, lda, ldz, mf, mb
+      complex(c_double_complex) :: a(*), z(*)
+      real(c_double) :: w(*)
+      character(kind=c_char), value :: mode
+    end function
+    ! EXTENSION (not in the reference): index and value windows of the complex Hermitian solver, one GPU
+    integer(c_int) function eigx_h_range(n, il, iu, a, lda, w, z, ldz, mf, mb, mode) bind(C, name="eigx_h_range")
+      import :: c_int, c_double, c_double_complex, c_char
+      integer(c_int), value :: n, il, iu, lda, ldz, mf, mb
+      complex(c_double_complex) :: a(*), z(*)
+      real(c_double) :: w(*)
+      character(kind=c_char), value :: mode
+    end function
+    integer(c_int) function eigx_h_range_v(n, vl, vu, mmax, m, il, a, lda, w, z, ldz, mf, mb, mode) &
+        bind(C, name="eigx_h_range_v")
+      import :: c_int, c_double, c_double_complex, c_char
+      integer(c_int), value :: n, mmax, lda, ldz, mf, mb
+      real(c_double), value :: vl, vu
+      integer(c_int), intent(out) :: m, il
       complex(c_double_complex) :: a(*), z(*)
       real(c_double) :: w(*)
       character(kind=c_char), value :: mode
@@ -787,6 +806,52 @@ contains
     rc = eigx_h(n, nvec, a, lda, w, z, ldz, mf, mb, md)
   end subroutine eigen_h
 
+  !> eigen_h_range(n, il, iu, a, lda, w, z, ldz, m_forward, m_backward, mode) -- EXTENSION, not in the reference:
+  !> eigenpairs il .. iu (1-based, inclusive) of the ascending spectrum of a complex Hermitian matrix on one GPU;
+  !> w(1:iu-il+1), z(:, 1:iu-il+1); modes 'A' and 'N'.  Same contract for a as eigen_h.
+  subroutine eigen_h_range(n, il, iu, a, lda, w, z, ldz, m_forward, m_backward, mode)
+    integer, intent(in) :: n, il, iu, lda, ldz
+    complex(8), intent(inout) :: a(lda, *)
+    real(8), intent(inout) :: w(*)
+    complex(8), intent(inout) :: z(ldz, *)
+    integer, intent(in), optional :: m_forward, m_backward
+    character(*), intent(in), optional :: mode
+    integer :: mf, mb, rc
+    character(kind=c_char) :: md
+    mf = eigen_NB_f; mb = eigen_NB_b; md = 'A'
+    if (present(m_forward)) mf = m_forward
+    if (present(m_backward)) mb = m_backward
+    if (present(mode)) md = mode(1:1)
+    rc = eigx_h_range(n, il, iu, a, lda, w, z, ldz, mf, mb, md)
+  end subroutine eigen_h_range
+
+  !> eigen_h_range_v(n, vl, vu, mmax, m, il, a, lda, w, z, ldz, m_forward, m_backward, mode) -- EXTENSION, not in the
+  !> reference (LAPACK's range = 'V'): the eigenpairs of a complex Hermitian matrix with vl <= lambda < vu on one GPU, at
+  !> the cost of one reduction.  m, il, mmax and the modes ('A', 'N', 'C') as for eigen_sx_range_v: w(1:m), z(:, 1:m) as from
+  !> eigen_h_range(n, il, il + m - 1, ...); m > mmax sets m and il and leaves w, z, a untouched; m = 0 leaves w, z
+  !> untouched; m = -1 when nothing was resolved (bad arguments, no eigen_init, non-finite input).
+  subroutine eigen_h_range_v(n, vl, vu, mmax, m, il, a, lda, w, z, ldz, m_forward, m_backward, mode)
+    integer, intent(in) :: n, mmax, lda, ldz
+    real(8), intent(in) :: vl, vu
+    integer, intent(out) :: m, il
+    complex(8), intent(inout) :: a(lda, *)
+    real(8), intent(inout) :: w(*)
+    complex(8), intent(inout) :: z(ldz, *)
+    integer, intent(in), optional :: m_forward, m_backward
+    character(*), intent(in), optional :: mode
+    integer :: mf, mb, rc
+    integer(c_int) :: mc, ilc
+    character(kind=c_char) :: md
+    mf = eigen_NB_f; mb = eigen_NB_b; md = 'A'
+    if (present(m_forward)) mf = m_forward
+    if (present(m_backward)) mb = m_backward
+    if (present(mode)) md = mode(1:1)
+    mc = 0; ilc = 0
+    rc = eigx_h_range_v(n, vl, vu, mmax, mc, ilc, a, lda, w, z, ldz, mf, mb, md)
+    m = mc; il = ilc
+    if (rc /= 0 .and. rc /= -9) m = -1
+  end subroutine eigen_h_range_v
+
 end module eigen_libs_mod
 
 #if defined(EIGX_WITH_BLACS) && defined(EIGX_WITH_MPI)
@@ -967,3 +1032,40 @@ subroutine KMATH_EIGEN_HGEV_RANGE(n, il, iu, a, lda, b, ldb, w, z, ldz, mode)
   rc = eigx_hgev_range(int(n, c_int), int(il, c_int), int(iu, c_int), a, int(lda, c_int), b, int(ldb, c_int), w, z, &
                        int(ldz, c_int), md)
 end subroutine KMATH_EIGEN_HGEV_RANGE
+
+! KMATH_EIGEN_HGEV_RANGE_V -- EXTENSION, not in the reference: the eigenpairs of the complex Hermitian-definite problem
+! A x = lambda B x with vl <= lambda < vu by the Cholesky route of KMATH_EIGEN_HGEV_RANGE on one GPU, with eigen_h_range_v as
+! the inner solve.  m, il, mmax and the modes ('A', 'N', 'C') as for eigen_sx_range_v of module eigen_libs_mod: w(1:m)
+! ascending, z(:, 1:m) with z^H B z = I; m > mmax sets m and il and leaves a, b, w, z as they were; m = -1 when nothing was
+! resolved.  External like KMATH_EIGEN_HGEV_RANGE.
+subroutine KMATH_EIGEN_HGEV_RANGE_V(n, vl, vu, mmax, m, il, a, lda, b, ldb, w, z, ldz, mode)
+  use, intrinsic :: iso_c_binding
+  implicit none
+  integer, intent(in) :: n, mmax, lda, ldb, ldz
+  real(8), intent(in) :: vl, vu
+  integer, intent(out) :: m, il
+  complex(8), intent(inout) :: a(lda, *), b(ldb, *), z(ldz, *)
+  real(8), intent(inout) :: w(*)
+  character(*), intent(in), optional :: mode
+  interface
+    integer(c_int) function eigx_hgev_range_v(n, vl, vu, mmax, m, il, a, lda, b, ldb, w, z, ldz, mode) &
+        bind(C, name="eigx_hgev_range_v")
+      import :: c_int, c_double, c_double_complex, c_char
+      integer(c_int), value :: n, mmax, lda, ldb, ldz
+      real(c_double), value :: vl, vu
+      integer(c_int), intent(out) :: m, il
+      complex(c_double_complex), intent(inout) :: a(lda, *), b(ldb, *), z(ldz, *)
+      real(c_double), intent(inout) :: w(*)
+      character(kind=c_char), value :: mode
+    end function
+  end interface
+  integer(c_int) :: rc, mc, ilc
+  character(kind=c_char) :: md
+  md = 'A'
+  if (present(mode)) md = mode(1:1)
+  mc = 0; ilc = 0
+  rc = eigx_hgev_range_v(int(n, c_int), real(vl, c_double), real(vu, c_double), int(mmax, c_int), mc, ilc, a, int(lda, c_int), &
+                         b, int(ldb, c_int), w, z, int(ldz, c_int), md)
+  m = mc; il = ilc
+  if (rc /= 0 .and. rc /= -9) m = -1
+end subroutine KMATH_EIGEN_HGEV_RANGE_V

@@ -27,7 +27,8 @@
  * of the ascending spectrum, one GPU), eigx_gev_range[_dev] (KMATH_EIGEN_GEV_RANGE, an extension: eigenpairs il .. iu of
  * the generalised problem by the Cholesky route, one GPU), eigx_hgev_range[_dev] (KMATH_EIGEN_HGEV_RANGE, an extension: the
  * same for the complex Hermitian generalised problem, one GPU), eigx_sx_range_v / eigx_s_range_v / eigx_gev_range_v[_dev] (an
- * extension: the eigenpairs with vl <= lambda < vu of the real solvers, LAPACK's range = 'V', one GPU) and the stage entry
+ * extension: the eigenpairs with vl <= lambda < vu of the real solvers, LAPACK's range = 'V', one GPU), eigx_h_range[_v] and
+ * eigx_hgev_range_v[_dev] (an extension: both kinds of window for the complex Hermitian solvers, one GPU) and the stage entry
  * eigx_band_count_dev (Sturm counts of a band matrix at caller-given points).
  */
 #ifndef EIGENEXA_AMD_H
@@ -266,6 +267,31 @@ int eigx_numroc(int n, int nb, int iproc, int nprocs);
 int eigx_h(int n, int nvec, double* a, int lda, double* w, double* z, int ldz, int m_forward, int m_backward, char mode);
 int eigx_h_dev(int n, int nvec, double* a_dev, int lda, double* w_dev, double* z_dev, int ldz, int m_forward,
                int m_backward, char mode);
+/* eigen_h range solves -- EXTENSION, not in the reference (csrc/herm.hip herm_range_dev): eigenpairs
+ * il .. iu of the ascending spectrum of a complex Hermitian matrix (eigx_h_range), or those with vl <= lambda < vu
+ * (eigx_h_range_v).  The contracts of eigx_s_range and eigx_s_range_v above, word for word, on the storage of eigx_h: a, z
+ * complex(8) as interleaved (re, im) doubles, lda / ldz in COMPLEX elements, upper triangle of a significant (Im of the
+ * diagonal ignored), a destroyed with a(1,1) = flops, a(2,1) = seconds; w real.  One GPU only: with more than one rank
+ * the entries print one line and return EIGX_ERR_BAD_ARG.  mode 'A' eigenpairs, 'N' eigenvalues only (z may be NULL), by
+ * value also 'C' (count only); eigen_h's modes 'X' and 'S' are not offered (EIGX_ERR_BAD_ARG).  w(1:m), z(:, 1:m) with
+ * z^H z = I_m; nothing beyond m entries / columns is touched.  NaN / Inf in the significant triangle: EIGX_ERR_NONFINITE,
+ * w(1:m) (by value: w(1:mmax)) = NaN, *m = 0.  By value: the half-open window, mmax, *m, *il (host pointers in the host AND
+ * the device forms), m = 0, EIGX_ERR_WINDOW and mode 'C' exactly as for eigx_s_range_v; the window is resolved on the real
+ * tridiagonal matrix of eigen_hrd after ONE reduction, and w, z are bit-identical to the index call il .. iu.
+ * Method: eigen_scaling_h, eigen_hrd and the T factors as eigx_h -> Sturm multi-section on the window -> inverse iteration
+ * + CholQR2 + Rayleigh-Ritz on the real tridiagonal matrix (csrc/subset.hip, written straight into the real plane of m
+ * columns; path 1) or the full divide and conquer with nvec = iu, of which the window is a pointer offset (path 3 by the
+ * size rule of key 17, path 2 after a refusal by the acceptance test of key 19) -> eigen_hrbakwyx on the m columns.
+ * eigx_range_info / eigx_range_timers are written as by the real range entries; eigx_get_timers as by eigx_h.  Inherits
+ * eigen_h's overflow above a matrix scale of about 1e77. */
+int eigx_h_range(int n, int il, int iu, double* a, int lda, double* w, double* z, int ldz, int m_forward, int m_backward,
+                 char mode);
+int eigx_h_range_dev(int n, int il, int iu, double* a_dev, int lda, double* w_dev, double* z_dev, int ldz, int m_forward,
+                     int m_backward, char mode);
+int eigx_h_range_v(int n, double vl, double vu, int mmax, int* m, int* il, double* a, int lda, double* w, double* z, int ldz,
+                   int m_forward, int m_backward, char mode);
+int eigx_h_range_v_dev(int n, double vl, double vu, int mmax, int* m, int* il, double* a_dev, int lda, double* w_dev,
+                       double* z_dev, int ldz, int m_forward, int m_backward, char mode);
 
 /* ---- stage entry points (device arrays; used by the parity tests and the profiler) ---------- */
 
@@ -329,7 +355,7 @@ int eigx_gev_range_dev(int n, int il, int iu, double* a_dev, int lda, double* b_
  * generalised ones), and the back-substitution runs on the m columns found -- not at all for m = 0, modes 'N' and 'C'.
  * b holds U on exit whenever the call returns EIGX_OK; on EIGX_ERR_WINDOW the host form leaves a and b as they were
  * passed, the device form has destroyed a and holds U in b.  eigx_get_timers [0..4] as for eigx_gev_range.  The complex
- * solver eigx_hgev_range has no value form (its inner solve has no index window to resolve into). */
+ * sibling is eigx_hgev_range_v below. */
 int eigx_gev_range_v(int n, double vl, double vu, int mmax, int* m, int* il, double* a, int lda, double* b, int ldb, double* w,
                      double* z, int ldz, char mode);
 int eigx_gev_range_v_dev(int n, double vl, double vu, int mmax, int* m, int* il, double* a_dev, int lda, double* b_dev,
@@ -366,6 +392,19 @@ int eigx_gev_reduce_dev(int n, double* a_dev, int lda, const double* u_dev, int 
 int eigx_hgev_range(int n, int il, int iu, double* a, int lda, double* b, int ldb, double* w, double* z, int ldz, char mode);
 int eigx_hgev_range_dev(int n, int il, int iu, double* a_dev, int lda, double* b_dev, int ldb, double* w_dev, double* z_dev,
                         int ldz, char mode);
+/* KMATH_EIGEN_HGEV_RANGE_V -- EXTENSION, not in the reference: the eigenpairs of the complex problem
+ * A x = lambda B x with vl <= lambda < vu; eigx_hgev_range with the window protocol of eigx_sx_range_v (vl, vu, mmax, *m,
+ * *il as host pointers in both forms, mode 'C', m = 0, EIGX_ERR_WINDOW, statuses).  B is factored and C formed as in
+ * eigx_hgev_range; the value window goes to eigx_h_range_v_dev on C (B is not scaled, so C's eigenvalues are the
+ * generalised ones): ONE Hermitian reduction, the window's m columns of Y only, and eigx_range_info / eigx_range_timers
+ * report on that inner call.  The back-substitution runs on the m columns found -- not at all for m = 0, modes 'N' and
+ * 'C'.  b holds U whenever the call returns EIGX_OK; on EIGX_ERR_WINDOW the host form leaves a and b as they were passed,
+ * the device form has destroyed a and holds U in b.  B not positive definite: EIGX_ERR_NOT_SPD, *m untouched.  The result
+ * agrees with eigx_hgev_range on the resolved window to rounding, not bit for bit (the inner routes differ). */
+int eigx_hgev_range_v(int n, double vl, double vu, int mmax, int* m, int* il, double* a, int lda, double* b, int ldb, double* w,
+                      double* z, int ldz, char mode);
+int eigx_hgev_range_v_dev(int n, double vl, double vu, int mmax, int* m, int* il, double* a_dev, int lda, double* b_dev,
+                          int ldb, double* w_dev, double* z_dev, int ldz, char mode);
 /* Its stages (one GPU, device arrays of interleaved complex(8), any leading dimension >= n in complex elements, LAPACK
  * uplo = 'U'; NB = eigx_tune key 20, shared with the real stages).
  * eigx_zchol_dev: B = U^H U, U in place in the upper triangle with a real positive diagonal (Im written as 0); nothing
