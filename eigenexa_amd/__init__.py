@@ -29,6 +29,7 @@ from .api import (  # noqa: F401
     eigen_s_range,
     eigen_sx_range_v,
     eigen_s_range_v,
+    eigen_s_batch,
     band_count,
     range_info,
     eigen_sx_bc,

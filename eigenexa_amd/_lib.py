@@ -122,6 +122,11 @@ SIGNATURES = {
                                     C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_char]),
     "eigx_hgev_range_v_dev": (C.c_int, [C.c_int, C.c_double, C.c_double, C.c_int, _c_int_p, _c_int_p, C.c_void_p, C.c_int,
                                         C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_char]),
+    # extension: many small symmetric matrices in one call (csrc/batch.hip); strides are int64_t, info int*
+    "eigx_s_batch": (C.c_int, [C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_int, C.c_void_p, C.c_int,
+                               C.c_int64, C.c_char, C.c_void_p]),
+    "eigx_s_batch_dev": (C.c_int, [C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_int, C.c_void_p, C.c_int,
+                                   C.c_int64, C.c_char, C.c_void_p]),
     "eigx_zchol_dev": (C.c_int, [C.c_int, C.c_void_p, C.c_int]),
     "eigx_ztrsm_upper_dev": (C.c_int, [C.c_char, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int]),
     "eigx_hgev_reduce_dev": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int]),

@@ -296,6 +296,67 @@ def eigen_s_range(n, il, iu, a, lda, w, z, ldz, m_forward=None, m_backward=None,
     _solve_range("s", n, il, iu, a, lda, w, z, ldz, m_forward, m_backward, mode)
 
 
+def eigen_s_batch(n, batch, a, lda, w, z, ldz, mode="A", info=None, stride_a=None, ldw=None, stride_z=None):
+    """EXTENSION (not in the reference): ``batch`` symmetric matrices of one size ``n`` in one call, one GPU.  ``a`` holds the
+    matrices as ``a[lda, n, batch]`` (numpy, Fortran order) or a GPU tensor with the same memory image: matrix ``k`` starts at
+    element ``k * stride_a``, upper triangle significant, destroyed.  ``w[ldw, batch]`` receives the ascending eigenvalues,
+    ``z[ldz, n, batch]`` the eigenvectors (mode 'A'; mode 'N': eigenvalues only, ``z`` may be None).  Defaults:
+    ``stride_a = lda * n``, ``stride_z = ldz * n``, ``ldw = n``.  ``info`` (optional, int32, ``batch`` entries, on the side of
+    ``a``) receives the per-matrix status: 0, -5 (NaN / Inf in the matrix: its ``w`` is NaN, its ``z`` untouched) or -6;
+    ``last_status()`` is 0 or the status of the first failed matrix.  For ``n <= 128`` one kernel launch solves the batch,
+    one workgroup per matrix with the matrix in LDS; larger ``n`` runs ``eigen_s`` matrix by matrix."""
+    # the arguments are checked here, before the library is touched (status -2 = EIGX_ERR_BAD_ARG)
+    md = _char(mode, "A").upper()
+    try:
+        n, batch, lda = int(n), int(batch), int(lda)
+        ldw = n if ldw is None else int(ldw)
+        ldz = int(ldz) if md == b"A" else (0 if ldz is None else int(ldz))
+        stride_a = lda * n if stride_a is None else int(stride_a)
+        stride_z = ldz * n if stride_z is None else int(stride_z)
+        ok = n >= 1 and batch >= 0 and lda >= n and ldw >= n and md in (b"A", b"N") and a is not None and w is not None
+        ok = ok and (batch <= 1 or stride_a >= lda * n)
+        if md == b"A":
+            ok = ok and z is not None and ldz >= n and (batch <= 1 or stride_z >= ldz * n)
+    except (TypeError, ValueError):
+        ok = False
+    if not ok:
+        _state["last_status"] = -2
+        print(f"Warning: eigen_s_batch: invalid arguments (n={n}, batch={batch}, lda={lda}, ldw={ldw}, ldz={ldz}, "
+              f"stride_a={stride_a}, stride_z={stride_z}, mode={mode!r})", file=sys.stderr)
+        return
+    lib = _lib.load()
+    if not _state["initialized"]:
+        _state["last_status"] = -1
+        return
+    dev = _is_torch(a)
+    if dev:
+        import torch
+
+        torch.cuda.current_stream().synchronize()
+    for x, name in ((a, "a"), (w, "w"), (z if md == b"A" else None, "z")):
+        if x is not None and not dev and x.ndim > 2 and not x.flags.f_contiguous:
+            raise ValueError(f"{name}: Fortran (column-major) order required, as in the reference")
+    pa, pw = _ptr(a, "a", dev), _ptr(w, "w", dev)
+    pz = _ptr(z, "z", dev) if md == b"A" else None
+    pi = None
+    if info is not None:
+        if dev != _is_torch(info):
+            raise ValueError("a, w, z, info must all be host arrays or all be device tensors")
+        if dev:
+            if not info.is_cuda or info.dtype != torch.int32:
+                raise ValueError("info: int32 GPU tensor required")
+            pi = info.data_ptr()
+        else:
+            if info.dtype != np.int32:
+                raise ValueError("info: int32 required")
+            pi = info.ctypes.data
+    fn = lib.eigx_s_batch_dev if dev else lib.eigx_s_batch
+    rc = fn(n, batch, pa, lda, stride_a, pw, ldw, pz, ldz, stride_z, md, pi)
+    _state["last_status"] = rc
+    if rc not in (0, -5, -6):
+        print(f"Warning: eigen_s_batch returned without computing (status {rc})", file=sys.stderr)
+
+
 def _value_window(name, n, vl, vu, w, z, mode, mmax):
     """checks of the value-window wrappers, made before the library is touched: (mode byte, mmax) or None (status -2)"""
     md = _char(mode, "A").upper()

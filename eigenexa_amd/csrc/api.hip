@@ -1,5 +1,5 @@
 // api.hip -- C-ABI entry points (include/eigenexa_amd.h): life cycle, queries, memory helpers.
-// The solver entry points live in solver.hip, gev.hip, hgev.hip and herm.hip.
+// The solver entry points live in solver.hip, gev.hip, hgev.hip, herm.hip and batch.hip.
 #include "eigx_context.h"
 #include "eigx_comm.h"
 #include "../../include/eigenexa_amd.h"
@@ -368,6 +368,7 @@ int eigx_tune(int key, int value) {
   if (key == 16) return set_dc_batch(value);   // D&C on one GPU: one product launch per low height
   if (key == 17 || key == 18 || key == 19) return set_range_knob(key, value);   // index-range solves (subset.hip)
   if (key == 20) return set_tri_nb(value);     // outer block width of the triangular stages (tri.hip)
+  if (key == 21) return set_batch_nmax(value); // largest n served by the batch kernel of eigx_s_batch (batch.hip)
   return -1;
 }
 

@@ -154,5 +154,7 @@ int set_dc_chunk(int v);
 // lab switches (eigx_tune keys 15, 16): pipelined D&C passes / one product launch per low height (one GPU)
 int set_dc_pipe(int v);
 int set_dc_batch(int v);
+// tuning hook (eigx_tune key 21, batch.hip): largest n served by the batch kernel of eigx_s_batch, 0 .. EIGX_BATCH_NMAX
+int set_batch_nmax(int v);
 
 }  // namespace eigx

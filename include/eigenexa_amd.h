@@ -28,8 +28,9 @@
  * the generalised problem by the Cholesky route, one GPU), eigx_hgev_range[_dev] (KMATH_EIGEN_HGEV_RANGE, an extension: the
  * same for the complex Hermitian generalised problem, one GPU), eigx_sx_range_v / eigx_s_range_v / eigx_gev_range_v[_dev] (an
  * extension: the eigenpairs with vl <= lambda < vu of the real solvers, LAPACK's range = 'V', one GPU), eigx_h_range[_v] and
- * eigx_hgev_range_v[_dev] (an extension: both kinds of window for the complex Hermitian solvers, one GPU) and the stage entry
- * eigx_band_count_dev (Sturm counts of a band matrix at caller-given points).
+ * eigx_hgev_range_v[_dev] (an extension: both kinds of window for the complex Hermitian solvers, one GPU), eigx_s_batch[_dev]
+ * (an extension: many small symmetric matrices in one call, one GPU) and the stage entry eigx_band_count_dev (Sturm counts of a
+ * band matrix at caller-given points).
  */
 #ifndef EIGENEXA_AMD_H
 #define EIGENEXA_AMD_H
@@ -243,6 +244,39 @@ int eigx_sx_range_v_dev(int n, double vl, double vu, int mmax, int* m, int* il, 
                         int ldz, int m_forward, int m_backward, char mode);
 int eigx_s_range_v_dev(int n, double vl, double vu, int mmax, int* m, int* il, double* a, int lda, double* w, double* z,
                        int ldz, int m_forward, int m_backward, char mode);
+
+/* Batched small symmetric eigensolves -- EXTENSION, not in the reference (which solves one large matrix per call): `batch`
+ * symmetric matrices of one size n, each solved completely (LAPACK callers know the per-matrix operation as dsyev; vendor
+ * libraries call this form "strided batched").  One GPU only: with more than one rank the two entries print the line of the
+ * range entries and return EIGX_ERR_BAD_ARG.
+ * Storage: matrix k (0-based) is a + k stride_a, column-major with leading dimension lda; its eigenvalues come back in
+ * w + k ldw, ascending; its orthonormal eigenvectors in z + k stride_z with leading dimension ldz.  Strides and leading
+ * dimensions are in doubles.  The upper triangle of each matrix is significant (the strict lower triangle and the rows
+ * beyond n may hold anything, NaN included); a is destroyed (contents unspecified, no statistics); a and z do not overlap.
+ * Only w(1:n) and z(1:n, 1:n) of each matrix are written: rows of z beyond n, entries of w beyond n and the gaps between
+ * matrices are left untouched.
+ * mode 'A' eigenpairs, 'N' eigenvalues only (z may be NULL; ldz and stride_z are ignored); anything else is
+ * EIGX_ERR_BAD_ARG.  EIGX_ERR_BAD_ARG also unless n >= 1, batch >= 0, lda >= n, ldw >= n, stride_a >= lda n where batch > 1,
+ * and in mode 'A' ldz >= n, stride_z >= ldz n where batch > 1.  batch = 0 returns EIGX_OK and touches nothing.
+ * Per-matrix status: info[k] = 0, EIGX_ERR_NONFINITE (a NaN / Inf in the upper triangle: w(:, k) = NaN, z(:, :, k) untouched)
+ * or EIGX_ERR_INTERNAL (the QL iteration used up its 30 n iterations, the budget of LAPACK's dsteqr: w(:, k) = NaN,
+ * z(:, :, k) unspecified).  info may be NULL; in the _dev form it is a device int array.  A failed matrix never disturbs the others;
+ * the call returns EIGX_OK or the code of the failed matrix with the lowest index.
+ * Method (csrc/batch.hip): for n <= EIGX_BATCH_NMAX one launch, one workgroup per matrix, the matrix in
+ * LDS from load to store: scaling by the rule of eigx_sx (each matrix by its own max|a|; scales of 1e120 and 1e-120 may sit
+ * in one batch), Householder tridiagonalisation with Q accumulated in place, implicit QL with Wilkinson shift, sort.  No
+ * workgroup waits for another.  The arithmetic of a matrix depends on n alone: the result at position k of a batch is bit
+ * for bit that of the matrix solved alone, and two runs agree bit for bit.  n above the cutoff (eigx_tune key 21, default
+ * EIGX_BATCH_NMAX): the entry calls eigx_s_dev(n, nvec = n, ..., m_forward = 48, m_backward = 128, mode) matrix by matrix,
+ * so every n works and such a matrix gets the result (a(1:3,1) included) that eigx_s_dev gives.
+ * The device form waits on the default stream on entry and returns after the result is complete.  eigx_get_timers [0] = the
+ * seconds of the call, the rest 0.  Workspace: none beyond the status words (pool buffers "batch.*"); the host form stages
+ * a, z and w through the pool buffers of the other host forms. */
+#define EIGX_BATCH_NMAX 128
+int eigx_s_batch(int n, int batch, double* a, int lda, int64_t stride_a, double* w, int ldw, double* z, int ldz,
+                 int64_t stride_z, char mode, int* info);
+int eigx_s_batch_dev(int n, int batch, double* a_dev, int lda, int64_t stride_a, double* w_dev, int ldw, double* z_dev, int ldz,
+                     int64_t stride_z, char mode, int* info_dev);
 
 /* ScaLAPACK interop without a redistribution step.  The reference asks block-cyclic callers to
  * convert with pdgemr2d into its cyclic layout first (manual 3.4; benchmark/ev_test.f:68-84 does the reverse for the
@@ -495,7 +529,10 @@ int eigx_profile_read_kinds(double* out, int nkinds);
  * key 19 = log10 of the acceptance bound on cond(L) (default 6; exists so that a test can force the fallback at a small
  * size, like keys 7-9; 0 .. 16); values outside the stated ranges of keys 17 - 19 are refused.  key 20 = outer block
  * width NB of the triangular stages of eigx_gev_range (csrc/tri.hip): a multiple of 64 from 64 to 1024 (default 256), other
- * values are refused; like keys 7-9 it lets tests reach the multi-panel paths at small n.  Returns the previous value, or
+ * values are refused; like keys 7-9 it lets tests reach the multi-panel paths at small n.  key 21 = largest n that
+ * eigx_s_batch serves with its batch kernel (0 .. EIGX_BATCH_NMAX, default EIGX_BATCH_NMAX by the measured table of DESIGN
+ * section 8h; other values are refused): larger matrices go through eigx_s_dev one by one, and a test reaches that path at a
+ * small n by lowering the key.  Returns the previous value, or
  * -1 for an unknown key or a refused value.
  * Not part of the reference's interface. */
 int eigx_tune(int key, int value);
