@@ -30,6 +30,7 @@ from .api import (  # noqa: F401
     eigen_sx_range_v,
     eigen_s_range_v,
     eigen_s_batch,
+    eigen_h_batch,
     band_count,
     range_info,
     eigen_sx_bc,

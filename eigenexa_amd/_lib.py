@@ -127,6 +127,11 @@ SIGNATURES = {
                                C.c_int64, C.c_char, C.c_void_p]),
     "eigx_s_batch_dev": (C.c_int, [C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_int, C.c_void_p, C.c_int,
                                    C.c_int64, C.c_char, C.c_void_p]),
+    # extension: many small complex Hermitian matrices in one call (csrc/hbatch.hip); a, z interleaved complex
+    "eigx_h_batch": (C.c_int, [C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_int, C.c_void_p, C.c_int,
+                               C.c_int64, C.c_char, C.c_void_p]),
+    "eigx_h_batch_dev": (C.c_int, [C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_int, C.c_void_p, C.c_int,
+                                   C.c_int64, C.c_char, C.c_void_p]),
     "eigx_zchol_dev": (C.c_int, [C.c_int, C.c_void_p, C.c_int]),
     "eigx_ztrsm_upper_dev": (C.c_int, [C.c_char, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int]),
     "eigx_hgev_reduce_dev": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int]),

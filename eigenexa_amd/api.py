@@ -760,6 +760,64 @@ def eigen_h_range(n, il, iu, a, lda, w, z, ldz, m_forward=None, m_backward=None,
         print(f"Warning: eigen_h_range returned without computing (status {rc})", file=sys.stderr)
 
 
+def eigen_h_batch(n, batch, a, lda, w, z, ldz, mode="A", info=None, stride_a=None, ldw=None, stride_z=None):
+    """EXTENSION (not in the reference): ``batch`` complex Hermitian matrices of one size ``n`` in one call, one GPU -- the
+    complex sibling of ``eigen_s_batch``.  ``a`` holds the matrices as ``a[lda, n, batch]`` (complex128 numpy, Fortran order)
+    or a complex128 GPU tensor with the same memory image: matrix ``k`` starts at complex element ``k * stride_a``, upper
+    triangle significant (of the diagonal the real parts only), destroyed.  ``w[ldw, batch]`` (float64) receives the ascending
+    eigenvalues, ``z[ldz, n, batch]`` (complex128) the orthonormal eigenvectors (mode 'A'; mode 'N': eigenvalues only, ``z``
+    may be None).  Defaults, ``info`` and ``last_status()`` as for ``eigen_s_batch``; leading dimensions and strides count
+    complex elements.  For ``n <= 96`` one kernel launch solves the batch, one workgroup per matrix with the matrix in LDS;
+    larger ``n`` runs ``eigen_h`` matrix by matrix."""
+    # the arguments are checked here, before the library is touched (status -2 = EIGX_ERR_BAD_ARG)
+    md = _char(mode, "A").upper()
+    try:
+        n, batch, lda = int(n), int(batch), int(lda)
+        ldw = n if ldw is None else int(ldw)
+        ldz = int(ldz) if md == b"A" else (0 if ldz is None else int(ldz))
+        stride_a = lda * n if stride_a is None else int(stride_a)
+        stride_z = ldz * n if stride_z is None else int(stride_z)
+        ok = n >= 1 and batch >= 0 and lda >= n and ldw >= n and md in (b"A", b"N") and a is not None and w is not None
+        ok = ok and (batch <= 1 or stride_a >= lda * n)
+        if md == b"A":
+            ok = ok and z is not None and ldz >= n and (batch <= 1 or stride_z >= ldz * n)
+    except (TypeError, ValueError):
+        ok = False
+    if not ok:
+        _state["last_status"] = -2
+        print(f"Warning: eigen_h_batch: invalid arguments (n={n}, batch={batch}, lda={lda}, ldw={ldw}, ldz={ldz}, "
+              f"stride_a={stride_a}, stride_z={stride_z}, mode={mode!r})", file=sys.stderr)
+        return
+    began = _complex_call_begins(a)
+    if began is None:
+        return
+    lib, dev = began
+    for x, name in ((a, "a"), (w, "w"), (z if md == b"A" else None, "z")):
+        if x is not None and not dev and not _is_torch(x) and x.ndim > 2 and not x.flags.f_contiguous:
+            raise ValueError(f"{name}: Fortran (column-major) order required, as in the reference")
+    pa, pw = _cptr(a, "a", dev), _cptr(w, "w", dev, real=True)
+    pz = _cptr(z, "z", dev) if md == b"A" else None
+    pi = None
+    if info is not None:
+        if dev != _is_torch(info):
+            raise ValueError("a, w, z, info must all be host arrays or all be device tensors")
+        if dev:
+            import torch
+
+            if not info.is_cuda or info.dtype != torch.int32:
+                raise ValueError("info: int32 GPU tensor required")
+            pi = info.data_ptr()
+        else:
+            if info.dtype != np.int32:
+                raise ValueError("info: int32 required")
+            pi = info.ctypes.data
+    fn = lib.eigx_h_batch_dev if dev else lib.eigx_h_batch
+    rc = fn(n, batch, pa, lda, stride_a, pw, ldw, pz, ldz, stride_z, md, pi)
+    _state["last_status"] = rc
+    if rc not in (0, -5, -6):
+        print(f"Warning: eigen_h_batch returned without computing (status {rc})", file=sys.stderr)
+
+
 def eigen_h_range_v(n, vl, vu, a, lda, w, z, ldz, m_forward=None, m_backward=None, mode="A", mmax=None):
     """EXTENSION (not in the reference; LAPACK's range = 'V'): the eigenpairs of a complex Hermitian matrix with
     ``vl <= lambda < vu``, one GPU, at the cost of ONE reduction.  Arrays as for ``eigen_h``; window, ``mmax``, modes

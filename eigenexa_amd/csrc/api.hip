@@ -1,5 +1,5 @@
 // api.hip -- C-ABI entry points (include/eigenexa_amd.h): life cycle, queries, memory helpers.
-// The solver entry points live in solver.hip, gev.hip, hgev.hip, herm.hip and batch.hip.
+// The solver entry points live in solver.hip, gev.hip, hgev.hip, herm.hip, batch.hip and hbatch.hip.
 #include "eigx_context.h"
 #include "eigx_comm.h"
 #include "../../include/eigenexa_amd.h"
@@ -369,6 +369,7 @@ int eigx_tune(int key, int value) {
   if (key == 17 || key == 18 || key == 19) return set_range_knob(key, value);   // index-range solves (subset.hip)
   if (key == 20) return set_tri_nb(value);     // outer block width of the triangular stages (tri.hip)
   if (key == 21) return set_batch_nmax(value); // largest n served by the batch kernel of eigx_s_batch (batch.hip)
+  if (key == 22) return set_hbatch_nmax(value);   // the same for eigx_h_batch (hbatch.hip)
   return -1;
 }
 

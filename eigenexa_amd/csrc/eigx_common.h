@@ -156,5 +156,7 @@ int set_dc_pipe(int v);
 int set_dc_batch(int v);
 // tuning hook (eigx_tune key 21, batch.hip): largest n served by the batch kernel of eigx_s_batch, 0 .. EIGX_BATCH_NMAX
 int set_batch_nmax(int v);
+// tuning hook (eigx_tune key 22, hbatch.hip): largest n served by the batch kernel of eigx_h_batch, 0 .. EIGX_HBATCH_NMAX
+int set_hbatch_nmax(int v);
 
 }  // namespace eigx

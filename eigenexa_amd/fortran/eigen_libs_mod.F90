@@ -35,6 +35,7 @@ module eigen_libs_mod
   public :: eigen_sx_range_v, eigen_s_range_v   ! EXTENSION: the eigenpairs with vl <= lambda < vu (one GPU)
   public :: eigen_h_range, eigen_h_range_v   ! EXTENSION: both kinds of window for the complex Hermitian solver (one GPU)
   public :: eigen_s_batch   ! EXTENSION: many small symmetric matrices in one call (one GPU)
+  public :: eigen_h_batch   ! EXTENSION: many small complex Hermitian matrices in one call (one GPU)
 
   interface
     integer(c_int) function eigx_init(device) bind(C, name="eigx_init")
@@ -139,6 +140,19 @@ module eigen_libs_mod
       integer(c_int64_t), value :: stride_a, stride_z
       real(c_double), intent(inout) :: a(*)
       real(c_double), intent(inout) :: w(*), z(*)
+      character(kind=c_char), value :: mode
+      integer(c_int), intent(out), optional :: info(*)
+    end function
+    ! EXTENSION (not in the reference): batch complex Hermitian matrices of one size, one GPU; leading dimensions and strides
+    ! in complex elements; info may be absent (NULL)
+    integer(c_int) function eigx_h_batch(n, batch, a, lda, stride_a, w, ldw, z, ldz, stride_z, mode, info) &
+        bind(C, name="eigx_h_batch")
+      import :: c_int, c_int64_t, c_double, c_double_complex, c_char
+      integer(c_int), value :: n, batch, lda, ldw, ldz
+      integer(c_int64_t), value :: stride_a, stride_z
+      complex(c_double_complex), intent(inout) :: a(*)
+      real(c_double), intent(inout) :: w(*)
+      complex(c_double_complex), intent(inout) :: z(*)
       character(kind=c_char), value :: mode
       integer(c_int), intent(out), optional :: info(*)
     end function
@@ -697,6 +711,26 @@ contains
     rc = eigx_s_batch(n, batch, a, lda, int(lda, c_int64_t) * size(a, 2), w, size(w, 1), z, ldz, &
                       int(ldz, c_int64_t) * size(z, 2), md, info)
   end subroutine eigen_s_batch
+
+  !> eigen_h_batch(n, batch, a, lda, w, z, ldz, mode, info) -- EXTENSION, not in the reference: the eigenpairs of batch complex
+  !> Hermitian matrices a(:, :, k) of one size n on one GPU, in one kernel launch for n <= 96 (one workgroup per matrix, the
+  !> matrix in LDS).  Upper triangles significant (of the diagonal the real parts), a destroyed; w(1:n, k) real and ascending,
+  !> z(1:n, 1:n, k) orthonormal; modes 'A' and 'N' (z not written).  info(k) = 0, or the status of matrix k (-5: NaN / Inf,
+  !> w(:, k) = NaN); the other matrices are solved all the same.
+  subroutine eigen_h_batch(n, batch, a, lda, w, z, ldz, mode, info)
+    integer, intent(in) :: n, batch, lda, ldz
+    complex(8), intent(inout), contiguous :: a(:, :, :)
+    real(8), intent(inout), contiguous :: w(:, :)
+    complex(8), intent(inout), contiguous :: z(:, :, :)
+    character(*), intent(in), optional :: mode
+    integer, intent(out), optional :: info(*)
+    integer :: rc
+    character(kind=c_char) :: md
+    md = 'A'
+    if (present(mode)) md = mode(1:1)
+    rc = eigx_h_batch(n, batch, a, lda, int(lda, c_int64_t) * size(a, 2), w, size(w, 1), z, ldz, &
+                      int(ldz, c_int64_t) * size(z, 2), md, info)
+  end subroutine eigen_h_batch
 
   !> eigen_sx_range_v(n, vl, vu, mmax, m, il, a, lda, w, z, ldz, m_forward, m_backward, mode) -- EXTENSION, not in the
   !> reference (LAPACK's range = 'V'): the eigenpairs with vl <= lambda < vu by the pentadiagonal route on one GPU.  On

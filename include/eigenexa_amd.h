@@ -29,8 +29,8 @@
  * same for the complex Hermitian generalised problem, one GPU), eigx_sx_range_v / eigx_s_range_v / eigx_gev_range_v[_dev] (an
  * extension: the eigenpairs with vl <= lambda < vu of the real solvers, LAPACK's range = 'V', one GPU), eigx_h_range[_v] and
  * eigx_hgev_range_v[_dev] (an extension: both kinds of window for the complex Hermitian solvers, one GPU), eigx_s_batch[_dev]
- * (an extension: many small symmetric matrices in one call, one GPU) and the stage entry eigx_band_count_dev (Sturm counts of a
- * band matrix at caller-given points).
+ * and eigx_h_batch[_dev] (an extension: many small symmetric / complex Hermitian matrices in one call, one GPU) and the stage
+ * entry eigx_band_count_dev (Sturm counts of a band matrix at caller-given points).
  */
 #ifndef EIGENEXA_AMD_H
 #define EIGENEXA_AMD_H
@@ -276,6 +276,40 @@ int eigx_s_range_v_dev(int n, double vl, double vu, int mmax, int* m, int* il, d
 int eigx_s_batch(int n, int batch, double* a, int lda, int64_t stride_a, double* w, int ldw, double* z, int ldz,
                  int64_t stride_z, char mode, int* info);
 int eigx_s_batch_dev(int n, int batch, double* a_dev, int lda, int64_t stride_a, double* w_dev, int ldw, double* z_dev, int ldz,
+                     int64_t stride_z, char mode, int* info_dev);
+
+/* Batched small complex Hermitian eigensolves -- EXTENSION, not in the reference: the complex sibling of eigx_s_batch (LAPACK
+ * callers know the per-matrix operation as zheev).  `batch` Hermitian matrices of one size n, each solved completely.  One
+ * GPU only: with more than one rank the two entries print the line of the range entries and return EIGX_ERR_BAD_ARG.
+ * Storage: a and z hold interleaved (re, im) doubles as for eigx_h; lda, ldz, stride_a and stride_z are in COMPLEX elements
+ * (matrix k starts at the double a + 2 k stride_a, its eigenvectors at z + 2 k stride_z); w is real, the ascending eigenvalues
+ * of matrix k in w + k ldw.  The upper triangle of each matrix is significant, and of the diagonal the real parts only: the
+ * strict lower triangle, the imaginary parts of the diagonal and the rows beyond n may hold anything, NaN included.  a is
+ * destroyed (contents unspecified, no statistics); a and z do not overlap.  Only w(1:n) and z(1:n, 1:n) of each matrix are
+ * written: rows of z beyond n, entries of w beyond n and the gaps between matrices are left untouched.  The eigenvectors are
+ * orthonormal (z^H z = I); their phases are whatever the method leaves.
+ * mode, the argument rules, batch = 0, info and the return value are exactly those of eigx_s_batch: 'A' eigenpairs, 'N'
+ * eigenvalues only (z may be NULL; ldz and stride_z are ignored); EIGX_ERR_BAD_ARG unless n >= 1, batch >= 0, lda >= n,
+ * ldw >= n, stride_a >= lda n where batch > 1, and in mode 'A' ldz >= n, stride_z >= ldz n where batch > 1; batch = 0 returns
+ * EIGX_OK and touches nothing; info[k] = 0, EIGX_ERR_NONFINITE (a NaN / Inf in what is read of matrix k: w(:, k) = NaN,
+ * z(:, :, k) untouched) or EIGX_ERR_INTERNAL (the QL iteration used up its 30 n iterations: w(:, k) = NaN, z(:, :, k)
+ * unspecified); info may be NULL, in the _dev form it is a device int array; a failed matrix never disturbs the others and the
+ * call returns EIGX_OK or the code of the failed matrix with the lowest index.
+ * Method (csrc/hbatch.hip): for n <= EIGX_HBATCH_NMAX one launch, one workgroup per matrix, the matrix as
+ * split real / imaginary planes in LDS from load to store: scaling by the rule of eigx_sx (each matrix by its own largest
+ * |Re|, |Im|), Householder tridiagonalisation with Hermitian reflectors to a Hermitian tridiagonal matrix, a chain of unit
+ * phases that makes it real (folded into the accumulated Q), implicit QL with Wilkinson shift on the real tridiagonal matrix,
+ * sort.  No workgroup waits for another.  The arithmetic of a matrix depends on n alone: the result at position k of a batch
+ * is bit for bit that of the matrix solved alone, and two runs agree bit for bit.  n above the cutoff (eigx_tune key 22,
+ * default EIGX_HBATCH_NMAX): the entry calls eigx_h_dev(n, nvec = n, ..., m_forward = 48, m_backward = 128, mode) matrix by
+ * matrix, so every n works and such a matrix gets the result (a(1:2,1) included) that eigx_h_dev gives.
+ * The device form waits on the default stream on entry and returns after the result is complete.  eigx_get_timers [0] = the
+ * seconds of the call, the rest 0.  Workspace: none beyond the status words (pool buffers "hbatch.*"); the host form stages
+ * a, z and w through the pool buffers of the other complex host forms. */
+#define EIGX_HBATCH_NMAX 96
+int eigx_h_batch(int n, int batch, double* a, int lda, int64_t stride_a, double* w, int ldw, double* z, int ldz,
+                 int64_t stride_z, char mode, int* info);
+int eigx_h_batch_dev(int n, int batch, double* a_dev, int lda, int64_t stride_a, double* w_dev, int ldw, double* z_dev, int ldz,
                      int64_t stride_z, char mode, int* info_dev);
 
 /* ScaLAPACK interop without a redistribution step.  The reference asks block-cyclic callers to
@@ -532,7 +566,9 @@ int eigx_profile_read_kinds(double* out, int nkinds);
  * values are refused; like keys 7-9 it lets tests reach the multi-panel paths at small n.  key 21 = largest n that
  * eigx_s_batch serves with its batch kernel (0 .. EIGX_BATCH_NMAX, default EIGX_BATCH_NMAX by the measured table of DESIGN
  * section 8h; other values are refused): larger matrices go through eigx_s_dev one by one, and a test reaches that path at a
- * small n by lowering the key.  Returns the previous value, or
+ * small n by lowering the key.  key 22 = the same for eigx_h_batch (0 .. EIGX_HBATCH_NMAX, default EIGX_HBATCH_NMAX by the
+ * measured table of DESIGN section 8i; other values are refused): larger matrices go through eigx_h_dev one by one.  Returns
+ * the previous value, or
  * -1 for an unknown key or a refused value.
  * Not part of the reference's interface. */
 int eigx_tune(int key, int value);
