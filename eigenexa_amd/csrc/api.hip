@@ -360,6 +360,7 @@ int eigx_tune(int key, int value) {
   if (key == 1) return set_bisect_threads(value);
   if (key == 2) return set_bt_q(value);
   if (key == 3 || key == 4 || key == 5 || key == 10 || key == 11) return set_reduce_knob(key, value);
+  if (key == 12) return (value >= 0 && value <= 2) ? set_reduce_knob(key, value) : -1;
   if (key == 6) return set_gemm_cstream(value);
   if (key == 7) return value > 0 ? set_reduce_knob(key, value) : -1;
   if (key == 8) return set_dc_chunk(value);

@@ -73,6 +73,8 @@ struct RedArgs {
   double* YR; double* YC;         // SYMV partials [tile col | tile row][a][ldp]
   double* KD;                     // panel-dot partials [chunk][kind 2*NB][m], then [chunk] uA.uB at the end
   double* SP;                     // [wg][3] bilinear partials
+  int sp_packed;                  // one GPU: 1 = tile t of the mat-vec's 1-D grid stores at SP[3 t]; 0 = SP[ty][tx], row stride maxseg
+  int kd_compact;                 // one GPU: 1 = K_A loads the panel dots in the compact form of the panel's width class
   double* GP;                     // [K_A workgroup][3] Gram partials of the new columns
   double* sc;                     // scalars
   double* d; double* e; int lde;
@@ -126,16 +128,19 @@ struct SymvGeom { int L, T, nt; };
 // and nothing when they stay inside L2.  Walking the triangle tile column by tile column instead
 // of row by row changes nothing (A/B on one buffer).
 int g_ka_fit = 1;     // K_A (eigx_tune key 10): 1 = load batches matched to the step (launch_ka), 0 = always the largest (A/B)
+// K_A on one GPU (eigx_tune key 12): 0 = the earlier load forms (A/B); 1 = the mat-vec stores its tile scalars packed by
+// tile index and K_A loads them packed; 2 = also the panel dots in the compact form of the panel's width class
+int g_ka_loads = 2;
 int g_ka_wgs = 256;   // K_A (eigx_tune key 7): beyond 2 * this many row groups a workgroup takes several of them, ~this many workgroups
 int g_symv_t128 = 4500, g_symv_t256 = 40000;
 int g_symv_nt = 9000;
 int g_symv_unc = 9000;   // the fused mat-vec's branch-free pipelined form up to this active size (eigx_tune key 11)
 }  // namespace
 
-// eigx_tune keys 3, 4, 5, 7, 10, 11 -> the knobs above (previous value; -1: not a key of the reduction)
+// eigx_tune keys 3, 4, 5, 7, 10, 11, 12 -> the knobs above (previous value; -1: not a key of the reduction)
 int set_reduce_knob(int key, int v) {
   int* t = key == 3 ? &g_symv_t128 : key == 4 ? &g_symv_t256 : key == 5 ? &g_symv_nt : key == 7 ? &g_ka_wgs
-         : key == 10 ? &g_ka_fit : key == 11 ? &g_symv_unc : nullptr;
+         : key == 10 ? &g_ka_fit : key == 11 ? &g_symv_unc : key == 12 ? &g_ka_loads : nullptr;
   if (!t) return -1;
   const int old = *t;
   *t = v;
@@ -318,10 +323,16 @@ __device__ __forceinline__ void step_wait_fused(const StepWait& W, bool first_bl
 }
 
 // (role body: workgroup `bid` of `nblocks`; XPp = where the X message goes, several GPUs only)
-template <int NB, bool MG, bool LG, int RPBT, int SPBT, int KBT>
+// PWT (one GPU): width class of the panel for the panel-dot loads, 1: m <= 64, 2: m <= 128, 0: any m (one load per chunk
+// and kind in every thread); SPKT (one GPU): the tile scalars are packed by tile index (RedArgs::sp_packed)
+template <int NB, bool MG, bool LG, int RPBT, int SPBT, int KBT, int PWT = 0, bool SPKT = false>
 __device__ __forceinline__ void ka_body(const RedArgs& R, const KAArgs& S, const StepPeers* XPp, const int bid, const int nblocks) {
+  constexpr int PW = MG ? 0 : PWT;
+  constexpr bool SPK = !MG && SPKT;
+  constexpr int PWC = PW == 1 ? 64 : 128;     // panel columns of a compact class
   __shared__ double red[64];
   __shared__ double kd[4][256];        // reduced panel-dot vectors: [UuA, WuA, UuB, WuB][kk]  (m <= 256)
+  __shared__ double kst[PW ? 4 : 1][PW ? 4 : 1][PW ? PWC : 1];   // compact classes: the chunk partials [chunk][kind][kk]
   __shared__ double rowU[2][258], rowW[2][258];  // U(c, kk), W(c, kk) for the new block columns c
   __shared__ double slice[4][KA_ROWS][4];        // per-wave slice sums
   __shared__ int lastw;                          // several GPUs: this workgroup publishes the X message
@@ -381,10 +392,15 @@ __device__ __forceinline__ void ka_body(const RedArgs& R, const KAArgs& S, const
   // half the unconditional loads of that phase); several GPUs: one message entry per slice
   constexpr int RPB = MG ? 1 : RPBT;
   constexpr int CHB = MG ? EIGX_MAXP : 4;   // K_P row chunks (pd_rows_for() never makes more); several GPUs: one share of the panel dots per rank
-  constexpr int SPB = MG ? 8 : SPBT;    // folded SP rows per wave in the first batch (covers nt <= 8 * SPB - 1)
+  // tile scalars in the first batch: SPK: entries tid + 256 j, j < SPB, of the packed array (covers 256 * SPB tiles);
+  // otherwise folded SP rows per wave (covers nt <= 8 * SPB - 1)
+  constexpr int SPB = MG ? 8 : SPBT;
+  // chunk partials of the panel dots that a thread loads per kind: all CHB for its column kk = tid; compact classes: wave w
+  // takes chunk w for column kk = lane (m <= 64), half h = tid >> 7 takes chunks h and h + 2 for column kk = tid & 127 (m <= 128)
+  constexpr int CHL = PW == 1 ? 1 : PW == 2 ? 2 : CHB;
   struct RowRegs { double tu[KB], tw[KB], ta[RPB], tb[RPB], uA, uB, ai, aim; };   // what a thread loads for its row of a group
   RowRegs cur, nxt;
-  double kdl[4][CHB];
+  double kdl[4][CHL];
   double spl[SPB][3];
   double abl = 0.0, pcl[2][2] = {{0.0, 0.0}, {0.0, 0.0}};
   double bA = 0.0, bB = 0.0;
@@ -392,7 +408,7 @@ __device__ __forceinline__ void ka_body(const RedArgs& R, const KAArgs& S, const
 #pragma unroll
   for (int q = 0; q < 4; ++q)
 #pragma unroll
-    for (int j = 0; j < CHB; ++j) kdl[q][j] = 0.0;
+    for (int j = 0; j < CHL; ++j) kdl[q][j] = 0.0;
 #pragma unroll
   for (int j = 0; j < SPB; ++j) { spl[j][0] = 0.0; spl[j][1] = 0.0; spl[j][2] = 0.0; }
   // Everything below is UNCONDITIONAL: no branch (not even a wave-uniform one), clamped addresses that are valid
@@ -495,7 +511,19 @@ __device__ __forceinline__ void ka_body(const RedArgs& R, const KAArgs& S, const
     load_rows_msg(r, cur);
   }
   // panel dots: thread kk = tid (< kp <= 256) sums entry (kind, kk) over the K_P row chunks
-  {
+  if (PW != 0) {   // (compile-time)  compact classes: every lane's entry is one of the panel's m columns, each loaded once
+    const int c0 = (PW == 1) ? wave : (tid >> 7);                    // uniform in the wave
+    const unsigned col = (PW == 1) ? (unsigned)lane : (unsigned)(tid & 127);
+#pragma unroll
+    for (int j = 0; j < CHL; ++j) {
+      const int c = c0 + 2 * j;
+#pragma unroll
+      for (int q = 0; q < 2 * NB; ++q) {
+        const double* bk = R.KD + (size_t)((c < S.nchunk_prev ? c : 0) * 2 * NB + q) * m;   // uniform
+        kdl[q][j] = bk[col];
+      }
+    }
+  } else {
 #pragma unroll
     for (int j = 0; j < CHB; ++j) {
 #pragma unroll
@@ -515,7 +543,21 @@ __device__ __forceinline__ void ka_body(const RedArgs& R, const KAArgs& S, const
   // bilinear partials of the SYMV tiles, SP[ty][tx] with the fixed row stride maxseg, tx >= ty only.
   // Folded rows: row f (nt - f tiles) and row nt-1-f (f + 1 tiles) together fill nt + 1 <= 64 lanes;
   // wave w takes the folded rows f = w, w + 4, ...
-  if (!mg) {   // (compile-time)
+  // Packed (SPK): the tile with index t in the mat-vec's 1-D grid stored its triple at SP[3 t]; thread tid takes the
+  // entries tid + 256 j: every lane below nt (nt + 1) / 2 holds a real entry.
+  const int ntl = nt * (nt + 1) / 2;
+  if (SPK) {   // (compile-time)
+#pragma unroll
+    for (int j = 0; j < SPB; ++j) {
+      const int t = tid + 256 * j;
+      const bool ok = hp && t < ntl;
+      const double* sp = R.SP + (size_t)(ok ? t : 0) * 3;
+      spr[j][0] = sp[0];
+      spr[j][1] = sp[NB == 2 ? 1 : 0];
+      spr[j][2] = sp[NB == 2 ? 2 : 0];
+      spok |= ok ? (1u << j) : 0u;
+    }
+  } else if (!mg) {   // (compile-time)
 #pragma unroll
     for (int j = 0; j < SPB; ++j) {
       const int f = wave + 4 * j;
@@ -571,8 +613,9 @@ __device__ __forceinline__ void ka_body(const RedArgs& R, const KAArgs& S, const
     if (NB == 1) bB = 0.0;
     mask_rows(r, cur);
 #pragma unroll
-    for (int j = 0; j < CHB; ++j) {
-      if (!(hp && j < S.nchunk_prev)) {
+    for (int j = 0; j < CHL; ++j) {
+      const int c = (PW == 1) ? wave : (PW == 2) ? (tid >> 7) + 2 * j : j;   // the chunk of kdl[.][j]
+      if (!(hp && c < S.nchunk_prev)) {
 #pragma unroll
         for (int q = 0; q < 4; ++q) kdl[q][j] = 0.0;
       }
@@ -604,7 +647,13 @@ __device__ __forceinline__ void ka_body(const RedArgs& R, const KAArgs& S, const
         v[0] += spl[j][0];
         if (NB == 2) { v[1] += spl[j][1]; v[2] += spl[j][2]; }
       }
-      if (nt > 8 * SPB - 1) {   // more tiles than the folded batch covers: plain sweep of the upper tile triangle
+      if (SPK) {   // (compile-time)  more tiles than the packed batch covers: the same packed index beyond it
+        for (int t = tid + 256 * SPB; t < ntl; t += 256) {
+          const double* sp = R.SP + (size_t)t * 3;
+          v[0] += sp[0];
+          if (NB == 2) { v[1] += sp[1]; v[2] += sp[2]; }
+        }
+      } else if (nt > 8 * SPB - 1) {   // more tiles than the folded batch covers: plain sweep of the upper tile triangle
         for (int ty = wave; ty < nt; ty += 4)
           for (int tx = ty + lane; tx < nt; tx += 64) {
             const double* sp = R.SP + ((size_t)ty * R.maxseg + tx) * 3;
@@ -636,7 +685,28 @@ __device__ __forceinline__ void ka_body(const RedArgs& R, const KAArgs& S, const
 
   // ============ phase 1: publish kd / rowU / rowW in LDS ============================================
   double kdr[4] = {0.0, 0.0, 0.0, 0.0};
-  if (hp && tid < kp) {
+  if (PW != 0 && hp) {   // (compile-time, uniform)
+    // compact classes: the chunk partials meet in LDS; thread kk adds them in the order of the wide form, ((c0 + c1) + c2) + c3,
+    // so that every class gives the same bits
+#pragma unroll
+    for (int j = 0; j < CHL; ++j) {
+      const int c = (PW == 1) ? wave : (tid >> 7) + 2 * j;
+      const int col = (PW == 1) ? lane : (tid & 127);
+#pragma unroll
+      for (int q = 0; q < 2 * NB; ++q) kst[PW ? c : 0][PW ? q : 0][PW ? col : 0] = kdl[q][j];
+    }
+    __syncthreads();
+    if (tid < kp) {
+#pragma unroll
+      for (int q = 0; q < 2 * NB; ++q) {
+        double acc = 0.0;
+#pragma unroll
+        for (int c = 0; c < 4; ++c) acc += kst[PW ? c : 0][PW ? q : 0][PW ? tid : 0];
+        kdr[q] = acc;
+        kd[q][tid] = acc;
+      }
+    }
+  } else if (hp && tid < kp) {
 #pragma unroll
     for (int q = 0; q < 2 * NB; ++q) {
       double acc = 0.0;
@@ -910,9 +980,9 @@ __device__ __forceinline__ void ka_body(const RedArgs& R, const KAArgs& S, const
 #endif
 }
 
-template <int NB, bool MG, bool LG, int RPBT, int SPBT, int KBT>
+template <int NB, bool MG, bool LG, int RPBT, int SPBT, int KBT, int PWT, bool SPKT>
 __global__ __launch_bounds__(256) void ka_kernel(RedArgs R, KAArgs S) {
-  ka_body<NB, MG, LG, RPBT, SPBT, KBT>(R, S, nullptr, blockIdx.x, gridDim.x);
+  ka_body<NB, MG, LG, RPBT, SPBT, KBT, PWT, SPKT>(R, S, nullptr, blockIdx.x, gridDim.x);
 }
 
 // =================================================================================================
@@ -1810,7 +1880,8 @@ __device__ __forceinline__ void symv_body(const RedArgs& R, const KBArgs& B, con
   }
   if (!EIGX_ABL(512)) block_sum_multi<3>(sp, red);
   if (tid == 0) {
-    const size_t w = (size_t)ty * R.maxseg + tx;
+    // one GPU, packed: the tile's index in the 1-D grid (K_A then reads nt (nt + 1) / 2 contiguous triples)
+    const size_t w = (!MG && R.sp_packed) ? (size_t)bid : (size_t)ty * R.maxseg + tx;
     R.SP[w * 3 + 0] = sp[0]; R.SP[w * 3 + 1] = sp[1]; R.SP[w * 3 + 2] = sp[2];
   }
   EIGX_STAMP(11);
@@ -1980,7 +2051,9 @@ RedArgs reduce_setup(Context& ctx, int n, double* A, int lda, double* d, double*
     R.kdab_off = maxchunk2 * 2 * NB * m;
     R.KD = ctx.pool.get_t<double>("red.KD2", (size_t)R.kdab_off + 4 * G.nranks + 4 + 8 + 512);
   }
-  R.SP = ctx.pool.get_t<double>("red.SP", (size_t)(maxseg * maxseg) * 3 + 8);
+  R.SP = ctx.pool.get_t<double>("red.SP", (size_t)(maxseg * maxseg) * 3 + 8);   // (covers the packed nt (nt + 1) / 2 triples)
+  R.sp_packed = (!mg && g_ka_loads >= 1) ? 1 : 0;
+  R.kd_compact = (!mg && g_ka_loads >= 2) ? 1 : 0;
   R.gp2_off = 0;
   R.GP = ctx.pool.get_t<double>("red.GP", (size_t)((n + KA_ROWS - 1) / KA_ROWS + 2) * 3 + 8);
   R.sc = ctx.pool.get_t<double>("red.sc", SC_COUNT + 8);
@@ -2104,25 +2177,52 @@ inline int ka_grid_one_gpu(int rows, int& G) {
 
 // ka_kernel's first batches of loads are unconditional (clamped), so their sizes are template parameters matched to the
 // step: partial sums of a row (nt + 1 slots: RPB = 1 / 2 / 3 / 5 / 10 batches of KA_SL = 16), folded rows of tile scalars
-// (nt <= 15 / 31 / 63: SPB = 2 / 4 / 8 per wave), panel columns (k <= 32 / 64 / more: KB = 2 / 4 / 8 per slice)
+// (packed, RedArgs::sp_packed: nt (nt + 1) / 2 <= 256 / 512 / 768 / 1024 / more: SPB = 1 / 2 / 3 / 4 / 8 per thread;
+// folded rows otherwise: nt <= 15 / 31 / 63: SPB = 2 / 4 / 8 per wave), panel columns (k <= 32 / 64 / more: KB = 2 / 4 / 8
+// per slice), and the panel's width class for the panel dots (RedArgs::kd_compact: m <= 64 / m <= 128 / any: PW = 1 / 2 / 0)
 template <int NB>
 void launch_ka(hipStream_t st, int nwg, const RedArgs& R, const KAArgs& K) {
   const bool fit = g_ka_fit != 0;
   const int nslot = fit ? K.nt_prev + 1 : 1 << 30, ntp = fit ? K.nt_prev : 1 << 30;
+  const int ntl = fit ? K.nt_prev * (K.nt_prev + 1) / 2 : 1 << 30;
   const int kk = fit ? (K.has_prev ? K.kprev : K.k) : 1 << 30;
-  auto go = [&](auto rpb, auto spb) {
-    auto go_kb = [&](auto kb) {   // (LG: several row groups per workgroup)
-      constexpr int RPB = decltype(rpb)::value, SPB = decltype(spb)::value, KB = decltype(kb)::value;
-      if (K.G > 1) hipLaunchKernelGGL((ka_kernel<NB, false, true, RPB, SPB, KB>), dim3(nwg), dim3(256), 0, st, R, K);
-      else hipLaunchKernelGGL((ka_kernel<NB, false, false, RPB, SPB, KB>), dim3(nwg), dim3(256), 0, st, R, K);
+  const int pw = (fit && R.kd_compact) ? (R.m <= 64 ? 1 : R.m <= 128 ? 2 : 0) : 0;
+  auto go = [&](auto rpb, auto spb, auto spk) {
+    auto go_kb = [&](auto kb, auto pwc) {   // (LG: several row groups per workgroup)
+      constexpr int RPB = decltype(rpb)::value, SPB = decltype(spb)::value, KB = decltype(kb)::value, PW = decltype(pwc)::value;
+      constexpr bool SPK = decltype(spk)::value;
+      if (K.G > 1) hipLaunchKernelGGL((ka_kernel<NB, false, true, RPB, SPB, KB, PW, SPK>), dim3(nwg), dim3(256), 0, st, R, K);
+      else hipLaunchKernelGGL((ka_kernel<NB, false, false, RPB, SPB, KB, PW, SPK>), dim3(nwg), dim3(256), 0, st, R, K);
     };
-    if (kk <= 2 * KA_SL) go_kb(IC<2>{}); else if (kk <= 4 * KA_SL) go_kb(IC<4>{}); else go_kb(IC<8>{});
+    auto go_pw = [&](auto kb) {
+      if constexpr (decltype(spk)::value) {   // (the compact classes exist with the packed tile scalars only: eigx_tune key 12)
+        if constexpr (decltype(kb)::value <= 4) {   // (k < m <= 64: never the 8-column batch)
+          if (pw == 1) return go_kb(kb, IC<1>{});
+        }
+        if (pw == 2) return go_kb(kb, IC<2>{});
+      }
+      go_kb(kb, IC<0>{});
+    };
+    if (kk <= 2 * KA_SL) go_pw(IC<2>{}); else if (kk <= 4 * KA_SL) go_pw(IC<4>{}); else go_pw(IC<8>{});
   };
-  if (nslot <= 1 * KA_SL && ntp <= 15) go(IC<1>{}, IC<2>{});
-  else if (nslot <= 2 * KA_SL && ntp <= 31) go(IC<2>{}, IC<4>{});
-  else if (nslot <= 3 * KA_SL) go(IC<3>{}, IC<8>{});
-  else if (nslot <= 5 * KA_SL) go(IC<5>{}, IC<8>{});
-  else go(IC<10>{}, IC<8>{});
+  if (R.sp_packed) {
+    const std::true_type pk{};
+    if (nslot <= 1 * KA_SL && ntl <= 256) go(IC<1>{}, IC<1>{}, pk);
+    else if (nslot <= 2 * KA_SL && ntl <= 256) go(IC<2>{}, IC<1>{}, pk);
+    else if (nslot <= 2 * KA_SL && ntl <= 512) go(IC<2>{}, IC<2>{}, pk);
+    else if (nslot <= 3 * KA_SL && ntl <= 768) go(IC<3>{}, IC<3>{}, pk);
+    else if (nslot <= 3 * KA_SL && ntl <= 1024) go(IC<3>{}, IC<4>{}, pk);
+    else if (nslot <= 3 * KA_SL) go(IC<3>{}, IC<8>{}, pk);
+    else if (nslot <= 5 * KA_SL) go(IC<5>{}, IC<8>{}, pk);
+    else go(IC<10>{}, IC<8>{}, pk);
+    return;
+  }
+  const std::false_type fl{};
+  if (nslot <= 1 * KA_SL && ntp <= 15) go(IC<1>{}, IC<2>{}, fl);
+  else if (nslot <= 2 * KA_SL && ntp <= 31) go(IC<2>{}, IC<4>{}, fl);
+  else if (nslot <= 3 * KA_SL) go(IC<3>{}, IC<8>{}, fl);
+  else if (nslot <= 5 * KA_SL) go(IC<5>{}, IC<8>{}, fl);
+  else go(IC<10>{}, IC<8>{}, fl);
 }
 
 // the mat-vec's instantiation (one GPU and the step launch alike): tile edge T = 128 / 256 / 512 (RB = 1 / 2 / 4),

@@ -553,7 +553,9 @@ int eigx_profile_read_kinds(double* out, int nkinds);
  * key 8 = chunk width (roots, 64 .. 2048) of the multi-rank D&C's eigenvector-row buffer; key 9 = doubles per slice of
  * the bounce window of the multi-rank eigenvector redistributions (keys 7-9 exist so that the tests reach the
  * large-N code paths at small sizes); key 10 = 0: the column-formation kernel always uses its largest load batches (A/B);
- * key 11 = largest active size at which the fused symmetric mat-vec uses its branch-free pipelined form; keys 15 / 16 = 0:
+ * key 11 = largest active size at which the fused symmetric mat-vec uses its branch-free pipelined form; key 12 = load
+ * forms of the column-formation kernel on one GPU (A/B): 2 [default] = tile scalars packed by tile index and panel dots
+ * loaded once per panel column, 1 = packed tile scalars only, 0 = the earlier forms; other values are refused; keys 15 / 16 = 0:
  * the one-GPU D&C runs its passes one after the other / one product launch per merge instead of one per low height
  * (key 15 >= 2: merges larger than this use the side stream).  Index-range solves (extension): key 17 = size rule in
  * percent (0 .. 100), windows with 100 m > key17 n go straight to the full D&C; a negative value (the default, -1) selects
