@@ -12,6 +12,32 @@ LIB_PATH = os.environ.get("EIGX_LIB") or os.path.join(_HERE, "lib", "libeigenexa
 _c_double_p = C.POINTER(C.c_double)
 _c_int_p = C.POINTER(C.c_int)
 
+# argument lists that several entries share: the host and the device form of an entry, the sx / s / h routes, the real
+# and the complex sibling.  Arrays are void*.
+_INT, _PTR = C.c_int, C.c_void_p
+# n, nvec, a, lda, w, z, ldz, m_forward, m_backward, mode
+_SOLVE = [_INT, _INT, _PTR, _INT, _PTR, _PTR, _INT, _INT, _INT, C.c_char]
+# route, n, nvec, a, lda, w, z, ldz, nb, m_forward, m_backward, mode
+_SOLVE_BC = [_INT, _INT, _INT, _PTR, _INT, _PTR, _PTR, _INT, _INT, _INT, _INT, C.c_char]
+# n, il, iu, a, lda, w, z, ldz, m_forward, m_backward, mode
+_RANGE = [_INT, _INT, _INT, _PTR, _INT, _PTR, _PTR, _INT, _INT, _INT, C.c_char]
+# n, vl, vu, mmax, m, il, a, lda, w, z, ldz, m_forward, m_backward, mode
+_RANGE_V = [_INT, C.c_double, C.c_double, _INT, _c_int_p, _c_int_p, _PTR, _INT, _PTR, _PTR, _INT, _INT, _INT, C.c_char]
+# n, a, lda, b, ldb, w, z, ldz
+_GEV = [_INT, _PTR, _INT, _PTR, _INT, _PTR, _PTR, _INT]
+# n, il, iu, a, lda, b, ldb, w, z, ldz, mode
+_GEV_RANGE = [_INT, _INT, _INT, _PTR, _INT, _PTR, _INT, _PTR, _PTR, _INT, C.c_char]
+# n, vl, vu, mmax, m, il, a, lda, b, ldb, w, z, ldz, mode
+_GEV_RANGE_V = [_INT, C.c_double, C.c_double, _INT, _c_int_p, _c_int_p, _PTR, _INT, _PTR, _INT, _PTR, _PTR, _INT, C.c_char]
+# n, batch, a, lda, stride_a, w, ldw, z, ldz, stride_z, mode, info
+_BATCH = [_INT, _INT, _PTR, _INT, C.c_int64, _PTR, _INT, _PTR, _INT, C.c_int64, C.c_char, _PTR]
+# the index helpers: index, nnod, inod
+_INDEX = [_INT, _INT, _INT]
+# stages of the Cholesky route: (n, b, ldb), (trans, n, nrhs, u, ldu, x, ldx), (n, a, lda, u, ldu)
+_CHOL = [_INT, _PTR, _INT]
+_TRSM = [C.c_char, _INT, _INT, _PTR, _INT, _PTR, _INT]
+_REDUCE = [_INT, _PTR, _INT, _PTR, _INT]
+
 # name -> (restype, argtypes); mirrors include/eigenexa_amd.h one to one
 SIGNATURES = {
     "eigx_init": (C.c_int, [C.c_int]),
@@ -33,61 +59,43 @@ SIGNATURES = {
     "eigx_held_bytes_named": (C.c_int64, [C.c_char_p]),
     "eigx_transpose_plan": (C.c_int, [C.c_int] * 6 + [C.POINTER(C.c_int)] * 5),
     "eigx_memory_internal": (C.c_int64, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
-    "eigx_loop_start": (C.c_int, [C.c_int, C.c_int, C.c_int]),
-    "eigx_loop_end": (C.c_int, [C.c_int, C.c_int, C.c_int]),
-    "eigx_translate_l2g": (C.c_int, [C.c_int, C.c_int, C.c_int]),
-    "eigx_translate_g2l": (C.c_int, [C.c_int, C.c_int, C.c_int]),
-    "eigx_owner_node": (C.c_int, [C.c_int, C.c_int, C.c_int]),
-    "eigx_owner_index": (C.c_int, [C.c_int, C.c_int, C.c_int]),
-    "eigx_sx": (C.c_int, [C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int,
-                          C.c_int, C.c_int, C.c_char]),
-    "eigx_s": (C.c_int, [C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int,
-                         C.c_int, C.c_int, C.c_char]),
-    "eigx_sx_dev": (C.c_int, [C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int,
-                              C.c_int, C.c_int, C.c_char]),
-    "eigx_s_dev": (C.c_int, [C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int,
-                             C.c_int, C.c_int, C.c_char]),
-    "eigx_solve_bc": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int,
-                                C.c_int, C.c_int, C.c_int, C.c_char]),
-    "eigx_solve_bc_dev": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int,
-                                    C.c_int, C.c_int, C.c_int, C.c_char]),
+    "eigx_loop_start": (C.c_int, _INDEX),
+    "eigx_loop_end": (C.c_int, _INDEX),
+    "eigx_translate_l2g": (C.c_int, _INDEX),
+    "eigx_translate_g2l": (C.c_int, _INDEX),
+    "eigx_owner_node": (C.c_int, _INDEX),
+    "eigx_owner_index": (C.c_int, _INDEX),
+    "eigx_sx": (C.c_int, _SOLVE),
+    "eigx_s": (C.c_int, _SOLVE),
+    "eigx_sx_dev": (C.c_int, _SOLVE),
+    "eigx_s_dev": (C.c_int, _SOLVE),
+    "eigx_solve_bc": (C.c_int, _SOLVE_BC),
+    "eigx_solve_bc_dev": (C.c_int, _SOLVE_BC),
     "eigx_numroc": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int]),
-    "eigx_h": (C.c_int, [C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int,
-                         C.c_int, C.c_int, C.c_char]),
-    "eigx_h_dev": (C.c_int, [C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int,
-                             C.c_int, C.c_int, C.c_char]),
+    "eigx_h": (C.c_int, _SOLVE),
+    "eigx_h_dev": (C.c_int, _SOLVE),
     "eigx_set_grid_dims": (C.c_int, [C.c_int, C.c_int]),
     "eigx_band_reduce_dev": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int,
                                        C.c_int, C.c_int]),
     "eigx_band_dc_dev": (C.c_int, [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
                                    C.c_void_p, C.c_void_p, C.c_int]),
-    "eigx_gev": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int]),
-    "eigx_gev_dev": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int]),
+    "eigx_gev": (C.c_int, _GEV),
+    "eigx_gev_dev": (C.c_int, _GEV),
     # extension (not in the reference): complex Hermitian generalised problem
-    "eigx_hgev": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int]),
-    "eigx_hgev_dev": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int]),
+    "eigx_hgev": (C.c_int, _GEV),
+    "eigx_hgev_dev": (C.c_int, _GEV),
     # extension (not in the reference): index-range solves on one GPU and their stages
-    "eigx_sx_range": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int,
-                                C.c_int, C.c_int, C.c_char]),
-    "eigx_s_range": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int,
-                                C.c_int, C.c_int, C.c_char]),
-    "eigx_sx_range_dev": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int,
-                                C.c_int, C.c_int, C.c_char]),
-    "eigx_s_range_dev": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int,
-                                C.c_int, C.c_int, C.c_char]),
+    "eigx_sx_range": (C.c_int, _RANGE),
+    "eigx_s_range": (C.c_int, _RANGE),
+    "eigx_sx_range_dev": (C.c_int, _RANGE),
+    "eigx_s_range_dev": (C.c_int, _RANGE),
     # extension: the same by value window (vl <= lambda < vu); m and il come back through host int pointers
-    "eigx_sx_range_v": (C.c_int, [C.c_int, C.c_double, C.c_double, C.c_int, _c_int_p, _c_int_p, C.c_void_p, C.c_int,
-                                  C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_char]),
-    "eigx_s_range_v": (C.c_int, [C.c_int, C.c_double, C.c_double, C.c_int, _c_int_p, _c_int_p, C.c_void_p, C.c_int,
-                                 C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_char]),
-    "eigx_sx_range_v_dev": (C.c_int, [C.c_int, C.c_double, C.c_double, C.c_int, _c_int_p, _c_int_p, C.c_void_p, C.c_int,
-                                      C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_char]),
-    "eigx_s_range_v_dev": (C.c_int, [C.c_int, C.c_double, C.c_double, C.c_int, _c_int_p, _c_int_p, C.c_void_p, C.c_int,
-                                     C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_char]),
-    "eigx_gev_range_v": (C.c_int, [C.c_int, C.c_double, C.c_double, C.c_int, _c_int_p, _c_int_p, C.c_void_p, C.c_int,
-                                   C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_char]),
-    "eigx_gev_range_v_dev": (C.c_int, [C.c_int, C.c_double, C.c_double, C.c_int, _c_int_p, _c_int_p, C.c_void_p, C.c_int,
-                                       C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_char]),
+    "eigx_sx_range_v": (C.c_int, _RANGE_V),
+    "eigx_s_range_v": (C.c_int, _RANGE_V),
+    "eigx_sx_range_v_dev": (C.c_int, _RANGE_V),
+    "eigx_s_range_v_dev": (C.c_int, _RANGE_V),
+    "eigx_gev_range_v": (C.c_int, _GEV_RANGE_V),
+    "eigx_gev_range_v_dev": (C.c_int, _GEV_RANGE_V),
     "eigx_band_count_dev": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "eigx_band_bisect_range_dev": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
                                              C.c_void_p]),
@@ -96,45 +104,31 @@ SIGNATURES = {
     "eigx_range_info": (C.c_int, [_c_int_p, _c_int_p, _c_double_p]),
     "eigx_range_timers": (C.c_int, [_c_double_p]),
     # extension (not in the reference): Cholesky-route generalised range solver and its triangular stages
-    "eigx_gev_range": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p,
-                                 C.c_void_p, C.c_int, C.c_char]),
-    "eigx_gev_range_dev": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p,
-                                     C.c_void_p, C.c_int, C.c_char]),
-    "eigx_chol_dev": (C.c_int, [C.c_int, C.c_void_p, C.c_int]),
-    "eigx_trsm_upper_dev": (C.c_int, [C.c_char, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int]),
-    "eigx_gev_reduce_dev": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int]),
+    "eigx_gev_range": (C.c_int, _GEV_RANGE),
+    "eigx_gev_range_dev": (C.c_int, _GEV_RANGE),
+    "eigx_chol_dev": (C.c_int, _CHOL),
+    "eigx_trsm_upper_dev": (C.c_int, _TRSM),
+    "eigx_gev_reduce_dev": (C.c_int, _REDUCE),
     # extension (not in the reference): the same for the complex Hermitian generalised problem (csrc/ztri.hip, on the
     # split planes of csrc/zplanes.hip)
-    "eigx_hgev_range": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p,
-                                  C.c_void_p, C.c_int, C.c_char]),
-    "eigx_hgev_range_dev": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p,
-                                      C.c_void_p, C.c_int, C.c_char]),
+    "eigx_hgev_range": (C.c_int, _GEV_RANGE),
+    "eigx_hgev_range_dev": (C.c_int, _GEV_RANGE),
     # extension: index and value windows of eigen_h, the value window of the complex generalised problem
-    "eigx_h_range": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int,
-                               C.c_int, C.c_int, C.c_char]),
-    "eigx_h_range_dev": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int,
-                                   C.c_int, C.c_int, C.c_char]),
-    "eigx_h_range_v": (C.c_int, [C.c_int, C.c_double, C.c_double, C.c_int, _c_int_p, _c_int_p, C.c_void_p, C.c_int,
-                                 C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_char]),
-    "eigx_h_range_v_dev": (C.c_int, [C.c_int, C.c_double, C.c_double, C.c_int, _c_int_p, _c_int_p, C.c_void_p, C.c_int,
-                                     C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_char]),
-    "eigx_hgev_range_v": (C.c_int, [C.c_int, C.c_double, C.c_double, C.c_int, _c_int_p, _c_int_p, C.c_void_p, C.c_int,
-                                    C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_char]),
-    "eigx_hgev_range_v_dev": (C.c_int, [C.c_int, C.c_double, C.c_double, C.c_int, _c_int_p, _c_int_p, C.c_void_p, C.c_int,
-                                        C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_char]),
+    "eigx_h_range": (C.c_int, _RANGE),
+    "eigx_h_range_dev": (C.c_int, _RANGE),
+    "eigx_h_range_v": (C.c_int, _RANGE_V),
+    "eigx_h_range_v_dev": (C.c_int, _RANGE_V),
+    "eigx_hgev_range_v": (C.c_int, _GEV_RANGE_V),
+    "eigx_hgev_range_v_dev": (C.c_int, _GEV_RANGE_V),
     # extension: many small symmetric matrices in one call (csrc/batch.hip); strides are int64_t, info int*
-    "eigx_s_batch": (C.c_int, [C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_int, C.c_void_p, C.c_int,
-                               C.c_int64, C.c_char, C.c_void_p]),
-    "eigx_s_batch_dev": (C.c_int, [C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_int, C.c_void_p, C.c_int,
-                                   C.c_int64, C.c_char, C.c_void_p]),
+    "eigx_s_batch": (C.c_int, _BATCH),
+    "eigx_s_batch_dev": (C.c_int, _BATCH),
     # extension: many small complex Hermitian matrices in one call (csrc/hbatch.hip); a, z interleaved complex
-    "eigx_h_batch": (C.c_int, [C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_int, C.c_void_p, C.c_int,
-                               C.c_int64, C.c_char, C.c_void_p]),
-    "eigx_h_batch_dev": (C.c_int, [C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_int, C.c_void_p, C.c_int,
-                                   C.c_int64, C.c_char, C.c_void_p]),
-    "eigx_zchol_dev": (C.c_int, [C.c_int, C.c_void_p, C.c_int]),
-    "eigx_ztrsm_upper_dev": (C.c_int, [C.c_char, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int]),
-    "eigx_hgev_reduce_dev": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int]),
+    "eigx_h_batch": (C.c_int, _BATCH),
+    "eigx_h_batch_dev": (C.c_int, _BATCH),
+    "eigx_zchol_dev": (C.c_int, _CHOL),
+    "eigx_ztrsm_upper_dev": (C.c_int, _TRSM),
+    "eigx_hgev_reduce_dev": (C.c_int, _REDUCE),
     "eigx_band_bisect_dev": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
     "eigx_trbak_dev": (C.c_int, [C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int,
                                  C.c_void_p, C.c_int, C.c_int, C.c_int]),

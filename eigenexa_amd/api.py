@@ -160,101 +160,114 @@ def _grid_dim(grid):
     return procs, idn
 
 
+def _index_helper(entry, i, grid):
+    nnod, inod = _grid_dim(grid)
+    return getattr(_lib.load(), entry)(int(i), nnod, inod)
+
+
 # index helpers: (value, 'X'|'Y') like the reference (src/eigen_libs0.F:1744-2356); 1-based
 def eigen_loop_start(istart, grid):
-    nnod, inod = _grid_dim(grid)
-    return _lib.load().eigx_loop_start(int(istart), nnod, inod)
+    return _index_helper("eigx_loop_start", istart, grid)
 
 
 def eigen_loop_end(iend, grid):
-    nnod, inod = _grid_dim(grid)
-    return _lib.load().eigx_loop_end(int(iend), nnod, inod)
+    return _index_helper("eigx_loop_end", iend, grid)
 
 
 def eigen_translate_l2g(ictr, grid):
-    nnod, inod = _grid_dim(grid)
-    return _lib.load().eigx_translate_l2g(int(ictr), nnod, inod)
+    return _index_helper("eigx_translate_l2g", ictr, grid)
 
 
 def eigen_translate_g2l(ictr, grid):
-    nnod, inod = _grid_dim(grid)
-    return _lib.load().eigx_translate_g2l(int(ictr), nnod, inod)
+    return _index_helper("eigx_translate_g2l", ictr, grid)
 
 
 def eigen_owner_node(ictr, grid):
-    nnod, inod = _grid_dim(grid)
-    return _lib.load().eigx_owner_node(int(ictr), nnod, inod)
+    return _index_helper("eigx_owner_node", ictr, grid)
 
 
 def eigen_owner_index(ictr, grid):
-    nnod, inod = _grid_dim(grid)
-    return _lib.load().eigx_owner_index(int(ictr), nnod, inod)
+    return _index_helper("eigx_owner_index", ictr, grid)
+
+
+# ---- the steps of a solver call: check the wrapper's own arguments, _begin, _addrs, the entry, _finish -----------------
+# ``which`` names the family and with it the entry (eigx_<which>...), the name in the warnings and the dtype of a, b, z:
+# float64 for 'sx', 's', 'gev', complex128 for 'h', 'hgev'; w is float64 everywhere.
+
+_MIXED = "the arrays must all be host arrays or all be device tensors"
 
 
 def _is_torch(x):
     return type(x).__module__.startswith("torch")
 
 
-def _ptr(x, name, want_device):
+def _addr(x, name, dev, dtype, cplx):
+    """address of the array argument ``x`` (None: null) of a host (``dev`` False) or a device call, after the checks of
+    its dtype (``dtype``: 'float64' or 'complex128'), its side and, on the host, its order.  The real wrappers
+    (``cplx`` False) judge a torch tensor by itself -- on the GPU, then its dtype -- before its side; the complex ones
+    take a tensor that is not on the GPU for a host array."""
     if x is None:
         return None
     if _is_torch(x):
-        if not x.is_cuda:
-            raise ValueError(f"{name}: torch tensors must live on the GPU (use numpy for host arrays)")
         import torch
 
-        if x.dtype != torch.float64:
-            raise ValueError(f"{name}: float64 required")
-        if not want_device:
-            raise ValueError("a, w, z must all be host arrays or all be device tensors")
+        if not cplx and not x.is_cuda:
+            raise ValueError(f"{name}: torch tensors must live on the GPU (use numpy for host arrays)")
+        same_side = dev and x.is_cuda
+        if cplx and not same_side:
+            raise ValueError(_MIXED)
+        if x.dtype != getattr(torch, dtype):
+            raise ValueError(f"{name}: {dtype} required")
+        if not same_side:
+            raise ValueError(_MIXED)
         return x.data_ptr()
-    if want_device:
-        raise ValueError("a, w, z must all be host arrays or all be device tensors")
-    if x.dtype != np.float64:
-        raise ValueError(f"{name}: float64 required")
+    if dev:
+        raise ValueError(_MIXED)
+    if x.dtype != getattr(np, dtype):
+        raise ValueError(f"{name}: {dtype} required")
     if x.ndim == 2 and not x.flags.f_contiguous:
         raise ValueError(f"{name}: Fortran (column-major) order required, as in the reference")
     return x.ctypes.data
 
 
-def _solve(which, n, nvec, a, lda, w, z, ldz, m_forward, m_backward, mode, nb=None):
+def _addrs(which, dev, **arrays):
+    """addresses of the named array arguments of one call, checked in the order given"""
+    cplx = which.startswith("h")
+    return [_addr(x, name, dev, "complex128" if cplx and name != "w" else "float64", cplx) for name, x in arrays.items()]
+
+
+def _begin(a):
+    """(library, device flag) -- or None when eigen_init has not been called: the reference returns silently then
+    (src/eigen_sx.F:82-86), here with status -1.  ``a`` decides the side of the call."""
     lib = _lib.load()
     if not _state["initialized"]:
-        # reference: silent return when eigen_init has not been called (src/eigen_sx.F:82-86)
         _state["last_status"] = -1
-        return
+        return None
     dev = _is_torch(a)
     if dev:
         import torch
 
         torch.cuda.current_stream().synchronize()  # inputs written on torch's stream must be visible
-    pa, pw, pz = _ptr(a, "a", dev), _ptr(w, "w", dev), _ptr(z, "z", dev)
-    mf = eigen_NB_f if m_forward is None else int(m_forward)
-    mb = eigen_NB_b if m_backward is None else int(m_backward)
-    if nb is None:
-        fn = getattr(lib, ("eigx_sx" if which == "sx" else "eigx_s") + ("_dev" if dev else ""))
-        rc = fn(int(n), int(nvec), pa, int(lda), pw, pz, int(ldz), mf, mb, _char(mode, "A"))
-    else:
-        fn = lib.eigx_solve_bc_dev if dev else lib.eigx_solve_bc
-        rc = fn(2 if which == "sx" else 1, int(n), int(nvec), pa, int(lda), pw, pz, int(ldz), int(nb), mf, mb,
-                _char(mode, "A"))
+    return lib, dev
+
+
+def _entry(lib, name, dev):
+    return getattr(lib, name + ("_dev" if dev else ""))
+
+
+def _blocks(m_forward, m_backward):
+    return eigen_NB_f if m_forward is None else int(m_forward), eigen_NB_b if m_backward is None else int(m_backward)
+
+
+def _finish(name, rc, quiet=(0, -5)):
     _state["last_status"] = rc
-    if rc not in (0, -5):
-        print(f"Warning: eigen_{which} returned without computing (status {rc})", file=sys.stderr)
+    if rc not in quiet:
+        print(f"Warning: {name} returned without computing (status {rc})", file=sys.stderr)
 
 
-def eigen_sx(n, nvec, a, lda, w, z, ldz, m_forward=None, m_backward=None, mode="A"):
-    """Pentadiagonal route (eigen_prd -> eigen_dcx -> trbakwy, src/eigen_sx.F:30-308)."""
-    _solve("sx", n, nvec, a, lda, w, z, ldz, m_forward, m_backward, mode)
-
-
-def eigen_s(n, nvec, a, lda, w, z, ldz, m_forward=None, m_backward=None, mode="A"):
-    """Tridiagonal route (eigen_trd -> dc2 -> trbakwy, src/eigen_libs.F:150-202)."""
-    _solve("s", n, nvec, a, lda, w, z, ldz, m_forward, m_backward, mode)
-
-
-def _solve_range(which, n, il, iu, a, lda, w, z, ldz, m_forward, m_backward, mode):
-    # the window and the mode are checked here, before the library is touched (status -2 = EIGX_ERR_BAD_ARG)
+def _index_window(name, n, il, iu, z, mode):
+    """checks of the index-range wrappers, made before the library is touched: the mode byte or None (status -2 =
+    EIGX_ERR_BAD_ARG)"""
     md = _char(mode, "A").upper()
     try:
         ok = 1 <= int(il) <= int(iu) <= int(n) and md in (b"A", b"N") and not (md == b"A" and z is None)
@@ -262,99 +275,9 @@ def _solve_range(which, n, il, iu, a, lda, w, z, ldz, m_forward, m_backward, mod
         ok = False
     if not ok:
         _state["last_status"] = -2
-        print(f"Warning: eigen_{which}_range: invalid window / mode (n={n}, il={il}, iu={iu}, mode={mode!r})", file=sys.stderr)
-        return
-    lib = _lib.load()
-    if not _state["initialized"]:
-        _state["last_status"] = -1
-        return
-    dev = _is_torch(a)
-    if dev:
-        import torch
-
-        torch.cuda.current_stream().synchronize()
-    pa, pw, pz = _ptr(a, "a", dev), _ptr(w, "w", dev), _ptr(z, "z", dev)
-    mf = eigen_NB_f if m_forward is None else int(m_forward)
-    mb = eigen_NB_b if m_backward is None else int(m_backward)
-    fn = getattr(lib, f"eigx_{which}_range" + ("_dev" if dev else ""))
-    rc = fn(int(n), int(il), int(iu), pa, int(lda), pw, pz, int(ldz), mf, mb, md)
-    _state["last_status"] = rc
-    if rc not in (0, -5):
-        print(f"Warning: eigen_{which}_range returned without computing (status {rc})", file=sys.stderr)
-
-
-def eigen_sx_range(n, il, iu, a, lda, w, z, ldz, m_forward=None, m_backward=None, mode="A"):
-    """EXTENSION (not in the reference): eigenpairs ``il .. iu`` (1-based, inclusive) of the ascending spectrum by the
-    pentadiagonal route, one GPU.  ``w[:m]``, ``z[:, :m]`` with ``m = iu - il + 1``; modes 'A' and 'N'.  Work and memory
-    after the reduction scale with ``m`` (Sturm multi-section on the window, inverse iteration, CholQR2 + Rayleigh-Ritz);
-    ``range_info()`` tells whether that path or the full divide and conquer produced the result."""
-    _solve_range("sx", n, il, iu, a, lda, w, z, ldz, m_forward, m_backward, mode)
-
-
-def eigen_s_range(n, il, iu, a, lda, w, z, ldz, m_forward=None, m_backward=None, mode="A"):
-    """EXTENSION: ``eigen_sx_range`` by the tridiagonal route."""
-    _solve_range("s", n, il, iu, a, lda, w, z, ldz, m_forward, m_backward, mode)
-
-
-def eigen_s_batch(n, batch, a, lda, w, z, ldz, mode="A", info=None, stride_a=None, ldw=None, stride_z=None):
-    """EXTENSION (not in the reference): ``batch`` symmetric matrices of one size ``n`` in one call, one GPU.  ``a`` holds the
-    matrices as ``a[lda, n, batch]`` (numpy, Fortran order) or a GPU tensor with the same memory image: matrix ``k`` starts at
-    element ``k * stride_a``, upper triangle significant, destroyed.  ``w[ldw, batch]`` receives the ascending eigenvalues,
-    ``z[ldz, n, batch]`` the eigenvectors (mode 'A'; mode 'N': eigenvalues only, ``z`` may be None).  Defaults:
-    ``stride_a = lda * n``, ``stride_z = ldz * n``, ``ldw = n``.  ``info`` (optional, int32, ``batch`` entries, on the side of
-    ``a``) receives the per-matrix status: 0, -5 (NaN / Inf in the matrix: its ``w`` is NaN, its ``z`` untouched) or -6;
-    ``last_status()`` is 0 or the status of the first failed matrix.  For ``n <= 128`` one kernel launch solves the batch,
-    one workgroup per matrix with the matrix in LDS; larger ``n`` runs ``eigen_s`` matrix by matrix."""
-    # the arguments are checked here, before the library is touched (status -2 = EIGX_ERR_BAD_ARG)
-    md = _char(mode, "A").upper()
-    try:
-        n, batch, lda = int(n), int(batch), int(lda)
-        ldw = n if ldw is None else int(ldw)
-        ldz = int(ldz) if md == b"A" else (0 if ldz is None else int(ldz))
-        stride_a = lda * n if stride_a is None else int(stride_a)
-        stride_z = ldz * n if stride_z is None else int(stride_z)
-        ok = n >= 1 and batch >= 0 and lda >= n and ldw >= n and md in (b"A", b"N") and a is not None and w is not None
-        ok = ok and (batch <= 1 or stride_a >= lda * n)
-        if md == b"A":
-            ok = ok and z is not None and ldz >= n and (batch <= 1 or stride_z >= ldz * n)
-    except (TypeError, ValueError):
-        ok = False
-    if not ok:
-        _state["last_status"] = -2
-        print(f"Warning: eigen_s_batch: invalid arguments (n={n}, batch={batch}, lda={lda}, ldw={ldw}, ldz={ldz}, "
-              f"stride_a={stride_a}, stride_z={stride_z}, mode={mode!r})", file=sys.stderr)
-        return
-    lib = _lib.load()
-    if not _state["initialized"]:
-        _state["last_status"] = -1
-        return
-    dev = _is_torch(a)
-    if dev:
-        import torch
-
-        torch.cuda.current_stream().synchronize()
-    for x, name in ((a, "a"), (w, "w"), (z if md == b"A" else None, "z")):
-        if x is not None and not dev and x.ndim > 2 and not x.flags.f_contiguous:
-            raise ValueError(f"{name}: Fortran (column-major) order required, as in the reference")
-    pa, pw = _ptr(a, "a", dev), _ptr(w, "w", dev)
-    pz = _ptr(z, "z", dev) if md == b"A" else None
-    pi = None
-    if info is not None:
-        if dev != _is_torch(info):
-            raise ValueError("a, w, z, info must all be host arrays or all be device tensors")
-        if dev:
-            if not info.is_cuda or info.dtype != torch.int32:
-                raise ValueError("info: int32 GPU tensor required")
-            pi = info.data_ptr()
-        else:
-            if info.dtype != np.int32:
-                raise ValueError("info: int32 required")
-            pi = info.ctypes.data
-    fn = lib.eigx_s_batch_dev if dev else lib.eigx_s_batch
-    rc = fn(n, batch, pa, lda, stride_a, pw, ldw, pz, ldz, stride_z, md, pi)
-    _state["last_status"] = rc
-    if rc not in (0, -5, -6):
-        print(f"Warning: eigen_s_batch returned without computing (status {rc})", file=sys.stderr)
+        print(f"Warning: {name}: invalid window / mode (n={n}, il={il}, iu={iu}, mode={mode!r})", file=sys.stderr)
+        return None
+    return md
 
 
 def _value_window(name, n, vl, vu, w, z, mode, mmax):
@@ -379,33 +302,107 @@ def _value_window(name, n, vl, vu, w, z, mode, mmax):
 
 
 def _finish_value_call(name, rc, m, il, quiet):
-    _state["last_status"] = rc
-    if rc not in quiet:
-        print(f"Warning: {name} returned without computing (status {rc})", file=sys.stderr)
+    _finish(name, rc, quiet)
     return (m.value, il.value) if rc in (0, -9) else None
 
 
-def _solve_range_v(which, n, vl, vu, a, lda, w, z, ldz, m_forward, m_backward, mode, mmax):
-    chk = _value_window(f"eigen_{which}_range_v", n, vl, vu, w, z, mode, mmax)
-    if chk is None:
-        return None
-    md, mmax = chk
-    lib = _lib.load()
-    if not _state["initialized"]:
-        _state["last_status"] = -1
-        return None
-    dev = _is_torch(a)
-    if dev:
-        import torch
+# ---- standard problem: 'sx', 's' (real symmetric), 'h' (complex Hermitian) --------------------------------------------
+def _solve(which, n, nvec, a, lda, w, z, ldz, m_forward, m_backward, mode, nb=None):
+    began = _begin(a)
+    if began is None:
+        return
+    lib, dev = began
+    pa, pw, pz = _addrs(which, dev, a=a, w=w, z=z)
+    mf, mb = _blocks(m_forward, m_backward)
+    if nb is None:
+        rc = _entry(lib, f"eigx_{which}", dev)(int(n), int(nvec), pa, int(lda), pw, pz, int(ldz), mf, mb, _char(mode, "A"))
+    else:
+        rc = _entry(lib, "eigx_solve_bc", dev)(2 if which == "sx" else 1, int(n), int(nvec), pa, int(lda), pw, pz, int(ldz),
+                                               int(nb), mf, mb, _char(mode, "A"))
+    _finish(f"eigen_{which}", rc)
 
-        torch.cuda.current_stream().synchronize()
-    pa, pw, pz = _ptr(a, "a", dev), _ptr(w, "w", dev), _ptr(z, "z", dev)
-    mf = eigen_NB_f if m_forward is None else int(m_forward)
-    mb = eigen_NB_b if m_backward is None else int(m_backward)
-    fn = getattr(lib, f"eigx_{which}_range_v" + ("_dev" if dev else ""))
+
+def eigen_sx(n, nvec, a, lda, w, z, ldz, m_forward=None, m_backward=None, mode="A"):
+    """Pentadiagonal route (eigen_prd -> eigen_dcx -> trbakwy, src/eigen_sx.F:30-308)."""
+    _solve("sx", n, nvec, a, lda, w, z, ldz, m_forward, m_backward, mode)
+
+
+def eigen_s(n, nvec, a, lda, w, z, ldz, m_forward=None, m_backward=None, mode="A"):
+    """Tridiagonal route (eigen_trd -> dc2 -> trbakwy, src/eigen_libs.F:150-202)."""
+    _solve("s", n, nvec, a, lda, w, z, ldz, m_forward, m_backward, mode)
+
+
+def eigen_h(n, nvec, a, lda, w, z, ldz, m_forward=None, m_backward=None, mode="A"):
+    """Complex Hermitian solver (src/eigen_h.F:30-322: eigen_hrd -> dc2 -> eigen_hrbakwyx).  ``a``, ``z``: complex128,
+    column-major (numpy, Fortran order) or GPU tensors holding the column-major image (``a[j, i] = A(i, j)``); upper
+    triangle of ``a`` significant, ``a`` destroyed; ``w`` float64 ascending.  modes 'A', 'N', 'X'.  One GPU."""
+    _solve("h", n, nvec, a, lda, w, z, ldz, m_forward, m_backward, mode)
+
+
+def eigen_sx_bc(n, nvec, a, lda, w, z, ldz, nb, m_forward=None, m_backward=None, mode="A"):
+    """eigen_sx on the local blocks of a 2-D block-cyclic (ScaLAPACK, MB = NB = nb) distribution over the process grid:
+    no pdgemr2d redistribution into the cyclic layout is needed (manual 3.4).  ``z`` returns in the same distribution."""
+    _solve("sx", n, nvec, a, lda, w, z, ldz, m_forward, m_backward, mode, nb=nb)
+
+
+def eigen_s_bc(n, nvec, a, lda, w, z, ldz, nb, m_forward=None, m_backward=None, mode="A"):
+    """eigen_s on block-cyclic local blocks (see eigen_sx_bc)."""
+    _solve("s", n, nvec, a, lda, w, z, ldz, m_forward, m_backward, mode, nb=nb)
+
+
+def numroc(n, nb, iproc, nprocs):
+    """ScaLAPACK NUMROC with source process 0: local extent of n indices in blocks of nb on process iproc of nprocs"""
+    return _lib.load().eigx_numroc(int(n), int(nb), int(iproc), int(nprocs))
+
+
+def _solve_range(which, n, il, iu, a, lda, w, z, ldz, m_forward, m_backward, mode):
+    name = f"eigen_{which}_range"
+    md = _index_window(name, n, il, iu, z, mode)
+    began = _begin(a) if md else None
+    if began is None:
+        return
+    lib, dev = began
+    pa, pw, pz = _addrs(which, dev, a=a, w=w, z=z)
+    rc = _entry(lib, f"eigx_{which}_range", dev)(int(n), int(il), int(iu), pa, int(lda), pw, pz, int(ldz),
+                                                 *_blocks(m_forward, m_backward), md)
+    _finish(name, rc)
+
+
+def eigen_sx_range(n, il, iu, a, lda, w, z, ldz, m_forward=None, m_backward=None, mode="A"):
+    """EXTENSION (not in the reference): eigenpairs ``il .. iu`` (1-based, inclusive) of the ascending spectrum by the
+    pentadiagonal route, one GPU.  ``w[:m]``, ``z[:, :m]`` with ``m = iu - il + 1``; modes 'A' and 'N'.  Work and memory
+    after the reduction scale with ``m`` (Sturm multi-section on the window, inverse iteration, CholQR2 + Rayleigh-Ritz);
+    ``range_info()`` tells whether that path or the full divide and conquer produced the result."""
+    _solve_range("sx", n, il, iu, a, lda, w, z, ldz, m_forward, m_backward, mode)
+
+
+def eigen_s_range(n, il, iu, a, lda, w, z, ldz, m_forward=None, m_backward=None, mode="A"):
+    """EXTENSION: ``eigen_sx_range`` by the tridiagonal route."""
+    _solve_range("s", n, il, iu, a, lda, w, z, ldz, m_forward, m_backward, mode)
+
+
+def eigen_h_range(n, il, iu, a, lda, w, z, ldz, m_forward=None, m_backward=None, mode="A"):
+    """EXTENSION (not in the reference): eigenpairs ``il .. iu`` (1-based, inclusive) of the ascending spectrum of a complex
+    Hermitian matrix, one GPU.  Arrays as for ``eigen_h`` (``a``, ``z`` complex128, ``w`` float64); ``w[:m]``, ``z[:, :m]``
+    with ``m = iu - il + 1``; modes 'A' and 'N' (``z`` may be None).  After eigen_h's reduction the work and the memory
+    scale with ``m`` (multi-section on the window, inverse iteration, CholQR2 + Rayleigh-Ritz on the real tridiagonal
+    matrix, back-transformation of ``m`` columns); ``range_info()`` tells whether that path or the full divide and conquer
+    produced the result."""
+    _solve_range("h", n, il, iu, a, lda, w, z, ldz, m_forward, m_backward, mode)
+
+
+def _solve_range_v(which, n, vl, vu, a, lda, w, z, ldz, m_forward, m_backward, mode, mmax):
+    name = f"eigen_{which}_range_v"
+    chk = _value_window(name, n, vl, vu, w, z, mode, mmax)
+    began = _begin(a) if chk else None
+    if began is None:
+        return None
+    (md, mmax), (lib, dev) = chk, began
+    pa, pw, pz = _addrs(which, dev, a=a, w=w, z=z)
     m, il = C.c_int(0), C.c_int(0)
-    rc = fn(int(n), float(vl), float(vu), mmax, C.byref(m), C.byref(il), pa, int(lda), pw, pz, int(ldz), mf, mb, md)
-    return _finish_value_call(f"eigen_{which}_range_v", rc, m, il, (0, -5, -9))
+    rc = _entry(lib, f"eigx_{which}_range_v", dev)(int(n), float(vl), float(vu), mmax, C.byref(m), C.byref(il), pa, int(lda),
+                                                   pw, pz, int(ldz), *_blocks(m_forward, m_backward), md)
+    return _finish_value_call(name, rc, m, il, (0, -5, -9))
 
 
 def eigen_sx_range_v(n, vl, vu, a, lda, w, z, ldz, m_forward=None, m_backward=None, mode="A", mmax=None):
@@ -423,6 +420,85 @@ def eigen_sx_range_v(n, vl, vu, a, lda, w, z, ldz, m_forward=None, m_backward=No
 def eigen_s_range_v(n, vl, vu, a, lda, w, z, ldz, m_forward=None, m_backward=None, mode="A", mmax=None):
     """EXTENSION: ``eigen_sx_range_v`` by the tridiagonal route."""
     return _solve_range_v("s", n, vl, vu, a, lda, w, z, ldz, m_forward, m_backward, mode, mmax)
+
+
+def eigen_h_range_v(n, vl, vu, a, lda, w, z, ldz, m_forward=None, m_backward=None, mode="A", mmax=None):
+    """EXTENSION (not in the reference; LAPACK's range = 'V'): the eigenpairs of a complex Hermitian matrix with
+    ``vl <= lambda < vu``, one GPU, at the cost of ONE reduction.  Arrays as for ``eigen_h``; window, ``mmax``, modes
+    ('A', 'N', 'C'), statuses and the returned ``(m, il)`` as for ``eigen_sx_range_v``; ``w[:m]``, ``z[:, :m]`` as from
+    ``eigen_h_range(n, il, il + m - 1, ...)``, bit for bit.  Returns None when nothing was resolved."""
+    return _solve_range_v("h", n, vl, vu, a, lda, w, z, ldz, m_forward, m_backward, mode, mmax)
+
+
+def _solve_batch(which, n, batch, a, lda, w, z, ldz, mode, info, stride_a, ldw, stride_z):
+    name = f"eigen_{which}_batch"
+    # the arguments are checked here, before the library is touched (status -2 = EIGX_ERR_BAD_ARG)
+    md = _char(mode, "A").upper()
+    try:
+        n, batch, lda = int(n), int(batch), int(lda)
+        ldw = n if ldw is None else int(ldw)
+        ldz = int(ldz) if md == b"A" else (0 if ldz is None else int(ldz))
+        stride_a = lda * n if stride_a is None else int(stride_a)
+        stride_z = ldz * n if stride_z is None else int(stride_z)
+        ok = n >= 1 and batch >= 0 and lda >= n and ldw >= n and md in (b"A", b"N") and a is not None and w is not None
+        ok = ok and (batch <= 1 or stride_a >= lda * n)
+        if md == b"A":
+            ok = ok and z is not None and ldz >= n and (batch <= 1 or stride_z >= ldz * n)
+    except (TypeError, ValueError):
+        ok = False
+    if not ok:
+        _state["last_status"] = -2
+        print(f"Warning: {name}: invalid arguments (n={n}, batch={batch}, lda={lda}, ldw={ldw}, ldz={ldz}, "
+              f"stride_a={stride_a}, stride_z={stride_z}, mode={mode!r})", file=sys.stderr)
+        return
+    began = _begin(a)
+    if began is None:
+        return
+    lib, dev = began
+    if md != b"A":
+        z = None
+    for x, xname in ((a, "a"), (w, "w"), (z, "z")):
+        if x is not None and not dev and not _is_torch(x) and x.ndim > 2 and not x.flags.f_contiguous:
+            raise ValueError(f"{xname}: Fortran (column-major) order required, as in the reference")
+    pa, pw, pz = _addrs(which, dev, a=a, w=w, z=z)
+    pi = None
+    if info is not None:
+        if dev != _is_torch(info):
+            raise ValueError("a, w, z, info must all be host arrays or all be device tensors")
+        if dev:
+            import torch
+
+            if not info.is_cuda or info.dtype != torch.int32:
+                raise ValueError("info: int32 GPU tensor required")
+        elif info.dtype != np.int32:
+            raise ValueError("info: int32 required")
+        pi = info.data_ptr() if dev else info.ctypes.data
+    rc = _entry(lib, f"eigx_{which}_batch", dev)(n, batch, pa, lda, stride_a, pw, ldw, pz, ldz, stride_z, md, pi)
+    _finish(name, rc, (0, -5, -6))
+
+
+def eigen_s_batch(n, batch, a, lda, w, z, ldz, mode="A", info=None, stride_a=None, ldw=None, stride_z=None):
+    """EXTENSION (not in the reference): ``batch`` symmetric matrices of one size ``n`` in one call, one GPU.  ``a`` holds the
+    matrices as ``a[lda, n, batch]`` (numpy, Fortran order) or a GPU tensor with the same memory image: matrix ``k`` starts at
+    element ``k * stride_a``, upper triangle significant, destroyed.  ``w[ldw, batch]`` receives the ascending eigenvalues,
+    ``z[ldz, n, batch]`` the eigenvectors (mode 'A'; mode 'N': eigenvalues only, ``z`` may be None).  Defaults:
+    ``stride_a = lda * n``, ``stride_z = ldz * n``, ``ldw = n``.  ``info`` (optional, int32, ``batch`` entries, on the side of
+    ``a``) receives the per-matrix status: 0, -5 (NaN / Inf in the matrix: its ``w`` is NaN, its ``z`` untouched) or -6;
+    ``last_status()`` is 0 or the status of the first failed matrix.  For ``n <= 128`` one kernel launch solves the batch,
+    one workgroup per matrix with the matrix in LDS; larger ``n`` runs ``eigen_s`` matrix by matrix."""
+    _solve_batch("s", n, batch, a, lda, w, z, ldz, mode, info, stride_a, ldw, stride_z)
+
+
+def eigen_h_batch(n, batch, a, lda, w, z, ldz, mode="A", info=None, stride_a=None, ldw=None, stride_z=None):
+    """EXTENSION (not in the reference): ``batch`` complex Hermitian matrices of one size ``n`` in one call, one GPU -- the
+    complex sibling of ``eigen_s_batch``.  ``a`` holds the matrices as ``a[lda, n, batch]`` (complex128 numpy, Fortran order)
+    or a complex128 GPU tensor with the same memory image: matrix ``k`` starts at complex element ``k * stride_a``, upper
+    triangle significant (of the diagonal the real parts only), destroyed.  ``w[ldw, batch]`` (float64) receives the ascending
+    eigenvalues, ``z[ldz, n, batch]`` (complex128) the orthonormal eigenvectors (mode 'A'; mode 'N': eigenvalues only, ``z``
+    may be None).  Defaults, ``info`` and ``last_status()`` as for ``eigen_s_batch``; leading dimensions and strides count
+    complex elements.  For ``n <= 96`` one kernel launch solves the batch, one workgroup per matrix with the matrix in LDS;
+    larger ``n`` runs ``eigen_h`` matrix by matrix."""
+    _solve_batch("h", n, batch, a, lda, w, z, ldz, mode, info, stride_a, ldw, stride_z)
 
 
 def band_count(d, e, band, x):
@@ -457,84 +533,48 @@ def range_info():
     return collections.namedtuple("RangeInfo", "path m cond")(p.value, m.value, c.value)
 
 
-def eigen_h(n, nvec, a, lda, w, z, ldz, m_forward=None, m_backward=None, mode="A"):
-    """Complex Hermitian solver (src/eigen_h.F:30-322: eigen_hrd -> dc2 -> eigen_hrbakwyx).  ``a``, ``z``: complex128,
-    column-major (numpy, Fortran order) or GPU tensors holding the column-major image (``a[j, i] = A(i, j)``); upper
-    triangle of ``a`` significant, ``a`` destroyed; ``w`` float64 ascending.  modes 'A', 'N', 'X'.  One GPU."""
-    lib = _lib.load()
-    if not _state["initialized"]:
-        _state["last_status"] = -1
+# ---- generalised problem A x = lambda B x: 'gev' (real symmetric-definite), 'hgev' (complex Hermitian-definite) -------
+def _gev(which, quiet, n, a, lda, b, ldb, w, z, ldz):
+    began = _begin(a)
+    if began is None:
         return
-    dev = _is_torch(a)
-
-    def cptr(x, name, real=False):
-        if x is None:
-            return None
-        if dev:
-            import torch
-
-            if not (_is_torch(x) and x.is_cuda):
-                raise ValueError("a, w, z must all be host arrays or all be device tensors")
-            if x.dtype != (torch.float64 if real else torch.complex128):
-                raise ValueError(f"{name}: {'float64' if real else 'complex128'} required")
-            return x.data_ptr()
-        if _is_torch(x):
-            raise ValueError("a, w, z must all be host arrays or all be device tensors")
-        if x.dtype != (np.float64 if real else np.complex128):
-            raise ValueError(f"{name}: {'float64' if real else 'complex128'} required")
-        if x.ndim == 2 and not x.flags.f_contiguous:
-            raise ValueError(f"{name}: Fortran (column-major) order required, as in the reference")
-        return x.ctypes.data
-
-    if dev:
-        import torch
-
-        torch.cuda.current_stream().synchronize()
-    mf = eigen_NB_f if m_forward is None else int(m_forward)
-    mb = eigen_NB_b if m_backward is None else int(m_backward)
-    fn = lib.eigx_h_dev if dev else lib.eigx_h
-    rc = fn(int(n), int(nvec), cptr(a, "a"), int(lda), cptr(w, "w", real=True), cptr(z, "z"), int(ldz), mf, mb,
-            _char(mode, "A"))
-    _state["last_status"] = rc
-    if rc not in (0, -5):
-        print(f"Warning: eigen_h returned without computing (status {rc})", file=sys.stderr)
+    lib, dev = began
+    pa, pb, pw, pz = _addrs(which, dev, a=a, b=b, w=w, z=z)
+    rc = _entry(lib, f"eigx_{which}", dev)(int(n), pa, int(lda), pb, int(ldb), pw, pz, int(ldz))
+    _finish(f"KMATH_EIGEN_{which.upper()}", rc, quiet)
 
 
-def eigen_sx_bc(n, nvec, a, lda, w, z, ldz, nb, m_forward=None, m_backward=None, mode="A"):
-    """eigen_sx on the local blocks of a 2-D block-cyclic (ScaLAPACK, MB = NB = nb) distribution over the process grid:
-    no pdgemr2d redistribution into the cyclic layout is needed (manual 3.4).  ``z`` returns in the same distribution."""
-    _solve("sx", n, nvec, a, lda, w, z, ldz, m_forward, m_backward, mode, nb=nb)
+def _gev_range(which, n, il, iu, a, lda, b, ldb, w, z, ldz, mode):
+    name = f"KMATH_EIGEN_{which.upper()}_RANGE"
+    md = _index_window(name, n, il, iu, z, mode)
+    began = _begin(a) if md else None
+    if began is None:
+        return
+    lib, dev = began
+    pa, pb, pw, pz = _addrs(which, dev, a=a, b=b, w=w, z=z)
+    rc = _entry(lib, f"eigx_{which}_range", dev)(int(n), int(il), int(iu), pa, int(lda), pb, int(ldb), pw, pz, int(ldz), md)
+    _finish(name, rc, (0, -5, -7))
 
 
-def eigen_s_bc(n, nvec, a, lda, w, z, ldz, nb, m_forward=None, m_backward=None, mode="A"):
-    """eigen_s on block-cyclic local blocks (see eigen_sx_bc)."""
-    _solve("s", n, nvec, a, lda, w, z, ldz, m_forward, m_backward, mode, nb=nb)
-
-
-def numroc(n, nb, iproc, nprocs):
-    """ScaLAPACK NUMROC with source process 0: local extent of n indices in blocks of nb on process iproc of nprocs"""
-    return _lib.load().eigx_numroc(int(n), int(nb), int(iproc), int(nprocs))
+def _gev_range_v(which, n, vl, vu, a, lda, b, ldb, w, z, ldz, mode, mmax):
+    name = f"KMATH_EIGEN_{which.upper()}_RANGE_V"
+    chk = _value_window(name, n, vl, vu, w, z, mode, mmax)
+    began = _begin(a) if chk else None
+    if began is None:
+        return None
+    (md, mmax), (lib, dev) = chk, began
+    pa, pb, pw, pz = _addrs(which, dev, a=a, b=b, w=w, z=z)
+    m, il = C.c_int(0), C.c_int(0)
+    rc = _entry(lib, f"eigx_{which}_range_v", dev)(int(n), float(vl), float(vu), mmax, C.byref(m), C.byref(il), pa, int(lda),
+                                                   pb, int(ldb), pw, pz, int(ldz), md)
+    return _finish_value_call(name, rc, m, il, (0, -5, -7, -9))
 
 
 def KMATH_EIGEN_GEV(n, a, lda, b, ldb, w, z, ldz):
     """Generalised symmetric-definite problem A x = lambda B x (src/KMATH_EIGEN_GEV.F:1-64): two eigen_s solves and
     three GEMMs.  Upper triangles of ``a``, ``b`` significant; ``w`` ascending, ``z`` B-orthonormal; ``a`` and ``b``
     are destroyed.  If B is not positive definite a message is printed and the call returns (status -7)."""
-    lib = _lib.load()
-    if not _state["initialized"]:
-        _state["last_status"] = -1
-        return
-    dev = _is_torch(a)
-    if dev:
-        import torch
-
-        torch.cuda.current_stream().synchronize()
-    pa, pb, pw, pz = _ptr(a, "a", dev), _ptr(b, "b", dev), _ptr(w, "w", dev), _ptr(z, "z", dev)
-    fn = lib.eigx_gev_dev if dev else lib.eigx_gev
-    rc = fn(int(n), pa, int(lda), pb, int(ldb), pw, pz, int(ldz))
-    _state["last_status"] = rc
-    if rc not in (0, -7):
-        print(f"Warning: KMATH_EIGEN_GEV returned without computing (status {rc})", file=sys.stderr)
+    _gev("gev", (0, -7), n, a, lda, b, ldb, w, z, ldz)
 
 
 def KMATH_EIGEN_GEV_RANGE(n, il, iu, a, lda, b, ldb, w, z, ldz, mode="A"):
@@ -543,32 +583,7 @@ def KMATH_EIGEN_GEV_RANGE(n, il, iu, a, lda, b, ldb, w, z, ldz, mode="A"):
     with ``z^T B z = I``, ``m = iu - il + 1``; modes 'A' and 'N' (``z`` may be None).  Upper triangles of ``a``, ``b``
     significant; ``a`` is destroyed, ``b`` holds U in its upper triangle.  Status -7 if B is not positive definite, -5
     (``w[:m]`` = NaN) for a non-finite entry of either triangle.  ``range_info()`` reports on the inner range solve."""
-    # the window and the mode are checked here, before the library is touched (status -2 = EIGX_ERR_BAD_ARG)
-    md = _char(mode, "A").upper()
-    try:
-        ok = 1 <= int(il) <= int(iu) <= int(n) and md in (b"A", b"N") and not (md == b"A" and z is None)
-    except (TypeError, ValueError):
-        ok = False
-    if not ok:
-        _state["last_status"] = -2
-        print(f"Warning: KMATH_EIGEN_GEV_RANGE: invalid window / mode (n={n}, il={il}, iu={iu}, mode={mode!r})",
-              file=sys.stderr)
-        return
-    lib = _lib.load()
-    if not _state["initialized"]:
-        _state["last_status"] = -1
-        return
-    dev = _is_torch(a)
-    if dev:
-        import torch
-
-        torch.cuda.current_stream().synchronize()
-    pa, pb, pw, pz = _ptr(a, "a", dev), _ptr(b, "b", dev), _ptr(w, "w", dev), _ptr(z, "z", dev)
-    fn = lib.eigx_gev_range_dev if dev else lib.eigx_gev_range
-    rc = fn(int(n), int(il), int(iu), pa, int(lda), pb, int(ldb), pw, pz, int(ldz), md)
-    _state["last_status"] = rc
-    if rc not in (0, -5, -7):
-        print(f"Warning: KMATH_EIGEN_GEV_RANGE returned without computing (status {rc})", file=sys.stderr)
+    _gev_range("gev", n, il, iu, a, lda, b, ldb, w, z, ldz, mode)
 
 
 def KMATH_EIGEN_GEV_RANGE_V(n, vl, vu, a, lda, b, ldb, w, z, ldz, mode="A", mmax=None):
@@ -576,24 +591,7 @@ def KMATH_EIGEN_GEV_RANGE_V(n, vl, vu, a, lda, b, ldb, w, z, ldz, mode="A", mmax
     of ``KMATH_EIGEN_GEV_RANGE``, one GPU.  Window, ``mmax``, modes, statuses and the returned ``(m, il)`` as for
     ``eigen_sx_range_v``; ``z[:, :m]`` with ``z^T B z = I``.  ``a`` is destroyed and ``b`` holds U on status 0; on status -9
     host arrays are left as they were passed.  Status -7 if B is not positive definite."""
-    chk = _value_window("KMATH_EIGEN_GEV_RANGE_V", n, vl, vu, w, z, mode, mmax)
-    if chk is None:
-        return None
-    md, mmax = chk
-    lib = _lib.load()
-    if not _state["initialized"]:
-        _state["last_status"] = -1
-        return None
-    dev = _is_torch(a)
-    if dev:
-        import torch
-
-        torch.cuda.current_stream().synchronize()
-    pa, pb, pw, pz = _ptr(a, "a", dev), _ptr(b, "b", dev), _ptr(w, "w", dev), _ptr(z, "z", dev)
-    fn = lib.eigx_gev_range_v_dev if dev else lib.eigx_gev_range_v
-    m, il = C.c_int(0), C.c_int(0)
-    rc = fn(int(n), float(vl), float(vu), mmax, C.byref(m), C.byref(il), pa, int(lda), pb, int(ldb), pw, pz, int(ldz), md)
-    return _finish_value_call("KMATH_EIGEN_GEV_RANGE_V", rc, m, il, (0, -5, -7, -9))
+    return _gev_range_v("gev", n, vl, vu, a, lda, b, ldb, w, z, ldz, mode, mmax)
 
 
 def KMATH_EIGEN_HGEV(n, a, lda, b, ldb, w, z, ldz):
@@ -603,39 +601,7 @@ def KMATH_EIGEN_HGEV(n, a, lda, b, ldb, w, z, ldz):
     (``a[j, i] = A(i, j)``), leading dimensions in complex elements; ``w`` float64.  Upper triangles of ``a``, ``b``
     significant; ``w`` ascending, ``z^H B z = I``; on exit ``a`` holds Y and ``b`` holds F = U mu^-1/2, as in
     KMATH_EIGEN_GEV.  If B is not positive definite a message is printed and the call returns (status -7)."""
-    lib = _lib.load()
-    if not _state["initialized"]:
-        _state["last_status"] = -1
-        return
-    dev = _is_torch(a)
-
-    def cptr(x, name, real=False):
-        if dev:
-            import torch
-
-            if not (_is_torch(x) and x.is_cuda):
-                raise ValueError("a, b, w, z must all be host arrays or all be device tensors")
-            if x.dtype != (torch.float64 if real else torch.complex128):
-                raise ValueError(f"{name}: {'float64' if real else 'complex128'} required")
-            return x.data_ptr()
-        if _is_torch(x):
-            raise ValueError("a, b, w, z must all be host arrays or all be device tensors")
-        if x.dtype != (np.float64 if real else np.complex128):
-            raise ValueError(f"{name}: {'float64' if real else 'complex128'} required")
-        if x.ndim == 2 and not x.flags.f_contiguous:
-            raise ValueError(f"{name}: Fortran (column-major) order required, as in the reference")
-        return x.ctypes.data
-
-    if dev:
-        import torch
-
-        torch.cuda.current_stream().synchronize()
-    pa, pb, pw, pz = cptr(a, "a"), cptr(b, "b"), cptr(w, "w", real=True), cptr(z, "z")
-    fn = lib.eigx_hgev_dev if dev else lib.eigx_hgev
-    rc = fn(int(n), pa, int(lda), pb, int(ldb), pw, pz, int(ldz))
-    _state["last_status"] = rc
-    if rc not in (0, -5, -7):
-        print(f"Warning: KMATH_EIGEN_HGEV returned without computing (status {rc})", file=sys.stderr)
+    _gev("hgev", (0, -5, -7), n, a, lda, b, ldb, w, z, ldz)
 
 
 def KMATH_EIGEN_HGEV_RANGE(n, il, iu, a, lda, b, ldb, w, z, ldz, mode="A"):
@@ -646,198 +612,7 @@ def KMATH_EIGEN_HGEV_RANGE(n, il, iu, a, lda, b, ldb, w, z, ldz, mode="A"):
     ascending, ``z[:, :m]`` with ``z^H B z = I``, ``m = iu - il + 1``; modes 'A' and 'N' (``z`` may be None).  Upper
     triangles of ``a``, ``b`` significant; ``a`` is destroyed, ``b`` holds U in its upper triangle.  Status -7 if B is
     not positive definite, -5 (``w[:m]`` = NaN) for a non-finite entry of either triangle."""
-    # the window and the mode are checked here, before the library is touched (status -2 = EIGX_ERR_BAD_ARG)
-    md = _char(mode, "A").upper()
-    try:
-        ok = 1 <= int(il) <= int(iu) <= int(n) and md in (b"A", b"N") and not (md == b"A" and z is None)
-    except (TypeError, ValueError):
-        ok = False
-    if not ok:
-        _state["last_status"] = -2
-        print(f"Warning: KMATH_EIGEN_HGEV_RANGE: invalid window / mode (n={n}, il={il}, iu={iu}, mode={mode!r})",
-              file=sys.stderr)
-        return
-    lib = _lib.load()
-    if not _state["initialized"]:
-        _state["last_status"] = -1
-        return
-    dev = _is_torch(a)
-
-    def cptr(x, name, real=False):
-        if x is None:
-            return None
-        if dev:
-            import torch
-
-            if not (_is_torch(x) and x.is_cuda):
-                raise ValueError("a, b, w, z must all be host arrays or all be device tensors")
-            if x.dtype != (torch.float64 if real else torch.complex128):
-                raise ValueError(f"{name}: {'float64' if real else 'complex128'} required")
-            return x.data_ptr()
-        if _is_torch(x):
-            raise ValueError("a, b, w, z must all be host arrays or all be device tensors")
-        if x.dtype != (np.float64 if real else np.complex128):
-            raise ValueError(f"{name}: {'float64' if real else 'complex128'} required")
-        if x.ndim == 2 and not x.flags.f_contiguous:
-            raise ValueError(f"{name}: Fortran (column-major) order required, as in the reference")
-        return x.ctypes.data
-
-    if dev:
-        import torch
-
-        torch.cuda.current_stream().synchronize()
-    pa, pb, pw, pz = cptr(a, "a"), cptr(b, "b"), cptr(w, "w", real=True), cptr(z, "z")
-    fn = lib.eigx_hgev_range_dev if dev else lib.eigx_hgev_range
-    rc = fn(int(n), int(il), int(iu), pa, int(lda), pb, int(ldb), pw, pz, int(ldz), md)
-    _state["last_status"] = rc
-    if rc not in (0, -5, -7):
-        print(f"Warning: KMATH_EIGEN_HGEV_RANGE returned without computing (status {rc})", file=sys.stderr)
-
-
-def _cptr(x, name, dev, real=False):
-    """address of a complex128 (``real``: float64) array of the complex range wrappers; all host or all device"""
-    if x is None:
-        return None
-    if dev:
-        import torch
-
-        if not (_is_torch(x) and x.is_cuda):
-            raise ValueError("a, b, w, z must all be host arrays or all be device tensors")
-        if x.dtype != (torch.float64 if real else torch.complex128):
-            raise ValueError(f"{name}: {'float64' if real else 'complex128'} required")
-        return x.data_ptr()
-    if _is_torch(x):
-        raise ValueError("a, b, w, z must all be host arrays or all be device tensors")
-    if x.dtype != (np.float64 if real else np.complex128):
-        raise ValueError(f"{name}: {'float64' if real else 'complex128'} required")
-    if x.ndim == 2 and not x.flags.f_contiguous:
-        raise ValueError(f"{name}: Fortran (column-major) order required, as in the reference")
-    return x.ctypes.data
-
-
-def _complex_call_begins(a):
-    """library, device flag -- or None when eigen_init has not been called (status -1)"""
-    lib = _lib.load()
-    if not _state["initialized"]:
-        _state["last_status"] = -1
-        return None
-    dev = _is_torch(a)
-    if dev:
-        import torch
-
-        torch.cuda.current_stream().synchronize()
-    return lib, dev
-
-
-def eigen_h_range(n, il, iu, a, lda, w, z, ldz, m_forward=None, m_backward=None, mode="A"):
-    """EXTENSION (not in the reference): eigenpairs ``il .. iu`` (1-based, inclusive) of the ascending spectrum of a complex
-    Hermitian matrix, one GPU.  Arrays as for ``eigen_h`` (``a``, ``z`` complex128, ``w`` float64); ``w[:m]``, ``z[:, :m]``
-    with ``m = iu - il + 1``; modes 'A' and 'N' (``z`` may be None).  After eigen_h's reduction the work and the memory
-    scale with ``m`` (multi-section on the window, inverse iteration, CholQR2 + Rayleigh-Ritz on the real tridiagonal
-    matrix, back-transformation of ``m`` columns); ``range_info()`` tells whether that path or the full divide and conquer
-    produced the result."""
-    # the window and the mode are checked here, before the library is touched (status -2 = EIGX_ERR_BAD_ARG)
-    md = _char(mode, "A").upper()
-    try:
-        ok = 1 <= int(il) <= int(iu) <= int(n) and md in (b"A", b"N") and not (md == b"A" and z is None)
-    except (TypeError, ValueError):
-        ok = False
-    if not ok:
-        _state["last_status"] = -2
-        print(f"Warning: eigen_h_range: invalid window / mode (n={n}, il={il}, iu={iu}, mode={mode!r})", file=sys.stderr)
-        return
-    began = _complex_call_begins(a)
-    if began is None:
-        return
-    lib, dev = began
-    mf = eigen_NB_f if m_forward is None else int(m_forward)
-    mb = eigen_NB_b if m_backward is None else int(m_backward)
-    fn = lib.eigx_h_range_dev if dev else lib.eigx_h_range
-    rc = fn(int(n), int(il), int(iu), _cptr(a, "a", dev), int(lda), _cptr(w, "w", dev, real=True), _cptr(z, "z", dev),
-            int(ldz), mf, mb, md)
-    _state["last_status"] = rc
-    if rc not in (0, -5):
-        print(f"Warning: eigen_h_range returned without computing (status {rc})", file=sys.stderr)
-
-
-def eigen_h_batch(n, batch, a, lda, w, z, ldz, mode="A", info=None, stride_a=None, ldw=None, stride_z=None):
-    """EXTENSION (not in the reference): ``batch`` complex Hermitian matrices of one size ``n`` in one call, one GPU -- the
-    complex sibling of ``eigen_s_batch``.  ``a`` holds the matrices as ``a[lda, n, batch]`` (complex128 numpy, Fortran order)
-    or a complex128 GPU tensor with the same memory image: matrix ``k`` starts at complex element ``k * stride_a``, upper
-    triangle significant (of the diagonal the real parts only), destroyed.  ``w[ldw, batch]`` (float64) receives the ascending
-    eigenvalues, ``z[ldz, n, batch]`` (complex128) the orthonormal eigenvectors (mode 'A'; mode 'N': eigenvalues only, ``z``
-    may be None).  Defaults, ``info`` and ``last_status()`` as for ``eigen_s_batch``; leading dimensions and strides count
-    complex elements.  For ``n <= 96`` one kernel launch solves the batch, one workgroup per matrix with the matrix in LDS;
-    larger ``n`` runs ``eigen_h`` matrix by matrix."""
-    # the arguments are checked here, before the library is touched (status -2 = EIGX_ERR_BAD_ARG)
-    md = _char(mode, "A").upper()
-    try:
-        n, batch, lda = int(n), int(batch), int(lda)
-        ldw = n if ldw is None else int(ldw)
-        ldz = int(ldz) if md == b"A" else (0 if ldz is None else int(ldz))
-        stride_a = lda * n if stride_a is None else int(stride_a)
-        stride_z = ldz * n if stride_z is None else int(stride_z)
-        ok = n >= 1 and batch >= 0 and lda >= n and ldw >= n and md in (b"A", b"N") and a is not None and w is not None
-        ok = ok and (batch <= 1 or stride_a >= lda * n)
-        if md == b"A":
-            ok = ok and z is not None and ldz >= n and (batch <= 1 or stride_z >= ldz * n)
-    except (TypeError, ValueError):
-        ok = False
-    if not ok:
-        _state["last_status"] = -2
-        print(f"Warning: eigen_h_batch: invalid arguments (n={n}, batch={batch}, lda={lda}, ldw={ldw}, ldz={ldz}, "
-              f"stride_a={stride_a}, stride_z={stride_z}, mode={mode!r})", file=sys.stderr)
-        return
-    began = _complex_call_begins(a)
-    if began is None:
-        return
-    lib, dev = began
-    for x, name in ((a, "a"), (w, "w"), (z if md == b"A" else None, "z")):
-        if x is not None and not dev and not _is_torch(x) and x.ndim > 2 and not x.flags.f_contiguous:
-            raise ValueError(f"{name}: Fortran (column-major) order required, as in the reference")
-    pa, pw = _cptr(a, "a", dev), _cptr(w, "w", dev, real=True)
-    pz = _cptr(z, "z", dev) if md == b"A" else None
-    pi = None
-    if info is not None:
-        if dev != _is_torch(info):
-            raise ValueError("a, w, z, info must all be host arrays or all be device tensors")
-        if dev:
-            import torch
-
-            if not info.is_cuda or info.dtype != torch.int32:
-                raise ValueError("info: int32 GPU tensor required")
-            pi = info.data_ptr()
-        else:
-            if info.dtype != np.int32:
-                raise ValueError("info: int32 required")
-            pi = info.ctypes.data
-    fn = lib.eigx_h_batch_dev if dev else lib.eigx_h_batch
-    rc = fn(n, batch, pa, lda, stride_a, pw, ldw, pz, ldz, stride_z, md, pi)
-    _state["last_status"] = rc
-    if rc not in (0, -5, -6):
-        print(f"Warning: eigen_h_batch returned without computing (status {rc})", file=sys.stderr)
-
-
-def eigen_h_range_v(n, vl, vu, a, lda, w, z, ldz, m_forward=None, m_backward=None, mode="A", mmax=None):
-    """EXTENSION (not in the reference; LAPACK's range = 'V'): the eigenpairs of a complex Hermitian matrix with
-    ``vl <= lambda < vu``, one GPU, at the cost of ONE reduction.  Arrays as for ``eigen_h``; window, ``mmax``, modes
-    ('A', 'N', 'C'), statuses and the returned ``(m, il)`` as for ``eigen_sx_range_v``; ``w[:m]``, ``z[:, :m]`` as from
-    ``eigen_h_range(n, il, il + m - 1, ...)``, bit for bit.  Returns None when nothing was resolved."""
-    chk = _value_window("eigen_h_range_v", n, vl, vu, w, z, mode, mmax)
-    if chk is None:
-        return None
-    md, mmax = chk
-    began = _complex_call_begins(a)
-    if began is None:
-        return None
-    lib, dev = began
-    mf = eigen_NB_f if m_forward is None else int(m_forward)
-    mb = eigen_NB_b if m_backward is None else int(m_backward)
-    fn = lib.eigx_h_range_v_dev if dev else lib.eigx_h_range_v
-    m, il = C.c_int(0), C.c_int(0)
-    rc = fn(int(n), float(vl), float(vu), mmax, C.byref(m), C.byref(il), _cptr(a, "a", dev), int(lda),
-            _cptr(w, "w", dev, real=True), _cptr(z, "z", dev), int(ldz), mf, mb, md)
-    return _finish_value_call("eigen_h_range_v", rc, m, il, (0, -5, -9))
+    _gev_range("hgev", n, il, iu, a, lda, b, ldb, w, z, ldz, mode)
 
 
 def KMATH_EIGEN_HGEV_RANGE_V(n, vl, vu, a, lda, b, ldb, w, z, ldz, mode="A", mmax=None):
@@ -847,16 +622,4 @@ def KMATH_EIGEN_HGEV_RANGE_V(n, vl, vu, a, lda, b, ldb, w, z, ldz, mode="A", mma
     for ``eigen_sx_range_v``; ``z[:, :m]`` with ``z^H B z = I``.  ``a`` is destroyed and ``b`` holds U on status 0; on
     status -9 host arrays are left as they were passed.  Status -7 if B is not positive definite.  Agrees with
     ``KMATH_EIGEN_HGEV_RANGE`` on the resolved window to rounding, not bit for bit (the inner routes differ)."""
-    chk = _value_window("KMATH_EIGEN_HGEV_RANGE_V", n, vl, vu, w, z, mode, mmax)
-    if chk is None:
-        return None
-    md, mmax = chk
-    began = _complex_call_begins(a)
-    if began is None:
-        return None
-    lib, dev = began
-    fn = lib.eigx_hgev_range_v_dev if dev else lib.eigx_hgev_range_v
-    m, il = C.c_int(0), C.c_int(0)
-    rc = fn(int(n), float(vl), float(vu), mmax, C.byref(m), C.byref(il), _cptr(a, "a", dev), int(lda), _cptr(b, "b", dev),
-            int(ldb), _cptr(w, "w", dev, real=True), _cptr(z, "z", dev), int(ldz), md)
-    return _finish_value_call("KMATH_EIGEN_HGEV_RANGE_V", rc, m, il, (0, -5, -7, -9))
+    return _gev_range_v("hgev", n, vl, vu, a, lda, b, ldb, w, z, ldz, mode, mmax)

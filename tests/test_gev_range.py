@@ -13,6 +13,8 @@ import sys
 import numpy as np
 import pytest
 
+from c_header import prototype as _prototype
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 FLANG = os.environ.get("FC", "/opt/rocm/lib/llvm/bin/flang")
 GEVR_SYMBOLS = ["eigx_gev_range", "eigx_gev_range_dev", "eigx_chol_dev", "eigx_trsm_upper_dev", "eigx_gev_reduce_dev"]
@@ -515,14 +517,6 @@ def test_fortran_gev_range_caller(gpu_lib, tmp_path):
 
 
 # ------------------------------------------------------------------------------------------------ CPU
-def _prototype(name):
-    txt = open(os.path.join(ROOT, "include", "eigenexa_amd.h")).read()
-    txt = re.sub(r"/\*.*?\*/", "", txt, flags=re.S)
-    m = re.search(r"\bint\s+" + name + r"\s*\(([^)]*)\)\s*;", txt)
-    assert m, name
-    return [" ".join(p.split()) for p in m.group(1).split(",")]
-
-
 @pytest.mark.parametrize("name", GEVR_SYMBOLS)
 def test_header_prototypes_match_the_ctypes_table(name):
     from eigenexa_amd import _lib

@@ -11,6 +11,8 @@ import sys
 import numpy as np
 import pytest
 
+from c_header import prototype as _prototype
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLD = json.load(open(os.path.join(ROOT, "tests", "golden", "known_answers.json")))
 FLANG = os.environ.get("FC", "/opt/rocm/lib/llvm/bin/flang")
@@ -280,14 +282,6 @@ def test_fortran_caller_known_answer(gpu_lib, tmp_path):
 
 
 # ---------------------------------------------------------------------------------------- CPU
-def _prototype(name):
-    txt = open(os.path.join(ROOT, "include", "eigenexa_amd.h")).read()
-    txt = re.sub(r"/\*.*?\*/", "", txt, flags=re.S)
-    m = re.search(r"\bint\s+" + name + r"\s*\(([^)]*)\)\s*;", txt)
-    assert m, name
-    return [p.strip() for p in m.group(1).split(",")]
-
-
 @pytest.mark.parametrize("name", ["eigx_hgev", "eigx_hgev_dev"])
 def test_header_prototypes_match_the_ctypes_table(name):
     from eigenexa_amd import _lib

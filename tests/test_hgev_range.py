@@ -15,6 +15,8 @@ import sys
 import numpy as np
 import pytest
 
+from c_header import prototype as _prototype
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 FLANG = os.environ.get("FC", "/opt/rocm/lib/llvm/bin/flang")
 HGEVR_SYMBOLS = ["eigx_hgev_range", "eigx_hgev_range_dev", "eigx_zchol_dev", "eigx_ztrsm_upper_dev", "eigx_hgev_reduce_dev"]
@@ -581,14 +583,6 @@ def test_fortran_hgev_range_caller(gpu_lib, tmp_path):
 
 
 # ------------------------------------------------------------------------------------------------ CPU
-def _prototype(name):
-    txt = open(os.path.join(ROOT, "include", "eigenexa_amd.h")).read()
-    txt = re.sub(r"/\*.*?\*/", "", txt, flags=re.S)
-    m = re.search(r"\bint\s+" + name + r"\s*\(([^)]*)\)\s*;", txt)
-    assert m, name
-    return [" ".join(p.split()) for p in m.group(1).split(",")]
-
-
 @pytest.mark.parametrize("name", HGEVR_SYMBOLS)
 def test_header_prototypes_match_the_ctypes_table(name):
     from eigenexa_amd import _lib

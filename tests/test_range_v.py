@@ -15,6 +15,8 @@ import sys
 import numpy as np
 import pytest
 
+from c_header import prototype as _prototype
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLD = json.load(open(os.path.join(os.path.dirname(__file__), "golden", "known_answers.json")))
 GATE_RES = GOLD["gates"]["residual"]
@@ -714,14 +716,6 @@ def test_fortran_value_window_caller(gpu_lib, tmp_path):
 
 
 # ------------------------------------------------------------------------------------------------ CPU
-def _prototype(name):
-    txt = open(os.path.join(ROOT, "include", "eigenexa_amd.h")).read()
-    txt = re.sub(r"/\*.*?\*/", "", txt, flags=re.S)
-    m = re.search(r"\bint\s+" + name + r"\s*\(([^)]*)\)\s*;", txt)
-    assert m, name
-    return [" ".join(p.split()) for p in m.group(1).split(",")]
-
-
 @pytest.mark.parametrize("name", SOLVER_SYMBOLS + GEV_SYMBOLS + ["eigx_band_count_dev"])
 def test_header_prototypes_match_the_ctypes_table(name):
     from eigenexa_amd import _lib
