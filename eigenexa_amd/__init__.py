@@ -31,6 +31,7 @@ from .api import (  # noqa: F401
     eigen_s_range_v,
     eigen_s_batch,
     eigen_h_batch,
+    eigen_gev_batch,
     band_count,
     range_info,
     eigen_sx_bc,

@@ -1,4 +1,4 @@
-"""ctypes binding of libeigenexa_amd.so (the C-ABI declared in include/eigenexa_amd.h).
+"""ctypes binding of libeigenexa_amd.so (the C-ABI declared in include/eigenexa_amd.h and the file it includes).
 
 There is no CPU fallback: if the HIP library is missing or no GPU is visible the calls fail loudly.
 """
@@ -31,6 +31,8 @@ _GEV_RANGE = [_INT, _INT, _INT, _PTR, _INT, _PTR, _INT, _PTR, _PTR, _INT, C.c_ch
 _GEV_RANGE_V = [_INT, C.c_double, C.c_double, _INT, _c_int_p, _c_int_p, _PTR, _INT, _PTR, _INT, _PTR, _PTR, _INT, C.c_char]
 # n, batch, a, lda, stride_a, w, ldw, z, ldz, stride_z, mode, info
 _BATCH = [_INT, _INT, _PTR, _INT, C.c_int64, _PTR, _INT, _PTR, _INT, C.c_int64, C.c_char, _PTR]
+# n, batch, a, lda, stride_a, b, ldb, stride_b, w, ldw, z, ldz, stride_z, mode, info
+_GEV_BATCH = [_INT, _INT, _PTR, _INT, C.c_int64, _PTR, _INT, C.c_int64, _PTR, _INT, _PTR, _INT, C.c_int64, C.c_char, _PTR]
 # the index helpers: index, nnod, inod
 _INDEX = [_INT, _INT, _INT]
 # stages of the Cholesky route: (n, b, ldb), (trans, n, nrhs, u, ldu, x, ldx), (n, a, lda, u, ldu)
@@ -149,6 +151,14 @@ SIGNATURES = {
     "eigx_memcpy_d2h": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64]),
 }
 
+# The same for include/eigenexa_amd_gbatch.h (which eigenexa_amd.h includes) -- extension: many small symmetric-definite
+# pencils in one call (csrc/gbatch.hip); b comes back as U.  A table of its own: SIGNATURES above is held fixed,
+# name by name and in order, by tests/test_api_frontend.py.
+GBATCH_SIGNATURES = {
+    "eigx_gev_batch": (C.c_int, _GEV_BATCH),
+    "eigx_gev_batch_dev": (C.c_int, _GEV_BATCH),
+}
+
 _lib = None
 
 
@@ -163,7 +173,7 @@ def load():
             "eigenexa_amd has no CPU fallback."
         )
     lib = C.CDLL(LIB_PATH, mode=C.RTLD_GLOBAL)
-    for name, (res, args) in SIGNATURES.items():
+    for name, (res, args) in {**SIGNATURES, **GBATCH_SIGNATURES}.items():
         fn = getattr(lib, name)  # AttributeError = header/library mismatch: fail loudly
         fn.restype = res
         fn.argtypes = args

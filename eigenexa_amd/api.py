@@ -430,6 +430,22 @@ def eigen_h_range_v(n, vl, vu, a, lda, w, z, ldz, m_forward=None, m_backward=Non
     return _solve_range_v("h", n, vl, vu, a, lda, w, z, ldz, m_forward, m_backward, mode, mmax)
 
 
+def _info_addr(info, dev, names):
+    """address of the per-matrix status array of a batch call (None: null): int32, on the side of the other arrays"""
+    if info is None:
+        return None
+    if dev != _is_torch(info):
+        raise ValueError(f"{names} must all be host arrays or all be device tensors")
+    if dev:
+        import torch
+
+        if not info.is_cuda or info.dtype != torch.int32:
+            raise ValueError("info: int32 GPU tensor required")
+    elif info.dtype != np.int32:
+        raise ValueError("info: int32 required")
+    return info.data_ptr() if dev else info.ctypes.data
+
+
 def _solve_batch(which, n, batch, a, lda, w, z, ldz, mode, info, stride_a, ldw, stride_z):
     name = f"eigen_{which}_batch"
     # the arguments are checked here, before the library is touched (status -2 = EIGX_ERR_BAD_ARG)
@@ -461,18 +477,7 @@ def _solve_batch(which, n, batch, a, lda, w, z, ldz, mode, info, stride_a, ldw, 
         if x is not None and not dev and not _is_torch(x) and x.ndim > 2 and not x.flags.f_contiguous:
             raise ValueError(f"{xname}: Fortran (column-major) order required, as in the reference")
     pa, pw, pz = _addrs(which, dev, a=a, w=w, z=z)
-    pi = None
-    if info is not None:
-        if dev != _is_torch(info):
-            raise ValueError("a, w, z, info must all be host arrays or all be device tensors")
-        if dev:
-            import torch
-
-            if not info.is_cuda or info.dtype != torch.int32:
-                raise ValueError("info: int32 GPU tensor required")
-        elif info.dtype != np.int32:
-            raise ValueError("info: int32 required")
-        pi = info.data_ptr() if dev else info.ctypes.data
+    pi = _info_addr(info, dev, "a, w, z, info")
     rc = _entry(lib, f"eigx_{which}_batch", dev)(n, batch, pa, lda, stride_a, pw, ldw, pz, ldz, stride_z, md, pi)
     _finish(name, rc, (0, -5, -6))
 
@@ -499,6 +504,54 @@ def eigen_h_batch(n, batch, a, lda, w, z, ldz, mode="A", info=None, stride_a=Non
     complex elements.  For ``n <= 96`` one kernel launch solves the batch, one workgroup per matrix with the matrix in LDS;
     larger ``n`` runs ``eigen_h`` matrix by matrix."""
     _solve_batch("h", n, batch, a, lda, w, z, ldz, mode, info, stride_a, ldw, stride_z)
+
+
+def eigen_gev_batch(n, batch, a, lda, b, ldb, w, z, ldz, mode="A", info=None, stride_a=None, stride_b=None, ldw=None, stride_z=None):
+    """EXTENSION (not in the reference): ``batch`` symmetric-definite pencils ``A x = lambda B x`` of one size ``n`` in one call,
+    one GPU.  ``a[lda, n, batch]`` and ``b[ldb, n, batch]`` (numpy, Fortran order, or GPU tensors with the same memory image:
+    pencil ``k`` starts at elements ``k * stride_a`` / ``k * stride_b``) hold the upper triangles; ``a`` is destroyed, ``b``
+    comes back with ``U`` (``B = U^T U``) in its upper triangle.  ``w[ldw, batch]`` receives the ascending eigenvalues,
+    ``z[ldz, n, batch]`` the eigenvectors with ``z^T B z = I`` (mode 'A'; mode 'N': eigenvalues and ``U`` only, ``z`` may be
+    None).  Defaults: ``stride_a = lda * n``, ``stride_b = ldb * n``, ``stride_z = ldz * n``, ``ldw = n``.  ``info`` (optional,
+    int32, ``batch`` entries, on the side of ``a``) receives the per-pencil status: 0, -5 (NaN / Inf in A or B: its ``w`` is
+    NaN, its ``z`` and ``b`` untouched), -7 (B not positive definite: ``w`` NaN, ``z`` untouched) or -6; ``last_status()`` is 0
+    or the status of the first failed pencil.  For ``n <= 96`` one kernel launch solves the batch, one workgroup per pencil
+    with both matrices in LDS; larger ``n`` runs ``KMATH_EIGEN_GEV_RANGE`` with ``il = 1, iu = n`` pencil by pencil."""
+    name = "eigen_gev_batch"
+    # the arguments are checked here, before the library is touched (status -2 = EIGX_ERR_BAD_ARG)
+    md = _char(mode, "A").upper()
+    try:
+        n, batch, lda, ldb = int(n), int(batch), int(lda), int(ldb)
+        ldw = n if ldw is None else int(ldw)
+        ldz = int(ldz) if md == b"A" else (0 if ldz is None else int(ldz))
+        stride_a = lda * n if stride_a is None else int(stride_a)
+        stride_b = ldb * n if stride_b is None else int(stride_b)
+        stride_z = ldz * n if stride_z is None else int(stride_z)
+        ok = n >= 1 and batch >= 0 and lda >= n and ldb >= n and ldw >= n and md in (b"A", b"N")
+        ok = ok and a is not None and b is not None and w is not None
+        ok = ok and (batch <= 1 or (stride_a >= lda * n and stride_b >= ldb * n))
+        if md == b"A":
+            ok = ok and z is not None and ldz >= n and (batch <= 1 or stride_z >= ldz * n)
+    except (TypeError, ValueError):
+        ok = False
+    if not ok:
+        _state["last_status"] = -2
+        print(f"Warning: {name}: invalid arguments (n={n}, batch={batch}, lda={lda}, ldb={ldb}, ldw={ldw}, ldz={ldz}, "
+              f"stride_a={stride_a}, stride_b={stride_b}, stride_z={stride_z}, mode={mode!r})", file=sys.stderr)
+        return
+    began = _begin(a)
+    if began is None:
+        return
+    lib, dev = began
+    if md != b"A":
+        z = None
+    for x, xname in ((a, "a"), (b, "b"), (w, "w"), (z, "z")):
+        if x is not None and not dev and not _is_torch(x) and x.ndim > 2 and not x.flags.f_contiguous:
+            raise ValueError(f"{xname}: Fortran (column-major) order required, as in the reference")
+    pa, pb, pw, pz = _addrs("gev", dev, a=a, b=b, w=w, z=z)
+    pi = _info_addr(info, dev, "a, b, w, z, info")
+    rc = _entry(lib, "eigx_gev_batch", dev)(n, batch, pa, lda, stride_a, pb, ldb, stride_b, pw, ldw, pz, ldz, stride_z, md, pi)
+    _finish(name, rc, (0, -5, -6, -7))
 
 
 def band_count(d, e, band, x):

@@ -1,5 +1,5 @@
 // api.hip -- C-ABI entry points (include/eigenexa_amd.h): life cycle, queries, memory helpers.
-// The solver entry points live in solver.hip, gev.hip, hgev.hip, herm.hip, batch.hip and hbatch.hip.
+// The solver entry points live in solver.hip, gev.hip, hgev.hip, herm.hip, batch.hip, hbatch.hip and gbatch.hip.
 #include "eigx_context.h"
 #include "eigx_comm.h"
 #include "../../include/eigenexa_amd.h"
@@ -371,6 +371,7 @@ int eigx_tune(int key, int value) {
   if (key == 20) return set_tri_nb(value);     // outer block width of the triangular stages (tri.hip)
   if (key == 21) return set_batch_nmax(value); // largest n served by the batch kernel of eigx_s_batch (batch.hip)
   if (key == 22) return set_hbatch_nmax(value);   // the same for eigx_h_batch (hbatch.hip)
+  if (key == 23) return set_gbatch_nmax(value);   // the same for eigx_gev_batch (gbatch.hip)
   return -1;
 }
 

@@ -1,6 +1,8 @@
 // batch_common.h -- what the one-workgroup-per-matrix kernels share (batch.hip: real symmetric, hbatch.hip: complex
-// Hermitian): the workgroup reductions, the failure word of a launch and the QL iteration on a real (d, e) held in LDS.
+// Hermitian, gbatch.hip: real symmetric-definite pencils): the workgroup reductions, the failure word of a launch, the QL
+// iteration on a real (d, e) held in LDS and, for the two real kernels, the whole reduction + QL of a matrix held in LDS.
 #pragma once
+#include <cfloat>
 #include <cstdint>
 #include <hip/hip_runtime.h>
 
@@ -115,6 +117,169 @@ __device__ inline void ql_sweep(int n, double* d, double* e, double* pt, int* ct
           ctl[1] = i + 1;                // rotations m-1 .. i+1 were made
         }
         ctl[2] = st;
+}
+
+// Phases 2 and 3 of a one-workgroup-per-matrix real symmetric solve (batch.hip: eigx_s_batch, gbatch.hip: eigx_gev_batch), 2 NMAX
+// threads, thread (r, hh) = (row, half): the full symmetric matrix of order n in A(LD, NMAX), LD = NMAX + 1 -> Householder
+// tridiagonalisation (tred2), Q accumulated in place in A (want_vec) -> implicit QL with Wilkinson shift on (d, e) with the
+// rotations applied to A's rows.  Every array is the caller's LDS: d, e, hv, u, q of NMAX entries, pt of 2 NMAX, red[4][4], ctl[4],
+// msk[2].  The caller has published A with a barrier; every thread of the workgroup makes the call and gets the same state back:
+// ST_DONE (d holds the eigenvalues in the order of A's columns) or ST_FAIL (the QL budget is used up); both behind a barrier.
+template <int NMAX>
+__device__ __forceinline__ int sym_tridiag_ql(int n, int want_vec, double* A, double* d, double* e, double* hv, double* u, double* q,
+                                              double* pt, double (*red)[4], int* ctl, unsigned long long* msk) {
+  constexpr int NT = 2 * NMAX, LD = NMAX + 1;
+  const int tid = threadIdx.x, r = tid % NMAX, hh = tid / NMAX;
+  const bool row = hh == 0 && r < n;     // the thread that owns row r where one thread per row is wanted
+  // ---- 2. tridiagonalisation, i = n-1 .. 1: H_i = I - u u^T / h annihilates A(0 .. i-2, i) (tred2) ------------------------
+  // u stays in A(0 .. i-1, i), h in hv[i]; the active matrix is the full symmetric block 0 .. i-1
+  for (int i = n - 1; i >= 1; --i) {
+    const int l = i - 1;
+    double* rd = red[2 * (i & 1)];     // by parity: a step that leaves early has no closing barrier
+    if (l == 0) {
+      if (tid == 0) { e[1] = A[LD]; hv[1] = 0.0; }
+      continue;
+    }
+    const double x = (hh == 0 && r <= l) ? A[r + i * LD] : 0.0;
+    const double f = A[l + i * LD];    // (read before the barrier: thread l overwrites it below)
+    double h = block_sum<NT>(x * x, rd);
+    if (h == 0.0) {                    // nothing to annihilate (uniform)
+      if (tid == 0) { e[i] = f; hv[i] = 0.0; }
+      continue;
+    }
+    const double g = f >= 0.0 ? -sqrt(h) : sqrt(h);
+    h -= f * g;
+    if (hh == 0 && r <= l) {
+      const double ur = r == l ? f - g : x;
+      u[r] = ur;
+      A[r + i * LD] = ur;
+    }
+    if (tid == 0) { e[i] = g; hv[i] = h; }
+    __syncthreads();
+    // p = A u, each half over its share of the columns.  Both halves make mid steps (a uniform trip count lets the loop be
+    // unrolled and its LDS reads be batched); the step that half 1 may have too many reads column l+1 and adds nothing
+    const int mid = (l + 2) / 2, k0 = hh ? mid : 0, k1 = hh ? l + 1 : mid;
+    if (r <= l) {
+      double acc = 0.0;
+#pragma unroll 4
+      for (int t = 0; t < mid; ++t) {
+        const int c = k0 + t;
+        const double uc = u[c];
+        acc = fma(A[r + c * LD], c < k1 ? uc : 0.0, acc);
+      }
+      pt[hh * NMAX + r] = acc;
+    }
+    __syncthreads();
+    double qr = 0.0, ur = 0.0;
+    if (hh == 0 && r <= l) { ur = u[r]; qr = (pt[r] + pt[NMAX + r]) / h; }
+    const double hk = block_sum<NT>(qr * ur, rd + 4) / (h + h);
+    if (hh == 0 && r <= l) q[r] = qr - hk * ur;
+    __syncthreads();
+    // A <- A - u q^T - q u^T on the whole block (both triangles, rounded alike)
+    if (r <= l) {
+      ur = u[r];
+      qr = q[r];
+#pragma unroll 4
+      for (int t = 0; t < mid; ++t) {
+        const int c = k0 + t;
+        const double ac = A[r + c * LD], qc = q[c], uc = u[c];
+        A[r + c * LD] = c < k1 ? ac - (ur * qc + qr * uc) : ac;
+      }
+    }
+    __syncthreads();
+  }
+  if (row) d[r] = A[r + r * LD];
+  if (tid == 0) { e[0] = 0.0; hv[0] = 0.0; }
+
+  // ---- Q = H_{n-1} ... H_1 accumulated in place, i = 0 .. n-1 (tred2's second loop) -----------------------------------
+  if (want_vec) {
+    if (r < n)
+      for (int c = hh; c < r; c += 2) A[r + c * LD] = 0.0;   // the strict lower triangle: rows of the identity to be
+    __syncthreads();
+    for (int i = 0; i < n; ++i) {
+      const int l = i - 1;
+      if (hh == 0 && r <= l) { u[r] = A[r + i * LD]; A[r + i * LD] = 0.0; }
+      if (hh == 0 && r == i) A[i + i * LD] = 1.0;
+      const double h = hv[i];
+      if (l < 0 || h == 0.0) continue;                       // uniform; the next step's first barrier publishes column i
+      __syncthreads();
+      const int mid = (l + 2) / 2, k0 = hh ? mid : 0, k1 = hh ? l + 1 : mid;
+      if (r <= l) {                                          // g = Q^T u: lane = column
+        double acc = 0.0;
+#pragma unroll 4
+        for (int t = 0; t < mid; ++t) {
+          const int c = k0 + t;
+          const double uc = u[c];
+          acc = fma(c < k1 ? uc : 0.0, A[c + r * LD], acc);
+        }
+        pt[hh * NMAX + r] = acc;
+      }
+      __syncthreads();
+      if (hh == 0 && r <= l) q[r] = (pt[r] + pt[NMAX + r]) / h;
+      __syncthreads();
+      if (r <= l) {                                          // Q <- Q - u g^T / h: lane = row
+        const double ur = u[r];
+#pragma unroll 4
+        for (int t = 0; t < mid; ++t) {
+          const int c = k0 + t;
+          const double ac = A[r + c * LD], qc = q[c];
+          A[r + c * LD] = c < k1 ? fma(-qc, ur, ac) : ac;
+        }
+      }
+      __syncthreads();
+    }
+  }
+  __syncthreads();
+
+  // ---- 3. implicit QL with Wilkinson shift on (d, e) (tql2) -------------------------------------------------------------
+  // A round: the row threads apply the rotations of the last sweep to Q and test every e[m] against its neighbours (one
+  // ballot per wave: bit m of msk = "e[m] is negligible"; bit n-1 is always set) -> barrier -> thread 0 steps l over the
+  // converged eigenvalues, finds the end m of the unreduced block in msk and makes one sweep: the rotations (c_i, s_i),
+  // i = m-1 .. l, go into pt -> barrier.  Two barriers per QL iteration, reached by every thread.
+  int ql_l = 0, ql_it = 0;
+  if (tid == 0) {
+    for (int i = 1; i < n; ++i) e[i - 1] = e[i];
+    e[n - 1] = 0.0;
+    ctl[0] = 0;                        // no rotations yet
+    ctl[1] = 1;
+    msk[1] = 0;
+  }
+  __syncthreads();
+  for (;;) {
+    {
+      const int m = ctl[0], lo = ctl[1];
+      if (want_vec && row && lo < m) {
+        double hc = A[r + m * LD];
+#pragma unroll 4
+        for (int i = m - 1; i >= lo; --i) {
+          const double zi = A[r + i * LD], c = pt[2 * i], s = pt[2 * i + 1];
+          A[r + (i + 1) * LD] = fma(s, zi, c * hc);
+          hc = fma(c, zi, -(s * hc));
+        }
+        A[r + lo * LD] = hc;
+      }
+      bool small = false;
+      if (row) small = r == n - 1 || fabs(e[r]) <= (0.5 * DBL_EPSILON) * (fabs(d[r]) + fabs(d[r + 1]));
+      const unsigned long long bits = __ballot(small);
+      if ((tid & 63) == 0 && tid < 128) msk[tid >> 6] = bits;   // (rows live in threads 0 .. n-1; the lanes of half 1 vote 0)
+    }
+    __syncthreads();
+    if (tid == 0) ql_sweep(n, d, e, pt, ctl, msk, ql_l, ql_it);
+    __syncthreads();
+    if (ctl[2] != ST_RUN) break;
+  }
+  return ctl[2];
+}
+
+// the place of d[r] in the ascending order of d[0 .. n-1] (rank by counting, ties by index)
+__device__ inline int ascending_rank(int n, const double* d, int r) {
+  const double dr = d[r];
+  int rank = 0;
+  for (int j = 0; j < n; ++j) {
+    const double dj = d[j];
+    rank += (dj < dr || (dj == dr && j < r)) ? 1 : 0;
+  }
+  return rank;
 }
 
 }  // namespace

@@ -158,5 +158,7 @@ int set_dc_batch(int v);
 int set_batch_nmax(int v);
 // tuning hook (eigx_tune key 22, hbatch.hip): largest n served by the batch kernel of eigx_h_batch, 0 .. EIGX_HBATCH_NMAX
 int set_hbatch_nmax(int v);
+// tuning hook (eigx_tune key 23, gbatch.hip): largest n served by the batch kernel of eigx_gev_batch, 0 .. EIGX_GBATCH_NMAX
+int set_gbatch_nmax(int v);
 
 }  // namespace eigx

@@ -315,6 +315,9 @@ struct SolveFrame {
 inline int host_ld(int nr) { return pad_ld(nr + 2); }
 void* host_to_dev(Context& ctx, const char* name, const void* h, int ld, int nr, int nc, int esz);
 void dev_to_host(void* h, int ld, const void* d, int ldd, int nr, int nc, int esz);
+// batch.hip: copy (kind: any direction) of the n x n blocks b0 .. b0 + nb - 1 of a strided batch of doubles, block k at
+// dst + k sd / src + k ss with leading dimensions ldd / lds
+void copy_blocks(double* dst, int ldd, int64_t sd, const double* src, int lds, int64_t ss, int n, int b0, int nb, hipMemcpyKind kind);
 // Host form of a solve on a local block of nr rows: a (nc columns), b (the same; b_h == nullptr: none), z (zcols columns,
 // allocated only) and w (nw entries) in the pool buffers host.a / host.b / host.z (esz 8) or host.ha / host.hb / host.hz
 // (esz 16, interleaved complex) and host.w, leading dimension ldd.  What comes back, and when, is each driver's contract:
@@ -339,6 +342,9 @@ struct GevFrame {
   void mark() { if (k < 4) t[++k] = now_s(); }
   int finish();
 };
+// gev.hip (EXTENSION, one GPU): the Cholesky-route range solve on device arrays (even leading dimensions); b <- U
+int gev_range_dev(Context& ctx, int n, RangeWindow W, double* a, int lda, double* b, int ldb, double* w, double* z, int ldz,
+                  char mode);
 // B's smallest eigenvalue w(1) > 0 (read back synchronously), else report_not_spd: the message (rank 0), EIGX_ERR_NOT_SPD
 bool b_is_positive_definite(const Context& ctx, const double* w);
 int report_not_spd(const Context& ctx);

@@ -334,6 +334,8 @@ void gev_reduce_dev(Context& ctx, int n, double* a, int lda, const double* u, in
   trsm_upper_dev(ctx, 'T', n, n, u, ldu, c, ldc, V, true);   // the solvers read the upper triangle only
 }
 
+}  // namespace
+
 // W by value: the window goes to range_solve_dev on C as it is (B is not scaled, so the eigenvalues of C are the
 // generalised ones; range_solve_dev applies its own sigma of C), m is read back for the back-substitution.
 int gev_range_dev(Context& ctx, int n, RangeWindow W, double* a, int lda, double* b, int ldb, double* w, double* z, int ldz,
@@ -371,6 +373,8 @@ int gev_range_dev(Context& ctx, int n, RangeWindow W, double* a, int lda, double
   }
   return F.finish();
 }
+
+namespace {
 
 int gev_range_host(Context& ctx, int n, RangeWindow W, double* a, int lda, double* b, int ldb, double* w, double* z, int ldz,
                    char mode) {

@@ -36,6 +36,7 @@ module eigen_libs_mod
   public :: eigen_h_range, eigen_h_range_v   ! EXTENSION: both kinds of window for the complex Hermitian solver (one GPU)
   public :: eigen_s_batch   ! EXTENSION: many small symmetric matrices in one call (one GPU)
   public :: eigen_h_batch   ! EXTENSION: many small complex Hermitian matrices in one call (one GPU)
+  public :: eigen_gev_batch   ! EXTENSION: many small symmetric-definite pencils in one call (one GPU)
 
   interface
     integer(c_int) function eigx_init(device) bind(C, name="eigx_init")
@@ -153,6 +154,17 @@ module eigen_libs_mod
       complex(c_double_complex), intent(inout) :: a(*)
       real(c_double), intent(inout) :: w(*)
       complex(c_double_complex), intent(inout) :: z(*)
+      character(kind=c_char), value :: mode
+      integer(c_int), intent(out), optional :: info(*)
+    end function
+    ! EXTENSION (not in the reference): batch symmetric-definite pencils of one size, one GPU; info may be absent (NULL)
+    integer(c_int) function eigx_gev_batch(n, batch, a, lda, stride_a, b, ldb, stride_b, w, ldw, z, ldz, stride_z, mode, info) &
+        bind(C, name="eigx_gev_batch")
+      import :: c_int, c_int64_t, c_double, c_char
+      integer(c_int), value :: n, batch, lda, ldb, ldw, ldz
+      integer(c_int64_t), value :: stride_a, stride_b, stride_z
+      real(c_double), intent(inout) :: a(*), b(*)
+      real(c_double), intent(inout) :: w(*), z(*)
       character(kind=c_char), value :: mode
       integer(c_int), intent(out), optional :: info(*)
     end function
@@ -731,6 +743,26 @@ contains
     rc = eigx_h_batch(n, batch, a, lda, int(lda, c_int64_t) * size(a, 2), w, size(w, 1), z, ldz, &
                       int(ldz, c_int64_t) * size(z, 2), md, info)
   end subroutine eigen_h_batch
+
+  !> eigen_gev_batch(n, batch, a, lda, b, ldb, w, z, ldz, mode, info) -- EXTENSION, not in the reference: the eigenpairs of batch
+  !> symmetric-definite pencils a(:, :, k) x = lambda b(:, :, k) x of one size n on one GPU, in one kernel launch for n <= 96
+  !> (one workgroup per pencil, both matrices in LDS).  Upper triangles significant, a destroyed, b(:, :, k) returns U with
+  !> B = U^T U in its upper triangle; w(1:n, k) ascending, z(1:n, 1:n, k) with z^T B z = I; modes 'A' and 'N' (z not written).
+  !> info(k) = 0, or the status of pencil k (-5: NaN / Inf, -7: B not positive definite; w(:, k) = NaN); the other pencils are
+  !> solved all the same.
+  subroutine eigen_gev_batch(n, batch, a, lda, b, ldb, w, z, ldz, mode, info)
+    integer, intent(in) :: n, batch, lda, ldb, ldz
+    real(8), intent(inout), contiguous :: a(:, :, :), b(:, :, :)
+    real(8), intent(inout), contiguous :: w(:, :), z(:, :, :)
+    character(*), intent(in), optional :: mode
+    integer, intent(out), optional :: info(*)
+    integer :: rc
+    character(kind=c_char) :: md
+    md = 'A'
+    if (present(mode)) md = mode(1:1)
+    rc = eigx_gev_batch(n, batch, a, lda, int(lda, c_int64_t) * size(a, 2), b, ldb, int(ldb, c_int64_t) * size(b, 2), &
+                        w, size(w, 1), z, ldz, int(ldz, c_int64_t) * size(z, 2), md, info)
+  end subroutine eigen_gev_batch
 
   !> eigen_sx_range_v(n, vl, vu, mmax, m, il, a, lda, w, z, ldz, m_forward, m_backward, mode) -- EXTENSION, not in the
   !> reference (LAPACK's range = 'V'): the eigenpairs with vl <= lambda < vu by the pentadiagonal route on one GPU.  On

@@ -29,7 +29,8 @@
  * same for the complex Hermitian generalised problem, one GPU), eigx_sx_range_v / eigx_s_range_v / eigx_gev_range_v[_dev] (an
  * extension: the eigenpairs with vl <= lambda < vu of the real solvers, LAPACK's range = 'V', one GPU), eigx_h_range[_v] and
  * eigx_hgev_range_v[_dev] (an extension: both kinds of window for the complex Hermitian solvers, one GPU), eigx_s_batch[_dev]
- * and eigx_h_batch[_dev] (an extension: many small symmetric / complex Hermitian matrices in one call, one GPU) and the stage
+ * and eigx_h_batch[_dev] (an extension: many small symmetric / complex Hermitian matrices in one call, one GPU),
+ * eigx_gev_batch[_dev] (an extension: many small symmetric-definite pencils in one call, one GPU) and the stage
  * entry eigx_band_count_dev (Sturm counts of a band matrix at caller-given points).
  */
 #ifndef EIGENEXA_AMD_H
@@ -312,6 +313,10 @@ int eigx_h_batch(int n, int batch, double* a, int lda, int64_t stride_a, double*
 int eigx_h_batch_dev(int n, int batch, double* a_dev, int lda, int64_t stride_a, double* w_dev, int ldw, double* z_dev, int ldz,
                      int64_t stride_z, char mode, int* info_dev);
 
+/* Batched small generalised eigensolves eigx_gev_batch[_dev] -- EXTENSION, not in the reference: declared and documented in
+ * eigenexa_amd_gbatch.h beside this file, which comes in here, so this header alone still gives a caller the whole interface. */
+#include "eigenexa_amd_gbatch.h"
+
 /* ScaLAPACK interop without a redistribution step.  The reference asks block-cyclic callers to
  * convert with pdgemr2d into its cyclic layout first (manual 3.4; benchmark/ev_test.f:68-84 does the reverse for the
  * check).  Here the layout is only an index map at the entry and exit of the solver, so the local blocks of a
@@ -569,7 +574,9 @@ int eigx_profile_read_kinds(double* out, int nkinds);
  * eigx_s_batch serves with its batch kernel (0 .. EIGX_BATCH_NMAX, default EIGX_BATCH_NMAX by the measured table of DESIGN
  * section 8h; other values are refused): larger matrices go through eigx_s_dev one by one, and a test reaches that path at a
  * small n by lowering the key.  key 22 = the same for eigx_h_batch (0 .. EIGX_HBATCH_NMAX, default EIGX_HBATCH_NMAX by the
- * measured table of DESIGN section 8i; other values are refused): larger matrices go through eigx_h_dev one by one.  Returns
+ * measured table of DESIGN section 8i; other values are refused): larger matrices go through eigx_h_dev one by one.
+ * key 23 = the same for eigx_gev_batch (0 .. EIGX_GBATCH_NMAX, default EIGX_GBATCH_NMAX by the measured table of DESIGN section
+ * 8j; other values are refused): larger pencils go through eigx_gev_range_dev one by one.  Returns
  * the previous value, or
  * -1 for an unknown key or a refused value.
  * Not part of the reference's interface. */
