@@ -8,20 +8,21 @@
 // No workgroup talks to another: no grid-wide barrier, no spin-wait, no atomics on the data.  Every sum is taken in an order
 // that depends on n alone, so a matrix's result does not depend on its position in the batch or on the batch size.
 // Matrices larger than the cutoff (eigx_tune key 21) go through solve_dev (eigen_s) one by one.
+// This file also holds the host side of all three batch families (eigx_h_batch: hbatch.hip, eigx_gev_batch: gbatch.hip): the
+// argument check, the device entry (batch_frame_dev: prologue, the loop above the cutoff, the launch and its first-failure
+// word, the timers), the host entry (batch_frame_host: staging in the pool, copy in, copy back) and copy_blocks.  A family
+// supplies its kernel launch by n-class and its full-size solve of one matrix; the kernels share batch_common.h.
 #include "eigx_context.h"
 #include "batch_common.h"
 #include "../../include/eigenexa_amd.h"
 #include <algorithm>
 #include <cfloat>
-#include <limits>
 
 // a*b + c is written out as fma() where it is wanted: the rank-2 update of the reduction has to round A(j, k) and A(k, j) alike
 #pragma clang fp contract(off)
 
 namespace eigx {
 namespace {
-
-int g_batch_nmax = EIGX_BATCH_NMAX;   // key 21: largest n served by the batch kernel
 
 // One workgroup of 2 NMAX threads per matrix (NMAX = 32, 64, 96, 128: the n-classes): thread (r, hh) = (row, half).  The full symmetric matrix, then Q, lives in
 // A(LD, NMAX), column-major with LD = NMAX + 1: row-wise loops (lane = row, a fixed column) are stride-1 across lanes, and
@@ -59,9 +60,7 @@ __global__ __launch_bounds__(2 * NMAX) void batch_kernel(int n, int batch, const
     bad = block_max<NT>(bad, red[0]);
     mx = block_max<NT>(mx, red[1]);      // (its barrier also publishes the mirrored entries)
     if (bad != 0.0) {                    // uniform
-      if (row) w[(size_t)k * ldw + r] = std::numeric_limits<double>::quiet_NaN();
-      if (tid == 0) report_failure(first, info, k, EIGX_ERR_NONFINITE);
-      __syncthreads();
+      fail_matrix(k, EIGX_ERR_NONFINITE, row, r, w, ldw, info, first);
       continue;
     }
     // outside [1e-90, 1e90]: scale by the power of two nearest to 1 / max|a| (eigen_scaling, solver.hip)
@@ -80,9 +79,7 @@ __global__ __launch_bounds__(2 * NMAX) void batch_kernel(int n, int batch, const
 
     // ---- 2., 3. tridiagonalisation, Q in place, implicit QL (batch_common.h) -------------------------------------------------
     if (sym_tridiag_ql<NMAX>(n, want_vec, A, d, e, hv, u, q, pt, red, ctl, msk) == ST_FAIL) {   // uniform
-      if (row) w[(size_t)k * ldw + r] = std::numeric_limits<double>::quiet_NaN();
-      if (tid == 0) report_failure(first, info, k, EIGX_ERR_INTERNAL);
-      __syncthreads();
+      fail_matrix(k, EIGX_ERR_INTERNAL, row, r, w, ldw, info, first);
       continue;
     }
 
@@ -102,30 +99,19 @@ __global__ __launch_bounds__(2 * NMAX) void batch_kernel(int n, int batch, const
   }
 }
 
-}  // namespace
+int g_batch_nmax = EIGX_BATCH_NMAX;   // key 21: largest n served by the batch kernel
 
-// kind: host <-> device copy of `batch` blocks of n x n doubles; one call where both sides are evenly spaced columns
-void copy_blocks(double* dst, int ldd, int64_t sd, const double* src, int lds, int64_t ss, int n, int b0, int nb, hipMemcpyKind kind) {
-  if (nb <= 0) return;
-  if (sd == (int64_t)ldd * n && ss == (int64_t)lds * n) {
-    EIGX_HIP_CHECK(hipMemcpy2D(dst + (size_t)b0 * sd, (size_t)ldd * 8, src + (size_t)b0 * ss, (size_t)lds * 8, (size_t)n * 8,
-                               (size_t)n * nb, kind));
-    return;
-  }
-  for (int k = b0; k < b0 + nb; ++k)
-    EIGX_HIP_CHECK(hipMemcpy2D(dst + (size_t)k * sd, (size_t)ldd * 8, src + (size_t)k * ss, (size_t)lds * 8, (size_t)n * 8, (size_t)n, kind));
+void batch_launch(const BatchArgs& g, hipStream_t st, unsigned long long* first) {
+  with_n_class<EIGX_BATCH_NMAX>(g.n, [&](auto nmax) {
+    constexpr int NMAX = decltype(nmax)::value;
+    hipLaunchKernelGGL(batch_kernel<NMAX>, dim3((unsigned)g.batch), dim3(2 * NMAX), 0, st, g.n, g.batch, (const double*)g.a, g.lda,
+                       g.stride_a, g.w, g.ldw, g.z, g.ldz, g.stride_z, (int)(g.mode == 'A'), g.info, first);
+  });
 }
-
-namespace {
-
-// what both entry points require of their arguments (mode in upper case)
-bool batch_args_ok(int n, int batch, const double* a, int lda, int64_t stride_a, const double* w, int ldw, const double* z, int ldz,
-                   int64_t stride_z, char mode) {
-  if (n < 1 || batch < 0 || lda < n || ldw < n || (mode != 'A' && mode != 'N')) return false;
-  if (batch > 1 && stride_a < (int64_t)lda * n) return false;
-  if (mode == 'A' && (ldz < n || (batch > 1 && stride_z < (int64_t)ldz * n))) return false;
-  if (batch > 0 && (!a || !w || (mode == 'A' && !z))) return false;
-  return true;
+// above the cutoff: eigen_s with the interface's default block sizes
+int batch_solve_one(Context& ctx, const BatchArgs& g, int k) {
+  return solve_dev(ctx, g.n, g.n, g.block(g.a, g.stride_a, k), g.lda, g.w + (size_t)k * g.ldw,
+                   g.mode == 'A' ? g.block(g.z, g.stride_z, k) : nullptr, g.ldz, 48, 128, g.mode, 1, 1);
 }
 
 }  // namespace
@@ -137,51 +123,80 @@ int set_batch_nmax(int v) {
   return old;
 }
 
-// device arrays; info_dev may be null
-int batch_solve_dev(Context& ctx, int n, int batch, double* a, int lda, int64_t stride_a, double* w, int ldw, double* z, int ldz,
-                    int64_t stride_z, char mode, int* info_dev) {
-  if (!ctx.initialized) return EIGX_ERR_NOT_INITIALIZED;
-  if (ctx.grid.nranks != 1) return refuse_several_ranks(ctx);
-  mode = upper_case(mode);
-  if (!batch_args_ok(n, batch, a, lda, stride_a, w, ldw, z, ldz, stride_z, mode)) return EIGX_ERR_BAD_ARG;
-  if (batch == 0) return EIGX_OK;
+// ---- the frame of the three families (declared in eigx_context.h) ------------------------------------------------------------
+bool batch_status_per_matrix(int rc) {   // (solve_dev and herm_solve_dev never return EIGX_ERR_NOT_SPD: one set serves all)
+  return rc == EIGX_OK || rc == EIGX_ERR_NONFINITE || rc == EIGX_ERR_NOT_SPD || rc == EIGX_ERR_INTERNAL;
+}
+
+void copy_blocks(void* dst, int ldd, int64_t sd, const void* src, int lds, int64_t ss, int n, int b0, int nb, int esz, hipMemcpyKind kind) {
+  if (nb <= 0) return;
+  char* d = (char*)dst;
+  const char* s = (const char*)src;
+  const size_t e = (size_t)esz;
+  if (sd == (int64_t)ldd * n && ss == (int64_t)lds * n) {
+    EIGX_HIP_CHECK(hipMemcpy2D(d + e * b0 * sd, e * ldd, s + e * b0 * ss, e * lds, e * n, (size_t)n * nb, kind));
+    return;
+  }
+  for (int k = b0; k < b0 + nb; ++k) EIGX_HIP_CHECK(hipMemcpy2D(d + e * k * sd, e * ldd, s + e * k * ss, e * lds, e * n, (size_t)n, kind));
+}
+
+// what both entries require of their arguments (mode in upper case)
+static bool batch_args_ok(const BatchArgs& g) {
+  const int n = g.n, batch = g.batch;
+  if (n < 1 || batch < 0 || g.lda < n || g.ldw < n || (g.mode != 'A' && g.mode != 'N')) return false;
+  if (batch > 1 && g.stride_a < (int64_t)g.lda * n) return false;
+  if (g.has_b && (g.ldb < n || (batch > 1 && g.stride_b < (int64_t)g.ldb * n))) return false;
+  if (g.mode == 'A' && (g.ldz < n || (batch > 1 && g.stride_z < (int64_t)g.ldz * n))) return false;
+  if (batch > 0 && (!g.a || (g.has_b && !g.b) || !g.w || (g.mode == 'A' && !g.z))) return false;
+  return true;
+}
+// What both entries begin with.  Returns true to go on (g.mode in upper case, the device set), or false with the status to
+// return in rc: a refusal, or EIGX_OK for an empty batch.
+static bool batch_begin(Context& ctx, BatchArgs& g, int& rc) {
+  rc = EIGX_OK;
+  if (!ctx.initialized) {
+    rc = EIGX_ERR_NOT_INITIALIZED;
+    return false;
+  }
+  if (ctx.grid.nranks != 1) {
+    rc = refuse_several_ranks(ctx);
+    return false;
+  }
+  g.mode = upper_case(g.mode);
+  if (!batch_args_ok(g)) {
+    rc = EIGX_ERR_BAD_ARG;
+    return false;
+  }
+  if (g.batch == 0) return false;
   EIGX_HIP_CHECK(hipSetDevice(ctx.device));
+  return true;
+}
+
+int batch_frame_dev(Context& ctx, BatchArgs g, int cutoff, BatchLaunch launch, BatchSolveOne solve_one) {
+  int rc;
+  if (!batch_begin(ctx, g, rc)) return rc;
   EIGX_HIP_CHECK(hipStreamSynchronize(nullptr));   // the caller's default-stream work on the arguments (SolveFrame::begin)
   const double t0 = now_s();
   ctx.errinfo = 0;
   hipStream_t st = ctx.stream;
-  const bool want_vec = mode == 'A';
-  int rc = EIGX_OK;
-  if (n > g_batch_nmax) {
-    // above the cutoff: eigen_s with the interface's default block sizes, matrix by matrix
-    for (int k = 0; k < batch; ++k) {
-      const int rk = solve_dev(ctx, n, n, a + (size_t)k * stride_a, lda, w + (size_t)k * ldw, want_vec ? z + (size_t)k * stride_z : nullptr,
-                               ldz, 48, 128, mode, 1, 1);
-      if (rk != EIGX_OK && rk != EIGX_ERR_NONFINITE && rk != EIGX_ERR_INTERNAL) return rk;   // nothing per matrix: out of memory, ...
-      if (info_dev) EIGX_HIP_CHECK(hipMemcpy(info_dev + k, &rk, sizeof(int), hipMemcpyHostToDevice));
+  if (g.n > cutoff) {
+    // above the cutoff: the full-size solver, matrix by matrix; the first failure is the call's status
+    for (int k = 0; k < g.batch; ++k) {
+      const int rk = solve_one(ctx, g, k);
+      if (!batch_status_per_matrix(rk)) return rk;   // nothing per matrix: out of memory, ...
+      if (g.info) EIGX_HIP_CHECK(hipMemcpy(g.info + k, &rk, sizeof(int), hipMemcpyHostToDevice));
       if (rc == EIGX_OK) rc = rk;
     }
   } else {
     unsigned long long* first = ctx.pool.get_t<unsigned long long>("batch.first", 1);
+    // memset 0xff of the first-failure word: all ones = "no matrix failed"; a failed one leaves (index << 8 | -code) by atomicMin
     EIGX_HIP_CHECK(hipMemsetAsync(first, 0xff, sizeof(unsigned long long), st));
-    const dim3 grid((unsigned)batch);
-    if (n <= 32)
-      hipLaunchKernelGGL(batch_kernel<32>, grid, dim3(64), 0, st, n, batch, (const double*)a, lda, stride_a, w, ldw, z, ldz, stride_z,
-                         (int)want_vec, info_dev, first);
-    else if (n <= 64)
-      hipLaunchKernelGGL(batch_kernel<64>, grid, dim3(128), 0, st, n, batch, (const double*)a, lda, stride_a, w, ldw, z, ldz, stride_z,
-                         (int)want_vec, info_dev, first);
-    else if (n <= 96)
-      hipLaunchKernelGGL(batch_kernel<96>, grid, dim3(192), 0, st, n, batch, (const double*)a, lda, stride_a, w, ldw, z, ldz, stride_z,
-                         (int)want_vec, info_dev, first);
-    else
-      hipLaunchKernelGGL(batch_kernel<128>, grid, dim3(256), 0, st, n, batch, (const double*)a, lda, stride_a, w, ldw, z, ldz, stride_z,
-                         (int)want_vec, info_dev, first);
+    launch(g, st, first);
     EIGX_HIP_CHECK(hipGetLastError());
     unsigned long long f = 0;
     EIGX_HIP_CHECK(hipMemcpyAsync(&f, first, sizeof(f), hipMemcpyDeviceToHost, st));
     EIGX_HIP_CHECK(hipStreamSynchronize(st));
-    if (f != ~0ull) {
+    if (f != ~0ull) {                    // (index << 8 | -code) of the first matrix that failed
       rc = -(int)(f & 0xff);
       ctx.errinfo = -1;
     }
@@ -191,39 +206,43 @@ int batch_solve_dev(Context& ctx, int n, int batch, double* a, int lda, int64_t 
   return rc;
 }
 
-// Host arrays: a, z and w are staged in the pool buffers of the other host forms (host.a / host.z / host.w, leading dimension
-// host_ld(n)), the per-matrix status words in batch.info.  w comes back for every matrix, z for those that succeeded.
-static int batch_solve_host(Context& ctx, int n, int batch, double* a, int lda, int64_t stride_a, double* w, int ldw, double* z, int ldz,
-                            int64_t stride_z, char mode, int* info) {
-  if (!ctx.initialized) return EIGX_ERR_NOT_INITIALIZED;
-  if (ctx.grid.nranks != 1) return refuse_several_ranks(ctx);
-  mode = upper_case(mode);
-  if (!batch_args_ok(n, batch, a, lda, stride_a, w, ldw, z, ldz, stride_z, mode)) return EIGX_ERR_BAD_ARG;
-  if (batch == 0) return EIGX_OK;
-  EIGX_HIP_CHECK(hipSetDevice(ctx.device));
-  const bool want_vec = mode == 'A';
-  const int ldd = host_ld(n);
+// Host arrays: a, b, z and w are staged in the pool buffers of the other host forms (host.a / host.b / host.z, or host.ha / host.hz
+// at 16 bytes per element, and host.w; leading dimension host_ld(n)), the per-matrix status words in batch.info.  info and w
+// come back for every matrix; z (mode 'A') and b (U, every mode) for those that succeeded: a failed matrix's stay untouched.
+int batch_frame_host(Context& ctx, BatchArgs g, int cutoff, BatchLaunch launch, BatchSolveOne solve_one) {
+  int rc;
+  if (!batch_begin(ctx, g, rc)) return rc;
+  const int n = g.n, batch = g.batch, esz = g.esz, ldd = host_ld(n);
+  const bool want_vec = g.mode == 'A', cplx = esz == 16;
   const int64_t sd = (int64_t)ldd * n;
-  double* ad = ctx.pool.get_t<double>("host.a", (size_t)sd * batch);
-  double* zd = want_vec ? ctx.pool.get_t<double>("host.z", (size_t)sd * batch) : nullptr;
-  double* wd = ctx.pool.get_t<double>("host.w", (size_t)n * batch);
-  int* id = ctx.pool.get_t<int>("batch.info", (size_t)batch);
-  copy_blocks(ad, ldd, sd, a, lda, batch > 1 ? stride_a : (int64_t)lda * n, n, 0, batch, hipMemcpyHostToDevice);
-  const int rc = batch_solve_dev(ctx, n, batch, ad, ldd, sd, wd, n, zd, ldd, sd, mode, id);
-  if (rc != EIGX_OK && rc != EIGX_ERR_NONFINITE && rc != EIGX_ERR_INTERNAL) return rc;
+  const size_t bytes = (size_t)esz * sd * batch;
+  BatchArgs dv = g;                      // the same call on the staged arrays
+  dv.a = (double*)ctx.pool.get(cplx ? "host.ha" : "host.a", bytes);
+  dv.b = g.has_b ? (double*)ctx.pool.get(cplx ? "host.hb" : "host.b", bytes) : nullptr;
+  dv.z = want_vec ? (double*)ctx.pool.get(cplx ? "host.hz" : "host.z", bytes) : nullptr;
+  dv.w = ctx.pool.get_t<double>("host.w", (size_t)n * batch);
+  dv.info = ctx.pool.get_t<int>("batch.info", (size_t)batch);
+  dv.lda = dv.ldb = dv.ldz = ldd;
+  dv.stride_a = dv.stride_b = dv.stride_z = sd;
+  dv.ldw = n;
+  const int64_t sa = batch > 1 ? g.stride_a : (int64_t)g.lda * n, sb = batch > 1 ? g.stride_b : (int64_t)g.ldb * n,
+                sz = batch > 1 ? g.stride_z : (int64_t)g.ldz * n;
+  copy_blocks(dv.a, ldd, sd, g.a, g.lda, sa, n, 0, batch, esz, hipMemcpyHostToDevice);
+  if (g.has_b) copy_blocks(dv.b, ldd, sd, g.b, g.ldb, sb, n, 0, batch, esz, hipMemcpyHostToDevice);
+  rc = batch_frame_dev(ctx, dv, cutoff, launch, solve_one);
+  if (!batch_status_per_matrix(rc)) return rc;
   std::vector<int> ih((size_t)batch);
-  EIGX_HIP_CHECK(hipMemcpy(ih.data(), id, (size_t)batch * sizeof(int), hipMemcpyDeviceToHost));
-  EIGX_HIP_CHECK(hipMemcpy2D(w, (size_t)ldw * 8, wd, (size_t)n * 8, (size_t)n * 8, (size_t)batch, hipMemcpyDeviceToHost));
-  if (want_vec) {
-    const int64_t sz = batch > 1 ? stride_z : (int64_t)ldz * n;
-    for (int k = 0; k < batch;) {        // runs of matrices that succeeded
-      int k1 = k;
-      while (k1 < batch && ih[k1] == EIGX_OK) ++k1;
-      copy_blocks(z, ldz, sz, zd, ldd, sd, n, k, k1 - k, hipMemcpyDeviceToHost);
-      k = k1 + 1;
-    }
+  EIGX_HIP_CHECK(hipMemcpy(ih.data(), dv.info, (size_t)batch * sizeof(int), hipMemcpyDeviceToHost));
+  EIGX_HIP_CHECK(hipMemcpy2D(g.w, (size_t)g.ldw * 8, dv.w, (size_t)n * 8, (size_t)n * 8, (size_t)batch, hipMemcpyDeviceToHost));
+  // z and b come back in runs of matrices that succeeded (one copy_blocks per run): what the caller holds for a failed one stays
+  for (int k = 0; k < batch;) {
+    int k1 = k;
+    while (k1 < batch && ih[k1] == EIGX_OK) ++k1;
+    if (want_vec) copy_blocks(g.z, g.ldz, sz, dv.z, ldd, sd, n, k, k1 - k, esz, hipMemcpyDeviceToHost);
+    if (g.has_b) copy_blocks(g.b, g.ldb, sb, dv.b, ldd, sd, n, k, k1 - k, esz, hipMemcpyDeviceToHost);
+    k = k1 + 1;
   }
-  if (info) std::copy(ih.begin(), ih.end(), info);
+  if (g.info) std::copy(ih.begin(), ih.end(), g.info);
   return rc;
 }
 
@@ -233,16 +252,16 @@ using namespace eigx;
 
 extern "C" {
 
-// EXTENSION: `batch` symmetric eigenproblems of one size (one GPU); see batch_solve_dev
+// EXTENSION: `batch` symmetric eigenproblems of one size (one GPU); see batch_frame_host / batch_frame_dev
 int eigx_s_batch(int n, int batch, double* a, int lda, int64_t stride_a, double* w, int ldw, double* z, int ldz, int64_t stride_z,
                  char mode, int* info) {
-  return eigx_guard(g_ctx, [&] { return batch_solve_host(g_ctx, n, batch, a, lda, stride_a, w, ldw, z, ldz, stride_z, mode, info); });
+  const BatchArgs g{n, batch, a, lda, stride_a, nullptr, 0, 0, w, ldw, z, ldz, stride_z, mode, info, 8, false};
+  return eigx_guard(g_ctx, [&] { return batch_frame_host(g_ctx, g, g_batch_nmax, batch_launch, batch_solve_one); });
 }
 int eigx_s_batch_dev(int n, int batch, double* a_dev, int lda, int64_t stride_a, double* w_dev, int ldw, double* z_dev, int ldz,
                      int64_t stride_z, char mode, int* info_dev) {
-  return eigx_guard(g_ctx, [&] {
-    return batch_solve_dev(g_ctx, n, batch, a_dev, lda, stride_a, w_dev, ldw, z_dev, ldz, stride_z, mode, info_dev);
-  });
+  const BatchArgs g{n, batch, a_dev, lda, stride_a, nullptr, 0, 0, w_dev, ldw, z_dev, ldz, stride_z, mode, info_dev, 8, false};
+  return eigx_guard(g_ctx, [&] { return batch_frame_dev(g_ctx, g, g_batch_nmax, batch_launch, batch_solve_one); });
 }
 
 }  // extern "C"

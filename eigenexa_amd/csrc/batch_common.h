@@ -1,9 +1,17 @@
 // batch_common.h -- what the one-workgroup-per-matrix kernels share (batch.hip: real symmetric, hbatch.hip: complex
-// Hermitian, gbatch.hip: real symmetric-definite pencils): the workgroup reductions, the failure word of a launch, the QL
-// iteration on a real (d, e) held in LDS and, for the two real kernels, the whole reduction + QL of a matrix held in LDS.
+// Hermitian, gbatch.hip: real symmetric-definite pencils): the workgroup reductions, the scaling rule, the failure word of a
+// launch and the exit of a failed matrix, thread 0's QL sweep on a real (d, e) held in LDS, the rank of the sort and, for the two
+// real kernels, the whole reduction + QL of a matrix held in LDS.  The QL round loop is written here (sym_tridiag_ql) and once
+// more in hbatch_kernel: as a function of its own, called from both, it changed the register allocation and block placement of
+// the real kernels and cost eigx_gev_batch 1.5 to 3 % at n <= 32 (profiles/batch_frame_bits.log).  For the same reason batch_kernel
+// and hbatch_kernel keep the scaling rule written out (scale_exponent here serves gbatch_kernel) and hbatch_kernel its rank count:
+// one instruction more in the prologue moves all the code behind it; with both helpers in use batch_kernel<64> measured 5 % and
+// hbatch_kernel<96> 1 % slower (the intermediate form in profiles/batch_frame_bits.log).  As it stands every kernel compiles to the
+// parent commit's instructions exactly.
 #pragma once
 #include <cfloat>
 #include <cstdint>
+#include <limits>
 #include <hip/hip_runtime.h>
 
 // a*b + c is written out as fma() where it is wanted (batch.hip, hbatch.hip: the rank-2 update has to round alike on both sides)
@@ -59,6 +67,23 @@ __device__ inline int first_set_from(const unsigned long long* msk, int l) {
 __device__ inline void report_failure(unsigned long long* first, int* info, int k, int code) {
   if (info) info[k] = code;
   atomicMin(first, ((unsigned long long)k << 8) | (unsigned long long)(-code));
+}
+// Matrix k of the launch failed with `code` (uniform over the workgroup): w(1:n, k) = NaN by the row threads (row: this is the
+// thread of row r), the failure word, a barrier.  The caller goes on with its next matrix.
+__device__ inline void fail_matrix(int k, int code, bool row, int r, double* w, int ldw, int* info, unsigned long long* first) {
+  if (row) w[(size_t)k * ldw + r] = std::numeric_limits<double>::quiet_NaN();
+  if (threadIdx.x == 0) report_failure(first, info, k, code);
+  __syncthreads();
+}
+
+// the exponent ex of the scaling 2^-ex of a matrix whose largest entry is mx: 0 inside [1e-90, 1e90] (and for the zero
+// matrix), else that of the power of two nearest to mx (eigen_scaling, solver.hip); even: rounded up to an even number
+__device__ inline int scale_exponent(double mx, bool even) {
+  if (!(mx > 0.0 && (mx < 1e-90 || mx > 1e90))) return 0;
+  int ex = 0;
+  (void)frexp(mx, &ex);
+  ex = ex < -1000 ? -1000 : ex;        // (a denormal maximum: 2^-ex has to stay finite)
+  return even ? ex + (ex & 1) : ex;
 }
 
 // One lane's part of a QL round on the real tridiagonal (d, e) of order n in LDS (tql2 / dsteqr): step ql_l over the converged

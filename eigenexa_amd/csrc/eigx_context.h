@@ -6,6 +6,7 @@
 #include <map>
 #include <vector>
 #include <string>
+#include <type_traits>
 
 namespace eigx {
 
@@ -315,9 +316,42 @@ struct SolveFrame {
 inline int host_ld(int nr) { return pad_ld(nr + 2); }
 void* host_to_dev(Context& ctx, const char* name, const void* h, int ld, int nr, int nc, int esz);
 void dev_to_host(void* h, int ld, const void* d, int ldd, int nr, int nc, int esz);
-// batch.hip: copy (kind: any direction) of the n x n blocks b0 .. b0 + nb - 1 of a strided batch of doubles, block k at
-// dst + k sd / src + k ss with leading dimensions ldd / lds
-void copy_blocks(double* dst, int ldd, int64_t sd, const double* src, int lds, int64_t ss, int n, int b0, int nb, hipMemcpyKind kind);
+// batch.hip: the frame of the three batched small solvers (batch.hip, hbatch.hip, gbatch.hip).  BatchArgs is a
+// call: the entry's arguments, b / ldb / stride_b for a family with has_b only, and esz = bytes per element of a, b and z (8, or
+// 16: interleaved complex, leading dimensions and strides in elements).  A family supplies its cutoff (n above it goes to the
+// full-size solver) and two functions: launch its kernel on `st` for the n-class of g.n (with_n_class; `first` is the launch's
+// first-failure word), and solve matrix k with the full-size solver (its status; g.mode is in upper case).
+struct BatchArgs {
+  int n, batch;
+  double* a; int lda; int64_t stride_a;
+  double* b; int ldb; int64_t stride_b;
+  double* w; int ldw;
+  double* z; int ldz; int64_t stride_z;
+  char mode; int* info;
+  int esz; bool has_b;
+  double* block(double* p, int64_t stride, int k) const { return p + (size_t)(esz / 8) * k * stride; }   // block k of a, b or z
+};
+typedef void (*BatchLaunch)(const BatchArgs& g, hipStream_t st, unsigned long long* first);
+typedef int (*BatchSolveOne)(Context& ctx, const BatchArgs& g, int k);
+// f(std::integral_constant<int, NMAX>()) for the n-class of n: NMAX = 32, 64, 96 or 128.  TOP, the family's largest class, is
+// 96 or 128: with TOP = 96 every n above 64 takes the class of 96 and the class of 128 is not instantiated.  (The classes are
+// named in ascending order, which is the order of the kernel instances in the code object.)
+template <int TOP, class F>
+void with_n_class(int n, F&& f) {
+  static_assert(TOP == 96 || TOP == 128, "the largest n-class is 96 or 128");
+  if (n <= 32) return f(std::integral_constant<int, 32>());
+  if (n <= 64) return f(std::integral_constant<int, 64>());
+  if (TOP == 96 || n <= 96) return f(std::integral_constant<int, 96>());
+  if constexpr (TOP == 128) f(std::integral_constant<int, 128>());
+}
+// a status that belongs to one matrix of a batch (the others are solved all the same), not to the call: out of memory, ...
+bool batch_status_per_matrix(int rc);
+// copy (kind: any direction) of the n x n blocks b0 .. b0 + nb - 1 of a strided batch of elements of esz bytes, block k at
+// dst + k sd / src + k ss (in elements) with leading dimensions ldd / lds; one call where both sides are evenly spaced columns
+void copy_blocks(void* dst, int ldd, int64_t sd, const void* src, int lds, int64_t ss, int n, int b0, int nb, int esz, hipMemcpyKind kind);
+// the device entry (device arrays; g.info may be null) and the host entry (host arrays) of a family
+int batch_frame_dev(Context& ctx, BatchArgs g, int cutoff, BatchLaunch launch, BatchSolveOne solve_one);
+int batch_frame_host(Context& ctx, BatchArgs g, int cutoff, BatchLaunch launch, BatchSolveOne solve_one);
 // Host form of a solve on a local block of nr rows: a (nc columns), b (the same; b_h == nullptr: none), z (zcols columns,
 // allocated only) and w (nw entries) in the pool buffers host.a / host.b / host.z (esz 8) or host.ha / host.hb / host.hz
 // (esz 16, interleaved complex) and host.w, leading dimension ldd.  What comes back, and when, is each driver's contract:

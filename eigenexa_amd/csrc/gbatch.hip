@@ -9,30 +9,18 @@
 // No workgroup talks to another: no grid-wide barrier, no spin-wait, no atomics on the data.  Every sum is taken in an order
 // that depends on n alone, so a pencil's result does not depend on its position in the batch or on the batch size.
 // Pencils larger than the cutoff (eigx_tune key 23) go through gev_range_dev (gev.hip) one by one.
+// Here: the kernel, the cutoff and the two functions the frame of the batch families asks for (batch_frame_dev / batch_frame_host,
+// batch.hip: checks, launch and failure word, the loop above the cutoff, host staging of a, b, z, w).
 #include "eigx_context.h"
 #include "batch_common.h"
 #include "../../include/eigenexa_amd.h"
-#include <algorithm>
 #include <cfloat>
-#include <limits>
 
 // (batch_common.h switches contraction off: every a*b + c that is wanted fused is written as fma())
 #pragma clang fp contract(off)
 
 namespace eigx {
 namespace {
-
-int g_gbatch_nmax = EIGX_GBATCH_NMAX;   // key 23: largest n served by the batch kernel
-
-// the exponent ex of the scaling 2^-ex of a matrix whose largest entry is mx: 0 inside [1e-90, 1e90] (and for the zero
-// matrix), else that of the power of two nearest to mx (the rule of batch_kernel); even: rounded up to an even number
-__device__ inline int scale_exponent(double mx, bool even) {
-  if (!(mx > 0.0 && (mx < 1e-90 || mx > 1e90))) return 0;
-  int ex = 0;
-  (void)frexp(mx, &ex);
-  ex = ex < -1000 ? -1000 : ex;        // (a denormal maximum: 2^-ex has to stay finite)
-  return even ? ex + (ex & 1) : ex;
-}
 
 // x(0 .. n-1), entry k at x[k * inc], <- U^-T x: x_k = (x_k - sum_{j < k} U(j, k) x_j) / U(k, k), k ascending.  The sum runs
 // in four interleaved chains from +0: with U = I it is +0 and x_k comes back as it was, the sign of a zero included.
@@ -90,7 +78,6 @@ __global__ __launch_bounds__(2 * NMAX) void gbatch_kernel(int n, int batch, cons
   __shared__ unsigned long long msk[2];  // QL: bit m = e[m] is negligible
   const int tid = threadIdx.x, r = tid % NMAX, hh = tid / NMAX;
   const bool row = hh == 0 && r < n;     // the thread that owns row r (or column r) where one thread per row is wanted
-  const double nan = std::numeric_limits<double>::quiet_NaN();
 
   for (int k = blockIdx.x; k < batch; k += gridDim.x) {
     // ---- 1. load both upper triangles, mirror A, scan, scale -----------------------------------------------------------------
@@ -111,9 +98,7 @@ __global__ __launch_bounds__(2 * NMAX) void gbatch_kernel(int n, int batch, cons
     mxa = block_max<NT>(mxa, red[1]);
     mxb = block_max<NT>(mxb, red[2]);    // (the barriers also publish the loaded entries)
     if (bad != 0.0) {                    // uniform; b is as it was passed
-      if (row) w[(size_t)k * ldw + r] = nan;
-      if (tid == 0) report_failure(first, info, k, EIGX_ERR_NONFINITE);
-      __syncthreads();
+      fail_matrix(k, EIGX_ERR_NONFINITE, row, r, w, ldw, info, first);
       continue;
     }
     // A by 2^-exa, B by 2^-exb with exb even: the factor of the caller's B is 2^(exb / 2) times the computed one
@@ -152,9 +137,7 @@ __global__ __launch_bounds__(2 * NMAX) void gbatch_kernel(int n, int batch, cons
       __syncthreads();
     }
     if (!spd) {
-      if (row) w[(size_t)k * ldw + r] = nan;
-      if (tid == 0) report_failure(first, info, k, EIGX_ERR_NOT_SPD);
-      __syncthreads();
+      fail_matrix(k, EIGX_ERR_NOT_SPD, row, r, w, ldw, info, first);
       continue;
     }
 
@@ -178,9 +161,7 @@ __global__ __launch_bounds__(2 * NMAX) void gbatch_kernel(int n, int batch, cons
     bad = block_max<NT>(bad, red[0]);
     mxc = block_max<NT>(mxc, red[1]);
     if (bad != 0.0) {                    // uniform: B was too close to singular for C to be formed
-      if (row) w[(size_t)k * ldw + r] = nan;
-      if (tid == 0) report_failure(first, info, k, EIGX_ERR_NOT_SPD);
-      __syncthreads();
+      fail_matrix(k, EIGX_ERR_NOT_SPD, row, r, w, ldw, info, first);
       continue;
     }
     const int exc = scale_exponent(mxc, false);
@@ -192,9 +173,7 @@ __global__ __launch_bounds__(2 * NMAX) void gbatch_kernel(int n, int batch, cons
 
     // ---- 4. tridiagonalisation, Q in place, implicit QL (batch_common.h), sort ------------------------------------------------
     if (sym_tridiag_ql<NMAX>(n, want_vec, S, d, e, hv, u, q, pt, red, ctl, msk) == ST_FAIL) {   // uniform
-      if (row) w[(size_t)k * ldw + r] = nan;
-      if (tid == 0) report_failure(first, info, k, EIGX_ERR_INTERNAL);
-      __syncthreads();
+      fail_matrix(k, EIGX_ERR_INTERNAL, row, r, w, ldw, info, first);
       continue;
     }
     if (row) {
@@ -219,54 +198,41 @@ __global__ __launch_bounds__(2 * NMAX) void gbatch_kernel(int n, int batch, cons
   }
 }
 
-// what both entry points require of their arguments (mode in upper case): the rules of eigx_s_batch, and the same for b
-bool gbatch_args_ok(int n, int batch, const double* a, int lda, int64_t stride_a, const double* b, int ldb, int64_t stride_b,
-                    const double* w, int ldw, const double* z, int ldz, int64_t stride_z, char mode) {
-  if (n < 1 || batch < 0 || lda < n || ldb < n || ldw < n || (mode != 'A' && mode != 'N')) return false;
-  if (batch > 1 && (stride_a < (int64_t)lda * n || stride_b < (int64_t)ldb * n)) return false;
-  if (mode == 'A' && (ldz < n || (batch > 1 && stride_z < (int64_t)ldz * n))) return false;
-  if (batch > 0 && (!a || !b || !w || (mode == 'A' && !z))) return false;
-  return true;
+int g_gbatch_nmax = EIGX_GBATCH_NMAX;   // key 23: largest n served by the batch kernel
+
+void gbatch_launch(const BatchArgs& g, hipStream_t st, unsigned long long* first) {
+  with_n_class<EIGX_GBATCH_NMAX>(g.n, [&](auto nmax) {
+    constexpr int NMAX = decltype(nmax)::value;
+    hipLaunchKernelGGL(gbatch_kernel<NMAX>, dim3((unsigned)g.batch), dim3(2 * NMAX), 0, st, g.n, g.batch, (const double*)g.a, g.lda,
+                       g.stride_a, g.b, g.ldb, g.stride_b, g.w, g.ldw, g.z, g.ldz, g.stride_z, (int)(g.mode == 'A'), g.info, first);
+  });
 }
-
-bool per_pencil(int rc) { return rc == EIGX_OK || rc == EIGX_ERR_NONFINITE || rc == EIGX_ERR_NOT_SPD || rc == EIGX_ERR_INTERNAL; }
-
-// Above the cutoff: gev_range_dev with il = 1, iu = n, pencil by pencil.  It wants even leading dimensions: a pencil with an odd
-// lda, ldb or ldz is staged through the pool buffers gbatch.a / gbatch.b / gbatch.z, and U and z are copied out where it succeeded.
-int gbatch_loop_dev(Context& ctx, int n, int batch, double* a, int lda, int64_t stride_a, double* b, int ldb, int64_t stride_b,
-                    double* w, int ldw, double* z, int ldz, int64_t stride_z, char mode, int* info_dev) {
-  const bool want_vec = mode == 'A';
-  const bool stage = ((lda | ldb) & 1) || (want_vec && (ldz & 1));
+// Above the cutoff: gev_range_dev with il = 1, iu = n.  It wants even leading dimensions: a pencil with an odd lda, ldb or ldz is
+// staged through the pool buffers gbatch.a / gbatch.b / gbatch.z, and U and z are copied out where it succeeded.  The frame
+// calls this once per pencil, so the three buffers are looked up by name per pencil (the same size every time: only the first
+// lookup of a call can allocate).
+int gbatch_solve_one(Context& ctx, const BatchArgs& g, int k) {
+  const int n = g.n;
+  const bool want_vec = g.mode == 'A';
+  double* ak = g.block(g.a, g.stride_a, k);
+  double* bk = g.block(g.b, g.stride_b, k);
+  double* wk = g.w + (size_t)k * g.ldw;
+  double* zk = want_vec ? g.block(g.z, g.stride_z, k) : nullptr;
+  const bool stage = ((g.lda | g.ldb) & 1) || (want_vec && (g.ldz & 1));
+  if (!stage) return gev_range_dev(ctx, n, RangeWindow::index(1, n), ak, g.lda, bk, g.ldb, wk, zk, g.ldz, g.mode);
   const int lds = pad_ld(n);
   const size_t col = (size_t)n * 8;
-  double *as = nullptr, *bs = nullptr, *zs = nullptr;
-  if (stage) {
-    as = ctx.pool.get_t<double>("gbatch.a", (size_t)lds * n);
-    bs = ctx.pool.get_t<double>("gbatch.b", (size_t)lds * n);
-    if (want_vec) zs = ctx.pool.get_t<double>("gbatch.z", (size_t)lds * n);
+  double* as = ctx.pool.get_t<double>("gbatch.a", (size_t)lds * n);
+  double* bs = ctx.pool.get_t<double>("gbatch.b", (size_t)lds * n);
+  double* zs = want_vec ? ctx.pool.get_t<double>("gbatch.z", (size_t)lds * n) : nullptr;
+  EIGX_HIP_CHECK(hipMemcpy2D(as, (size_t)lds * 8, ak, (size_t)g.lda * 8, col, (size_t)n, hipMemcpyDeviceToDevice));
+  EIGX_HIP_CHECK(hipMemcpy2D(bs, (size_t)lds * 8, bk, (size_t)g.ldb * 8, col, (size_t)n, hipMemcpyDeviceToDevice));
+  const int rk = gev_range_dev(ctx, n, RangeWindow::index(1, n), as, lds, bs, lds, wk, zs, lds, g.mode);
+  if (rk == EIGX_OK) {
+    EIGX_HIP_CHECK(hipMemcpy2D(bk, (size_t)g.ldb * 8, bs, (size_t)lds * 8, col, (size_t)n, hipMemcpyDeviceToDevice));
+    if (want_vec) EIGX_HIP_CHECK(hipMemcpy2D(zk, (size_t)g.ldz * 8, zs, (size_t)lds * 8, col, (size_t)n, hipMemcpyDeviceToDevice));
   }
-  int rc = EIGX_OK;
-  for (int k = 0; k < batch; ++k) {
-    double* ak = a + (size_t)k * stride_a;
-    double* bk = b + (size_t)k * stride_b;
-    double* zk = want_vec ? z + (size_t)k * stride_z : nullptr;
-    int rk;
-    if (stage) {
-      EIGX_HIP_CHECK(hipMemcpy2D(as, (size_t)lds * 8, ak, (size_t)lda * 8, col, (size_t)n, hipMemcpyDeviceToDevice));
-      EIGX_HIP_CHECK(hipMemcpy2D(bs, (size_t)lds * 8, bk, (size_t)ldb * 8, col, (size_t)n, hipMemcpyDeviceToDevice));
-      rk = gev_range_dev(ctx, n, RangeWindow::index(1, n), as, lds, bs, lds, w + (size_t)k * ldw, zs, lds, mode);
-      if (rk == EIGX_OK) {
-        EIGX_HIP_CHECK(hipMemcpy2D(bk, (size_t)ldb * 8, bs, (size_t)lds * 8, col, (size_t)n, hipMemcpyDeviceToDevice));
-        if (want_vec) EIGX_HIP_CHECK(hipMemcpy2D(zk, (size_t)ldz * 8, zs, (size_t)lds * 8, col, (size_t)n, hipMemcpyDeviceToDevice));
-      }
-    } else {
-      rk = gev_range_dev(ctx, n, RangeWindow::index(1, n), ak, lda, bk, ldb, w + (size_t)k * ldw, zk, ldz, mode);
-    }
-    if (!per_pencil(rk)) return rk;      // nothing per pencil: out of memory, ...
-    if (info_dev) EIGX_HIP_CHECK(hipMemcpy(info_dev + k, &rk, sizeof(int), hipMemcpyHostToDevice));
-    if (rc == EIGX_OK) rc = rk;
-  }
-  return rc;
+  return rk;
 }
 
 }  // namespace
@@ -278,109 +244,22 @@ int set_gbatch_nmax(int v) {
   return old;
 }
 
-// device arrays; info_dev may be null
-static int gbatch_solve_dev(Context& ctx, int n, int batch, double* a, int lda, int64_t stride_a, double* b, int ldb, int64_t stride_b,
-                            double* w, int ldw, double* z, int ldz, int64_t stride_z, char mode, int* info_dev) {
-  if (!ctx.initialized) return EIGX_ERR_NOT_INITIALIZED;
-  if (ctx.grid.nranks != 1) return refuse_several_ranks(ctx);
-  mode = upper_case(mode);
-  if (!gbatch_args_ok(n, batch, a, lda, stride_a, b, ldb, stride_b, w, ldw, z, ldz, stride_z, mode)) return EIGX_ERR_BAD_ARG;
-  if (batch == 0) return EIGX_OK;
-  EIGX_HIP_CHECK(hipSetDevice(ctx.device));
-  EIGX_HIP_CHECK(hipStreamSynchronize(nullptr));   // the caller's default-stream work on the arguments (SolveFrame::begin)
-  const double t0 = now_s();
-  ctx.errinfo = 0;
-  hipStream_t st = ctx.stream;
-  const bool want_vec = mode == 'A';
-  int rc = EIGX_OK;
-  if (n > g_gbatch_nmax) {
-    rc = gbatch_loop_dev(ctx, n, batch, a, lda, stride_a, b, ldb, stride_b, w, ldw, z, ldz, stride_z, mode, info_dev);
-    if (!per_pencil(rc)) return rc;
-  } else {
-    unsigned long long* first = ctx.pool.get_t<unsigned long long>("gbatch.first", 1);
-    EIGX_HIP_CHECK(hipMemsetAsync(first, 0xff, sizeof(unsigned long long), st));
-    const dim3 grid((unsigned)batch);
-    if (n <= 32)
-      hipLaunchKernelGGL(gbatch_kernel<32>, grid, dim3(64), 0, st, n, batch, (const double*)a, lda, stride_a, b, ldb, stride_b, w, ldw,
-                         z, ldz, stride_z, (int)want_vec, info_dev, first);
-    else if (n <= 64)
-      hipLaunchKernelGGL(gbatch_kernel<64>, grid, dim3(128), 0, st, n, batch, (const double*)a, lda, stride_a, b, ldb, stride_b, w, ldw,
-                         z, ldz, stride_z, (int)want_vec, info_dev, first);
-    else
-      hipLaunchKernelGGL(gbatch_kernel<96>, grid, dim3(192), 0, st, n, batch, (const double*)a, lda, stride_a, b, ldb, stride_b, w, ldw,
-                         z, ldz, stride_z, (int)want_vec, info_dev, first);
-    EIGX_HIP_CHECK(hipGetLastError());
-    unsigned long long f = 0;
-    EIGX_HIP_CHECK(hipMemcpyAsync(&f, first, sizeof(f), hipMemcpyDeviceToHost, st));
-    EIGX_HIP_CHECK(hipStreamSynchronize(st));
-    if (f != ~0ull) {
-      rc = -(int)(f & 0xff);
-      ctx.errinfo = -1;
-    }
-  }
-  for (int q = 0; q < 16; ++q) ctx.timers[q] = 0.0;
-  ctx.timers[0] = now_s() - t0;
-  return rc;
-}
-
-// Host arrays: a, b, z and w are staged in the pool buffers of the other host forms (host.a / host.b / host.z / host.w, leading
-// dimension host_ld(n)), the per-pencil status words in gbatch.info.  w comes back for every pencil, z and U for those that
-// succeeded.
-static int gbatch_solve_host(Context& ctx, int n, int batch, double* a, int lda, int64_t stride_a, double* b, int ldb, int64_t stride_b,
-                             double* w, int ldw, double* z, int ldz, int64_t stride_z, char mode, int* info) {
-  if (!ctx.initialized) return EIGX_ERR_NOT_INITIALIZED;
-  if (ctx.grid.nranks != 1) return refuse_several_ranks(ctx);
-  mode = upper_case(mode);
-  if (!gbatch_args_ok(n, batch, a, lda, stride_a, b, ldb, stride_b, w, ldw, z, ldz, stride_z, mode)) return EIGX_ERR_BAD_ARG;
-  if (batch == 0) return EIGX_OK;
-  EIGX_HIP_CHECK(hipSetDevice(ctx.device));
-  const bool want_vec = mode == 'A';
-  const int ldd = host_ld(n);
-  const int64_t sd = (int64_t)ldd * n;
-  double* ad = ctx.pool.get_t<double>("host.a", (size_t)sd * batch);
-  double* bd = ctx.pool.get_t<double>("host.b", (size_t)sd * batch);
-  double* zd = want_vec ? ctx.pool.get_t<double>("host.z", (size_t)sd * batch) : nullptr;
-  double* wd = ctx.pool.get_t<double>("host.w", (size_t)n * batch);
-  int* id = ctx.pool.get_t<int>("gbatch.info", (size_t)batch);
-  const int64_t sb = batch > 1 ? stride_b : (int64_t)ldb * n;
-  copy_blocks(ad, ldd, sd, a, lda, batch > 1 ? stride_a : (int64_t)lda * n, n, 0, batch, hipMemcpyHostToDevice);
-  copy_blocks(bd, ldd, sd, b, ldb, sb, n, 0, batch, hipMemcpyHostToDevice);
-  const int rc = gbatch_solve_dev(ctx, n, batch, ad, ldd, sd, bd, ldd, sd, wd, n, zd, ldd, sd, mode, id);
-  if (!per_pencil(rc)) return rc;
-  std::vector<int> ih((size_t)batch);
-  EIGX_HIP_CHECK(hipMemcpy(ih.data(), id, (size_t)batch * sizeof(int), hipMemcpyDeviceToHost));
-  EIGX_HIP_CHECK(hipMemcpy2D(w, (size_t)ldw * 8, wd, (size_t)n * 8, (size_t)n * 8, (size_t)batch, hipMemcpyDeviceToHost));
-  const int64_t sz = batch > 1 ? stride_z : (int64_t)ldz * n;
-  for (int k = 0; k < batch;) {          // runs of pencils that succeeded
-    int k1 = k;
-    while (k1 < batch && ih[k1] == EIGX_OK) ++k1;
-    if (want_vec) copy_blocks(z, ldz, sz, zd, ldd, sd, n, k, k1 - k, hipMemcpyDeviceToHost);
-    copy_blocks(b, ldb, sb, bd, ldd, sd, n, k, k1 - k, hipMemcpyDeviceToHost);
-    k = k1 + 1;
-  }
-  if (info) std::copy(ih.begin(), ih.end(), info);
-  return rc;
-}
-
 }  // namespace eigx
 
 using namespace eigx;
 
 extern "C" {
 
-// EXTENSION: `batch` symmetric-definite pencils of one size (one GPU); see gbatch_solve_dev
+// EXTENSION: `batch` symmetric-definite pencils of one size (one GPU); see batch_frame_host / batch_frame_dev (batch.hip)
 int eigx_gev_batch(int n, int batch, double* a, int lda, int64_t stride_a, double* b, int ldb, int64_t stride_b, double* w, int ldw,
                    double* z, int ldz, int64_t stride_z, char mode, int* info) {
-  return eigx_guard(g_ctx, [&] {
-    return gbatch_solve_host(g_ctx, n, batch, a, lda, stride_a, b, ldb, stride_b, w, ldw, z, ldz, stride_z, mode, info);
-  });
+  const BatchArgs g{n, batch, a, lda, stride_a, b, ldb, stride_b, w, ldw, z, ldz, stride_z, mode, info, 8, true};
+  return eigx_guard(g_ctx, [&] { return batch_frame_host(g_ctx, g, g_gbatch_nmax, gbatch_launch, gbatch_solve_one); });
 }
 int eigx_gev_batch_dev(int n, int batch, double* a_dev, int lda, int64_t stride_a, double* b_dev, int ldb, int64_t stride_b,
                        double* w_dev, int ldw, double* z_dev, int ldz, int64_t stride_z, char mode, int* info_dev) {
-  return eigx_guard(g_ctx, [&] {
-    return gbatch_solve_dev(g_ctx, n, batch, a_dev, lda, stride_a, b_dev, ldb, stride_b, w_dev, ldw, z_dev, ldz, stride_z, mode,
-                            info_dev);
-  });
+  const BatchArgs g{n, batch, a_dev, lda, stride_a, b_dev, ldb, stride_b, w_dev, ldw, z_dev, ldz, stride_z, mode, info_dev, 8, true};
+  return eigx_guard(g_ctx, [&] { return batch_frame_dev(g_ctx, g, g_gbatch_nmax, gbatch_launch, gbatch_solve_one); });
 }
 
 }  // extern "C"

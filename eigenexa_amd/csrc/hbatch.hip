@@ -14,21 +14,18 @@
 // No workgroup talks to another: no grid-wide barrier, no spin-wait, no atomics on the data.  Every sum is taken in an order
 // that depends on n alone, so a matrix's result does not depend on its position in the batch or on the batch size.
 // Matrices larger than the cutoff (eigx_tune key 22) go through herm_solve_dev (eigen_h) one by one.
+// Here: the kernel, the cutoff and the two functions the frame of the batch families asks for (batch_frame_dev / batch_frame_host,
+// batch.hip: checks, launch and failure word, the loop above the cutoff, host staging); QL sweep and failure exit are those of batch_common.h.
 #include "eigx_context.h"
 #include "batch_common.h"
 #include "../../include/eigenexa_amd.h"
-#include <algorithm>
 #include <cfloat>
-#include <limits>
-#include <vector>
 
 // (batch_common.h switches contraction off: the rank-2 update has to round A(r, c) and conj(A(c, r)) alike)
 #pragma clang fp contract(off)
 
 namespace eigx {
 namespace {
-
-int g_hbatch_nmax = EIGX_HBATCH_NMAX;   // key 22: largest n served by the batch kernel
 
 // One workgroup of 2 NMAX threads per matrix (NMAX = 32, 64, 96: the n-classes): thread (r, hh) = (row, half).  The full
 // Hermitian matrix, then Q, lives in the planes Ar(LD, NMAX), Ai(LD, NMAX), column-major with LD = NMAX + 1: the access
@@ -72,9 +69,7 @@ __global__ __launch_bounds__(2 * NMAX) void hbatch_kernel(int n, int batch, cons
     bad = block_max<NT>(bad, red[0]);
     mx = block_max<NT>(mx, red[1]);      // (its barrier also publishes the mirrored entries)
     if (bad != 0.0) {                    // uniform
-      if (row) w[(size_t)k * ldw + r] = std::numeric_limits<double>::quiet_NaN();
-      if (tid == 0) report_failure(first, info, k, EIGX_ERR_NONFINITE);
-      __syncthreads();
+      fail_matrix(k, EIGX_ERR_NONFINITE, row, r, w, ldw, info, first);
       continue;
     }
     // outside [1e-90, 1e90]: scale by the power of two nearest to 1 / max|a| (eigen_scaling, solver.hip)
@@ -284,9 +279,7 @@ __global__ __launch_bounds__(2 * NMAX) void hbatch_kernel(int n, int batch, cons
       if (ctl[2] != ST_RUN) break;
     }
     if (ctl[2] == ST_FAIL) {             // uniform
-      if (row) w[(size_t)k * ldw + r] = std::numeric_limits<double>::quiet_NaN();
-      if (tid == 0) report_failure(first, info, k, EIGX_ERR_INTERNAL);
-      __syncthreads();
+      fail_matrix(k, EIGX_ERR_INTERNAL, row, r, w, ldw, info, first);
       continue;
     }
 
@@ -316,28 +309,19 @@ __global__ __launch_bounds__(2 * NMAX) void hbatch_kernel(int n, int batch, cons
   }
 }
 
-// kind: host <-> device copy of `nb` blocks (from block b0 on) of n x n complex elements; leading dimensions and strides in
-// complex elements; one call where both sides are evenly spaced columns
-void copy_zblocks(double* dst, int ldd, int64_t sd, const double* src, int lds, int64_t ss, int n, int b0, int nb, hipMemcpyKind kind) {
-  if (nb <= 0) return;
-  if (sd == (int64_t)ldd * n && ss == (int64_t)lds * n) {
-    EIGX_HIP_CHECK(hipMemcpy2D(dst + 2 * (size_t)b0 * sd, (size_t)ldd * 16, src + 2 * (size_t)b0 * ss, (size_t)lds * 16, (size_t)n * 16,
-                               (size_t)n * nb, kind));
-    return;
-  }
-  for (int k = b0; k < b0 + nb; ++k)
-    EIGX_HIP_CHECK(hipMemcpy2D(dst + 2 * (size_t)k * sd, (size_t)ldd * 16, src + 2 * (size_t)k * ss, (size_t)lds * 16, (size_t)n * 16,
-                               (size_t)n, kind));
-}
+int g_hbatch_nmax = EIGX_HBATCH_NMAX;   // key 22: largest n served by the batch kernel
 
-// what both entry points require of their arguments (mode in upper case): the rules of eigx_s_batch
-bool hbatch_args_ok(int n, int batch, const double* a, int lda, int64_t stride_a, const double* w, int ldw, const double* z, int ldz,
-                    int64_t stride_z, char mode) {
-  if (n < 1 || batch < 0 || lda < n || ldw < n || (mode != 'A' && mode != 'N')) return false;
-  if (batch > 1 && stride_a < (int64_t)lda * n) return false;
-  if (mode == 'A' && (ldz < n || (batch > 1 && stride_z < (int64_t)ldz * n))) return false;
-  if (batch > 0 && (!a || !w || (mode == 'A' && !z))) return false;
-  return true;
+void hbatch_launch(const BatchArgs& g, hipStream_t st, unsigned long long* first) {
+  with_n_class<EIGX_HBATCH_NMAX>(g.n, [&](auto nmax) {
+    constexpr int NMAX = decltype(nmax)::value;
+    hipLaunchKernelGGL(hbatch_kernel<NMAX>, dim3((unsigned)g.batch), dim3(2 * NMAX), 0, st, g.n, g.batch, (const double*)g.a, g.lda,
+                       g.stride_a, g.w, g.ldw, g.z, g.ldz, g.stride_z, (int)(g.mode == 'A'), g.info, first);
+  });
+}
+// above the cutoff: eigen_h with the interface's default block sizes
+int hbatch_solve_one(Context& ctx, const BatchArgs& g, int k) {
+  return herm_solve_dev(ctx, g.n, g.n, g.block(g.a, g.stride_a, k), g.lda, g.w + (size_t)k * g.ldw,
+                        g.mode == 'A' ? g.block(g.z, g.stride_z, k) : nullptr, g.ldz, 48, 128, g.mode);
 }
 
 }  // namespace
@@ -349,110 +333,23 @@ int set_hbatch_nmax(int v) {
   return old;
 }
 
-// device arrays (a, z interleaved complex; lda, ldz and the strides in complex elements); info_dev may be null
-static int hbatch_solve_dev(Context& ctx, int n, int batch, double* a, int lda, int64_t stride_a, double* w, int ldw, double* z,
-                            int ldz, int64_t stride_z, char mode, int* info_dev) {
-  if (!ctx.initialized) return EIGX_ERR_NOT_INITIALIZED;
-  if (ctx.grid.nranks != 1) return refuse_several_ranks(ctx);
-  mode = upper_case(mode);
-  if (!hbatch_args_ok(n, batch, a, lda, stride_a, w, ldw, z, ldz, stride_z, mode)) return EIGX_ERR_BAD_ARG;
-  if (batch == 0) return EIGX_OK;
-  EIGX_HIP_CHECK(hipSetDevice(ctx.device));
-  EIGX_HIP_CHECK(hipStreamSynchronize(nullptr));   // the caller's default-stream work on the arguments (SolveFrame::begin)
-  const double t0 = now_s();
-  ctx.errinfo = 0;
-  hipStream_t st = ctx.stream;
-  const bool want_vec = mode == 'A';
-  int rc = EIGX_OK;
-  if (n > g_hbatch_nmax) {
-    // above the cutoff: eigen_h with the interface's default block sizes, matrix by matrix
-    for (int k = 0; k < batch; ++k) {
-      const int rk = herm_solve_dev(ctx, n, n, a + 2 * (size_t)k * stride_a, lda, w + (size_t)k * ldw,
-                                    want_vec ? z + 2 * (size_t)k * stride_z : nullptr, ldz, 48, 128, mode);
-      if (rk != EIGX_OK && rk != EIGX_ERR_NONFINITE && rk != EIGX_ERR_INTERNAL) return rk;   // nothing per matrix: out of memory, ...
-      if (info_dev) EIGX_HIP_CHECK(hipMemcpy(info_dev + k, &rk, sizeof(int), hipMemcpyHostToDevice));
-      if (rc == EIGX_OK) rc = rk;
-    }
-  } else {
-    unsigned long long* first = ctx.pool.get_t<unsigned long long>("hbatch.first", 1);
-    EIGX_HIP_CHECK(hipMemsetAsync(first, 0xff, sizeof(unsigned long long), st));
-    const dim3 grid((unsigned)batch);
-    if (n <= 32)
-      hipLaunchKernelGGL(hbatch_kernel<32>, grid, dim3(64), 0, st, n, batch, (const double*)a, lda, stride_a, w, ldw, z, ldz, stride_z,
-                         (int)want_vec, info_dev, first);
-    else if (n <= 64)
-      hipLaunchKernelGGL(hbatch_kernel<64>, grid, dim3(128), 0, st, n, batch, (const double*)a, lda, stride_a, w, ldw, z, ldz, stride_z,
-                         (int)want_vec, info_dev, first);
-    else
-      hipLaunchKernelGGL(hbatch_kernel<96>, grid, dim3(192), 0, st, n, batch, (const double*)a, lda, stride_a, w, ldw, z, ldz, stride_z,
-                         (int)want_vec, info_dev, first);
-    EIGX_HIP_CHECK(hipGetLastError());
-    unsigned long long f = 0;
-    EIGX_HIP_CHECK(hipMemcpyAsync(&f, first, sizeof(f), hipMemcpyDeviceToHost, st));
-    EIGX_HIP_CHECK(hipStreamSynchronize(st));
-    if (f != ~0ull) {
-      rc = -(int)(f & 0xff);
-      ctx.errinfo = -1;
-    }
-  }
-  for (int q = 0; q < 16; ++q) ctx.timers[q] = 0.0;
-  ctx.timers[0] = now_s() - t0;
-  return rc;
-}
-
-// Host arrays: a, z and w are staged in the pool buffers of the complex host forms (host.ha / host.hz, 16 bytes per element,
-// and host.w; leading dimension host_ld(n)), the per-matrix status words in hbatch.info.  w comes back for every matrix, z
-// for those that succeeded.
-static int hbatch_solve_host(Context& ctx, int n, int batch, double* a, int lda, int64_t stride_a, double* w, int ldw, double* z,
-                             int ldz, int64_t stride_z, char mode, int* info) {
-  if (!ctx.initialized) return EIGX_ERR_NOT_INITIALIZED;
-  if (ctx.grid.nranks != 1) return refuse_several_ranks(ctx);
-  mode = upper_case(mode);
-  if (!hbatch_args_ok(n, batch, a, lda, stride_a, w, ldw, z, ldz, stride_z, mode)) return EIGX_ERR_BAD_ARG;
-  if (batch == 0) return EIGX_OK;
-  EIGX_HIP_CHECK(hipSetDevice(ctx.device));
-  const bool want_vec = mode == 'A';
-  const int ldd = host_ld(n);
-  const int64_t sd = (int64_t)ldd * n;
-  double* ad = (double*)ctx.pool.get("host.ha", (size_t)16 * sd * batch);
-  double* zd = want_vec ? (double*)ctx.pool.get("host.hz", (size_t)16 * sd * batch) : nullptr;
-  double* wd = ctx.pool.get_t<double>("host.w", (size_t)n * batch);
-  int* id = ctx.pool.get_t<int>("hbatch.info", (size_t)batch);
-  copy_zblocks(ad, ldd, sd, a, lda, batch > 1 ? stride_a : (int64_t)lda * n, n, 0, batch, hipMemcpyHostToDevice);
-  const int rc = hbatch_solve_dev(ctx, n, batch, ad, ldd, sd, wd, n, zd, ldd, sd, mode, id);
-  if (rc != EIGX_OK && rc != EIGX_ERR_NONFINITE && rc != EIGX_ERR_INTERNAL) return rc;
-  std::vector<int> ih((size_t)batch);
-  EIGX_HIP_CHECK(hipMemcpy(ih.data(), id, (size_t)batch * sizeof(int), hipMemcpyDeviceToHost));
-  EIGX_HIP_CHECK(hipMemcpy2D(w, (size_t)ldw * 8, wd, (size_t)n * 8, (size_t)n * 8, (size_t)batch, hipMemcpyDeviceToHost));
-  if (want_vec) {
-    const int64_t sz = batch > 1 ? stride_z : (int64_t)ldz * n;
-    for (int k = 0; k < batch;) {        // runs of matrices that succeeded
-      int k1 = k;
-      while (k1 < batch && ih[k1] == EIGX_OK) ++k1;
-      copy_zblocks(z, ldz, sz, zd, ldd, sd, n, k, k1 - k, hipMemcpyDeviceToHost);
-      k = k1 + 1;
-    }
-  }
-  if (info) std::copy(ih.begin(), ih.end(), info);
-  return rc;
-}
-
 }  // namespace eigx
 
 using namespace eigx;
 
 extern "C" {
 
-// EXTENSION: `batch` complex Hermitian eigenproblems of one size (one GPU); see hbatch_solve_dev
+// EXTENSION: `batch` complex Hermitian eigenproblems of one size (one GPU; a, z interleaved complex; lda, ldz and the strides in
+// complex elements); see batch_frame_host / batch_frame_dev (batch.hip)
 int eigx_h_batch(int n, int batch, double* a, int lda, int64_t stride_a, double* w, int ldw, double* z, int ldz, int64_t stride_z,
                  char mode, int* info) {
-  return eigx_guard(g_ctx, [&] { return hbatch_solve_host(g_ctx, n, batch, a, lda, stride_a, w, ldw, z, ldz, stride_z, mode, info); });
+  const BatchArgs g{n, batch, a, lda, stride_a, nullptr, 0, 0, w, ldw, z, ldz, stride_z, mode, info, 16, false};
+  return eigx_guard(g_ctx, [&] { return batch_frame_host(g_ctx, g, g_hbatch_nmax, hbatch_launch, hbatch_solve_one); });
 }
 int eigx_h_batch_dev(int n, int batch, double* a_dev, int lda, int64_t stride_a, double* w_dev, int ldw, double* z_dev, int ldz,
                      int64_t stride_z, char mode, int* info_dev) {
-  return eigx_guard(g_ctx, [&] {
-    return hbatch_solve_dev(g_ctx, n, batch, a_dev, lda, stride_a, w_dev, ldw, z_dev, ldz, stride_z, mode, info_dev);
-  });
+  const BatchArgs g{n, batch, a_dev, lda, stride_a, nullptr, 0, 0, w_dev, ldw, z_dev, ldz, stride_z, mode, info_dev, 16, false};
+  return eigx_guard(g_ctx, [&] { return batch_frame_dev(g_ctx, g, g_hbatch_nmax, hbatch_launch, hbatch_solve_one); });
 }
 
 }  // extern "C"

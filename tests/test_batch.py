@@ -30,6 +30,7 @@ def _dev():
 
 
 # ------------------------------------------------------------------------------------------------ matrices
+# (tools/gpu_frame_dump.py imports _families for its batch section)
 def _families(n, seed=0):
     """random symmetric, Frank, three clusters Q D Q^T, graded by 1e-12 across rows and columns, Wilkinson, identity, zero,
     diagonal -- and a second random matrix"""

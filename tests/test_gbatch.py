@@ -58,6 +58,7 @@ def _gram(n, seed):
     return 0.5 * (B + B.T)
 
 
+# (tools/gpu_frame_dump.py imports _overlaps for its batch section)
 def _overlaps(n):
     """Helmert (cond about 1.2), Q diag(logspace(0, -4, n)) Q^T (cond 1e4), identity, a diagonal, a seeded Gram matrix"""
     from eigenexa_amd import layout

@@ -44,6 +44,7 @@ def _herm(M):
     return U + U.conj().T + np.diag(np.diag(M).real)
 
 
+# (tools/gpu_frame_dump.py imports _families for its batch section)
 def _families(n, seed=0):
     """random Hermitian, phased Frank D F D^H, three clusters Q D Q^H, graded by 1e-12 across rows and columns, Wilkinson with
     unit-modulus off-diagonals, identity, zero, real diagonal, a real symmetric matrix, i K with K real antisymmetric"""

@@ -1,5 +1,5 @@
 """Bit-for-bit record of what the whole-solve drivers return, for comparing two builds of the library.
-usage: [EIGX_LIB=other/libeigenexa_amd.so] gpu_frame_dump.py OUTDIR [--quick]
+usage: [EIGX_LIB=other/libeigenexa_amd.so] gpu_frame_dump.py OUTDIR [--quick | --batch]
 
 Runs a fixed list of seeded calls of eigen_sx / eigen_s, the index-range solves and eigen_h (device and host entry
 points; every mode, panel widths, nvec < n, odd leading dimensions, scaled and non-finite inputs) and writes for each
@@ -9,7 +9,8 @@ eigx_hgev_range_dev and their stages (Cholesky, triangular solves, reduction; ei
 the status, w, z and the arrays a / b as the call leaves them.  Then the real generalised solvers eigx_gev[_range][_dev],
 the value-window solves (m and il as well), the host forms of all four generalised solvers and their statuses (non-finite
 A or B, B not positive definite, a bad window, ldb < n) from sentinel-filled w and z.  An array above 8 MiB is stored as
-its SHA-256.
+its SHA-256.  Last the batched small solvers eigx_s_batch, eigx_h_batch and eigx_gev_batch (batch_section below); --batch
+runs that section alone (well under a minute).
 The library is deterministic, so two builds that compute the same leave directories that `cmp` finds equal:
     for f in A/*; do cmp $f B/$(basename $f); done
 Run each build in a fresh process.  --quick leaves out n >= 2048."""
@@ -44,7 +45,85 @@ def save(label, **arrays):
     print(f"{idx:03d} {label} rc={int(arrays['rc'])} flops={float(arrays.get('flops', 0.0)):.6e}", flush=True)
 
 
+def batch_section():
+    """eigx_{s,h,gev}_batch[_dev], modes A and N and mode A with info = NULL, at n = 1, 2, 17, 33, 64, 96 (s: 128 too) and, with
+    the cutoff key lowered to 32, at n = 40 through the full-size solvers (gev: odd and even leading dimensions).  A batch is the
+    families of the family's test file, the first of them scaled by 1e-200 and by 1e+200, one matrix with a NaN and (gev) one
+    pencil with an indefinite B.  Padded leading dimensions and strides, NaN outside the upper triangles, w / z / info prefilled;
+    recorded: the status and the whole buffers w, z, info and (gev) b as the call leaves them."""
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests"))
+    import test_batch
+    import test_gbatch
+    import test_hbatch
+
+    def image(mats, ld, stride, cplx):
+        """upper triangles (complex: interleaved, Im of the diagonal NaN); NaN in the lower triangles, the padding and the gaps"""
+        n, c = mats[0].shape[0], 2 if cplx else 1
+        buf = np.full(c * stride * len(mats), np.nan)
+        upper = np.tri(n, dtype=bool)   # [j, i]: i <= j
+        for k, M in enumerate(mats):
+            v = buf[c * k * stride:c * (k * stride + ld * n)].reshape(n, ld, c)   # v[j, i] = m(i, j)
+            v[:, :n, 0] = np.where(upper, M.T.real, np.nan)
+            if cplx:
+                v[:, :n, 1] = np.where(upper & ~np.eye(n, dtype=bool), M.T.imag, np.nan)
+        return buf
+
+    def one(fam, n, even, tag):
+        cplx, gev = fam == "h", fam == "gev"
+        mats = (test_hbatch if cplx else test_batch)._families(n)
+        bad = mats[0].copy()
+        bad[0, n - 1] = bad[n - 1, 0] = np.nan
+        mats = mats + [mats[0] * 1e-200, mats[0] * 1e200, bad]
+        nb = len(mats) + gev
+        lda, ldb, ldz, ldw = (n + 4, n + 2, n + 2, n + 2) if even else (n + 3, n + 2, n + 1, n + 2)
+        sa, sb, sz = lda * n + 5, ldb * n + 3, ldz * n + 7
+        if gev:
+            ov = test_gbatch._overlaps(n)
+            indef = ov[0].copy()
+            indef[n // 2, n // 2] = -1.0
+            mats, bs = mats + [mats[1]], [ov[k % len(ov)] for k in range(nb - 1)] + [indef]
+        a0 = image(mats, lda, sa, cplx)
+        b0 = image(bs, ldb, sb, False) if gev else None
+        c = 2 if cplx else 1
+        for form in ("dev", "host"):
+            fn = getattr(lib, f"eigx_{fam}_batch" + ("_dev" if form == "dev" else ""))
+            for mode, with_info in (("A", True), ("N", True), ("A", False)):
+                w, z = np.full(ldw * nb, SENT_B), np.full(c * sz * nb, SENT_B)
+                info = np.full(nb, 77, dtype=np.int32)
+                arrs = dict(a=a0.copy(), w=w, z=z, info=info, **(dict(b=b0.copy()) if gev else {}))
+                if form == "dev":
+                    arrs = {k: torch.from_numpy(v).to(dev) for k, v in arrs.items()}
+                    ptr = {k: v.data_ptr() for k, v in arrs.items()}
+                else:
+                    ptr = {k: v.ctypes.data for k, v in arrs.items()}
+                args = (n, nb, ptr["a"], lda, sa) + ((ptr["b"], ldb, sb) if gev else ()) + (
+                    ptr["w"], ldw, ptr["z"] if mode == "A" else None, ldz, sz, mode.encode(), ptr["info"] if with_info else None)
+                rc = fn(*args)
+                if form == "dev":
+                    torch.cuda.synchronize()
+                    arrs = {k: v.cpu().numpy() for k, v in arrs.items()}
+                del arrs["a"]
+                save(f"{fam}batch_{form}_n{n}{tag}_{mode}{'' if with_info else '_noinfo'}", rc=np.int64(rc), **arrs)
+
+    for fam, key, sizes in (("s", 21, (1, 2, 17, 33, 64, 96, 128)), ("h", 22, (1, 2, 17, 33, 64, 96)), ("gev", 23, (1, 2, 17, 33, 64, 96))):
+        for n in sizes:
+            one(fam, n, False, "")
+        cutoff = lib.eigx_tune(key, 32)
+        one(fam, 40, False, "_loop")
+        if fam == "gev":
+            one(fam, 40, True, "_loop_evenld")
+        lib.eigx_tune(key, cutoff)
+
+
+SENT_B = -7.25   # what w and z of the batch section start from
 _sym = {}
+
+
+if "--batch" in sys.argv[2:]:
+    batch_section()
+    lib.eigx_free()
+    print(f"DUMPED {count[0]} calls into {out}", flush=True)
+    sys.exit(0)
 
 
 def sym(n):
@@ -353,5 +432,6 @@ for fam, cplx, pen in (("gev", False, rpencil(n)), ("hgev", True, pencil(n))):
             gen_host(f"st_{fam}_host_{cname}", full, Ax, Bx, None, ldb=ldb, fill=SENT)
         gen_dev(f"st_{fam}r_dev_{cname}", rng_d, Ax, Bx, win, cplx=cplx, ldb=ldb, fill=SENT)
         gen_host(f"st_{fam}r_host_{cname}", rng, Ax, Bx, win, ldb=ldb, fill=SENT)
+batch_section()
 lib.eigx_free()
 print(f"DUMPED {count[0]} calls into {out}", flush=True)
