@@ -1,4 +1,4 @@
-"""ctypes binding of libeigenexa_amd.so (the C-ABI declared in include/eigenexa_amd.h and the file it includes).
+"""ctypes binding of libeigenexa_amd.so (the C-ABI declared in include/eigenexa_amd.h and the files it includes).
 
 There is no CPU fallback: if the HIP library is missing or no GPU is visible the calls fail loudly.
 """
@@ -159,6 +159,13 @@ GBATCH_SIGNATURES = {
     "eigx_gev_batch_dev": (C.c_int, _GEV_BATCH),
 }
 
+# The same for include/eigenexa_amd_hgbatch.h -- extension: many small Hermitian-definite pencils in one call
+# (csrc/hgbatch.hip); a, b, z interleaved complex, b comes back as U.  The argument kinds are those of eigx_gev_batch.
+HGBATCH_SIGNATURES = {
+    "eigx_hgev_batch": (C.c_int, _GEV_BATCH),
+    "eigx_hgev_batch_dev": (C.c_int, _GEV_BATCH),
+}
+
 _lib = None
 
 
@@ -173,7 +180,7 @@ def load():
             "eigenexa_amd has no CPU fallback."
         )
     lib = C.CDLL(LIB_PATH, mode=C.RTLD_GLOBAL)
-    for name, (res, args) in {**SIGNATURES, **GBATCH_SIGNATURES}.items():
+    for name, (res, args) in {**SIGNATURES, **GBATCH_SIGNATURES, **HGBATCH_SIGNATURES}.items():
         fn = getattr(lib, name)  # AttributeError = header/library mismatch: fail loudly
         fn.restype = res
         fn.argtypes = args

@@ -506,18 +506,8 @@ def eigen_h_batch(n, batch, a, lda, w, z, ldz, mode="A", info=None, stride_a=Non
     _solve_batch("h", n, batch, a, lda, w, z, ldz, mode, info, stride_a, ldw, stride_z)
 
 
-def eigen_gev_batch(n, batch, a, lda, b, ldb, w, z, ldz, mode="A", info=None, stride_a=None, stride_b=None, ldw=None, stride_z=None):
-    """EXTENSION (not in the reference): ``batch`` symmetric-definite pencils ``A x = lambda B x`` of one size ``n`` in one call,
-    one GPU.  ``a[lda, n, batch]`` and ``b[ldb, n, batch]`` (numpy, Fortran order, or GPU tensors with the same memory image:
-    pencil ``k`` starts at elements ``k * stride_a`` / ``k * stride_b``) hold the upper triangles; ``a`` is destroyed, ``b``
-    comes back with ``U`` (``B = U^T U``) in its upper triangle.  ``w[ldw, batch]`` receives the ascending eigenvalues,
-    ``z[ldz, n, batch]`` the eigenvectors with ``z^T B z = I`` (mode 'A'; mode 'N': eigenvalues and ``U`` only, ``z`` may be
-    None).  Defaults: ``stride_a = lda * n``, ``stride_b = ldb * n``, ``stride_z = ldz * n``, ``ldw = n``.  ``info`` (optional,
-    int32, ``batch`` entries, on the side of ``a``) receives the per-pencil status: 0, -5 (NaN / Inf in A or B: its ``w`` is
-    NaN, its ``z`` and ``b`` untouched), -7 (B not positive definite: ``w`` NaN, ``z`` untouched) or -6; ``last_status()`` is 0
-    or the status of the first failed pencil.  For ``n <= 96`` one kernel launch solves the batch, one workgroup per pencil
-    with both matrices in LDS; larger ``n`` runs ``KMATH_EIGEN_GEV_RANGE`` with ``il = 1, iu = n`` pencil by pencil."""
-    name = "eigen_gev_batch"
+def _solve_pencil_batch(which, n, batch, a, lda, b, ldb, w, z, ldz, mode, info, stride_a, stride_b, ldw, stride_z):
+    name = f"eigen_{which}_batch"
     # the arguments are checked here, before the library is touched (status -2 = EIGX_ERR_BAD_ARG)
     md = _char(mode, "A").upper()
     try:
@@ -548,10 +538,38 @@ def eigen_gev_batch(n, batch, a, lda, b, ldb, w, z, ldz, mode="A", info=None, st
     for x, xname in ((a, "a"), (b, "b"), (w, "w"), (z, "z")):
         if x is not None and not dev and not _is_torch(x) and x.ndim > 2 and not x.flags.f_contiguous:
             raise ValueError(f"{xname}: Fortran (column-major) order required, as in the reference")
-    pa, pb, pw, pz = _addrs("gev", dev, a=a, b=b, w=w, z=z)
+    pa, pb, pw, pz = _addrs(which, dev, a=a, b=b, w=w, z=z)
     pi = _info_addr(info, dev, "a, b, w, z, info")
-    rc = _entry(lib, "eigx_gev_batch", dev)(n, batch, pa, lda, stride_a, pb, ldb, stride_b, pw, ldw, pz, ldz, stride_z, md, pi)
+    rc = _entry(lib, f"eigx_{which}_batch", dev)(n, batch, pa, lda, stride_a, pb, ldb, stride_b, pw, ldw, pz, ldz, stride_z, md, pi)
     _finish(name, rc, (0, -5, -6, -7))
+
+
+def eigen_gev_batch(n, batch, a, lda, b, ldb, w, z, ldz, mode="A", info=None, stride_a=None, stride_b=None, ldw=None, stride_z=None):
+    """EXTENSION (not in the reference): ``batch`` symmetric-definite pencils ``A x = lambda B x`` of one size ``n`` in one call,
+    one GPU.  ``a[lda, n, batch]`` and ``b[ldb, n, batch]`` (numpy, Fortran order, or GPU tensors with the same memory image:
+    pencil ``k`` starts at elements ``k * stride_a`` / ``k * stride_b``) hold the upper triangles; ``a`` is destroyed, ``b``
+    comes back with ``U`` (``B = U^T U``) in its upper triangle.  ``w[ldw, batch]`` receives the ascending eigenvalues,
+    ``z[ldz, n, batch]`` the eigenvectors with ``z^T B z = I`` (mode 'A'; mode 'N': eigenvalues and ``U`` only, ``z`` may be
+    None).  Defaults: ``stride_a = lda * n``, ``stride_b = ldb * n``, ``stride_z = ldz * n``, ``ldw = n``.  ``info`` (optional,
+    int32, ``batch`` entries, on the side of ``a``) receives the per-pencil status: 0, -5 (NaN / Inf in A or B: its ``w`` is
+    NaN, its ``z`` and ``b`` untouched), -7 (B not positive definite: ``w`` NaN, ``z`` untouched) or -6; ``last_status()`` is 0
+    or the status of the first failed pencil.  For ``n <= 96`` one kernel launch solves the batch, one workgroup per pencil
+    with both matrices in LDS; larger ``n`` runs ``KMATH_EIGEN_GEV_RANGE`` with ``il = 1, iu = n`` pencil by pencil."""
+    _solve_pencil_batch("gev", n, batch, a, lda, b, ldb, w, z, ldz, mode, info, stride_a, stride_b, ldw, stride_z)
+
+
+def eigen_hgev_batch(n, batch, a, lda, b, ldb, w, z, ldz, mode="A", info=None, stride_a=None, stride_b=None, ldw=None, stride_z=None):
+    """EXTENSION (not in the reference): ``batch`` Hermitian-definite pencils ``A x = lambda B x`` of one size ``n`` in one
+    call, one GPU -- ``eigen_gev_batch`` over complex numbers, on the storage of ``eigen_h_batch``.  ``a[lda, n, batch]`` and
+    ``b[ldb, n, batch]`` (complex128 numpy, Fortran order, or complex128 GPU tensors with the same memory image: pencil ``k``
+    starts at complex elements ``k * stride_a`` / ``k * stride_b``) hold the upper triangles (of the diagonals the real parts
+    only); ``a`` is destroyed, ``b`` comes back with ``U`` (``B = U^H U``, real positive diagonal) in its upper triangle.
+    ``w[ldw, batch]`` (float64) receives the ascending eigenvalues, ``z[ldz, n, batch]`` (complex128) the eigenvectors with
+    ``z^H B z = I`` (mode 'A'; mode 'N': eigenvalues and ``U`` only, ``z`` may be None).  Defaults, ``info`` and
+    ``last_status()`` as for ``eigen_gev_batch``; leading dimensions and strides count complex elements.  For ``n <= 64`` one
+    kernel launch solves the batch, one workgroup per pencil with both matrices in LDS; larger ``n`` runs
+    ``KMATH_EIGEN_HGEV_RANGE`` with ``il = 1, iu = n`` pencil by pencil."""
+    _solve_pencil_batch("hgev", n, batch, a, lda, b, ldb, w, z, ldz, mode, info, stride_a, stride_b, ldw, stride_z)
 
 
 def band_count(d, e, band, x):

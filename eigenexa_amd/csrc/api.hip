@@ -1,5 +1,5 @@
 // api.hip -- C-ABI entry points (include/eigenexa_amd.h): life cycle, queries, memory helpers.
-// The solver entry points live in solver.hip, gev.hip, hgev.hip, herm.hip, batch.hip, hbatch.hip and gbatch.hip.
+// The solver entry points live in solver.hip, gev.hip, hgev.hip, herm.hip, batch.hip, hbatch.hip, gbatch.hip and hgbatch.hip.
 #include "eigx_context.h"
 #include "eigx_comm.h"
 #include "../../include/eigenexa_amd.h"
@@ -372,6 +372,7 @@ int eigx_tune(int key, int value) {
   if (key == 21) return set_batch_nmax(value); // largest n served by the batch kernel of eigx_s_batch (batch.hip)
   if (key == 22) return set_hbatch_nmax(value);   // the same for eigx_h_batch (hbatch.hip)
   if (key == 23) return set_gbatch_nmax(value);   // the same for eigx_gev_batch (gbatch.hip)
+  if (key == 24) return set_hgbatch_nmax(value);  // the same for eigx_hgev_batch (hgbatch.hip)
   return -1;
 }
 

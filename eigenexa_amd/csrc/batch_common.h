@@ -1,13 +1,15 @@
 // batch_common.h -- what the one-workgroup-per-matrix kernels share (batch.hip: real symmetric, hbatch.hip: complex
-// Hermitian, gbatch.hip: real symmetric-definite pencils): the workgroup reductions, the scaling rule, the failure word of a
-// launch and the exit of a failed matrix, thread 0's QL sweep on a real (d, e) held in LDS, the rank of the sort and, for the two
-// real kernels, the whole reduction + QL of a matrix held in LDS.  The QL round loop is written here (sym_tridiag_ql) and once
-// more in hbatch_kernel: as a function of its own, called from both, it changed the register allocation and block placement of
-// the real kernels and cost eigx_gev_batch 1.5 to 3 % at n <= 32 (profiles/batch_frame_bits.log).  For the same reason batch_kernel
-// and hbatch_kernel keep the scaling rule written out (scale_exponent here serves gbatch_kernel) and hbatch_kernel its rank count:
+// Hermitian, gbatch.hip: real symmetric-definite pencils, hgbatch.hip: complex Hermitian-definite pencils): the workgroup
+// reductions, the scaling rule, the failure word of a launch and the exit of a failed matrix, thread 0's QL sweep on a real (d, e)
+// held in LDS, the rank of the sort, for the two real kernels the whole reduction + QL of a matrix held in LDS (sym_tridiag_ql)
+// and for the two complex ones the same on split planes (herm_tridiag_ql).  The QL round loop is written in both: as a function
+// of its own, called from both, it changed the register allocation and block placement of the real kernels and cost
+// eigx_gev_batch 1.5 to 3 % at n <= 32 (profiles/batch_frame_bits.log).  For the same reason batch_kernel and hbatch_kernel keep
+// the scaling rule written out (scale_exponent here serves gbatch_kernel and hgbatch_kernel) and hbatch_kernel its rank count:
 // one instruction more in the prologue moves all the code behind it; with both helpers in use batch_kernel<64> measured 5 % and
-// hbatch_kernel<96> 1 % slower (the intermediate form in profiles/batch_frame_bits.log).  As it stands every kernel compiles to the
-// parent commit's instructions exactly.
+// hbatch_kernel<96> 1 % slower (the intermediate form in profiles/batch_frame_bits.log).  The move of hbatch_kernel's phases
+// into herm_tridiag_ql changed its register allocation but neither a bit of its results nor, beyond the spread of the repeats,
+// its time (profiles/hgbatch_hbatch_bits.log).
 #pragma once
 #include <cfloat>
 #include <cstdint>
@@ -282,6 +284,217 @@ __device__ __forceinline__ int sym_tridiag_ql(int n, int want_vec, double* A, do
           hc = fma(c, zi, -(s * hc));
         }
         A[r + lo * LD] = hc;
+      }
+      bool small = false;
+      if (row) small = r == n - 1 || fabs(e[r]) <= (0.5 * DBL_EPSILON) * (fabs(d[r]) + fabs(d[r + 1]));
+      const unsigned long long bits = __ballot(small);
+      if ((tid & 63) == 0 && tid < 128) msk[tid >> 6] = bits;   // (rows live in threads 0 .. n-1; the lanes of half 1 vote 0)
+    }
+    __syncthreads();
+    if (tid == 0) ql_sweep(n, d, e, pt, ctl, msk, ql_l, ql_it);
+    __syncthreads();
+    if (ctl[2] != ST_RUN) break;
+  }
+  return ctl[2];
+}
+
+// Phases 2 and 3 of a one-workgroup-per-matrix complex Hermitian solve (hbatch.hip: eigx_h_batch, hgbatch.hip: eigx_hgev_batch),
+// 2 NMAX threads, thread (r, hh) = (row, half): the full Hermitian matrix of order n in the split planes Ar, Ai(LD, NMAX),
+// LD = NMAX + 1 -> Householder tridiagonalisation with Hermitian reflectors (the shape of EISPACK's htridi) -> a chain of unit
+// phases D that makes D^H T D real with e >= 0 -> Q D accumulated in place in the planes (want_vec) -> implicit QL with Wilkinson
+// shift on the real (d, e), half 0 applying the rotations to the real plane of its row and half 1 to the imaginary one.  Every
+// array is the caller's LDS: d, e, hv, pr, pi, ur, ui, qr, qi of NMAX entries, pt of 4 NMAX, red[4][4], ctl[4], msk[2].  The
+// caller has published the planes with a barrier; every thread of the workgroup makes the call and gets the same state back:
+// ST_DONE (d holds the eigenvalues in the order of the planes' columns) or ST_FAIL (the QL budget is used up); both behind a
+// barrier.
+template <int NMAX>
+__device__ __forceinline__ int herm_tridiag_ql(int n, int want_vec, double* Ar, double* Ai, double* d, double* e, double* hv,
+                                               double* pr, double* pi, double* ur, double* ui, double* qr, double* qi, double* pt,
+                                               double (*red)[4], int* ctl, unsigned long long* msk) {
+  constexpr int NT = 2 * NMAX, LD = NMAX + 1;
+  const int tid = threadIdx.x, r = tid % NMAX, hh = tid / NMAX;
+  const bool row = hh == 0 && r < n;     // the thread that owns row r where one thread per row is wanted
+  // ---- 2. tridiagonalisation, i = n-1 .. 1: H_i = I - u u^H / h annihilates A(0 .. i-2, i) and leaves g in A(i-1, i) -----
+  // u stays in A(0 .. i-1, i), h in hv[i], g in (pr, pi)[i]; the active matrix is the full Hermitian block 0 .. i-1
+  for (int i = n - 1; i >= 1; --i) {
+    const int l = i - 1;
+    double* rd = red[2 * (i & 1)];     // by parity: a step that leaves early has no closing barrier
+    if (l == 0) {
+      if (tid == 0) { pr[1] = Ar[LD]; pi[1] = Ai[LD]; hv[1] = 0.0; }
+      continue;
+    }
+    const bool act = hh == 0 && r <= l;
+    const double xr = act ? Ar[r + i * LD] : 0.0, xi = act ? Ai[r + i * LD] : 0.0;
+    const double fr = Ar[l + i * LD], fi = Ai[l + i * LD];   // (read before the barrier: thread l overwrites them below)
+    double h = block_sum<NT>(xr * xr + xi * xi, rd);
+    if (h == 0.0) {                    // nothing to annihilate (uniform): the column is zero, or lost to underflow
+      if (tid == 0) { pr[i] = fr; pi[i] = fi; hv[i] = 0.0; }
+      continue;
+    }
+    const double nrm = sqrt(h), af = hypot2(fr, fi);
+    double gr = -nrm, gi = 0.0;        // g = -(f / |f|) ||x||
+    if (af != 0.0) {
+      gr = -(fr / af) * nrm;
+      gi = -(fi / af) * nrm;
+    }
+    h += af * nrm;                     // h = u^H u / 2
+    if (act) {
+      const double vr = r == l ? fr - gr : xr, vi = r == l ? fi - gi : xi;
+      ur[r] = vr;
+      ui[r] = vi;
+      Ar[r + i * LD] = vr;
+      Ai[r + i * LD] = vi;
+    }
+    if (tid == 0) { pr[i] = gr; pi[i] = gi; hv[i] = h; }
+    __syncthreads();
+    // p = A u, each half over its share of the columns.  Both halves make mid steps (a uniform trip count lets the loop be
+    // unrolled and its LDS reads be batched); the step that half 1 may have too many reads column l+1 and adds nothing
+    const int mid = (l + 2) / 2, k0 = hh ? mid : 0, k1 = hh ? l + 1 : mid;
+    if (r <= l) {
+      double sr = 0.0, si = 0.0;
+#pragma unroll 4
+      for (int t = 0; t < mid; ++t) {
+        const int c = k0 + t;
+        const double ucr = c < k1 ? ur[c] : 0.0, uci = c < k1 ? ui[c] : 0.0;
+        const double ar = Ar[r + c * LD], ai = Ai[r + c * LD];
+        sr = fma(ar, ucr, sr);
+        sr = fma(-ai, uci, sr);
+        si = fma(ar, uci, si);
+        si = fma(ai, ucr, si);
+      }
+      pt[hh * 2 * NMAX + r] = sr;
+      pt[hh * 2 * NMAX + NMAX + r] = si;
+    }
+    __syncthreads();
+    double vr = 0.0, vi = 0.0, wr = 0.0, wi = 0.0;
+    if (act) {
+      vr = ur[r];
+      vi = ui[r];
+      wr = (pt[r] + pt[2 * NMAX + r]) / h;
+      wi = (pt[NMAX + r] + pt[3 * NMAX + r]) / h;
+    }
+    const double hk = block_sum<NT>(vr * wr + vi * wi, rd + 4) / (h + h);   // K = u^H p / 2h (real: A is Hermitian)
+    if (act) {
+      qr[r] = wr - hk * vr;
+      qi[r] = wi - hk * vi;
+    }
+    __syncthreads();
+    // A <- A - u q^H - q u^H on the whole block: A(r, c) and conj(A(c, r)) are made of the same products and round alike
+    if (r <= l) {
+      vr = ur[r]; vi = ui[r];
+      wr = qr[r]; wi = qi[r];
+#pragma unroll 4
+      for (int t = 0; t < mid; ++t) {
+        const int c = k0 + t;
+        const double ar = Ar[r + c * LD], ai = Ai[r + c * LD];
+        const double qcr = qr[c], qci = qi[c], ucr = ur[c], uci = ui[c];
+        const double tr = (vr * qcr + vi * qci) + (wr * ucr + wi * uci);
+        const double ti = (vi * qcr - vr * qci) + (wi * ucr - wr * uci);
+        if (c < k1) {
+          Ar[r + c * LD] = ar - tr;
+          Ai[r + c * LD] = ai - ti;
+        }
+      }
+    }
+    __syncthreads();
+  }
+  if (row) d[r] = Ar[r + r * LD];
+  // the phases: (pr, pi)[i] = g_i -> p_i, e[i] = |conj(p_{i-1}) g_i| >= 0
+  if (tid == 0) {
+    e[0] = 0.0; hv[0] = 0.0;
+    double cr = 1.0, ci = 0.0;
+    pr[0] = 1.0; pi[0] = 0.0;
+    for (int i = 1; i < n; ++i) {
+      const double gr = pr[i], gi = pi[i];
+      const double tr = cr * gr + ci * gi, ti = cr * gi - ci * gr;   // t = conj(p_{i-1}) g_i
+      const double at = hypot2(tr, ti);
+      e[i] = at;
+      if (at != 0.0) { cr = tr / at; ci = -(ti / at); }
+      else { cr = 1.0; ci = 0.0; }
+      pr[i] = cr; pi[i] = ci;
+    }
+  }
+
+  // ---- Q D, Q = H_{n-1} ... H_1 accumulated in place, i = 0 .. n-1 (tred2's second loop; column i starts as p_i e_i) -----
+  if (want_vec) {
+    if (r < n)
+      for (int c = hh; c < r; c += 2) { Ar[r + c * LD] = 0.0; Ai[r + c * LD] = 0.0; }   // the strict lower triangle
+    __syncthreads();                                         // (also publishes hv[0] and the phases)
+    for (int i = 0; i < n; ++i) {
+      const int l = i - 1;
+      if (hh == 0 && r <= l) {
+        ur[r] = Ar[r + i * LD]; ui[r] = Ai[r + i * LD];
+        Ar[r + i * LD] = 0.0; Ai[r + i * LD] = 0.0;
+      }
+      if (hh == 0 && r == i) { Ar[i + i * LD] = pr[i]; Ai[i + i * LD] = pi[i]; }
+      const double h = hv[i];
+      if (l < 0 || h == 0.0) continue;                       // uniform; the next step's first barrier publishes column i
+      __syncthreads();
+      const int mid = (l + 2) / 2, k0 = hh ? mid : 0, k1 = hh ? l + 1 : mid;
+      if (r <= l) {                                          // s = u^H Q: lane = column
+        double sr = 0.0, si = 0.0;
+#pragma unroll 4
+        for (int t = 0; t < mid; ++t) {
+          const int c = k0 + t;
+          const double ucr = c < k1 ? ur[c] : 0.0, uci = c < k1 ? ui[c] : 0.0;
+          const double ar = Ar[c + r * LD], ai = Ai[c + r * LD];
+          sr = fma(ucr, ar, sr);
+          sr = fma(uci, ai, sr);
+          si = fma(ucr, ai, si);
+          si = fma(-uci, ar, si);
+        }
+        pt[hh * 2 * NMAX + r] = sr;
+        pt[hh * 2 * NMAX + NMAX + r] = si;
+      }
+      __syncthreads();
+      if (hh == 0 && r <= l) {
+        qr[r] = (pt[r] + pt[2 * NMAX + r]) / h;
+        qi[r] = (pt[NMAX + r] + pt[3 * NMAX + r]) / h;
+      }
+      __syncthreads();
+      if (r <= l) {                                          // Q <- Q - u s / h: lane = row
+        const double vr = ur[r], vi = ui[r];
+#pragma unroll 4
+        for (int t = 0; t < mid; ++t) {
+          const int c = k0 + t;
+          const double ar = Ar[r + c * LD], ai = Ai[r + c * LD], scr = qr[c], sci = qi[c];
+          if (c < k1) {
+            Ar[r + c * LD] = fma(sci, vi, fma(-scr, vr, ar));
+            Ai[r + c * LD] = fma(-sci, vr, fma(-scr, vi, ai));
+          }
+        }
+      }
+      __syncthreads();
+    }
+  }
+  __syncthreads();
+
+  // ---- 3. implicit QL with Wilkinson shift on (d, e) (tql2): the rounds of batch_kernel ------------------------------------
+  // A round: the threads of both halves apply the rotations of the last sweep to their plane of their row of Q, the row
+  // threads test every e[m] against its neighbours (one ballot per wave: bit m of msk = "e[m] is negligible"; bit n-1 is
+  // always set) -> barrier -> thread 0 makes one sweep (ql_sweep) -> barrier.
+  int ql_l = 0, ql_it = 0;
+  if (tid == 0) {
+    for (int i = 1; i < n; ++i) e[i - 1] = e[i];
+    e[n - 1] = 0.0;
+    ctl[0] = 0;                        // no rotations yet
+    ctl[1] = 1;
+    msk[1] = 0;
+  }
+  __syncthreads();
+  for (;;) {
+    {
+      const int m = ctl[0], lo = ctl[1];
+      if (want_vec && r < n && lo < m) {
+        double* P = hh ? Ai : Ar;
+        double hc = P[r + m * LD];
+#pragma unroll 4
+        for (int i = m - 1; i >= lo; --i) {
+          const double zi = P[r + i * LD], c = pt[2 * i], s = pt[2 * i + 1];
+          P[r + (i + 1) * LD] = fma(s, zi, c * hc);
+          hc = fma(c, zi, -(s * hc));
+        }
+        P[r + lo * LD] = hc;
       }
       bool small = false;
       if (row) small = r == n - 1 || fabs(e[r]) <= (0.5 * DBL_EPSILON) * (fabs(d[r]) + fabs(d[r + 1]));

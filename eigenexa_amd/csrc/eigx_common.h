@@ -160,5 +160,7 @@ int set_batch_nmax(int v);
 int set_hbatch_nmax(int v);
 // tuning hook (eigx_tune key 23, gbatch.hip): largest n served by the batch kernel of eigx_gev_batch, 0 .. EIGX_GBATCH_NMAX
 int set_gbatch_nmax(int v);
+// tuning hook (eigx_tune key 24, hgbatch.hip): largest n served by the batch kernel of eigx_hgev_batch, 0 .. EIGX_HGBATCH_NMAX
+int set_hgbatch_nmax(int v);
 
 }  // namespace eigx

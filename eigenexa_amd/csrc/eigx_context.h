@@ -316,7 +316,7 @@ struct SolveFrame {
 inline int host_ld(int nr) { return pad_ld(nr + 2); }
 void* host_to_dev(Context& ctx, const char* name, const void* h, int ld, int nr, int nc, int esz);
 void dev_to_host(void* h, int ld, const void* d, int ldd, int nr, int nc, int esz);
-// batch.hip: the frame of the three batched small solvers (batch.hip, hbatch.hip, gbatch.hip).  BatchArgs is a
+// batch.hip: the frame of the batched small solvers (batch.hip, hbatch.hip, gbatch.hip, hgbatch.hip).  BatchArgs is a
 // call: the entry's arguments, b / ldb / stride_b for a family with has_b only, and esz = bytes per element of a, b and z (8, or
 // 16: interleaved complex, leading dimensions and strides in elements).  A family supplies its cutoff (n above it goes to the
 // full-size solver) and two functions: launch its kernel on `st` for the n-class of g.n (with_n_class; `first` is the launch's
@@ -399,5 +399,9 @@ int herm_solve_dev(Context& ctx, int n, int nvec, double* a, int lda, double* w,
                    char mode);
 int herm_range_dev(Context& ctx, int n, RangeWindow W, double* a, int lda, double* w, double* z, int ldz, int mf, int mb,
                    char mode);
+// hgev.hip (EXTENSION, one GPU): the complex Cholesky-route range solve on device arrays (interleaved complex, every leading
+// dimension >= n); b <- U
+int hgev_range_dev(Context& ctx, int n, const RangeWindow& W, double* a, int lda, double* b, int ldb, double* w, double* z,
+                   int ldz, char mode);
 
 }  // namespace eigx

@@ -1,0 +1,312 @@
+// hgbatch.hip -- eigx_hgev_batch (EXTENSION, not in the reference): many small Hermitian-definite pencils A x = lambda B x
+// (n <= EIGX_HGBATCH_NMAX) in one launch, one workgroup per pencil, both matrices resident in LDS from load to store (DESIGN
+// section 8k).  The Cholesky route of gbatch.hip over complex numbers, on the split planes and the reduction of hbatch.hip:
+//   load the upper triangles of A (mirrored with conjugation) and B (interleaved complex; of the diagonals the real parts
+//   only), scan both for NaN / Inf, scale each by a power of two (B by an even one)
+//   -> B = U^H U, upper and right-looking, one column per step; the diagonal of U is real
+//   -> C = U^-H A U^-1: a forward substitution down every column, then the same along every row; mirrored, scanned, scaled
+//   -> Hermitian tridiagonalisation, phase chain, Q D in place, implicit QL on the real (d, e): herm_tridiag_ql of
+//      batch_common.h, the code eigx_h_batch runs
+//   -> sort ascending, Z = U^-1 Y by a backward substitution down every column, unscale, store w, z and U (into b).
+// No workgroup talks to another: no grid-wide barrier, no spin-wait, no atomics on the data.  Every sum is taken in an order
+// that depends on n alone, so a pencil's result does not depend on its position in the batch or on the batch size.
+// Pencils larger than the cutoff (eigx_tune key 24) go through hgev_range_dev (hgev.hip) one by one.
+// Here: the kernel, the cutoff and the two functions the frame of the batch families asks for (batch_frame_dev / batch_frame_host,
+// batch.hip: checks, launch and failure word, the loop above the cutoff, host staging of a, b, z, w).
+#include "eigx_context.h"
+#include "batch_common.h"
+#include "../../include/eigenexa_amd.h"
+#include <cfloat>
+
+// (batch_common.h switches contraction off: every a*b + c that is wanted fused is written as fma())
+#pragma clang fp contract(off)
+
+namespace eigx {
+namespace {
+
+// x(0 .. n-1), entry k at (xr, xi)[k * inc], <- the solution of a lower triangular system with the columns of U as rows:
+// x_k = (x_k - sum_{j < k} op(U(j, k)) x_j) / U(k, k), k ascending, op = conj (CONJ: U^-H x down a column) or the identity
+// (x U^-1 along a row).  The real and the imaginary sum each run in four interleaved chains from +0 (two products per term,
+// two terms in flight), in an order that depends on k alone: with U = I every chain stays +0 and x_k comes back as it was, the
+// sign of a zero included.  The diagonal of U is real: one division per plane.
+template <int LD, bool CONJ>
+__device__ inline void zsolve_ut(int n, const double* Ur, const double* Ui, double* xr, double* xi, int inc) {
+  for (int k = 0; k < n; ++k) {
+    const double* ukr = Ur + k * LD;
+    const double* uki = Ui + k * LD;
+    double r0 = 0.0, r1 = 0.0, r2 = 0.0, r3 = 0.0, i0 = 0.0, i1 = 0.0, i2 = 0.0, i3 = 0.0;
+    int j = 0;
+    for (; j + 1 < k; j += 2) {
+      const double ar = ukr[j], at = CONJ ? -uki[j] : uki[j], br = ukr[j + 1], bt = CONJ ? -uki[j + 1] : uki[j + 1];
+      const double pr = xr[j * inc], pi = xi[j * inc], qr = xr[(j + 1) * inc], qi = xi[(j + 1) * inc];
+      r0 = fma(ar, pr, r0);
+      r1 = fma(-at, pi, r1);
+      i0 = fma(ar, pi, i0);
+      i1 = fma(at, pr, i1);
+      r2 = fma(br, qr, r2);
+      r3 = fma(-bt, qi, r3);
+      i2 = fma(br, qi, i2);
+      i3 = fma(bt, qr, i3);
+    }
+    if (j < k) {
+      const double ar = ukr[j], at = CONJ ? -uki[j] : uki[j];
+      const double pr = xr[j * inc], pi = xi[j * inc];
+      r0 = fma(ar, pr, r0);
+      r1 = fma(-at, pi, r1);
+      i0 = fma(ar, pi, i0);
+      i1 = fma(at, pr, i1);
+    }
+    const double dk = ukr[k];
+    xr[k * inc] = (xr[k * inc] - ((r0 + r1) + (r2 + r3))) / dk;
+    xi[k * inc] = (xi[k * inc] - ((i0 + i1) + (i2 + i3))) / dk;
+  }
+}
+// x(0 .. n-1) <- U^-1 x: x_k = (x_k - sum_{j > k} U(k, j) x_j) / U(k, k), k descending, the sums as above
+template <int LD>
+__device__ inline void zsolve_u(int n, const double* Ur, const double* Ui, double* xr, double* xi) {
+  for (int k = n - 1; k >= 0; --k) {
+    const double* ukr = Ur + k;
+    const double* uki = Ui + k;
+    double r0 = 0.0, r1 = 0.0, r2 = 0.0, r3 = 0.0, i0 = 0.0, i1 = 0.0, i2 = 0.0, i3 = 0.0;
+    int j = k + 1;
+    for (; j + 1 < n; j += 2) {
+      const double ar = ukr[j * LD], at = uki[j * LD], br = ukr[(j + 1) * LD], bt = uki[(j + 1) * LD];
+      const double pr = xr[j], pi = xi[j], qr = xr[j + 1], qi = xi[j + 1];
+      r0 = fma(ar, pr, r0);
+      r1 = fma(-at, pi, r1);
+      i0 = fma(ar, pi, i0);
+      i1 = fma(at, pr, i1);
+      r2 = fma(br, qr, r2);
+      r3 = fma(-bt, qi, r3);
+      i2 = fma(br, qi, i2);
+      i3 = fma(bt, qr, i3);
+    }
+    if (j < n) {
+      const double ar = ukr[j * LD], at = uki[j * LD];
+      const double pr = xr[j], pi = xi[j];
+      r0 = fma(ar, pr, r0);
+      r1 = fma(-at, pi, r1);
+      i0 = fma(ar, pi, i0);
+      i1 = fma(at, pr, i1);
+    }
+    const double dk = ukr[k * LD];
+    xr[k] = (xr[k] - ((r0 + r1) + (r2 + r3))) / dk;
+    xi[k] = (xi[k] - ((i0 + i1) + (i2 + i3))) / dk;
+  }
+}
+
+// One workgroup of 2 NMAX threads per pencil (NMAX = 32, 64: the n-classes): thread (r, hh) = (row, half) as in every batch
+// kernel.  The split planes Sr, Si(LD, NMAX) hold A, then C, then Q, then Z; Ur, Ui(LD, NMAX) hold B, then its factor (upper
+// triangle; the strict lower triangle is never read, the imaginary part of the diagonal never computed); column-major with
+// LD = NMAX + 1, the access patterns of hbatch_kernel: lane = row at a fixed column is stride 1, lane = column is a stride of LD
+// doubles, an entry of U that all lanes read is a broadcast.
+template <int NMAX>
+__global__ __launch_bounds__(2 * NMAX) void hgbatch_kernel(int n, int batch, const double* __restrict__ a, int lda, int64_t stride_a,
+                                                           double* __restrict__ b, int ldb, int64_t stride_b, double* __restrict__ w,
+                                                           int ldw, double* __restrict__ z, int ldz, int64_t stride_z, int want_vec,
+                                                           int* __restrict__ info, unsigned long long* __restrict__ first) {
+  constexpr int NT = 2 * NMAX, LD = NMAX + 1;
+  __shared__ double Sr[LD * NMAX], Si[LD * NMAX];
+  __shared__ double Ur[LD * NMAX], Ui[LD * NMAX];
+  __shared__ double d[NMAX], e[NMAX], hv[NMAX];
+  __shared__ double pr[NMAX], pi[NMAX];  // the off-diagonal entries g of the Hermitian tridiagonal matrix, then the phases
+  __shared__ double ur[NMAX], ui[NMAX], qr[NMAX], qi[NMAX];
+  __shared__ double pt[4 * NMAX];        // the two halves' partial sums (re, im); (c_i, s_i) of a QL iteration
+  __shared__ double red[4][4];           // wave partials of block_sum / block_max
+  __shared__ int perm[NMAX];
+  __shared__ int ctl[4];                 // QL: top index m, lowest rotation, state
+  __shared__ unsigned long long msk[2];  // QL: bit m = e[m] is negligible
+  const int tid = threadIdx.x, r = tid % NMAX, hh = tid / NMAX;
+  const bool row = hh == 0 && r < n;     // the thread that owns row r (or column r) where one thread per row is wanted
+
+  for (int k = blockIdx.x; k < batch; k += gridDim.x) {
+    // ---- 1. load both upper triangles, mirror A with conjugation, scan, scale ----------------------------------------------------
+    const double* ak = a + 2 * (size_t)k * stride_a;
+    double* bk = b + 2 * (size_t)k * stride_b;
+    double mxa = 0.0, mxb = 0.0, bad = 0.0;
+    for (int j = hh; j < n; j += 2) {
+      if (r <= j) {
+        const size_t at = 2 * (r + (size_t)j * lda), bt = 2 * (r + (size_t)j * ldb);
+        const double xr = ak[at], yr = bk[bt];
+        const double xi = r < j ? ak[at + 1] : 0.0, yi = r < j ? bk[bt + 1] : 0.0;   // Im of the diagonals is not read
+        if (!(fabs(xr) <= DBL_MAX) || !(fabs(xi) <= DBL_MAX) || !(fabs(yr) <= DBL_MAX) || !(fabs(yi) <= DBL_MAX)) bad = 1.0;
+        else {
+          mxa = fmax(mxa, fmax(fabs(xr), fabs(xi)));
+          mxb = fmax(mxb, fmax(fabs(yr), fabs(yi)));
+        }
+        Sr[r + j * LD] = xr;
+        Si[r + j * LD] = xi;
+        Sr[j + r * LD] = xr;
+        Si[j + r * LD] = -xi;
+        Ur[r + j * LD] = yr;
+        Ui[r + j * LD] = yi;
+      }
+    }
+    bad = block_max<NT>(bad, red[0]);
+    mxa = block_max<NT>(mxa, red[1]);
+    mxb = block_max<NT>(mxb, red[2]);    // (the barriers also publish the loaded entries)
+    if (bad != 0.0) {                    // uniform; b is as it was passed
+      fail_matrix(k, EIGX_ERR_NONFINITE, row, r, w, ldw, info, first);
+      continue;
+    }
+    // A by 2^-exa, B by 2^-exb with exb even: the factor of the caller's B is 2^(exb / 2) times the computed one
+    const int exa = scale_exponent(mxa, false), exb = scale_exponent(mxb, true);
+    if (exa != 0 && r < n) {
+      const double sigma = ldexp(1.0, -exa);
+      for (int j = hh; j < n; j += 2) { Sr[r + j * LD] *= sigma; Si[r + j * LD] *= sigma; }
+    }
+    if (exb != 0 && r < n) {
+      const double sigma = ldexp(1.0, -exb);
+      for (int j = hh; j < n; j += 2)
+        if (r <= j) { Ur[r + j * LD] *= sigma; Ui[r + j * LD] *= sigma; }
+    }
+    if (row) perm[r] = r;
+    __syncthreads();
+
+    // ---- 2. B = U^H U, right-looking: two barriers per column ----------------------------------------------------------------
+    bool spd = true;
+    for (int c = 0; c < n; ++c) {
+      const double p = Ur[c + c * LD];
+      if (!(p > 0.0) || !(p <= DBL_MAX)) {   // the rule of eigx_zchol_dev (uniform)
+        spd = false;
+        break;
+      }
+      const double s = sqrt(p);
+      if (row && r > c) {
+        Ur[c + r * LD] = Ur[c + r * LD] / s;
+        Ui[c + r * LD] = Ui[c + r * LD] / s;
+      }
+      __syncthreads();
+      if (tid == 0) Ur[c + c * LD] = s;      // (every thread has read the pivot; nothing below reads the diagonal)
+      if (r > c && r < n) {                  // the trailing block, lane = row: U(r, j) -= conj(U(c, r)) U(c, j), j >= r
+        const double vr = Ur[c + r * LD], vi = Ui[c + r * LD];
+        for (int j = c + 1 + hh; j < n; j += 2) {
+          const double ujr = Ur[c + j * LD], uji = Ui[c + j * LD], xr = Ur[r + j * LD], xi = Ui[r + j * LD];
+          if (r <= j) Ur[r + j * LD] = fma(-vi, uji, fma(-vr, ujr, xr));
+          if (r < j) Ui[r + j * LD] = fma(vi, ujr, fma(-vr, uji, xi));   // (the diagonal stays real: its Im is left alone)
+        }
+      }
+      __syncthreads();
+    }
+    if (!spd) {
+      fail_matrix(k, EIGX_ERR_NOT_SPD, row, r, w, ldw, info, first);
+      continue;
+    }
+
+    // ---- 3. C = U^-H A U^-1: X = U^-H A down the columns (lane = column), C = X U^-1 along the rows (lane = row) ----------------
+    if (row) zsolve_ut<LD, true>(n, Ur, Ui, Sr + r * LD, Si + r * LD, 1);
+    __syncthreads();
+    if (row) zsolve_ut<LD, false>(n, Ur, Ui, Sr + r, Si + r, LD);
+    __syncthreads();
+    // the upper triangle over the lower one with conjugation (the reduction wants C(r, c) and conj(C(c, r)) to be one number),
+    // a real diagonal, scan, scale
+    double mxc = 0.0;
+    if (r < n) {
+      for (int j = hh; j < n; j += 2) {
+        if (r <= j) {
+          const double xr = Sr[r + j * LD], xi = r < j ? Si[r + j * LD] : 0.0;
+          if (!(fabs(xr) <= DBL_MAX) || !(fabs(xi) <= DBL_MAX)) bad = 1.0;
+          else mxc = fmax(mxc, fmax(fabs(xr), fabs(xi)));
+          Si[r + j * LD] = xi;
+          Sr[j + r * LD] = xr;
+          Si[j + r * LD] = -xi;
+        }
+      }
+    }
+    bad = block_max<NT>(bad, red[0]);
+    mxc = block_max<NT>(mxc, red[1]);
+    if (bad != 0.0) {                    // uniform: B was too close to singular for C to be formed
+      fail_matrix(k, EIGX_ERR_NOT_SPD, row, r, w, ldw, info, first);
+      continue;
+    }
+    const int exc = scale_exponent(mxc, false);
+    if (exc != 0 && r < n) {
+      const double sigma = ldexp(1.0, -exc);
+      for (int j = hh; j < n; j += 2) { Sr[r + j * LD] *= sigma; Si[r + j * LD] *= sigma; }
+    }
+    __syncthreads();
+
+    // ---- 4. tridiagonalisation, phase chain, Q D in place, implicit QL (batch_common.h) -------------------------------------
+    if (herm_tridiag_ql<NMAX>(n, want_vec, Sr, Si, d, e, hv, pr, pi, ur, ui, qr, qi, pt, red, ctl, msk) == ST_FAIL) {   // uniform
+      fail_matrix(k, EIGX_ERR_INTERNAL, row, r, w, ldw, info, first);
+      continue;
+    }
+    if (row) {
+      const int rank = ascending_rank(n, d, r);
+      perm[rank] = r;
+      w[(size_t)k * ldw + rank] = ldexp(d[r], exa - exb + exc);   // C = 2^(exb - exa - exc) times the matrix that was solved
+    }
+    if (tid == 0 && info) info[k] = 0;
+
+    // ---- 5. Z = U^-1 Y down the columns (lane = column), unscale, store ---------------------------------------------------------
+    if (want_vec && row) zsolve_u<LD>(n, Ur, Ui, Sr + r * LD, Si + r * LD);
+    __syncthreads();
+    if (r < n) {
+      if (want_vec) {
+        double* zk = z + 2 * (size_t)k * stride_z;
+        for (int j = hh; j < n; j += 2) {
+          const int c = perm[j];
+          const size_t at = 2 * (r + (size_t)j * ldz);
+          zk[at] = ldexp(Sr[r + c * LD], -(exb / 2));
+          zk[at + 1] = ldexp(Si[r + c * LD], -(exb / 2));
+        }
+      }
+      for (int j = hh; j < n; j += 2) {
+        if (r <= j) {
+          const size_t at = 2 * (r + (size_t)j * ldb);
+          bk[at] = ldexp(Ur[r + j * LD], exb / 2);
+          bk[at + 1] = r < j ? ldexp(Ui[r + j * LD], exb / 2) : 0.0;
+        }
+      }
+    }
+    __syncthreads();
+  }
+}
+
+int g_hgbatch_nmax = EIGX_HGBATCH_NMAX;   // key 24: largest n served by the batch kernel
+
+// the n-classes 32 and 64 (with_n_class serves the families whose largest class is 96 or 128)
+void hgbatch_launch(const BatchArgs& g, hipStream_t st, unsigned long long* first) {
+  const auto go = [&](auto nmax) {
+    constexpr int NMAX = decltype(nmax)::value;
+    hipLaunchKernelGGL(hgbatch_kernel<NMAX>, dim3((unsigned)g.batch), dim3(2 * NMAX), 0, st, g.n, g.batch, (const double*)g.a, g.lda,
+                       g.stride_a, g.b, g.ldb, g.stride_b, g.w, g.ldw, g.z, g.ldz, g.stride_z, (int)(g.mode == 'A'), g.info, first);
+  };
+  if (g.n <= 32) go(std::integral_constant<int, 32>());
+  else go(std::integral_constant<int, EIGX_HGBATCH_NMAX>());
+}
+// above the cutoff: hgev_range_dev with il = 1, iu = n; it takes every leading dimension >= n, so nothing is staged
+int hgbatch_solve_one(Context& ctx, const BatchArgs& g, int k) {
+  return hgev_range_dev(ctx, g.n, RangeWindow::index(1, g.n), g.block(g.a, g.stride_a, k), g.lda, g.block(g.b, g.stride_b, k), g.ldb,
+                        g.w + (size_t)k * g.ldw, g.mode == 'A' ? g.block(g.z, g.stride_z, k) : nullptr, g.ldz, g.mode);
+}
+
+}  // namespace
+
+int set_hgbatch_nmax(int v) {
+  if (v < 0 || v > EIGX_HGBATCH_NMAX) return -1;
+  const int old = g_hgbatch_nmax;
+  g_hgbatch_nmax = v;
+  return old;
+}
+
+}  // namespace eigx
+
+using namespace eigx;
+
+extern "C" {
+
+// EXTENSION: `batch` Hermitian-definite pencils of one size (one GPU; a, b, z interleaved complex; lda, ldb, ldz and the strides
+// in complex elements); see batch_frame_host / batch_frame_dev (batch.hip)
+int eigx_hgev_batch(int n, int batch, double* a, int lda, int64_t stride_a, double* b, int ldb, int64_t stride_b, double* w, int ldw,
+                    double* z, int ldz, int64_t stride_z, char mode, int* info) {
+  const BatchArgs g{n, batch, a, lda, stride_a, b, ldb, stride_b, w, ldw, z, ldz, stride_z, mode, info, 16, true};
+  return eigx_guard(g_ctx, [&] { return batch_frame_host(g_ctx, g, g_hgbatch_nmax, hgbatch_launch, hgbatch_solve_one); });
+}
+int eigx_hgev_batch_dev(int n, int batch, double* a_dev, int lda, int64_t stride_a, double* b_dev, int ldb, int64_t stride_b,
+                        double* w_dev, int ldw, double* z_dev, int ldz, int64_t stride_z, char mode, int* info_dev) {
+  const BatchArgs g{n, batch, a_dev, lda, stride_a, b_dev, ldb, stride_b, w_dev, ldw, z_dev, ldz, stride_z, mode, info_dev, 16, true};
+  return eigx_guard(g_ctx, [&] { return batch_frame_dev(g_ctx, g, g_hgbatch_nmax, hgbatch_launch, hgbatch_solve_one); });
+}
+
+}  // extern "C"

@@ -37,6 +37,7 @@ module eigen_libs_mod
   public :: eigen_s_batch   ! EXTENSION: many small symmetric matrices in one call (one GPU)
   public :: eigen_h_batch   ! EXTENSION: many small complex Hermitian matrices in one call (one GPU)
   public :: eigen_gev_batch   ! EXTENSION: many small symmetric-definite pencils in one call (one GPU)
+  public :: eigen_hgev_batch   ! EXTENSION: many small Hermitian-definite pencils in one call (one GPU)
 
   interface
     integer(c_int) function eigx_init(device) bind(C, name="eigx_init")
@@ -165,6 +166,19 @@ module eigen_libs_mod
       integer(c_int64_t), value :: stride_a, stride_b, stride_z
       real(c_double), intent(inout) :: a(*), b(*)
       real(c_double), intent(inout) :: w(*), z(*)
+      character(kind=c_char), value :: mode
+      integer(c_int), intent(out), optional :: info(*)
+    end function
+    ! EXTENSION (not in the reference): batch Hermitian-definite pencils of one size, one GPU; leading dimensions and strides
+    ! in complex elements; info may be absent (NULL)
+    integer(c_int) function eigx_hgev_batch(n, batch, a, lda, stride_a, b, ldb, stride_b, w, ldw, z, ldz, stride_z, mode, info) &
+        bind(C, name="eigx_hgev_batch")
+      import :: c_int, c_int64_t, c_double, c_double_complex, c_char
+      integer(c_int), value :: n, batch, lda, ldb, ldw, ldz
+      integer(c_int64_t), value :: stride_a, stride_b, stride_z
+      complex(c_double_complex), intent(inout) :: a(*), b(*)
+      real(c_double), intent(inout) :: w(*)
+      complex(c_double_complex), intent(inout) :: z(*)
       character(kind=c_char), value :: mode
       integer(c_int), intent(out), optional :: info(*)
     end function
@@ -763,6 +777,27 @@ contains
     rc = eigx_gev_batch(n, batch, a, lda, int(lda, c_int64_t) * size(a, 2), b, ldb, int(ldb, c_int64_t) * size(b, 2), &
                         w, size(w, 1), z, ldz, int(ldz, c_int64_t) * size(z, 2), md, info)
   end subroutine eigen_gev_batch
+
+  !> eigen_hgev_batch(n, batch, a, lda, b, ldb, w, z, ldz, mode, info) -- EXTENSION, not in the reference: the eigenpairs of batch
+  !> Hermitian-definite pencils a(:, :, k) x = lambda b(:, :, k) x of one size n on one GPU, in one kernel launch for n <= 64
+  !> (one workgroup per pencil, both matrices in LDS).  Upper triangles significant (of the diagonals the real parts), a
+  !> destroyed, b(:, :, k) returns U with B = U^H U and a real positive diagonal in its upper triangle; w(1:n, k) real and
+  !> ascending, z(1:n, 1:n, k) with z^H B z = I; modes 'A' and 'N' (z not written).  info(k) = 0, or the status of pencil k
+  !> (-5: NaN / Inf, -7: B not positive definite; w(:, k) = NaN); the other pencils are solved all the same.
+  subroutine eigen_hgev_batch(n, batch, a, lda, b, ldb, w, z, ldz, mode, info)
+    integer, intent(in) :: n, batch, lda, ldb, ldz
+    complex(8), intent(inout), contiguous :: a(:, :, :), b(:, :, :)
+    real(8), intent(inout), contiguous :: w(:, :)
+    complex(8), intent(inout), contiguous :: z(:, :, :)
+    character(*), intent(in), optional :: mode
+    integer, intent(out), optional :: info(*)
+    integer :: rc
+    character(kind=c_char) :: md
+    md = 'A'
+    if (present(mode)) md = mode(1:1)
+    rc = eigx_hgev_batch(n, batch, a, lda, int(lda, c_int64_t) * size(a, 2), b, ldb, int(ldb, c_int64_t) * size(b, 2), &
+                         w, size(w, 1), z, ldz, int(ldz, c_int64_t) * size(z, 2), md, info)
+  end subroutine eigen_hgev_batch
 
   !> eigen_sx_range_v(n, vl, vu, mmax, m, il, a, lda, w, z, ldz, m_forward, m_backward, mode) -- EXTENSION, not in the
   !> reference (LAPACK's range = 'V'): the eigenpairs with vl <= lambda < vu by the pentadiagonal route on one GPU.  On

@@ -30,7 +30,8 @@
  * extension: the eigenpairs with vl <= lambda < vu of the real solvers, LAPACK's range = 'V', one GPU), eigx_h_range[_v] and
  * eigx_hgev_range_v[_dev] (an extension: both kinds of window for the complex Hermitian solvers, one GPU), eigx_s_batch[_dev]
  * and eigx_h_batch[_dev] (an extension: many small symmetric / complex Hermitian matrices in one call, one GPU),
- * eigx_gev_batch[_dev] (an extension: many small symmetric-definite pencils in one call, one GPU) and the stage
+ * eigx_gev_batch[_dev] and eigx_hgev_batch[_dev] (an extension: many small symmetric-definite / Hermitian-definite pencils in
+ * one call, one GPU) and the stage
  * entry eigx_band_count_dev (Sturm counts of a band matrix at caller-given points).
  */
 #ifndef EIGENEXA_AMD_H
@@ -316,6 +317,8 @@ int eigx_h_batch_dev(int n, int batch, double* a_dev, int lda, int64_t stride_a,
 /* Batched small generalised eigensolves eigx_gev_batch[_dev] -- EXTENSION, not in the reference: declared and documented in
  * eigenexa_amd_gbatch.h beside this file, which comes in here, so this header alone still gives a caller the whole interface. */
 #include "eigenexa_amd_gbatch.h"
+/* The same over complex numbers, eigx_hgev_batch[_dev] -- EXTENSION: declared and documented in eigenexa_amd_hgbatch.h. */
+#include "eigenexa_amd_hgbatch.h"
 
 /* ScaLAPACK interop without a redistribution step.  The reference asks block-cyclic callers to
  * convert with pdgemr2d into its cyclic layout first (manual 3.4; benchmark/ev_test.f:68-84 does the reverse for the
@@ -576,7 +579,9 @@ int eigx_profile_read_kinds(double* out, int nkinds);
  * small n by lowering the key.  key 22 = the same for eigx_h_batch (0 .. EIGX_HBATCH_NMAX, default EIGX_HBATCH_NMAX by the
  * measured table of DESIGN section 8i; other values are refused): larger matrices go through eigx_h_dev one by one.
  * key 23 = the same for eigx_gev_batch (0 .. EIGX_GBATCH_NMAX, default EIGX_GBATCH_NMAX by the measured table of DESIGN section
- * 8j; other values are refused): larger pencils go through eigx_gev_range_dev one by one.  Returns
+ * 8j; other values are refused): larger pencils go through eigx_gev_range_dev one by one.  key 24 = the same for
+ * eigx_hgev_batch (0 .. EIGX_HGBATCH_NMAX, default EIGX_HGBATCH_NMAX by the measured table of DESIGN section 8k; other values are
+ * refused): larger pencils go through eigx_hgev_range_dev one by one.  Returns
  * the previous value, or
  * -1 for an unknown key or a refused value.
  * Not part of the reference's interface. */
