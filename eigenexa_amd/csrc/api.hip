@@ -373,6 +373,7 @@ int eigx_tune(int key, int value) {
   if (key == 22) return set_hbatch_nmax(value);   // the same for eigx_h_batch (hbatch.hip)
   if (key == 23) return set_gbatch_nmax(value);   // the same for eigx_gev_batch (gbatch.hip)
   if (key == 24) return set_hgbatch_nmax(value);  // the same for eigx_hgev_batch (hgbatch.hip)
+  if (key == 25) return set_gemm_latec_kmax(value);  // largest K of the one-GPU trailing update's late-C path, 0 = never (gemm_f64.hip)
   return -1;
 }
 

@@ -143,6 +143,7 @@ inline void stage_trace(int rank, const char* what, long detail = -1) {
 int set_gemm_variant(int v);
 // tuning hook (eigx_tune key 6): 1 = the trailing update streams its C tiles with non-temporal loads / stores
 int set_gemm_cstream(int v);
+int set_gemm_latec_kmax(int v);
 // tuning hook (eigx_tune key 1): target number of concurrent Sturm sweeps of the bisection
 int set_bisect_threads(int v);
 // tuning hook (eigx_tune key 2): super-block factor of the back-transformation (0 = automatic, 1, 2, 4)

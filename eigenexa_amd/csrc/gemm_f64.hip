@@ -383,11 +383,18 @@ __device__ __forceinline__ void g2_cols(const int* __restrict__ kmap, int k0, in
   }
 }
 
-template <bool A_KC, bool B_KC, bool GATHER>
+// LATE_C (the one-GPU trailing update at short K, 'N','T' only): the accumulators start from zero, the first half of
+// the C tile is requested once the last slab has been issued -- S-1 slabs before the end of the K loop, where the
+// early-C form has only zero-page slabs left to issue -- and the second half as the first is stored; the epilogue adds
+// the tile as alpha*acc + beta*C.  The early-C form scales the tile into the accumulators, so it waits for all of it
+// before it issues its first slab: with K = 128 that costs about as much as the 16 slabs.
+template <bool A_KC, bool B_KC, bool GATHER, bool LATE_C = false>
 __global__ __launch_bounds__(256, 2) void gemm2_kernel(GemmArgs g) {
+  static_assert(!LATE_C || (!A_KC && !B_KC && !GATHER), "late C: plain 'N','T' operands only");
   extern __shared__ __attribute__((aligned(16))) double smem[];
   constexpr int S = 4;                    // ring stages
   constexpr int GI = 4;                   // LDS-DMA instructions per wave per slab (2 per operand)
+  constexpr int CI = 8;                   // LATE_C: 16-byte loads per wave per C chunk (one accumulator column group)
   g.A += (long)blockIdx.y * g.sA + (long)blockIdx.z * g.sA2;
   g.B += (long)blockIdx.y * g.sB + (long)blockIdx.z * g.sB2;
   g.C += (long)blockIdx.y * g.sC + (long)blockIdx.z * g.sC2;
@@ -475,7 +482,7 @@ __global__ __launch_bounds__(256, 2) void gemm2_kernel(GemmArgs g) {
   auto ncol = [&](int j, int rho) { return B_KC ? j * 16 + rho : (j >> 1) * 32 + 2 * rho + (j & 1); };
 
   d4_t acc[4][4];
-  const bool use_c = (g.beta != 0.0) && (g.alpha != 0.0);
+  const bool use_c = !LATE_C && (g.beta != 0.0) && (g.alpha != 0.0);
   if (use_c) {
     const double cscale = g.beta / g.alpha;
 #pragma unroll
@@ -530,7 +537,10 @@ __global__ __launch_bounds__(256, 2) void gemm2_kernel(GemmArgs g) {
   g2_cols<GATHER && !A_KC>(g.kmapA, (S - 1) * G2_BK, g.K, wave, ca0, ca1);
   g2_cols<GATHER && !B_KC>(g.kmapB, (S - 1) * G2_BK, g.K, wave, cb0, cb1);
 
-  for (int kt = 0; kt < nk; ++kt) {
+  // LATE_C: the ring loop stops S-1 slabs early (no zero-page slab is issued past the last real one) and the tail below
+  // multiplies them; K of fewer than S-1 slabs is padded with the prologue's zero-page slabs, which add nothing
+  const int nk_ring = LATE_C ? ((nk > S - 1 ? nk : S - 1) - (S - 1)) : nk;
+  for (int kt = 0; kt < nk_ring; ++kt) {
     // my DMAs of slab kt have landed (the 2 younger slabs may still be in flight); after the barrier
     // everybody's have, and everybody has finished reading slab kt-1, whose stage is refilled next
     if (GATHER)  // also: the map entries fetched during the previous iteration are in their SGPRs now
@@ -585,6 +595,106 @@ __global__ __launch_bounds__(256, 2) void gemm2_kernel(GemmArgs g) {
           acc[i][j] = __builtin_amdgcn_mfma_f64_16x16x4f64(fb[j], fa[i], acc[i][j], 0, 0, 0);
     }
   }
+
+  if constexpr (LATE_C) {
+    // One chunk of the C tile = accumulator column group j: CI = 8 16-byte loads per lane, each issued whatever the
+    // lane's predicate (a lane outside the tile's valid part, or on the single last row of an odd M, reads the zero
+    // page instead and its value is not used), so that the number of vector-memory instructions in flight is the same
+    // in every wave: the counted waits of the tail depend on it.  (More instructions in flight than counted would only
+    // make those waits stricter; fewer would let a slab be read before it has landed.)
+    double2 cv[4][4][2];
+    const double* const zero16 = g_zero_page + 2 * lane;
+    typedef const __attribute__((address_space(1))) d2s_t* c16_t;   // a flat load would also count in lgkmcnt
+    auto c_load = [&](int j) {
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int n = n0 + wn * 64 + ncol(j, fk + 4 * r);
+        const double* col = g.C + (size_t)n * g.ldc;
+#pragma unroll
+        for (int p = 0; p < 2; ++p) {
+          const int m = m0 + wm * 64 + p * 32 + 2 * fm;
+          c16_t src = (c16_t)((n < g.N && m + 1 < g.M) ? col + m : zero16);
+          // the empty asm pins the selected address in a register: otherwise hipcc moves the address arithmetic into
+          // the select's arms and branches around two loads, and a wave with lanes on both sides issues both
+          asm volatile("" : "+v"(src));
+          const d2s_t t = *src;
+          cv[j][r][p] = make_double2(t.x, t.y);
+        }
+      }
+    };
+    // multiply slab kt out of its ring stage (the ring loop's body for two m/n-contiguous operands)
+    auto mul_slab = [&](int kt) {
+      const double* as = smem + (kt % S) * G2_STAGE;
+      const double* bs = as + G2_BK * 128;
+#pragma unroll
+      for (int ks = 0; ks < G2_BK / 4; ++ks) {
+        const int k = ks * 4 + fk;
+        double fa[4], fb[4];
+#pragma unroll
+        for (int p = 0; p < 2; ++p) {
+          const double2 va = *reinterpret_cast<const double2*>(as + k * 128 + wm * 64 + p * 32 + 2 * fm);
+          const double2 vb = *reinterpret_cast<const double2*>(bs + k * 128 + wn * 64 + p * 32 + 2 * fm);
+          fa[2 * p] = va.x; fa[2 * p + 1] = va.y;
+          fb[2 * p] = vb.x; fb[2 * p + 1] = vb.y;
+        }
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+#pragma unroll
+          for (int i = 0; i < 4; ++i)
+            acc[i][j] = __builtin_amdgcn_mfma_f64_16x16x4f64(fb[j], fa[i], acc[i][j], 0, 0, 0);
+      }
+    };
+    // The tail: slabs kt0 .. kt0+S-2 are the last ones and all of them have been issued.  Plain loads and LDS-DMAs
+    // share the in-order vmcnt queue; "outstanding" lists what this wave may still have in flight at each wait, oldest
+    // first, and the count leaves everything after the slab that is multiplied next.
+    const int kt0 = nk_ring;
+    // outstanding: slab kt0 (GI), slab kt0+1 (GI), slab kt0+2 (GI)
+    asm volatile("s_waitcnt vmcnt(%0)\n\ts_barrier" ::"n"((S - 2) * GI) : "memory");
+    c_load(0); c_load(1);
+    mul_slab(kt0);
+    // outstanding: slab kt0+1 (GI), slab kt0+2 (GI), C chunks 0, 1 (2 CI)
+    asm volatile("s_waitcnt vmcnt(%0)\n\ts_barrier" ::"n"((S - 3) * GI + 2 * CI) : "memory");
+    mul_slab(kt0 + 1);
+    // outstanding: slab kt0+2 (GI), C chunks 0, 1 (2 CI); no DMA is in flight after this wait
+    asm volatile("s_waitcnt vmcnt(%0)\n\ts_barrier" ::"n"(2 * CI) : "memory");
+    mul_slab(kt0 + 2);
+
+    // epilogue: chunk by chunk (the compiler counts these waits: only its own loads and stores are in flight).  A chunk
+    // is combined in place, acc = alpha*acc + beta*C, which frees its C registers: chunk j+2 is requested into chunk j's
+    // before chunk j is stored (the registers hold two chunks beside the accumulators, not three: 256 VGPRs).  A lane
+    // that read the zero page holds alpha*acc.
+    const double alpha = g.alpha, beta = g.beta;
+    auto combine = [&](int j) {
+#pragma unroll
+      for (int r = 0; r < 4; ++r)
+#pragma unroll
+        for (int p = 0; p < 2; ++p) {
+          acc[2 * p][j][r] = alpha * acc[2 * p][j][r] + beta * cv[j][r][p].x;
+          acc[2 * p + 1][j][r] = alpha * acc[2 * p + 1][j][r] + beta * cv[j][r][p].y;
+        }
+    };
+    auto store = [&](int j) {
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int n = n0 + wn * 64 + ncol(j, fk + 4 * r);
+        if (n >= g.N) continue;
+        double* cp = g.C + (size_t)n * g.ldc;
+#pragma unroll
+        for (int p = 0; p < 2; ++p) {
+          const int m = m0 + wm * 64 + p * 32 + 2 * fm;
+          if (m + 1 < g.M) *reinterpret_cast<double2*>(cp + m) = make_double2(acc[2 * p][j][r], acc[2 * p + 1][j][r]);
+          else if (m < g.M) cp[m] = acc[2 * p][j][r] + beta * cp[m];   // the single last row of an odd M
+        }
+      }
+    };
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      combine(j);
+      if (j + 2 < 4) c_load(j + 2);
+      store(j);
+    }
+    return;
+  }
   // drain the (zero-page) DMAs still in flight before the LDS allocation is released
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 
@@ -619,6 +729,7 @@ __global__ __launch_bounds__(256, 2) void gemm2_kernel(GemmArgs g) {
 
 int g_gemm_cstream = 0;   // tuning hook (eigx_tune key 6): stream the C tiles of the trailing update past L2
 int g_gemm_variant = 2;   // 2 = gemm2 where supported and worthwhile, 3 = wherever supported (tests), 1 = never
+int g_gemm_latec_kmax = 256;   // tuning hook (eigx_tune key 25): largest K whose one-GPU trailing update takes the late-C path
 
 // gemm2 needs 16-byte aligned operand columns (even leading dimensions, aligned bases, even batch strides);
 // KC operands additionally need an even K (a 16-byte chunk must not straddle K)
@@ -639,6 +750,10 @@ static bool gemm2_ok(const GemmArgs& g, bool a_kc, bool b_kc, int batch, int bat
 
 int set_gemm_variant(int v) { const int old = g_gemm_variant; g_gemm_variant = v; return old; }
 int set_gemm_cstream(int v) { const int old = g_gemm_cstream; g_gemm_cstream = v; return old; }
+int set_gemm_latec_kmax(int v) {
+  if (v < 0 || v >= 512) return -1;   // from K = 512 on the MFMA phase is four times the C phase: early C stays
+  const int old = g_gemm_latec_kmax; g_gemm_latec_kmax = v; return old;
+}
 
 void dgemm_dev(hipStream_t stream, char opA, char opB, int M, int N, int K, double alpha, const double* A,
                int lda, const double* B, int ldb, double beta, double* C, int ldc, int tri_mode,
@@ -694,21 +809,25 @@ void dgemm_dev(hipStream_t stream, char opA, char opB, int M, int N, int K, doub
       }
       dim3 grd2(gx2, batch, batch2), blk2(256);
       const size_t shmem2 = (size_t)4 * G2_STAGE * sizeof(double);
-#define EIGX_LAUNCH2(AK, BK_, GA_)                                                                 \
+#define EIGX_LAUNCH2(AK, BK_, GA_, LC_)                                                            \
   do {                                                                                             \
     static bool attr_set2 = false;                                                                 \
     if (!attr_set2) {                                                                              \
-      EIGX_HIP_CHECK(hipFuncSetAttribute((const void*)gemm2_kernel<AK, BK_, GA_>,                  \
+      EIGX_HIP_CHECK(hipFuncSetAttribute((const void*)gemm2_kernel<AK, BK_, GA_, LC_>,             \
                                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem2)); \
       attr_set2 = true;                                                                            \
     }                                                                                              \
-    hipLaunchKernelGGL((gemm2_kernel<AK, BK_, GA_>), grd2, blk2, shmem2, stream, g);               \
+    hipLaunchKernelGGL((gemm2_kernel<AK, BK_, GA_, LC_>), grd2, blk2, shmem2, stream, g);          \
   } while (0)
-      if (gather) EIGX_LAUNCH2(false, false, true);
-      else if (a_kc && b_kc) EIGX_LAUNCH2(true, true, false);
-      else if (a_kc) EIGX_LAUNCH2(true, false, false);
-      else if (b_kc) EIGX_LAUNCH2(false, true, false);
-      else EIGX_LAUNCH2(false, false, false);
+      // the one-GPU trailing update at short K: C requested under the last MFMAs (eigx_tune key 25); the streaming hook
+      // (key 6) exists in the early-C form only
+      const bool late_c = tri_mode == 1 && beta != 0.0 && K <= g_gemm_latec_kmax && !g.c_stream;
+      if (gather) EIGX_LAUNCH2(false, false, true, false);
+      else if (a_kc && b_kc) EIGX_LAUNCH2(true, true, false, false);
+      else if (a_kc) EIGX_LAUNCH2(true, false, false, false);
+      else if (b_kc) EIGX_LAUNCH2(false, true, false, false);
+      else if (late_c) EIGX_LAUNCH2(false, false, false, true);
+      else EIGX_LAUNCH2(false, false, false, false);
 #undef EIGX_LAUNCH2
       EIGX_HIP_CHECK(hipGetLastError());
       return;

@@ -581,7 +581,10 @@ int eigx_profile_read_kinds(double* out, int nkinds);
  * key 23 = the same for eigx_gev_batch (0 .. EIGX_GBATCH_NMAX, default EIGX_GBATCH_NMAX by the measured table of DESIGN section
  * 8j; other values are refused): larger pencils go through eigx_gev_range_dev one by one.  key 24 = the same for
  * eigx_hgev_batch (0 .. EIGX_HGBATCH_NMAX, default EIGX_HGBATCH_NMAX by the measured table of DESIGN section 8k; other values are
- * refused): larger pencils go through eigx_hgev_range_dev one by one.  Returns
+ * refused): larger pencils go through eigx_hgev_range_dev one by one.  key 25 = largest K at which the one-GPU trailing
+ * update reads its C tile under the last MFMAs instead of before the first (0 .. 511, default 256: the measurements of
+ * DESIGN sections 3 and 5; 0 = never, for A/B; other values are refused; the update is rounded as C - sum below it and as
+ * -((-C) + sum) above).  Returns
  * the previous value, or
  * -1 for an unknown key or a refused value.
  * Not part of the reference's interface. */

@@ -181,6 +181,27 @@ if mode == "pmc":
         torch.cuda.synchronize()
     once("N", "T", 32768, 32768, 256, tri=1)
     once("N", "T", 8192, 8192, 8192)
+if mode in ("short", "pmc_short"):
+    # the one-GPU trailing update at short K, one buffer per shape: "short" launches each shape 12 times (host time per
+    # call printed; the kernel durations come from a rocprofv3 --kernel-trace of this run, tools/short_k_trace_table.py),
+    # "pmc_short" launches each K = 128 shape once for a --pmc pass.  EIGX_LIB selects the library, EIGX_TUNE="25=0" a key.
+    for kv in os.environ.get("EIGX_TUNE", "").split(","):
+        if "=" in kv:
+            lib.eigx_tune(*(int(t) for t in kv.split("=")))
+    shapes = ((2048, 128), (4096, 128), (8192, 128)) if mode == "pmc_short" else \
+             ((2048, 128), (4096, 128), (8192, 128), (8192, 96), (8192, 256), (32768, 512))
+    for nn, kk in shapes:
+        A, lda = mk(nn, kk, 32); B, ldb = mk(nn, kk, 32); C, ldc = mk(nn, nn, 32)
+        torch.cuda.synchronize()
+        fn = lambda: call("N", "T", nn, nn, kk, -1.0, A, lda, B, ldb, 1.0, C, ldc, 1)
+        if mode == "pmc_short":
+            fn()
+        else:
+            dt = timeit(fn, 11)
+            print(f"{os.environ.get('EIGX_LIB', 'default')[-28:]} tune[{os.environ.get('EIGX_TUNE', '')}] tri n={nn} K={kk}: "
+                  f"{dt*1e6:9.1f} us per call (host, with the stream sync)  {nn*(nn+128.0)*kk/dt/1e12:6.2f} TF", flush=True)
+        torch.cuda.synchronize()
+        del A, B, C
 if mode == "pmc_k1":
     # one ring-kernel launch per trailing-update shape for the rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes
     lib.eigx_tune(0, 2)
