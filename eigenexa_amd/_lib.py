@@ -166,6 +166,21 @@ HGBATCH_SIGNATURES = {
     "eigx_hgev_batch_dev": (C.c_int, _GEV_BATCH),
 }
 
+# The same for include/eigenexa_amd_gemm_lab.h, which eigenexa_amd.h does NOT include: a test interface to the GEMM dispatcher
+# (csrc/gemm_lab.hip) for tests/test_gemm_paths.py; nothing in the package calls it.  Strides are int64_t; the table of
+# eigx_dgemm_gather_table_dev is a host int64_t array.
+LAB_SIGNATURES = {
+    # opa, opb, m, n, k, alpha, a, lda, b, ldb, beta, c, ldc, tri_mode, px_n, px, py_n, py, batch, stride_a, stride_b, stride_c,
+    # batch2, stride_a2, stride_b2, stride_c2, tn_lo, tn_hi, kmap_a, kmap_b
+    "eigx_dgemm_ex_dev": (C.c_int, [C.c_char, C.c_char, _INT, _INT, _INT, C.c_double, _PTR, _INT, _PTR, _INT, C.c_double, _PTR,
+                                    _INT, _INT, _INT, _INT, _INT, _INT, _INT, C.c_int64, C.c_int64, C.c_int64, _INT, C.c_int64,
+                                    C.c_int64, C.c_int64, _INT, _INT, _PTR, _PTR]),
+    # m, n, px_n, px, py_n, py, tn_lo, tn_hi (host arithmetic only)
+    "eigx_dgemm_tri2_launch_tiles": (C.c_int, [_INT] * 8),
+    # nbatch, entries, a, lda, b, ldb, c, ldc, kmap_a, kmap_b
+    "eigx_dgemm_gather_table_dev": (C.c_int, [_INT, _PTR, _PTR, _INT, _PTR, _INT, _PTR, _INT, _PTR, _PTR]),
+}
+
 _lib = None
 
 
@@ -184,6 +199,13 @@ def load():
         fn = getattr(lib, name)  # AttributeError = header/library mismatch: fail loudly
         fn.restype = res
         fn.argtypes = args
+    # the test interface is no load requirement of the package: an earlier build of the library (EIGX_LIB, the A/B runs of
+    # profiles/) has none; tests/test_gemm_paths.py holds this tree's build to the whole table
+    for name, (res, args) in LAB_SIGNATURES.items():
+        fn = getattr(lib, name, None)
+        if fn is not None:
+            fn.restype = res
+            fn.argtypes = args
     _lib = lib
     return lib
 

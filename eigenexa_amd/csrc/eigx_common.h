@@ -102,6 +102,10 @@ __global__ void fill_vec_kernel(double* __restrict__ w, int n, double v);
 __global__ void scale_vec_kernel(double* __restrict__ w, int n, double s);
 
 // C = alpha*op(A)*op(B) + beta*C ; opA/opB in {'N','T'}.
+// As in BLAS: alpha == 0 or K == 0 does not reference A and B (C = beta*C, whatever A and B hold), and beta == 0 does not
+// read C (it may hold NaN: workspace is passed as it is).  The gather maps are the exception: at K = 0 the kernel still reads
+// kmapA[0] and kmapB[0] (load_map clamps k >= K to index 0), so a map that is passed has one readable element; the same holds
+// for the entries of dgemm_gather_batch_dev's table (dc.hip's K = 0 entries point into its arena).
 // tri_mode: 0 = full, 1 = only tiles that intersect the upper triangle (global row <= global col)
 // of a matrix whose local element (i,j) is global (i*Px+px, j*Py+py), square tile grid, block-triangular order;
 // 2 = the same test on the rectangular local block of a 2-D cyclic distribution (full-mode tile order).
@@ -115,6 +119,11 @@ void dgemm_dev(hipStream_t stream, char opA, char opB, int M, int N, int K, doub
                const int* cmapC = nullptr, int batch = 1, long strideA = 0, long strideB = 0, long strideC = 0,
                int batch2 = 1, long strideA2 = 0, long strideB2 = 0, long strideC2 = 0, int ownP = 1,
                int ownp = 0, const int* kmapB = nullptr, int tn_lo = 0, int tn_hi = 0x7fffffff);
+
+// tri_mode 2 through the ring kernel launches only the tiles of the active region (row groups of tile rows, each from its
+// first column on or above the global diagonal): the number of workgroups that launch has for a local M x N block.  Host
+// arithmetic only; for the tests, which hold it against the count from the definition above.
+int gemm_tri2_launch_tiles(int M, int N, const Grid& g, int tn_lo, int tn_hi);
 
 // Batch of independent gather products C_b = A(:, kmapA_b) * B(:, kmapB_b)^T with their own sizes (the merges of one D&C
 // height): ONE launch, the table lives in device memory (blockIdx.y = entry); offsets are in elements from the bases.

@@ -746,7 +746,31 @@ static bool gemm2_ok(const GemmArgs& g, bool a_kc, bool b_kc, int batch, int bat
   return true;
 }
 
+// tri mode 2, host side of the active-region launch: the row groups of g (M, N, the grid and [tn_lo, tn_hi) are set) and
+// the number of tiles = workgroups of the launch
+static int tri2_plan(GemmArgs& g) {
+  const int tiles_m = ceil_div(g.M, 128), tiles_n = ceil_div(g.N, 128);
+  g.rg_h = (tiles_m <= 256) ? 8 : ceil_div(tiles_m, 32);
+  g.nrg = ceil_div(tiles_m, g.rg_h);
+  g.rg_c1 = tiles_n < g.tn_hi ? tiles_n : g.tn_hi;
+  g.rg_magic = (unsigned)(((1ull << 32) / (unsigned long long)g.Py) + 1ull);
+  int total = 0;
+  for (int q = 0; q < g.nrg; ++q) {
+    const int rows = (tiles_m - q * g.rg_h < g.rg_h) ? tiles_m - q * g.rg_h : g.rg_h;
+    total += rows * (g.rg_c1 - tri2_c0(g, q, tiles_n));
+  }
+  return total;
+}
+
 }  // namespace
+
+int gemm_tri2_launch_tiles(int M, int N, const Grid& grid, int tn_lo, int tn_hi) {
+  if (M <= 0 || N <= 0) return 0;
+  GemmArgs g = {};
+  g.M = M; g.N = N; g.tn_lo = tn_lo; g.tn_hi = tn_hi;
+  g.Px = grid.Px; g.px = grid.px; g.Py = grid.Py; g.py = grid.py;
+  return tri2_plan(g);
+}
 
 int set_gemm_variant(int v) { const int old = g_gemm_variant; g_gemm_variant = v; return old; }
 int set_gemm_cstream(int v) { const int old = g_gemm_cstream; g_gemm_cstream = v; return old; }
@@ -761,6 +785,9 @@ void dgemm_dev(hipStream_t stream, char opA, char opB, int M, int N, int K, doub
                long strideC, int batch2, long strideA2, long strideB2, long strideC2, int ownP, int ownp,
                const int* kmapB, int tn_lo, int tn_hi) {
   if (M <= 0 || N <= 0 || batch <= 0 || batch2 <= 0) return;
+  // alpha == 0 does not reference A and B (BLAS): run it as K = 0, where every operand load of gemm_f64_kernel is predicated
+  // off (load_slab: k < Kmax) and the K loop has no trip, so a NaN or Inf in A or B cannot reach C through 0 * acc
+  if (alpha == 0.0) K = 0;
   GemmArgs g;
   g.M = M; g.N = N; g.K = K; g.alpha = alpha; g.beta = beta;
   g.A = A; g.lda = lda; g.B = B; g.ldb = ldb; g.C = C; g.ldc = ldc;
@@ -794,16 +821,7 @@ void dgemm_dev(hipStream_t stream, char opA, char opB, int M, int N, int K, doub
       if (tri_mode == 2 && batch == 1 && batch2 == 1 && ownP == 1) {
         // active region of the local block: tile (tm, tn) holds an element on or above the global diagonal iff the first
         // global row of tile row tm <= the last global column of tile column tn; the window [tn_lo, tn_hi) cuts columns
-        const int tiles_m = ceil_div(M, 128), tiles_n = ceil_div(N, 128);
-        g.rg_h = (tiles_m <= 256) ? 8 : ceil_div(tiles_m, 32);
-        g.nrg = ceil_div(tiles_m, g.rg_h);
-        g.rg_c1 = tiles_n < tn_hi ? tiles_n : tn_hi;
-        g.rg_magic = (unsigned)(((1ull << 32) / (unsigned long long)g.Py) + 1ull);
-        int total = 0;
-        for (int q = 0; q < g.nrg; ++q) {
-          const int rows = (tiles_m - q * g.rg_h < g.rg_h) ? tiles_m - q * g.rg_h : g.rg_h;
-          total += rows * (g.rg_c1 - tri2_c0(g, q, tiles_n));
-        }
+        const int total = tri2_plan(g);
         if (total == 0) return;
         gx2 = total;
       }

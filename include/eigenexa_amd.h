@@ -521,7 +521,11 @@ int eigx_trbak_dev(int n, int nvec, const double* a_dev, int lda, double* z_dev,
 
 /* replaces the BLAS dgemm call sites of the path (src/eigen_t1.F:285-295, src/trbakwy4_body.F:604-608,
  * :721-725, src/FS_PDLAED3.F90:833-860): C = alpha*op(A)*op(B)+beta*C on device arrays.
- * tri_upper != 0 restricts the update to 128x128 tiles touching the upper triangle. */
+ * tri_upper != 0 restricts the update to 128x128 tiles touching the upper triangle.
+ * As in BLAS, alpha == 0 or k == 0 does not reference a_dev and b_dev (C = beta*C whatever they hold, NaN and Inf
+ * included), and beta == 0 does not read c_dev (it may hold NaN).  The same holds for eigx_dgemm_gather_dev, with one
+ * exception: its maps are still read at index 0 when alpha == 0 or k == 0, so each map that is passed needs one readable
+ * element even then. */
 int eigx_dgemm_dev(char opa, char opb, int m, int n, int k, double alpha, const double* a_dev, int lda,
                    const double* b_dev, int ldb, double beta, double* c_dev, int ldc, int tri_upper);
 
