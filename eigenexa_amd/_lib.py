@@ -166,6 +166,19 @@ HGBATCH_SIGNATURES = {
     "eigx_hgev_batch_dev": (C.c_int, _GEV_BATCH),
 }
 
+# The same for include/eigenexa_amd_vbatch.h -- extension: ragged batches, every block with its own order (csrc/vbatch.hip,
+# csrc/hvbatch.hip).  The six descriptor arrays (n, off_a, lda, off_w, off_z, ldz) are host arrays in both forms.
+# batch, n, a, off_a, lda, w, off_w, z, off_z, ldz, mode, info
+_VBATCH = [_INT, _PTR, _PTR, _PTR, _PTR, _PTR, _PTR, _PTR, _PTR, _PTR, C.c_char, _PTR]
+VBATCH_SIGNATURES = {
+    "eigx_s_vbatch": (C.c_int, _VBATCH),
+    "eigx_s_vbatch_dev": (C.c_int, _VBATCH),
+    "eigx_h_vbatch": (C.c_int, _VBATCH),
+    "eigx_h_vbatch_dev": (C.c_int, _VBATCH),
+    # batch, n, cutoff, top, order, counts6 (host arithmetic only)
+    "eigx_vbatch_plan": (C.c_int, [_INT, _PTR, _INT, _INT, _PTR, _PTR]),
+}
+
 # The same for include/eigenexa_amd_gemm_lab.h, which eigenexa_amd.h does NOT include: a test interface to the GEMM dispatcher
 # (csrc/gemm_lab.hip) for tests/test_gemm_paths.py; nothing in the package calls it.  Strides are int64_t; the table of
 # eigx_dgemm_gather_table_dev is a host int64_t array.
@@ -195,7 +208,7 @@ def load():
             "eigenexa_amd has no CPU fallback."
         )
     lib = C.CDLL(LIB_PATH, mode=C.RTLD_GLOBAL)
-    for name, (res, args) in {**SIGNATURES, **GBATCH_SIGNATURES, **HGBATCH_SIGNATURES}.items():
+    for name, (res, args) in {**SIGNATURES, **GBATCH_SIGNATURES, **HGBATCH_SIGNATURES, **VBATCH_SIGNATURES}.items():
         fn = getattr(lib, name)  # AttributeError = header/library mismatch: fail loudly
         fn.restype = res
         fn.argtypes = args

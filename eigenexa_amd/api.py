@@ -506,6 +506,77 @@ def eigen_h_batch(n, batch, a, lda, w, z, ldz, mode="A", info=None, stride_a=Non
     _solve_batch("h", n, batch, a, lda, w, z, ldz, mode, info, stride_a, ldw, stride_z)
 
 
+def _solve_vbatch(which, batch, n, a, off_a, lda, w, off_w, z, off_z, ldz, mode, info):
+    name = f"eigen_{which}_vbatch"
+    # the arguments are checked here, before the library is touched (status -2 = EIGX_ERR_BAD_ARG)
+    md = _char(mode, "A").upper()
+    want_vec = md == b"A"
+    desc = {}
+    try:
+        batch = int(batch)
+        ok = batch >= 0 and md in (b"A", b"N") and (batch == 0 or (a is not None and w is not None))
+        ok = ok and not (want_vec and batch > 0 and z is None)
+        for key, x, dtype, needed in (("n", n, np.int32, True), ("off_a", off_a, np.int64, True), ("lda", lda, np.int32, True),
+                                      ("off_w", off_w, np.int64, True), ("off_z", off_z, np.int64, want_vec),
+                                      ("ldz", ldz, np.int32, want_vec)):
+            if not ok:
+                break
+            if x is None or not needed:
+                desc[key] = None
+                ok = not needed or batch == 0
+                continue
+            v = np.asarray(x)
+            ok = v.ndim == 1 and v.size == batch and (batch == 0 or v.dtype.kind in "iu")
+            if ok:
+                ok = batch == 0 or bool((v >= 0).all() and (v <= np.iinfo(dtype).max).all())
+                desc[key] = np.ascontiguousarray(v, dtype=dtype)
+        if ok and batch > 0:
+            ok = bool((desc["lda"] >= desc["n"]).all()) and (not want_vec or bool((desc["ldz"] >= desc["n"]).all()))
+    except (TypeError, ValueError):
+        ok = False
+    if not ok:
+        _state["last_status"] = -2
+        print(f"Warning: {name}: invalid arguments (batch={batch}, mode={mode!r}; n >= 0, lda >= n, offsets >= 0 and in mode 'A' "
+              f"ldz >= n are required of every block, with {batch} entries per descriptor)", file=sys.stderr)
+        return
+    began = _begin(a)
+    if began is None:
+        return
+    lib, dev = began
+    if not want_vec:
+        z = None
+    pa, pw, pz = _addrs(which, dev, a=a, w=w, z=z)
+    pi = _info_addr(info, dev, "a, w, z, info")
+    pd = {key: (None if v is None else v.ctypes.data) for key, v in desc.items()}
+    rc = _entry(lib, f"eigx_{which}_vbatch", dev)(batch, pd["n"], pa, pd["off_a"], pd["lda"], pw, pd["off_w"], pz, pd["off_z"],
+                                                 pd["ldz"], md, pi)
+    _finish(name, rc, (0, -5, -6))
+
+
+def eigen_s_vbatch(batch, n, a, off_a, lda, w, off_w, z, off_z, ldz, mode="A", info=None):
+    """EXTENSION (not in the reference): ``batch`` symmetric matrices of differing orders in one call, one GPU -- the ragged
+    sibling of ``eigen_s_batch``.  ``a``, ``w`` and ``z`` are flat arrays (numpy float64, host form) or GPU tensors (device form);
+    ``n``, ``off_a``, ``lda``, ``off_w``, ``off_z``, ``ldz`` are integer sequences of ``batch`` entries, always on the host:
+    block ``k`` of order ``n[k]`` starts at element ``off_a[k]`` of ``a``, column-major with the leading dimension ``lda[k]``,
+    upper triangle significant, destroyed; its ascending eigenvalues go to ``w[off_w[k]:off_w[k] + n[k]]``, its eigenvectors to
+    ``z`` from ``off_z[k]`` on with the leading dimension ``ldz[k]`` (mode 'A'; mode 'N': eigenvalues only, ``z``, ``off_z`` and
+    ``ldz`` may be None).  ``layout.ragged_offsets`` packs a list of blocks.  Blocks must not overlap (not checked); ``n[k] = 0``
+    is an empty block.  Nothing outside ``w(1:n_k)`` and ``z(1:n_k, 1:n_k)`` is written.  ``info`` (optional, int32, ``batch``
+    entries, on the side of ``a``) receives the per-block status: 0, -5 (NaN / Inf in the block: its ``w`` is NaN, its ``z``
+    untouched) or -6; ``last_status()`` is 0 or the status of the failed block with the lowest index.  Blocks with ``n <= 128``
+    are solved by one kernel launch per size class, bit for bit as ``eigen_s_batch`` solves them; larger ones by ``eigen_s``."""
+    _solve_vbatch("s", batch, n, a, off_a, lda, w, off_w, z, off_z, ldz, mode, info)
+
+
+def eigen_h_vbatch(batch, n, a, off_a, lda, w, off_w, z, off_z, ldz, mode="A", info=None):
+    """EXTENSION (not in the reference): ``batch`` complex Hermitian matrices of differing orders in one call, one GPU -- the
+    ragged sibling of ``eigen_h_batch``, the arguments of ``eigen_s_vbatch``: ``a`` and ``z`` flat complex128 (numpy or GPU
+    tensors), ``w`` float64; ``off_a``, ``lda``, ``off_z`` and ``ldz`` count complex elements, ``off_w`` doubles.  Of a block's
+    diagonal only the real parts are read.  Blocks with ``n <= 96`` are solved by one kernel launch per size class, bit for bit
+    as ``eigen_h_batch`` solves them; larger ones by ``eigen_h``."""
+    _solve_vbatch("h", batch, n, a, off_a, lda, w, off_w, z, off_z, ldz, mode, info)
+
+
 def _solve_pencil_batch(which, n, batch, a, lda, b, ldb, w, z, ldz, mode, info, stride_a, stride_b, ldw, stride_z):
     name = f"eigen_{which}_batch"
     # the arguments are checked here, before the library is touched (status -2 = EIGX_ERR_BAD_ARG)

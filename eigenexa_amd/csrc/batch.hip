@@ -122,6 +122,7 @@ int set_batch_nmax(int v) {
   g_batch_nmax = v;
   return old;
 }
+int get_batch_nmax() { return g_batch_nmax; }
 
 // ---- the frame of the three families (declared in eigx_context.h) ------------------------------------------------------------
 bool batch_status_per_matrix(int rc) {   // (solve_dev and herm_solve_dev never return EIGX_ERR_NOT_SPD: one set serves all)

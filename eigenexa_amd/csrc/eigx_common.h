@@ -168,6 +168,9 @@ int set_dc_batch(int v);
 int set_batch_nmax(int v);
 // tuning hook (eigx_tune key 22, hbatch.hip): largest n served by the batch kernel of eigx_h_batch, 0 .. EIGX_HBATCH_NMAX
 int set_hbatch_nmax(int v);
+// the current values of keys 21 and 22: the ragged batches (vbatch.hip, hvbatch.hip) apply them block by block
+int get_batch_nmax();
+int get_hbatch_nmax();
 // tuning hook (eigx_tune key 23, gbatch.hip): largest n served by the batch kernel of eigx_gev_batch, 0 .. EIGX_GBATCH_NMAX
 int set_gbatch_nmax(int v);
 // tuning hook (eigx_tune key 24, hgbatch.hip): largest n served by the batch kernel of eigx_hgev_batch, 0 .. EIGX_HGBATCH_NMAX

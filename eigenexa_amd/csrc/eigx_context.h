@@ -352,6 +352,30 @@ void copy_blocks(void* dst, int ldd, int64_t sd, const void* src, int lds, int64
 // the device entry (device arrays; g.info may be null) and the host entry (host arrays) of a family
 int batch_frame_dev(Context& ctx, BatchArgs g, int cutoff, BatchLaunch launch, BatchSolveOne solve_one);
 int batch_frame_host(Context& ctx, BatchArgs g, int cutoff, BatchLaunch launch, BatchSolveOne solve_one);
+// vbatch.hip: the frame of the ragged batches (vbatch.hip: eigx_s_vbatch, hvbatch.hip: eigx_h_vbatch).  VbArgs is
+// a call: block k is a + off_a[k] (leading dimension lda[k]) of order n[k], its eigenvalues go to w + off_w[k], its
+// eigenvectors to z + off_z[k] (ldz[k]); the six descriptor arrays are host arrays of `batch` entries, offsets and leading
+// dimensions in elements of esz bytes (w: doubles).  VbDesc is what a workgroup reads of its block (k = the caller's index; its
+// three offsets count doubles).
+// A family supplies its cutoff, its largest n-class (top: 96 or 128) and two functions: launch its kernel of class nclass on `st`
+// for `count` descriptors, one workgroup each (`first`: the call's first-failure word), and solve block k with the full-size
+// solver (its status; g.mode in upper case).
+struct VbDesc { int k, n, lda, ldz; int64_t off_a, off_w, off_z; };
+struct VbArgs {
+  int batch; const int* n;
+  double* a; const int64_t* off_a; const int* lda;
+  double* w; const int64_t* off_w;
+  double* z; const int64_t* off_z; const int* ldz;
+  char mode; int* info;
+  int esz;
+  double* block(double* p, int64_t off) const { return p + (size_t)(esz / 8) * off; }   // a or z from element `off` on
+};
+typedef void (*VbLaunch)(int nclass, int count, const VbDesc* desc, const VbArgs& g, hipStream_t st, unsigned long long* first);
+typedef int (*VbSolveOne)(Context& ctx, const VbArgs& g, int k);
+// the schedule of a call (eigx_vbatch_plan, pure host arithmetic): see include/eigenexa_amd_vbatch.h
+int vbatch_plan(int batch, const int* n, int cutoff, int top, int* order, int* counts6);
+int vbatch_frame_dev(Context& ctx, VbArgs g, int cutoff, int top, VbLaunch launch, VbSolveOne solve_one);
+int vbatch_frame_host(Context& ctx, VbArgs g, int cutoff, int top, VbLaunch launch, VbSolveOne solve_one);
 // Host form of a solve on a local block of nr rows: a (nc columns), b (the same; b_h == nullptr: none), z (zcols columns,
 // allocated only) and w (nw entries) in the pool buffers host.a / host.b / host.z (esz 8) or host.ha / host.hb / host.hz
 // (esz 16, interleaved complex) and host.w, leading dimension ldd.  What comes back, and when, is each driver's contract:

@@ -142,6 +142,7 @@ int set_hbatch_nmax(int v) {
   g_hbatch_nmax = v;
   return old;
 }
+int get_hbatch_nmax() { return g_hbatch_nmax; }
 
 }  // namespace eigx
 

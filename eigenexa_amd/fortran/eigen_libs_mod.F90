@@ -36,6 +36,8 @@ module eigen_libs_mod
   public :: eigen_h_range, eigen_h_range_v   ! EXTENSION: both kinds of window for the complex Hermitian solver (one GPU)
   public :: eigen_s_batch   ! EXTENSION: many small symmetric matrices in one call (one GPU)
   public :: eigen_h_batch   ! EXTENSION: many small complex Hermitian matrices in one call (one GPU)
+  public :: eigen_s_vbatch  ! EXTENSION: many small symmetric matrices of differing sizes in one call (one GPU)
+  public :: eigen_h_vbatch  ! EXTENSION: many small complex Hermitian matrices of differing sizes in one call (one GPU)
   public :: eigen_gev_batch   ! EXTENSION: many small symmetric-definite pencils in one call (one GPU)
   public :: eigen_hgev_batch   ! EXTENSION: many small Hermitian-definite pencils in one call (one GPU)
 
@@ -152,6 +154,33 @@ module eigen_libs_mod
       import :: c_int, c_int64_t, c_double, c_double_complex, c_char
       integer(c_int), value :: n, batch, lda, ldw, ldz
       integer(c_int64_t), value :: stride_a, stride_z
+      complex(c_double_complex), intent(inout) :: a(*)
+      real(c_double), intent(inout) :: w(*)
+      complex(c_double_complex), intent(inout) :: z(*)
+      character(kind=c_char), value :: mode
+      integer(c_int), intent(out), optional :: info(*)
+    end function
+    ! EXTENSION (not in the reference): batch symmetric matrices of differing sizes, one GPU; 0-based offsets in elements; z, off_z,
+    ! ldz (mode 'N') and info may be absent (NULL)
+    integer(c_int) function eigx_s_vbatch(batch, n, a, off_a, lda, w, off_w, z, off_z, ldz, mode, info) &
+        bind(C, name="eigx_s_vbatch")
+      import :: c_int, c_int64_t, c_double, c_char
+      integer(c_int), value :: batch
+      integer(c_int), intent(in) :: n(*), lda(*), ldz(*)
+      integer(c_int64_t), intent(in) :: off_a(*), off_w(*), off_z(*)
+      real(c_double), intent(inout) :: a(*)
+      real(c_double), intent(inout) :: w(*), z(*)
+      character(kind=c_char), value :: mode
+      integer(c_int), intent(out), optional :: info(*)
+    end function
+    ! EXTENSION (not in the reference): batch complex Hermitian matrices of differing sizes, one GPU; offsets and leading
+    ! dimensions of a and z in complex elements
+    integer(c_int) function eigx_h_vbatch(batch, n, a, off_a, lda, w, off_w, z, off_z, ldz, mode, info) &
+        bind(C, name="eigx_h_vbatch")
+      import :: c_int, c_int64_t, c_double, c_double_complex, c_char
+      integer(c_int), value :: batch
+      integer(c_int), intent(in) :: n(*), lda(*), ldz(*)
+      integer(c_int64_t), intent(in) :: off_a(*), off_w(*), off_z(*)
       complex(c_double_complex), intent(inout) :: a(*)
       real(c_double), intent(inout) :: w(*)
       complex(c_double_complex), intent(inout) :: z(*)
@@ -757,6 +786,61 @@ contains
     rc = eigx_h_batch(n, batch, a, lda, int(lda, c_int64_t) * size(a, 2), w, size(w, 1), z, ldz, &
                       int(ldz, c_int64_t) * size(z, 2), md, info)
   end subroutine eigen_h_batch
+
+  !> eigen_s_vbatch(batch, n, a, ia, lda, w, iw, z, iz, ldz, mode, info) -- EXTENSION, not in the reference: the eigenpairs of batch
+  !> symmetric matrices of differing orders n(k) on one GPU, held in the flat arrays a, w and z: block k starts at a(ia(k)),
+  !> column-major with the leading dimension lda(k); its ascending eigenvalues come back in w(iw(k) : iw(k) + n(k) - 1), its
+  !> eigenvectors from z(iz(k)) on with the leading dimension ldz(k).  ia, iw, iz are 1-BASED start indices (the C entry takes
+  !> 0-based offsets: the conversion is made here).  Upper triangles significant, a destroyed; nothing between the blocks is
+  !> written; n(k) = 0 is an empty block; the blocks must not overlap.  Modes 'A' and 'N' (z not written).  info(k) = 0, or the
+  !> status of block k (-5: NaN / Inf, its w = NaN); the other blocks are solved all the same.  Blocks of n(k) <= 128 are solved
+  !> by one kernel launch per size class, as eigen_s_batch solves them; larger ones by eigen_s.
+  subroutine eigen_s_vbatch(batch, n, a, ia, lda, w, iw, z, iz, ldz, mode, info)
+    integer, intent(in) :: batch
+    integer, intent(in) :: n(*), lda(*), ldz(*)
+    integer(8), intent(in) :: ia(*), iw(*), iz(*)
+    real(8), intent(inout), contiguous :: a(:)
+    real(8), intent(inout), contiguous :: w(:), z(:)
+    character(*), intent(in), optional :: mode
+    integer, intent(out), optional :: info(*)
+    integer :: rc, nb
+    integer(c_int64_t), allocatable :: off_a(:), off_w(:), off_z(:)
+    character(kind=c_char) :: md
+    md = 'A'
+    if (present(mode)) md = mode(1:1)
+    nb = max(batch, 0)
+    allocate(off_a(nb), off_w(nb), off_z(nb))
+    off_a = ia(1:nb) - 1   ! 1-based start index -> 0-based offset
+    off_w = iw(1:nb) - 1
+    off_z = iz(1:nb) - 1
+    rc = eigx_s_vbatch(batch, n, a, off_a, lda, w, off_w, z, off_z, ldz, md, info)
+  end subroutine eigen_s_vbatch
+
+  !> eigen_h_vbatch(batch, n, a, ia, lda, w, iw, z, iz, ldz, mode, info) -- EXTENSION, not in the reference: eigen_s_vbatch for
+  !> complex Hermitian blocks.  a and z are flat complex arrays, w is real; ia, lda, iz and ldz count complex elements, iw
+  !> entries of w; all three start indices are 1-based.  Of a block's diagonal only the real parts are read.  Blocks of
+  !> n(k) <= 96 are solved by one kernel launch per size class, as eigen_h_batch solves them; larger ones by eigen_h.
+  subroutine eigen_h_vbatch(batch, n, a, ia, lda, w, iw, z, iz, ldz, mode, info)
+    integer, intent(in) :: batch
+    integer, intent(in) :: n(*), lda(*), ldz(*)
+    integer(8), intent(in) :: ia(*), iw(*), iz(*)
+    complex(8), intent(inout), contiguous :: a(:)
+    real(8), intent(inout), contiguous :: w(:)
+    complex(8), intent(inout), contiguous :: z(:)
+    character(*), intent(in), optional :: mode
+    integer, intent(out), optional :: info(*)
+    integer :: rc, nb
+    integer(c_int64_t), allocatable :: off_a(:), off_w(:), off_z(:)
+    character(kind=c_char) :: md
+    md = 'A'
+    if (present(mode)) md = mode(1:1)
+    nb = max(batch, 0)
+    allocate(off_a(nb), off_w(nb), off_z(nb))
+    off_a = ia(1:nb) - 1   ! 1-based start index -> 0-based offset
+    off_w = iw(1:nb) - 1
+    off_z = iz(1:nb) - 1
+    rc = eigx_h_vbatch(batch, n, a, off_a, lda, w, off_w, z, off_z, ldz, md, info)
+  end subroutine eigen_h_vbatch
 
   !> eigen_gev_batch(n, batch, a, lda, b, ldb, w, z, ldz, mode, info) -- EXTENSION, not in the reference: the eigenpairs of batch
   !> symmetric-definite pencils a(:, :, k) x = lambda b(:, :, k) x of one size n on one GPU, in one kernel launch for n <= 96

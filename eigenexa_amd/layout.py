@@ -105,6 +105,23 @@ def gather_block_cyclic(blocks, n0, n1, nb, order="C", dims=None):
     return out
 
 
+def ragged_offsets(n, ld=None, gap=0):
+    """(offsets, total) for packing blocks of the orders ``n`` one behind the other in a flat array (eigen_s_vbatch /
+    eigen_h_vbatch): block k takes ``ld[k] * n[k]`` elements -- ``ld`` None: tight, ``n[k] * n[k]``; a sequence: padded columns;
+    a scalar: the same for every block, ``ld=1`` gives the ``n[k]`` entries of a vector such as ``w`` -- followed by ``gap``
+    unused elements.  ``offsets`` is an int64 array of 0-based starts, ``total`` the length of the flat array."""
+    n = np.asarray(n, dtype=np.int64).reshape(-1)
+    ld = n if ld is None else np.broadcast_to(np.asarray(ld, dtype=np.int64), n.shape)
+    gap = int(gap)
+    if (n < 0).any() or (ld < 0).any() or gap < 0:
+        raise ValueError("ragged_offsets: negative size, leading dimension or gap")
+    size = ld * n + gap
+    off = np.zeros(len(n), dtype=np.int64)
+    if len(n):
+        off[1:] = np.cumsum(size)[:-1]
+    return off, int(size.sum())
+
+
 # ---- synthetic matrices -------------------------------------------------------------------------
 
 def frank(n, rows=None, cols=None):
