@@ -179,6 +179,17 @@ VBATCH_SIGNATURES = {
     "eigx_vbatch_plan": (C.c_int, [_INT, _PTR, _INT, _INT, _PTR, _PTR]),
 }
 
+# The same for include/eigenexa_amd_gvbatch.h -- extension: ragged batches of pencils (csrc/gvbatch.hip, csrc/hgvbatch.hip,
+# DESIGN 8m).  The eight descriptor arrays (n, off_a, lda, off_b, ldb, off_w, off_z, ldz) are host arrays in both forms.
+# batch, n, a, off_a, lda, b, off_b, ldb, w, off_w, z, off_z, ldz, mode, info
+_GVBATCH = [_INT, _PTR, _PTR, _PTR, _PTR, _PTR, _PTR, _PTR, _PTR, _PTR, _PTR, _PTR, _PTR, C.c_char, _PTR]
+GVBATCH_SIGNATURES = {
+    "eigx_gev_vbatch": (C.c_int, _GVBATCH),
+    "eigx_gev_vbatch_dev": (C.c_int, _GVBATCH),
+    "eigx_hgev_vbatch": (C.c_int, _GVBATCH),
+    "eigx_hgev_vbatch_dev": (C.c_int, _GVBATCH),
+}
+
 # The same for include/eigenexa_amd_gemm_lab.h, which eigenexa_amd.h does NOT include: a test interface to the GEMM dispatcher
 # (csrc/gemm_lab.hip) for tests/test_gemm_paths.py; nothing in the package calls it.  Strides are int64_t; the table of
 # eigx_dgemm_gather_table_dev is a host int64_t array.
@@ -208,7 +219,8 @@ def load():
             "eigenexa_amd has no CPU fallback."
         )
     lib = C.CDLL(LIB_PATH, mode=C.RTLD_GLOBAL)
-    for name, (res, args) in {**SIGNATURES, **GBATCH_SIGNATURES, **HGBATCH_SIGNATURES, **VBATCH_SIGNATURES}.items():
+    for name, (res, args) in {**SIGNATURES, **GBATCH_SIGNATURES, **HGBATCH_SIGNATURES, **VBATCH_SIGNATURES,
+                               **GVBATCH_SIGNATURES}.items():
         fn = getattr(lib, name)  # AttributeError = header/library mismatch: fail loudly
         fn.restype = res
         fn.argtypes = args

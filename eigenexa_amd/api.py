@@ -506,17 +506,21 @@ def eigen_h_batch(n, batch, a, lda, w, z, ldz, mode="A", info=None, stride_a=Non
     _solve_batch("h", n, batch, a, lda, w, z, ldz, mode, info, stride_a, ldw, stride_z)
 
 
-def _solve_vbatch(which, batch, n, a, off_a, lda, w, off_w, z, off_z, ldz, mode, info):
+def _solve_vbatch(which, batch, n, a, off_a, lda, w, off_w, z, off_z, ldz, mode, info, pencil=None):
+    """the ragged wrappers; pencil = (b, off_b, ldb) for the generalised families, which need all three in both modes"""
     name = f"eigen_{which}_vbatch"
     # the arguments are checked here, before the library is touched (status -2 = EIGX_ERR_BAD_ARG)
     md = _char(mode, "A").upper()
     want_vec = md == b"A"
+    has_b = pencil is not None
+    b, off_b, ldb = pencil if has_b else (None, None, None)
     desc = {}
     try:
         batch = int(batch)
         ok = batch >= 0 and md in (b"A", b"N") and (batch == 0 or (a is not None and w is not None))
-        ok = ok and not (want_vec and batch > 0 and z is None)
+        ok = ok and not (want_vec and batch > 0 and z is None) and not (has_b and batch > 0 and b is None)
         for key, x, dtype, needed in (("n", n, np.int32, True), ("off_a", off_a, np.int64, True), ("lda", lda, np.int32, True),
+                                      ("off_b", off_b, np.int64, has_b), ("ldb", ldb, np.int32, has_b),
                                       ("off_w", off_w, np.int64, True), ("off_z", off_z, np.int64, want_vec),
                                       ("ldz", ldz, np.int32, want_vec)):
             if not ok:
@@ -532,11 +536,13 @@ def _solve_vbatch(which, batch, n, a, off_a, lda, w, off_w, z, off_z, ldz, mode,
                 desc[key] = np.ascontiguousarray(v, dtype=dtype)
         if ok and batch > 0:
             ok = bool((desc["lda"] >= desc["n"]).all()) and (not want_vec or bool((desc["ldz"] >= desc["n"]).all()))
+            ok = ok and (not has_b or bool((desc["ldb"] >= desc["n"]).all()))
     except (TypeError, ValueError):
         ok = False
     if not ok:
         _state["last_status"] = -2
-        print(f"Warning: {name}: invalid arguments (batch={batch}, mode={mode!r}; n >= 0, lda >= n, offsets >= 0 and in mode 'A' "
+        print(f"Warning: {name}: invalid arguments (batch={batch}, mode={mode!r}; n >= 0, lda >= n, {'ldb >= n, ' if has_b else ''}"
+              f"offsets >= 0 and in mode 'A' "
               f"ldz >= n are required of every block, with {batch} entries per descriptor)", file=sys.stderr)
         return
     began = _begin(a)
@@ -545,9 +551,16 @@ def _solve_vbatch(which, batch, n, a, off_a, lda, w, off_w, z, off_z, ldz, mode,
     lib, dev = began
     if not want_vec:
         z = None
+    pd = {key: (None if v is None else v.ctypes.data) for key, v in desc.items()}
+    if has_b:
+        pa, pb, pw, pz = _addrs(which, dev, a=a, b=b, w=w, z=z)
+        pi = _info_addr(info, dev, "a, b, w, z, info")
+        rc = _entry(lib, f"eigx_{which}_vbatch", dev)(batch, pd["n"], pa, pd["off_a"], pd["lda"], pb, pd["off_b"], pd["ldb"], pw,
+                                                     pd["off_w"], pz, pd["off_z"], pd["ldz"], md, pi)
+        _finish(name, rc, (0, -5, -6, -7))
+        return
     pa, pw, pz = _addrs(which, dev, a=a, w=w, z=z)
     pi = _info_addr(info, dev, "a, w, z, info")
-    pd = {key: (None if v is None else v.ctypes.data) for key, v in desc.items()}
     rc = _entry(lib, f"eigx_{which}_vbatch", dev)(batch, pd["n"], pa, pd["off_a"], pd["lda"], pw, pd["off_w"], pz, pd["off_z"],
                                                  pd["ldz"], md, pi)
     _finish(name, rc, (0, -5, -6))
@@ -641,6 +654,45 @@ def eigen_hgev_batch(n, batch, a, lda, b, ldb, w, z, ldz, mode="A", info=None, s
     kernel launch solves the batch, one workgroup per pencil with both matrices in LDS; larger ``n`` runs
     ``KMATH_EIGEN_HGEV_RANGE`` with ``il = 1, iu = n`` pencil by pencil."""
     _solve_pencil_batch("hgev", n, batch, a, lda, b, ldb, w, z, ldz, mode, info, stride_a, stride_b, ldw, stride_z)
+
+
+def eigen_gev_vbatch(batch, n, a, off_a, lda, b, off_b, ldb, w, off_w, z, off_z, ldz, mode="A", info=None):
+    """EXTENSION (not in the reference): ``batch`` symmetric-definite pencils ``A x = lambda B x`` of differing orders in one
+    call, one GPU -- the ragged sibling of ``eigen_gev_batch``, in the storage of ``eigen_s_vbatch`` with ``b``, ``off_b`` and
+    ``ldb`` added.  ``a``, ``b``, ``w`` and ``z`` are flat arrays (numpy float64, host form) or GPU tensors (device form);
+    ``n``, ``off_a``, ``lda``, ``off_b``, ``ldb``, ``off_w``, ``off_z``, ``ldz`` are integer sequences of ``batch`` entries,
+    always on the host: pencil ``k`` of order ``n[k]`` starts at elements ``off_a[k]`` of ``a`` and ``off_b[k]`` of ``b``,
+    column-major with the leading dimensions ``lda[k]`` and ``ldb[k]``, upper triangles significant; ``a`` is destroyed, the block
+    of ``b`` comes back with ``U`` (``B = U^T U``) in its upper triangle.  The ascending eigenvalues go to
+    ``w[off_w[k]:off_w[k] + n[k]]``, the eigenvectors with ``z^T B z = I`` to ``z`` from ``off_z[k]`` on with the leading
+    dimension ``ldz[k]`` (mode 'A'; mode 'N': eigenvalues and ``U`` only, ``z``, ``off_z`` and ``ldz`` may be None; ``b``,
+    ``off_b`` and ``ldb`` are needed in both modes).  Packing a list of pencils with ``layout.ragged_offsets``::
+
+        n = [A.shape[0] for A in As]
+        off, total = layout.ragged_offsets(n)                    # tight blocks: lda = ldb = ldz = n[k]
+        off_w, len_w = layout.ragged_offsets(n, ld=1)
+        a = np.concatenate([A.T.reshape(-1) for A in As])        # column-major
+        b = np.concatenate([B.T.reshape(-1) for B in Bs])
+        w, z = np.empty(len_w), np.empty(total)
+        eigen_gev_vbatch(len(n), n, a, off, n, b, off, n, w, off_w, z, off, n)
+
+    Blocks must not overlap (not checked); ``n[k] = 0`` is an empty block.  ``info`` (optional, int32, ``batch`` entries, on the
+    side of ``a``) receives the per-block status: 0, -5 (NaN / Inf in A or B: its ``w`` is NaN, its ``z`` and ``b`` untouched),
+    -7 (B not positive definite: ``w`` NaN, ``z`` untouched) or -6; ``last_status()`` is 0 or the status of the failed block
+    with the lowest index.  Blocks with ``n <= 96`` are solved by one kernel launch per size class, bit for bit as
+    ``eigen_gev_batch`` solves them; larger ones by ``KMATH_EIGEN_GEV_RANGE`` with ``il = 1, iu = n``."""
+    _solve_vbatch("gev", batch, n, a, off_a, lda, w, off_w, z, off_z, ldz, mode, info, pencil=(b, off_b, ldb))
+
+
+def eigen_hgev_vbatch(batch, n, a, off_a, lda, b, off_b, ldb, w, off_w, z, off_z, ldz, mode="A", info=None):
+    """EXTENSION (not in the reference): ``batch`` Hermitian-definite pencils of differing orders in one call, one GPU -- the
+    ragged sibling of ``eigen_hgev_batch``, the arguments of ``eigen_gev_vbatch`` (packed in the same way with
+    ``layout.ragged_offsets``): ``a``, ``b`` and ``z`` flat complex128 (numpy or GPU tensors), ``w`` float64; ``off_a``,
+    ``lda``, ``off_b``, ``ldb``, ``off_z`` and ``ldz`` count complex elements, ``off_w`` doubles.  Of the diagonals only the real
+    parts are read; ``U`` (``B = U^H U``) comes back with a real positive diagonal, ``z^H B z = I``.  Blocks with ``n <= 64`` are
+    solved by one kernel launch per size class, bit for bit as ``eigen_hgev_batch`` solves them; larger ones by
+    ``KMATH_EIGEN_HGEV_RANGE`` with ``il = 1, iu = n``."""
+    _solve_vbatch("hgev", batch, n, a, off_a, lda, w, off_w, z, off_z, ldz, mode, info, pencil=(b, off_b, ldb))
 
 
 def band_count(d, e, band, x):

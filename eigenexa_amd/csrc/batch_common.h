@@ -77,6 +77,12 @@ __device__ inline void fail_matrix(int k, int code, bool row, int r, double* w, 
   if (threadIdx.x == 0) report_failure(first, info, k, code);
   __syncthreads();
 }
+// The same for a workgroup that serves one block of a ragged batch (gvbatch.hip, hgvbatch.hip) and ends with it: the block's
+// eigenvalues are at wk, k is its caller index; no barrier.
+__device__ inline void fail_block(int k, int code, bool row, int r, double* wk, int* info, unsigned long long* first) {
+  if (row) wk[r] = std::numeric_limits<double>::quiet_NaN();
+  if (threadIdx.x == 0) report_failure(first, info, k, code);
+}
 
 // the exponent ex of the scaling 2^-ex of a matrix whose largest entry is mx: 0 inside [1e-90, 1e90] (and for the zero
 // matrix), else that of the power of two nearest to mx (eigen_scaling, solver.hip); even: rounded up to an even number

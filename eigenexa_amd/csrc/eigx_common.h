@@ -175,5 +175,8 @@ int get_hbatch_nmax();
 int set_gbatch_nmax(int v);
 // tuning hook (eigx_tune key 24, hgbatch.hip): largest n served by the batch kernel of eigx_hgev_batch, 0 .. EIGX_HGBATCH_NMAX
 int set_hgbatch_nmax(int v);
+// the current values of keys 23 and 24: the ragged pencil batches (gvbatch.hip, hgvbatch.hip) apply them block by block
+int get_gbatch_nmax();
+int get_hgbatch_nmax();
 
 }  // namespace eigx

@@ -368,14 +368,28 @@ struct VbArgs {
   double* z; const int64_t* off_z; const int* ldz;
   char mode; int* info;
   int esz;
-  double* block(double* p, int64_t off) const { return p + (size_t)(esz / 8) * off; }   // a or z from element `off` on
+  // the pencil families (gvbatch.hip: eigx_gev_vbatch, hgvbatch.hip: eigx_hgev_vbatch) only: has_b, and
+  // the second matrix of block k at b + off_b[k] with the leading dimension ldb[k], required in both modes
+  bool has_b = false;
+  double* b = nullptr; const int64_t* off_b = nullptr; const int* ldb = nullptr;
+  double* block(double* p, int64_t off) const { return p + (size_t)(esz / 8) * off; }   // a, b or z from element `off` on
 };
+// what a workgroup of a pencil family reads of its block: VbDesc with ldb and off_b (the four offsets count doubles)
+struct VbPencilDesc { int k, n, lda, ldb, ldz; int64_t off_a, off_b, off_w, off_z; };
 typedef void (*VbLaunch)(int nclass, int count, const VbDesc* desc, const VbArgs& g, hipStream_t st, unsigned long long* first);
+typedef void (*VbPencilLaunch)(int nclass, int count, const VbPencilDesc* desc, const VbArgs& g, hipStream_t st,
+                               unsigned long long* first);
 typedef int (*VbSolveOne)(Context& ctx, const VbArgs& g, int k);
 // the schedule of a call (eigx_vbatch_plan, pure host arithmetic): see include/eigenexa_amd_vbatch.h
 int vbatch_plan(int batch, const int* n, int cutoff, int top, int* order, int* counts6);
+// the device entry and the host entry of a family; the overloads with a VbPencilLaunch are those of a family with has_b
 int vbatch_frame_dev(Context& ctx, VbArgs g, int cutoff, int top, VbLaunch launch, VbSolveOne solve_one);
 int vbatch_frame_host(Context& ctx, VbArgs g, int cutoff, int top, VbLaunch launch, VbSolveOne solve_one);
+int vbatch_frame_dev(Context& ctx, VbArgs g, int cutoff, int top, VbPencilLaunch launch, VbSolveOne solve_one);
+int vbatch_frame_host(Context& ctx, VbArgs g, int cutoff, int top, VbPencilLaunch launch, VbSolveOne solve_one);
+// gbatch.hip, hgbatch.hip: pencil k of a uniform batch above the cutoff, through gev_range_dev / hgev_range_dev
+int gbatch_solve_one(Context& ctx, const BatchArgs& g, int k);
+int hgbatch_solve_one(Context& ctx, const BatchArgs& g, int k);
 // Host form of a solve on a local block of nr rows: a (nc columns), b (the same; b_h == nullptr: none), z (zcols columns,
 // allocated only) and w (nw entries) in the pool buffers host.a / host.b / host.z (esz 8) or host.ha / host.hb / host.hz
 // (esz 16, interleaved complex) and host.w, leading dimension ldd.  What comes back, and when, is each driver's contract:

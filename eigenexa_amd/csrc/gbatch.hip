@@ -13,6 +13,7 @@
 // batch.hip: checks, launch and failure word, the loop above the cutoff, host staging of a, b, z, w).
 #include "eigx_context.h"
 #include "batch_common.h"
+#include "batch_solve.h"
 #include "../../include/eigenexa_amd.h"
 #include <cfloat>
 
@@ -22,41 +23,7 @@
 namespace eigx {
 namespace {
 
-// x(0 .. n-1), entry k at x[k * inc], <- U^-T x: x_k = (x_k - sum_{j < k} U(j, k) x_j) / U(k, k), k ascending.  The sum runs
-// in four interleaved chains from +0: with U = I it is +0 and x_k comes back as it was, the sign of a zero included.
-template <int LD>
-__device__ inline void solve_ut(int n, const double* U, double* x, int inc) {
-  for (int k = 0; k < n; ++k) {
-    const double* uk = U + k * LD;
-    double s0 = 0.0, s1 = 0.0, s2 = 0.0, s3 = 0.0;
-    int j = 0;
-    for (; j + 3 < k; j += 4) {
-      s0 = fma(uk[j], x[j * inc], s0);
-      s1 = fma(uk[j + 1], x[(j + 1) * inc], s1);
-      s2 = fma(uk[j + 2], x[(j + 2) * inc], s2);
-      s3 = fma(uk[j + 3], x[(j + 3) * inc], s3);
-    }
-    for (; j < k; ++j) s0 = fma(uk[j], x[j * inc], s0);
-    x[k * inc] = (x[k * inc] - ((s0 + s1) + (s2 + s3))) / uk[k];
-  }
-}
-// x(0 .. n-1) <- U^-1 x: x_k = (x_k - sum_{j > k} U(k, j) x_j) / U(k, k), k descending, the sums as above
-template <int LD>
-__device__ inline void solve_u(int n, const double* U, double* x) {
-  for (int k = n - 1; k >= 0; --k) {
-    const double* uk = U + k;
-    double s0 = 0.0, s1 = 0.0, s2 = 0.0, s3 = 0.0;
-    int j = k + 1;
-    for (; j + 3 < n; j += 4) {
-      s0 = fma(uk[j * LD], x[j], s0);
-      s1 = fma(uk[(j + 1) * LD], x[j + 1], s1);
-      s2 = fma(uk[(j + 2) * LD], x[j + 2], s2);
-      s3 = fma(uk[(j + 3) * LD], x[j + 3], s3);
-    }
-    for (; j < n; ++j) s0 = fma(uk[j * LD], x[j], s0);
-    x[k] = (x[k] - ((s0 + s1) + (s2 + s3))) / uk[k * LD];
-  }
-}
+// (the substitutions solve_ut and solve_u: batch_solve.h, shared with gvbatch_kernel)
 
 // One workgroup of 2 NMAX threads per pencil (NMAX = 32, 64, 96: the n-classes): thread (r, hh) = (row, half) as in
 // batch_kernel.  S(LD, NMAX) holds A, then C, then Q, then Z; U(LD, NMAX) holds B, then its factor (upper triangle; the
@@ -207,10 +174,13 @@ void gbatch_launch(const BatchArgs& g, hipStream_t st, unsigned long long* first
                        g.stride_a, g.b, g.ldb, g.stride_b, g.w, g.ldw, g.z, g.ldz, g.stride_z, (int)(g.mode == 'A'), g.info, first);
   });
 }
+
+}  // namespace
+
 // Above the cutoff: gev_range_dev with il = 1, iu = n.  It wants even leading dimensions: a pencil with an odd lda, ldb or ldz is
 // staged through the pool buffers gbatch.a / gbatch.b / gbatch.z, and U and z are copied out where it succeeded.  The frame
 // calls this once per pencil, so the three buffers are looked up by name per pencil (the same size every time: only the first
-// lookup of a call can allocate).
+// lookup of a call can allocate).  (Also what eigx_gev_vbatch does with a block above the cutoff: gvbatch.hip.)
 int gbatch_solve_one(Context& ctx, const BatchArgs& g, int k) {
   const int n = g.n;
   const bool want_vec = g.mode == 'A';
@@ -235,14 +205,13 @@ int gbatch_solve_one(Context& ctx, const BatchArgs& g, int k) {
   return rk;
 }
 
-}  // namespace
-
 int set_gbatch_nmax(int v) {
   if (v < 0 || v > EIGX_GBATCH_NMAX) return -1;
   const int old = g_gbatch_nmax;
   g_gbatch_nmax = v;
   return old;
 }
+int get_gbatch_nmax() { return g_gbatch_nmax; }
 
 }  // namespace eigx
 

@@ -15,6 +15,7 @@
 // batch.hip: checks, launch and failure word, the loop above the cutoff, host staging of a, b, z, w).
 #include "eigx_context.h"
 #include "batch_common.h"
+#include "batch_solve.h"
 #include "../../include/eigenexa_amd.h"
 #include <cfloat>
 
@@ -24,76 +25,7 @@
 namespace eigx {
 namespace {
 
-// x(0 .. n-1), entry k at (xr, xi)[k * inc], <- the solution of a lower triangular system with the columns of U as rows:
-// x_k = (x_k - sum_{j < k} op(U(j, k)) x_j) / U(k, k), k ascending, op = conj (CONJ: U^-H x down a column) or the identity
-// (x U^-1 along a row).  The real and the imaginary sum each run in four interleaved chains from +0 (two products per term,
-// two terms in flight), in an order that depends on k alone: with U = I every chain stays +0 and x_k comes back as it was, the
-// sign of a zero included.  The diagonal of U is real: one division per plane.
-template <int LD, bool CONJ>
-__device__ inline void zsolve_ut(int n, const double* Ur, const double* Ui, double* xr, double* xi, int inc) {
-  for (int k = 0; k < n; ++k) {
-    const double* ukr = Ur + k * LD;
-    const double* uki = Ui + k * LD;
-    double r0 = 0.0, r1 = 0.0, r2 = 0.0, r3 = 0.0, i0 = 0.0, i1 = 0.0, i2 = 0.0, i3 = 0.0;
-    int j = 0;
-    for (; j + 1 < k; j += 2) {
-      const double ar = ukr[j], at = CONJ ? -uki[j] : uki[j], br = ukr[j + 1], bt = CONJ ? -uki[j + 1] : uki[j + 1];
-      const double pr = xr[j * inc], pi = xi[j * inc], qr = xr[(j + 1) * inc], qi = xi[(j + 1) * inc];
-      r0 = fma(ar, pr, r0);
-      r1 = fma(-at, pi, r1);
-      i0 = fma(ar, pi, i0);
-      i1 = fma(at, pr, i1);
-      r2 = fma(br, qr, r2);
-      r3 = fma(-bt, qi, r3);
-      i2 = fma(br, qi, i2);
-      i3 = fma(bt, qr, i3);
-    }
-    if (j < k) {
-      const double ar = ukr[j], at = CONJ ? -uki[j] : uki[j];
-      const double pr = xr[j * inc], pi = xi[j * inc];
-      r0 = fma(ar, pr, r0);
-      r1 = fma(-at, pi, r1);
-      i0 = fma(ar, pi, i0);
-      i1 = fma(at, pr, i1);
-    }
-    const double dk = ukr[k];
-    xr[k * inc] = (xr[k * inc] - ((r0 + r1) + (r2 + r3))) / dk;
-    xi[k * inc] = (xi[k * inc] - ((i0 + i1) + (i2 + i3))) / dk;
-  }
-}
-// x(0 .. n-1) <- U^-1 x: x_k = (x_k - sum_{j > k} U(k, j) x_j) / U(k, k), k descending, the sums as above
-template <int LD>
-__device__ inline void zsolve_u(int n, const double* Ur, const double* Ui, double* xr, double* xi) {
-  for (int k = n - 1; k >= 0; --k) {
-    const double* ukr = Ur + k;
-    const double* uki = Ui + k;
-    double r0 = 0.0, r1 = 0.0, r2 = 0.0, r3 = 0.0, i0 = 0.0, i1 = 0.0, i2 = 0.0, i3 = 0.0;
-    int j = k + 1;
-    for (; j + 1 < n; j += 2) {
-      const double ar = ukr[j * LD], at = uki[j * LD], br = ukr[(j + 1) * LD], bt = uki[(j + 1) * LD];
-      const double pr = xr[j], pi = xi[j], qr = xr[j + 1], qi = xi[j + 1];
-      r0 = fma(ar, pr, r0);
-      r1 = fma(-at, pi, r1);
-      i0 = fma(ar, pi, i0);
-      i1 = fma(at, pr, i1);
-      r2 = fma(br, qr, r2);
-      r3 = fma(-bt, qi, r3);
-      i2 = fma(br, qi, i2);
-      i3 = fma(bt, qr, i3);
-    }
-    if (j < n) {
-      const double ar = ukr[j * LD], at = uki[j * LD];
-      const double pr = xr[j], pi = xi[j];
-      r0 = fma(ar, pr, r0);
-      r1 = fma(-at, pi, r1);
-      i0 = fma(ar, pi, i0);
-      i1 = fma(at, pr, i1);
-    }
-    const double dk = ukr[k * LD];
-    xr[k] = (xr[k] - ((r0 + r1) + (r2 + r3))) / dk;
-    xi[k] = (xi[k] - ((i0 + i1) + (i2 + i3))) / dk;
-  }
-}
+// (the substitutions zsolve_ut and zsolve_u: batch_solve.h, shared with hgvbatch_kernel)
 
 // One workgroup of 2 NMAX threads per pencil (NMAX = 32, 64: the n-classes): thread (r, hh) = (row, half) as in every batch
 // kernel.  The split planes Sr, Si(LD, NMAX) hold A, then C, then Q, then Z; Ur, Ui(LD, NMAX) hold B, then its factor (upper
@@ -275,13 +207,15 @@ void hgbatch_launch(const BatchArgs& g, hipStream_t st, unsigned long long* firs
   if (g.n <= 32) go(std::integral_constant<int, 32>());
   else go(std::integral_constant<int, EIGX_HGBATCH_NMAX>());
 }
+
+}  // namespace
+
 // above the cutoff: hgev_range_dev with il = 1, iu = n; it takes every leading dimension >= n, so nothing is staged
+// (also what eigx_hgev_vbatch does with a block above the cutoff: hgvbatch.hip)
 int hgbatch_solve_one(Context& ctx, const BatchArgs& g, int k) {
   return hgev_range_dev(ctx, g.n, RangeWindow::index(1, g.n), g.block(g.a, g.stride_a, k), g.lda, g.block(g.b, g.stride_b, k), g.ldb,
                         g.w + (size_t)k * g.ldw, g.mode == 'A' ? g.block(g.z, g.stride_z, k) : nullptr, g.ldz, g.mode);
 }
-
-}  // namespace
 
 int set_hgbatch_nmax(int v) {
   if (v < 0 || v > EIGX_HGBATCH_NMAX) return -1;
@@ -289,6 +223,7 @@ int set_hgbatch_nmax(int v) {
   g_hgbatch_nmax = v;
   return old;
 }
+int get_hgbatch_nmax() { return g_hgbatch_nmax; }
 
 }  // namespace eigx
 

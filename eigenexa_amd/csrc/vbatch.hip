@@ -6,8 +6,9 @@
 // iteration are sym_tridiag_ql of batch_common.h, so a block's w and z are bit for bit those of eigx_s_batch_dev(n, 1, ...).
 // No workgroup talks to another: no grid-wide barrier, no spin-wait, no atomics on the data.
 // Blocks above the cutoff go through solve_dev (eigen_s) one by one; empty blocks (n = 0) are skipped.
-// This file also holds the host side of both ragged families (eigx_h_vbatch: hvbatch.hip): the schedule, the argument check, the
-// device entry (vbatch_frame_dev) and the host entry (vbatch_frame_host: staging of the spans of a, w and z in the pool).
+// This file also holds the host side of every ragged family (eigx_h_vbatch: hvbatch.hip; the pencil families eigx_gev_vbatch and
+// eigx_hgev_vbatch with their second matrix b: gvbatch.hip, hgvbatch.hip): the schedule, the argument check, the
+// device entry (vbatch_frame_dev) and the host entry (vbatch_frame_host: staging of the spans of a, b, w and z in the pool).
 #include "eigx_context.h"
 #include "batch_common.h"
 #include "../../include/eigenexa_amd.h"
@@ -120,10 +121,12 @@ bool vbatch_args_ok(const VbArgs& g) {
   if (batch == 0) return true;
   if (!g.n || !g.a || !g.off_a || !g.lda || !g.w || !g.off_w) return false;
   if (want_vec && (!g.z || !g.off_z || !g.ldz)) return false;
+  if (g.has_b && (!g.b || !g.off_b || !g.ldb)) return false;
   for (int k = 0; k < batch; ++k) {
     const int n = g.n[k];
     if (n < 0 || g.lda[k] < n || g.off_a[k] < 0 || g.off_w[k] < 0) return false;
     if (want_vec && (g.ldz[k] < n || g.off_z[k] < 0)) return false;
+    if (g.has_b && (g.ldb[k] < n || g.off_b[k] < 0)) return false;
   }
   return true;
 }
@@ -161,6 +164,17 @@ void span_of(int batch, const int* n, const int64_t* off, const int* ld, int64_t
   }
   if (lo > hi) lo = hi = 0;
 }
+
+// the descriptor of block k (cs = doubles per element of a, b and z) and the pool buffer of a call's descriptors
+void fill_desc(VbDesc& d, const VbArgs& g, int k, bool want_vec, int64_t cs) {
+  d = VbDesc{k, g.n[k], g.lda[k], want_vec ? g.ldz[k] : 0, cs * g.off_a[k], g.off_w[k], want_vec ? cs * g.off_z[k] : 0};
+}
+void fill_desc(VbPencilDesc& d, const VbArgs& g, int k, bool want_vec, int64_t cs) {
+  d = VbPencilDesc{k, g.n[k], g.lda[k], g.ldb[k], want_vec ? g.ldz[k] : 0, cs * g.off_a[k], cs * g.off_b[k], g.off_w[k],
+                   want_vec ? cs * g.off_z[k] : 0};
+}
+inline const char* desc_buffer(const VbDesc*) { return "vbatch.desc"; }
+inline const char* desc_buffer(const VbPencilDesc*) { return "vbatch.pdesc"; }
 
 }  // namespace
 
@@ -202,7 +216,11 @@ int vbatch_plan(int batch, const int* n, int cutoff, int top, int* order, int* c
   return EIGX_OK;
 }
 
-int vbatch_frame_dev(Context& ctx, VbArgs g, int cutoff, int top, VbLaunch launch, VbSolveOne solve_one) {
+namespace {
+
+// the frame over the descriptor type: Desc = VbDesc (eigx_s_vbatch, eigx_h_vbatch) or VbPencilDesc (the families with has_b)
+template <class Desc, class Launch>
+int frame_dev(Context& ctx, VbArgs g, int cutoff, int top, Launch launch, VbSolveOne solve_one) {
   int rc;
   if (!vbatch_begin(ctx, g, rc)) return rc;
   EIGX_HIP_CHECK(hipStreamSynchronize(nullptr));   // the caller's default-stream work on the arguments (SolveFrame::begin)
@@ -236,18 +254,15 @@ int vbatch_frame_dev(Context& ctx, VbArgs g, int cutoff, int top, VbLaunch launc
     EIGX_HIP_CHECK(hipMemsetAsync(g.info, 0, (size_t)batch * sizeof(int), st));
     for (const auto& s : status) EIGX_HIP_CHECK(hipMemcpyAsync(g.info + s.first, &s.second, sizeof(int), hipMemcpyHostToDevice, st));
   }
-  std::vector<VbDesc> desc((size_t)nk);            // (alive until the stream is drained below)
+  std::vector<Desc> desc((size_t)nk);              // (alive until the stream is drained below)
   unsigned long long f = ~0ull;
   if (nk > 0) {
     const bool want_vec = g.mode == 'A';
     const int64_t cs = g.esz / 8;                  // doubles per element of a and z
-    for (int i = 0; i < nk; ++i) {
-      const int k = order[i];
-      desc[i] = VbDesc{k, g.n[k], g.lda[k], want_vec ? g.ldz[k] : 0, cs * g.off_a[k], g.off_w[k], want_vec ? cs * g.off_z[k] : 0};
-    }
-    VbDesc* desc_dev = ctx.pool.get_t<VbDesc>("vbatch.desc", (size_t)nk);
+    for (int i = 0; i < nk; ++i) fill_desc(desc[i], g, order[i], want_vec, cs);
+    Desc* desc_dev = ctx.pool.get_t<Desc>(desc_buffer((const Desc*)nullptr), (size_t)nk);
     unsigned long long* first = ctx.pool.get_t<unsigned long long>("batch.first", 1);
-    EIGX_HIP_CHECK(hipMemcpyAsync(desc_dev, desc.data(), (size_t)nk * sizeof(VbDesc), hipMemcpyHostToDevice, st));
+    EIGX_HIP_CHECK(hipMemcpyAsync(desc_dev, desc.data(), (size_t)nk * sizeof(Desc), hipMemcpyHostToDevice, st));
     // memset 0xff of the first-failure word: all ones = "no block failed"; a failed one leaves (index << 8 | -code) by atomicMin
     EIGX_HIP_CHECK(hipMemsetAsync(first, 0xff, sizeof(unsigned long long), st));
     static const int class_n[4] = {32, 64, 96, 128};
@@ -270,22 +285,26 @@ int vbatch_frame_dev(Context& ctx, VbArgs g, int cutoff, int top, VbLaunch launc
 // Host arrays: of each of a, w and z the span from the lowest offset to the highest last element is staged in one copy, the
 // caller's layout kept and the offsets rebased, in the pool buffers of the other host forms (host.a / host.z, or host.ha / host.hz
 // at 16 bytes per element, and host.w), the per-block status words in batch.info.  The spans of w and z go up before the solve
-// and come back after it: gaps, padding and the z of a failed block return as they were passed.
-int vbatch_frame_host(Context& ctx, VbArgs g, int cutoff, int top, VbLaunch launch, VbSolveOne solve_one) {
+// and come back after it: gaps, padding and the z of a failed block return as they were passed.  A family with has_b: the span
+// of b (host.b / host.hb) goes up before the solve and comes back after it as well, with U in the blocks that were solved.
+template <class Desc, class Launch>
+int frame_host(Context& ctx, VbArgs g, int cutoff, int top, Launch launch, VbSolveOne solve_one) {
   int rc;
   if (!vbatch_begin(ctx, g, rc)) return rc;
   const int batch = g.batch, esz = g.esz;
   const bool want_vec = g.mode == 'A', cplx = esz == 16;
-  int64_t a0, a1, w0, w1, z0 = 0, z1 = 0;
+  int64_t a0, a1, w0, w1, z0 = 0, z1 = 0, b0 = 0, b1 = 0;
   span_of(batch, g.n, g.off_a, g.lda, a0, a1);
   span_of(batch, g.n, g.off_w, nullptr, w0, w1);
   if (want_vec) span_of(batch, g.n, g.off_z, g.ldz, z0, z1);
-  std::vector<int64_t> oa((size_t)batch), ow((size_t)batch), oz((size_t)batch);
+  if (g.has_b) span_of(batch, g.n, g.off_b, g.ldb, b0, b1);
+  std::vector<int64_t> oa((size_t)batch), ow((size_t)batch), oz((size_t)batch), ob((size_t)(g.has_b ? batch : 0));
   for (int k = 0; k < batch; ++k) {      // (an empty block's offsets are never used: any value that passes the check)
     const bool some = g.n[k] > 0;
     oa[k] = some ? g.off_a[k] - a0 : 0;
     ow[k] = some ? g.off_w[k] - w0 : 0;
     oz[k] = some && want_vec ? g.off_z[k] - z0 : 0;
+    if (g.has_b) ob[k] = some ? g.off_b[k] - b0 : 0;
   }
   VbArgs dv = g;                         // the same call on the staged spans
   dv.a = (double*)ctx.pool.get(cplx ? "host.ha" : "host.a", (size_t)esz * std::max<int64_t>(a1 - a0, 1));
@@ -295,18 +314,41 @@ int vbatch_frame_host(Context& ctx, VbArgs g, int cutoff, int top, VbLaunch laun
   dv.off_a = oa.data();
   dv.off_w = ow.data();
   dv.off_z = want_vec ? oz.data() : nullptr;
+  char* bh = nullptr;
+  if (g.has_b) {
+    dv.b = (double*)ctx.pool.get(cplx ? "host.hb" : "host.b", (size_t)esz * std::max<int64_t>(b1 - b0, 1));
+    dv.off_b = ob.data();
+    bh = (char*)g.b + (size_t)esz * b0;
+    if (b1 > b0) EIGX_HIP_CHECK(hipMemcpy(dv.b, bh, (size_t)esz * (b1 - b0), hipMemcpyHostToDevice));
+  }
   char* ah = (char*)g.a + (size_t)esz * a0;
   char* zh = want_vec ? (char*)g.z + (size_t)esz * z0 : nullptr;
   double* wh = g.w + w0;
   if (a1 > a0) EIGX_HIP_CHECK(hipMemcpy(dv.a, ah, (size_t)esz * (a1 - a0), hipMemcpyHostToDevice));
   if (w1 > w0) EIGX_HIP_CHECK(hipMemcpy(dv.w, wh, (size_t)8 * (w1 - w0), hipMemcpyHostToDevice));
   if (z1 > z0) EIGX_HIP_CHECK(hipMemcpy(dv.z, zh, (size_t)esz * (z1 - z0), hipMemcpyHostToDevice));
-  rc = vbatch_frame_dev(ctx, dv, cutoff, top, launch, solve_one);
+  rc = frame_dev<Desc>(ctx, dv, cutoff, top, launch, solve_one);
   if (!batch_status_per_matrix(rc)) return rc;
+  if (b1 > b0) EIGX_HIP_CHECK(hipMemcpy(bh, dv.b, (size_t)esz * (b1 - b0), hipMemcpyDeviceToHost));
   if (w1 > w0) EIGX_HIP_CHECK(hipMemcpy(wh, dv.w, (size_t)8 * (w1 - w0), hipMemcpyDeviceToHost));
   if (z1 > z0) EIGX_HIP_CHECK(hipMemcpy(zh, dv.z, (size_t)esz * (z1 - z0), hipMemcpyDeviceToHost));
   if (g.info) EIGX_HIP_CHECK(hipMemcpy(g.info, dv.info, (size_t)batch * sizeof(int), hipMemcpyDeviceToHost));
   return rc;
+}
+
+}  // namespace
+
+int vbatch_frame_dev(Context& ctx, VbArgs g, int cutoff, int top, VbLaunch launch, VbSolveOne solve_one) {
+  return frame_dev<VbDesc>(ctx, g, cutoff, top, launch, solve_one);
+}
+int vbatch_frame_host(Context& ctx, VbArgs g, int cutoff, int top, VbLaunch launch, VbSolveOne solve_one) {
+  return frame_host<VbDesc>(ctx, g, cutoff, top, launch, solve_one);
+}
+int vbatch_frame_dev(Context& ctx, VbArgs g, int cutoff, int top, VbPencilLaunch launch, VbSolveOne solve_one) {
+  return frame_dev<VbPencilDesc>(ctx, g, cutoff, top, launch, solve_one);
+}
+int vbatch_frame_host(Context& ctx, VbArgs g, int cutoff, int top, VbPencilLaunch launch, VbSolveOne solve_one) {
+  return frame_host<VbPencilDesc>(ctx, g, cutoff, top, launch, solve_one);
 }
 
 }  // namespace eigx

@@ -38,6 +38,8 @@ module eigen_libs_mod
   public :: eigen_h_batch   ! EXTENSION: many small complex Hermitian matrices in one call (one GPU)
   public :: eigen_s_vbatch  ! EXTENSION: many small symmetric matrices of differing sizes in one call (one GPU)
   public :: eigen_h_vbatch  ! EXTENSION: many small complex Hermitian matrices of differing sizes in one call (one GPU)
+  public :: eigen_gev_vbatch  ! EXTENSION: many small symmetric-definite pencils of differing sizes in one call (one GPU)
+  public :: eigen_hgev_vbatch  ! EXTENSION: many small Hermitian-definite pencils of differing sizes in one call (one GPU)
   public :: eigen_gev_batch   ! EXTENSION: many small symmetric-definite pencils in one call (one GPU)
   public :: eigen_hgev_batch   ! EXTENSION: many small Hermitian-definite pencils in one call (one GPU)
 
@@ -182,6 +184,33 @@ module eigen_libs_mod
       integer(c_int), intent(in) :: n(*), lda(*), ldz(*)
       integer(c_int64_t), intent(in) :: off_a(*), off_w(*), off_z(*)
       complex(c_double_complex), intent(inout) :: a(*)
+      real(c_double), intent(inout) :: w(*)
+      complex(c_double_complex), intent(inout) :: z(*)
+      character(kind=c_char), value :: mode
+      integer(c_int), intent(out), optional :: info(*)
+    end function
+    ! EXTENSION (not in the reference): batch symmetric-definite pencils of differing sizes, one GPU; 0-based offsets in elements;
+    ! z, off_z, ldz (mode 'N') and info may be absent (NULL)
+    integer(c_int) function eigx_gev_vbatch(batch, n, a, off_a, lda, b, off_b, ldb, w, off_w, z, off_z, ldz, mode, info) &
+        bind(C, name="eigx_gev_vbatch")
+      import :: c_int, c_int64_t, c_double, c_char
+      integer(c_int), value :: batch
+      integer(c_int), intent(in) :: n(*), lda(*), ldb(*), ldz(*)
+      integer(c_int64_t), intent(in) :: off_a(*), off_b(*), off_w(*), off_z(*)
+      real(c_double), intent(inout) :: a(*), b(*)
+      real(c_double), intent(inout) :: w(*), z(*)
+      character(kind=c_char), value :: mode
+      integer(c_int), intent(out), optional :: info(*)
+    end function
+    ! EXTENSION (not in the reference): batch Hermitian-definite pencils of differing sizes, one GPU; offsets and leading
+    ! dimensions of a, b and z in complex elements
+    integer(c_int) function eigx_hgev_vbatch(batch, n, a, off_a, lda, b, off_b, ldb, w, off_w, z, off_z, ldz, mode, info) &
+        bind(C, name="eigx_hgev_vbatch")
+      import :: c_int, c_int64_t, c_double, c_double_complex, c_char
+      integer(c_int), value :: batch
+      integer(c_int), intent(in) :: n(*), lda(*), ldb(*), ldz(*)
+      integer(c_int64_t), intent(in) :: off_a(*), off_b(*), off_w(*), off_z(*)
+      complex(c_double_complex), intent(inout) :: a(*), b(*)
       real(c_double), intent(inout) :: w(*)
       complex(c_double_complex), intent(inout) :: z(*)
       character(kind=c_char), value :: mode
@@ -841,6 +870,66 @@ contains
     off_z = iz(1:nb) - 1
     rc = eigx_h_vbatch(batch, n, a, off_a, lda, w, off_w, z, off_z, ldz, md, info)
   end subroutine eigen_h_vbatch
+
+  !> eigen_gev_vbatch(batch, n, a, ia, lda, b, ib, ldb, w, iw, z, iz, ldz, mode, info) -- EXTENSION, not in the reference: the
+  !> eigenpairs of batch symmetric-definite pencils a_k x = lambda b_k x of differing orders n(k) on one GPU, held in the flat
+  !> arrays a, b, w and z: pencil k starts at a(ia(k)) and b(ib(k)), column-major with the leading dimensions lda(k) and ldb(k);
+  !> its ascending eigenvalues come back in w(iw(k) : iw(k) + n(k) - 1), its eigenvectors (z^T b z = I) from z(iz(k)) on with
+  !> the leading dimension ldz(k).  ia, ib, iw, iz are 1-BASED start indices (the C entry takes 0-based offsets: the conversion
+  !> is made here).  Upper triangles significant, a destroyed, the block of b returns U with b = U^T U in its upper triangle;
+  !> nothing between the blocks is written; n(k) = 0 is an empty block; the blocks must not overlap.  Modes 'A' and 'N' (z not
+  !> written).  info(k) = 0, or the status of block k (-5: NaN / Inf, -7: b not positive definite; its w = NaN); the other blocks
+  !> are solved all the same.  Blocks of n(k) <= 96 are solved by one kernel launch per size class, as eigen_gev_batch solves
+  !> them; larger ones by KMATH_EIGEN_GEV_RANGE with il = 1, iu = n(k).
+  subroutine eigen_gev_vbatch(batch, n, a, ia, lda, b, ib, ldb, w, iw, z, iz, ldz, mode, info)
+    integer, intent(in) :: batch
+    integer, intent(in) :: n(*), lda(*), ldb(*), ldz(*)
+    integer(8), intent(in) :: ia(*), ib(*), iw(*), iz(*)
+    real(8), intent(inout), contiguous :: a(:), b(:)
+    real(8), intent(inout), contiguous :: w(:), z(:)
+    character(*), intent(in), optional :: mode
+    integer, intent(out), optional :: info(*)
+    integer :: rc, nb
+    integer(c_int64_t), allocatable :: off_a(:), off_b(:), off_w(:), off_z(:)
+    character(kind=c_char) :: md
+    md = 'A'
+    if (present(mode)) md = mode(1:1)
+    nb = max(batch, 0)
+    allocate(off_a(nb), off_b(nb), off_w(nb), off_z(nb))
+    off_a = ia(1:nb) - 1   ! 1-based start index -> 0-based offset
+    off_b = ib(1:nb) - 1
+    off_w = iw(1:nb) - 1
+    off_z = iz(1:nb) - 1
+    rc = eigx_gev_vbatch(batch, n, a, off_a, lda, b, off_b, ldb, w, off_w, z, off_z, ldz, md, info)
+  end subroutine eigen_gev_vbatch
+
+  !> eigen_hgev_vbatch(batch, n, a, ia, lda, b, ib, ldb, w, iw, z, iz, ldz, mode, info) -- EXTENSION, not in the reference:
+  !> eigen_gev_vbatch for Hermitian-definite pencils.  a, b and z are flat complex arrays, w is real; ia, lda, ib, ldb, iz and ldz
+  !> count complex elements, iw entries of w; all four start indices are 1-based.  Of the diagonals only the real parts are
+  !> read; U (b = U^H U) has a real positive diagonal, z^H b z = I.  Blocks of n(k) <= 64 are solved by one kernel launch per size
+  !> class, as eigen_hgev_batch solves them; larger ones by KMATH_EIGEN_HGEV_RANGE with il = 1, iu = n(k).
+  subroutine eigen_hgev_vbatch(batch, n, a, ia, lda, b, ib, ldb, w, iw, z, iz, ldz, mode, info)
+    integer, intent(in) :: batch
+    integer, intent(in) :: n(*), lda(*), ldb(*), ldz(*)
+    integer(8), intent(in) :: ia(*), ib(*), iw(*), iz(*)
+    complex(8), intent(inout), contiguous :: a(:), b(:)
+    real(8), intent(inout), contiguous :: w(:)
+    complex(8), intent(inout), contiguous :: z(:)
+    character(*), intent(in), optional :: mode
+    integer, intent(out), optional :: info(*)
+    integer :: rc, nb
+    integer(c_int64_t), allocatable :: off_a(:), off_b(:), off_w(:), off_z(:)
+    character(kind=c_char) :: md
+    md = 'A'
+    if (present(mode)) md = mode(1:1)
+    nb = max(batch, 0)
+    allocate(off_a(nb), off_b(nb), off_w(nb), off_z(nb))
+    off_a = ia(1:nb) - 1   ! 1-based start index -> 0-based offset
+    off_b = ib(1:nb) - 1
+    off_w = iw(1:nb) - 1
+    off_z = iz(1:nb) - 1
+    rc = eigx_hgev_vbatch(batch, n, a, off_a, lda, b, off_b, ldb, w, off_w, z, off_z, ldz, md, info)
+  end subroutine eigen_hgev_vbatch
 
   !> eigen_gev_batch(n, batch, a, lda, b, ldb, w, z, ldz, mode, info) -- EXTENSION, not in the reference: the eigenpairs of batch
   !> symmetric-definite pencils a(:, :, k) x = lambda b(:, :, k) x of one size n on one GPU, in one kernel launch for n <= 96

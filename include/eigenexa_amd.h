@@ -31,7 +31,8 @@
  * eigx_hgev_range_v[_dev] (an extension: both kinds of window for the complex Hermitian solvers, one GPU), eigx_s_batch[_dev]
  * and eigx_h_batch[_dev] (an extension: many small symmetric / complex Hermitian matrices in one call, one GPU),
  * eigx_gev_batch[_dev] and eigx_hgev_batch[_dev] (an extension: many small symmetric-definite / Hermitian-definite pencils in
- * one call, one GPU), eigx_s_vbatch[_dev] and eigx_h_vbatch[_dev] (an extension: the same for blocks of differing sizes) and the stage
+ * one call, one GPU), eigx_s_vbatch[_dev], eigx_h_vbatch[_dev], eigx_gev_vbatch[_dev] and eigx_hgev_vbatch[_dev] (an extension: the
+ * same for blocks of differing sizes) and the stage
  * entry eigx_band_count_dev (Sturm counts of a band matrix at caller-given points).
  */
 #ifndef EIGENEXA_AMD_H
@@ -322,6 +323,9 @@ int eigx_h_batch_dev(int n, int batch, double* a_dev, int lda, int64_t stride_a,
 /* Ragged batches, eigx_s_vbatch[_dev] and eigx_h_vbatch[_dev] with their schedule eigx_vbatch_plan -- EXTENSION: declared and
  * documented in eigenexa_amd_vbatch.h. */
 #include "eigenexa_amd_vbatch.h"
+/* Ragged batches of pencils, eigx_gev_vbatch[_dev] and eigx_hgev_vbatch[_dev] -- EXTENSION: declared and documented in
+ * eigenexa_amd_gvbatch.h. */
+#include "eigenexa_amd_gvbatch.h"
 
 /* ScaLAPACK interop without a redistribution step.  The reference asks block-cyclic callers to
  * convert with pdgemr2d into its cyclic layout first (manual 3.4; benchmark/ev_test.f:68-84 does the reverse for the
