@@ -190,6 +190,16 @@ GVBATCH_SIGNATURES = {
     "eigx_hgev_vbatch_dev": (C.c_int, _GVBATCH),
 }
 
+# The same for include/eigenexa_amd_batch_range.h -- extension: eigenpairs il .. iu of every matrix of a uniform batch
+# (csrc/batch_range.hip), and what the last such call did (three host int pointers).
+# n, batch, il, iu, a, lda, stride_a, w, ldw, z, ldz, stride_z, mode, info
+_BATCH_RANGE = [_INT, _INT, _INT, _INT, _PTR, _INT, C.c_int64, _PTR, _INT, _PTR, _INT, C.c_int64, C.c_char, _PTR]
+BATCH_RANGE_SIGNATURES = {
+    "eigx_s_batch_range": (C.c_int, _BATCH_RANGE),
+    "eigx_s_batch_range_dev": (C.c_int, _BATCH_RANGE),
+    "eigx_batch_range_info": (C.c_int, [_c_int_p, _c_int_p, _c_int_p]),
+}
+
 # The same for include/eigenexa_amd_gemm_lab.h, which eigenexa_amd.h does NOT include: a test interface to the GEMM dispatcher
 # (csrc/gemm_lab.hip) for tests/test_gemm_paths.py; nothing in the package calls it.  Strides are int64_t; the table of
 # eigx_dgemm_gather_table_dev is a host int64_t array.
@@ -220,7 +230,7 @@ def load():
         )
     lib = C.CDLL(LIB_PATH, mode=C.RTLD_GLOBAL)
     for name, (res, args) in {**SIGNATURES, **GBATCH_SIGNATURES, **HGBATCH_SIGNATURES, **VBATCH_SIGNATURES,
-                               **GVBATCH_SIGNATURES}.items():
+                               **GVBATCH_SIGNATURES, **BATCH_RANGE_SIGNATURES}.items():
         fn = getattr(lib, name)  # AttributeError = header/library mismatch: fail loudly
         fn.restype = res
         fn.argtypes = args

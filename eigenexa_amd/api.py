@@ -506,6 +506,64 @@ def eigen_h_batch(n, batch, a, lda, w, z, ldz, mode="A", info=None, stride_a=Non
     _solve_batch("h", n, batch, a, lda, w, z, ldz, mode, info, stride_a, ldw, stride_z)
 
 
+def eigen_s_batch_range(n, batch, il, iu, a, lda, w, z, ldz, mode="A", info=None, stride_a=None, ldw=None, stride_z=None):
+    """EXTENSION (not in the reference): eigenpairs ``il .. iu`` (1-based, inclusive, the same window for every matrix) of
+    ``batch`` symmetric matrices of one size ``n`` in one call, one GPU.  ``a`` as for ``eigen_s_batch``.  With
+    ``m = iu - il + 1``: ``w[ldw, batch]`` receives ``w[:m, k]``, ascending; ``z[ldz, m, batch]`` the eigenvectors
+    ``z[:n, :m, k]`` (mode 'A'; mode 'N': eigenvalues only, ``z`` may be None).  Defaults: ``stride_a = lda * n``,
+    ``stride_z = ldz * m``, ``ldw = m``.  ``info`` and ``last_status()`` as for ``eigen_s_batch``.  For ``n <= 128`` either a
+    window kernel (tridiagonalisation, Sturm-count bisection, inverse iteration and Rayleigh-Ritz in LDS, no QL sweep) or the
+    kernel of ``eigen_s_batch`` with a slice solves the batch, by a measured rule (``eigx_tune`` key 26);
+    ``batch_range_info()`` tells which.  Larger ``n`` runs ``eigen_s_range`` matrix by matrix."""
+    name = "eigen_s_batch_range"
+    # the arguments are checked here, before the library is touched (status -2 = EIGX_ERR_BAD_ARG)
+    md = _char(mode, "A").upper()
+    m = None
+    try:
+        n, batch, il, iu, lda = int(n), int(batch), int(il), int(iu), int(lda)
+        m = iu - il + 1
+        ldw = m if ldw is None else int(ldw)
+        ldz = int(ldz) if md == b"A" else (0 if ldz is None else int(ldz))
+        stride_a = lda * n if stride_a is None else int(stride_a)
+        stride_z = ldz * m if stride_z is None else int(stride_z)
+        ok = n >= 1 and batch >= 0 and 1 <= il <= iu <= n and lda >= n and ldw >= m and md in (b"A", b"N")
+        ok = ok and a is not None and w is not None and (batch <= 1 or stride_a >= lda * n)
+        if md == b"A":
+            ok = ok and z is not None and ldz >= n and (batch <= 1 or stride_z >= ldz * m)
+    except (TypeError, ValueError):
+        ok = False
+    if not ok:
+        _state["last_status"] = -2
+        print(f"Warning: {name}: invalid arguments (n={n}, batch={batch}, il={il}, iu={iu}, lda={lda}, ldw={ldw}, ldz={ldz}, "
+              f"stride_a={stride_a}, stride_z={stride_z}, mode={mode!r})", file=sys.stderr)
+        return
+    began = _begin(a)
+    if began is None:
+        return
+    lib, dev = began
+    if md != b"A":
+        z = None
+    for x, xname in ((a, "a"), (w, "w"), (z, "z")):
+        if x is not None and not dev and not _is_torch(x) and x.ndim > 2 and not x.flags.f_contiguous:
+            raise ValueError(f"{xname}: Fortran (column-major) order required, as in the reference")
+    pa, pw, pz = _addrs("s", dev, a=a, w=w, z=z)
+    pi = _info_addr(info, dev, "a, w, z, info")
+    rc = _entry(lib, "eigx_s_batch_range", dev)(n, batch, il, iu, pa, lda, stride_a, pw, ldw, pz, ldz, stride_z, md, pi)
+    _finish(name, rc, (0, -5, -6))
+
+
+def batch_range_info():
+    """What the last ``eigen_s_batch_range`` call did: ``route`` (1 the window kernel, 2 the full batch solve and a slice, 3
+    ``eigen_s_range`` matrix by matrix above the cutoff), ``m`` and ``redone`` (how many matrices the acceptance test of the
+    window kernel sent to route 2)."""
+    import collections
+
+    lib = _lib.load()
+    r, m, d = C.c_int(), C.c_int(), C.c_int()
+    _lib.check(lib.eigx_batch_range_info(C.byref(r), C.byref(m), C.byref(d)), "eigx_batch_range_info")
+    return collections.namedtuple("BatchRangeInfo", "route m redone")(r.value, m.value, d.value)
+
+
 def _solve_vbatch(which, batch, n, a, off_a, lda, w, off_w, z, off_z, ldz, mode, info, pencil=None):
     """the ragged wrappers; pencil = (b, off_b, ldb) for the generalised families, which need all three in both modes"""
     name = f"eigen_{which}_vbatch"

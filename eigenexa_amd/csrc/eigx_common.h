@@ -178,5 +178,9 @@ int set_hgbatch_nmax(int v);
 // the current values of keys 23 and 24: the ragged pencil batches (gvbatch.hip, hgvbatch.hip) apply them block by block
 int get_gbatch_nmax();
 int get_hgbatch_nmax();
+// tuning hooks (eigx_tune keys 26 and 27, batch_range.hip): the route of eigx_s_batch_range (0 automatic, 1 the window kernel
+// wherever eligible, 2 the full solve and a slice) and the acceptance bound of the window kernel in percent, 0 .. 101
+int set_batch_range_route(int v);
+int set_batch_range_accept(int v);
 
 }  // namespace eigx

@@ -35,6 +35,7 @@ module eigen_libs_mod
   public :: eigen_sx_range_v, eigen_s_range_v   ! EXTENSION: the eigenpairs with vl <= lambda < vu (one GPU)
   public :: eigen_h_range, eigen_h_range_v   ! EXTENSION: both kinds of window for the complex Hermitian solver (one GPU)
   public :: eigen_s_batch   ! EXTENSION: many small symmetric matrices in one call (one GPU)
+  public :: eigen_s_batch_range   ! EXTENSION: eigenpairs il .. iu of many small symmetric matrices in one call (one GPU)
   public :: eigen_h_batch   ! EXTENSION: many small complex Hermitian matrices in one call (one GPU)
   public :: eigen_s_vbatch  ! EXTENSION: many small symmetric matrices of differing sizes in one call (one GPU)
   public :: eigen_h_vbatch  ! EXTENSION: many small complex Hermitian matrices of differing sizes in one call (one GPU)
@@ -143,6 +144,17 @@ module eigen_libs_mod
         bind(C, name="eigx_s_batch")
       import :: c_int, c_int64_t, c_double, c_char
       integer(c_int), value :: n, batch, lda, ldw, ldz
+      integer(c_int64_t), value :: stride_a, stride_z
+      real(c_double), intent(inout) :: a(*)
+      real(c_double), intent(inout) :: w(*), z(*)
+      character(kind=c_char), value :: mode
+      integer(c_int), intent(out), optional :: info(*)
+    end function
+    ! EXTENSION (not in the reference): eigenpairs il .. iu of batch symmetric matrices of one size, one GPU
+    integer(c_int) function eigx_s_batch_range(n, batch, il, iu, a, lda, stride_a, w, ldw, z, ldz, stride_z, mode, info) &
+        bind(C, name="eigx_s_batch_range")
+      import :: c_int, c_int64_t, c_double, c_char
+      integer(c_int), value :: n, batch, il, iu, lda, ldw, ldz
       integer(c_int64_t), value :: stride_a, stride_z
       real(c_double), intent(inout) :: a(*)
       real(c_double), intent(inout) :: w(*), z(*)
@@ -795,6 +807,27 @@ contains
     rc = eigx_s_batch(n, batch, a, lda, int(lda, c_int64_t) * size(a, 2), w, size(w, 1), z, ldz, &
                       int(ldz, c_int64_t) * size(z, 2), md, info)
   end subroutine eigen_s_batch
+
+  !> eigen_s_batch_range(n, batch, il, iu, a, lda, w, z, ldz, mode, info) -- EXTENSION, not in the reference: eigenpairs
+  !> il .. iu (of the ascending spectrum, the same window for every matrix) of batch symmetric matrices a(:, :, k) of one size n
+  !> on one GPU.  Upper triangles significant, a destroyed; with m = iu - il + 1, w(1:m, k) ascending and z(1:n, 1:m, k)
+  !> orthonormal (w needs m rows, z m columns); modes 'A' and 'N' (z not written).  info(k) = 0, or the status of matrix k
+  !> (-5: NaN / Inf, w(1:m, k) = NaN); the other matrices are solved all the same.  For n <= 128 one launch of a window kernel
+  !> (bisection and inverse iteration in LDS) or of eigen_s_batch's kernel with a slice, by a measured rule; larger n by
+  !> eigen_s_range matrix by matrix.
+  subroutine eigen_s_batch_range(n, batch, il, iu, a, lda, w, z, ldz, mode, info)
+    integer, intent(in) :: n, batch, il, iu, lda, ldz
+    real(8), intent(inout), contiguous :: a(:, :, :)
+    real(8), intent(inout), contiguous :: w(:, :), z(:, :, :)
+    character(*), intent(in), optional :: mode
+    integer, intent(out), optional :: info(*)
+    integer :: rc
+    character(kind=c_char) :: md
+    md = 'A'
+    if (present(mode)) md = mode(1:1)
+    rc = eigx_s_batch_range(n, batch, il, iu, a, lda, int(lda, c_int64_t) * size(a, 2), w, size(w, 1), z, ldz, &
+                            int(ldz, c_int64_t) * size(z, 2), md, info)
+  end subroutine eigen_s_batch_range
 
   !> eigen_h_batch(n, batch, a, lda, w, z, ldz, mode, info) -- EXTENSION, not in the reference: the eigenpairs of batch complex
   !> Hermitian matrices a(:, :, k) of one size n on one GPU, in one kernel launch for n <= 96 (one workgroup per matrix, the
