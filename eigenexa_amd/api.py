@@ -446,26 +446,38 @@ def _info_addr(info, dev, names):
     return info.data_ptr() if dev else info.ctypes.data
 
 
-def _solve_batch(which, n, batch, a, lda, w, z, ldz, mode, info, stride_a, ldw, stride_z):
-    name = f"eigen_{which}_batch"
+def _solve_batch(which, n, batch, a, lda, w, z, ldz, mode, info, stride_a, ldw, stride_z, window=None, pencil=None):
+    """the uniform-batch wrappers; window = (il, iu) for eigen_s_batch_range (z has m = iu - il + 1 columns and w has m entries per
+    matrix, otherwise n), pencil = (b, ldb, stride_b) for the generalised families"""
+    name = f"eigen_{which}_batch" + ("_range" if window else "")
+    has_b = pencil is not None
+    il, iu = window or (None, None)
+    b, ldb, stride_b = pencil or (None, None, None)
     # the arguments are checked here, before the library is touched (status -2 = EIGX_ERR_BAD_ARG)
     md = _char(mode, "A").upper()
     try:
-        n, batch, lda = int(n), int(batch), int(lda)
-        ldw = n if ldw is None else int(ldw)
+        n, batch, il, iu, lda, ldb = (int(x) if used else None for x, used in (
+            (n, True), (batch, True), (il, window), (iu, window), (lda, True), (ldb, has_b)))   # (all of them, or none)
+        m = iu - il + 1 if window else n
+        ldw = m if ldw is None else int(ldw)
         ldz = int(ldz) if md == b"A" else (0 if ldz is None else int(ldz))
         stride_a = lda * n if stride_a is None else int(stride_a)
-        stride_z = ldz * n if stride_z is None else int(stride_z)
-        ok = n >= 1 and batch >= 0 and lda >= n and ldw >= n and md in (b"A", b"N") and a is not None and w is not None
-        ok = ok and (batch <= 1 or stride_a >= lda * n)
+        if has_b:
+            stride_b = ldb * n if stride_b is None else int(stride_b)
+        stride_z = ldz * m if stride_z is None else int(stride_z)
+        ok = n >= 1 and batch >= 0 and lda >= n and ldw >= m and md in (b"A", b"N") and a is not None and w is not None
+        ok = ok and (not window or 1 <= il <= iu <= n) and (batch <= 1 or stride_a >= lda * n)
+        ok = ok and (not has_b or (ldb >= n and b is not None and (batch <= 1 or stride_b >= ldb * n)))
         if md == b"A":
-            ok = ok and z is not None and ldz >= n and (batch <= 1 or stride_z >= ldz * n)
+            ok = ok and z is not None and ldz >= n and (batch <= 1 or stride_z >= ldz * m)
     except (TypeError, ValueError):
         ok = False
     if not ok:
         _state["last_status"] = -2
-        print(f"Warning: {name}: invalid arguments (n={n}, batch={batch}, lda={lda}, ldw={ldw}, ldz={ldz}, "
-              f"stride_a={stride_a}, stride_z={stride_z}, mode={mode!r})", file=sys.stderr)
+        shown = [("n", n), ("batch", batch)] + ([("il", il), ("iu", iu)] if window else []) + [("lda", lda)]
+        shown += ([("ldb", ldb)] if has_b else []) + [("ldw", ldw), ("ldz", ldz), ("stride_a", stride_a)]
+        shown += ([("stride_b", stride_b)] if has_b else []) + [("stride_z", stride_z)]
+        print(f"Warning: {name}: invalid arguments ({', '.join(f'{key}={v}' for key, v in shown)}, mode={mode!r})", file=sys.stderr)
         return
     began = _begin(a)
     if began is None:
@@ -473,13 +485,15 @@ def _solve_batch(which, n, batch, a, lda, w, z, ldz, mode, info, stride_a, ldw, 
     lib, dev = began
     if md != b"A":
         z = None
-    for x, xname in ((a, "a"), (w, "w"), (z, "z")):
+    arrays = dict(a=a, **(dict(b=b) if has_b else {}), w=w, z=z)
+    for xname, x in arrays.items():
         if x is not None and not dev and not _is_torch(x) and x.ndim > 2 and not x.flags.f_contiguous:
             raise ValueError(f"{xname}: Fortran (column-major) order required, as in the reference")
-    pa, pw, pz = _addrs(which, dev, a=a, w=w, z=z)
-    pi = _info_addr(info, dev, "a, w, z, info")
-    rc = _entry(lib, f"eigx_{which}_batch", dev)(n, batch, pa, lda, stride_a, pw, ldw, pz, ldz, stride_z, md, pi)
-    _finish(name, rc, (0, -5, -6))
+    p = dict(zip(arrays, _addrs(which, dev, **arrays)))
+    pi = _info_addr(info, dev, f"{', '.join(arrays)}, info")
+    args = (n, batch) + ((il, iu) if window else ()) + (p["a"], lda, stride_a) + ((p["b"], ldb, stride_b) if has_b else ())
+    rc = _entry(lib, name.replace("eigen_", "eigx_"), dev)(*args, p["w"], ldw, p["z"], ldz, stride_z, md, pi)
+    _finish(name, rc, (0, -5, -6, -7) if has_b else (0, -5, -6))
 
 
 def eigen_s_batch(n, batch, a, lda, w, z, ldz, mode="A", info=None, stride_a=None, ldw=None, stride_z=None):
@@ -515,41 +529,7 @@ def eigen_s_batch_range(n, batch, il, iu, a, lda, w, z, ldz, mode="A", info=None
     window kernel (tridiagonalisation, Sturm-count bisection, inverse iteration and Rayleigh-Ritz in LDS, no QL sweep) or the
     kernel of ``eigen_s_batch`` with a slice solves the batch, by a measured rule (``eigx_tune`` key 26);
     ``batch_range_info()`` tells which.  Larger ``n`` runs ``eigen_s_range`` matrix by matrix."""
-    name = "eigen_s_batch_range"
-    # the arguments are checked here, before the library is touched (status -2 = EIGX_ERR_BAD_ARG)
-    md = _char(mode, "A").upper()
-    m = None
-    try:
-        n, batch, il, iu, lda = int(n), int(batch), int(il), int(iu), int(lda)
-        m = iu - il + 1
-        ldw = m if ldw is None else int(ldw)
-        ldz = int(ldz) if md == b"A" else (0 if ldz is None else int(ldz))
-        stride_a = lda * n if stride_a is None else int(stride_a)
-        stride_z = ldz * m if stride_z is None else int(stride_z)
-        ok = n >= 1 and batch >= 0 and 1 <= il <= iu <= n and lda >= n and ldw >= m and md in (b"A", b"N")
-        ok = ok and a is not None and w is not None and (batch <= 1 or stride_a >= lda * n)
-        if md == b"A":
-            ok = ok and z is not None and ldz >= n and (batch <= 1 or stride_z >= ldz * m)
-    except (TypeError, ValueError):
-        ok = False
-    if not ok:
-        _state["last_status"] = -2
-        print(f"Warning: {name}: invalid arguments (n={n}, batch={batch}, il={il}, iu={iu}, lda={lda}, ldw={ldw}, ldz={ldz}, "
-              f"stride_a={stride_a}, stride_z={stride_z}, mode={mode!r})", file=sys.stderr)
-        return
-    began = _begin(a)
-    if began is None:
-        return
-    lib, dev = began
-    if md != b"A":
-        z = None
-    for x, xname in ((a, "a"), (w, "w"), (z, "z")):
-        if x is not None and not dev and not _is_torch(x) and x.ndim > 2 and not x.flags.f_contiguous:
-            raise ValueError(f"{xname}: Fortran (column-major) order required, as in the reference")
-    pa, pw, pz = _addrs("s", dev, a=a, w=w, z=z)
-    pi = _info_addr(info, dev, "a, w, z, info")
-    rc = _entry(lib, "eigx_s_batch_range", dev)(n, batch, il, iu, pa, lda, stride_a, pw, ldw, pz, ldz, stride_z, md, pi)
-    _finish(name, rc, (0, -5, -6))
+    _solve_batch("s", n, batch, a, lda, w, z, ldz, mode, info, stride_a, ldw, stride_z, window=(il, iu))
 
 
 def batch_range_info():
@@ -610,18 +590,12 @@ def _solve_vbatch(which, batch, n, a, off_a, lda, w, off_w, z, off_z, ldz, mode,
     if not want_vec:
         z = None
     pd = {key: (None if v is None else v.ctypes.data) for key, v in desc.items()}
-    if has_b:
-        pa, pb, pw, pz = _addrs(which, dev, a=a, b=b, w=w, z=z)
-        pi = _info_addr(info, dev, "a, b, w, z, info")
-        rc = _entry(lib, f"eigx_{which}_vbatch", dev)(batch, pd["n"], pa, pd["off_a"], pd["lda"], pb, pd["off_b"], pd["ldb"], pw,
-                                                     pd["off_w"], pz, pd["off_z"], pd["ldz"], md, pi)
-        _finish(name, rc, (0, -5, -6, -7))
-        return
-    pa, pw, pz = _addrs(which, dev, a=a, w=w, z=z)
-    pi = _info_addr(info, dev, "a, w, z, info")
-    rc = _entry(lib, f"eigx_{which}_vbatch", dev)(batch, pd["n"], pa, pd["off_a"], pd["lda"], pw, pd["off_w"], pz, pd["off_z"],
-                                                 pd["ldz"], md, pi)
-    _finish(name, rc, (0, -5, -6))
+    arrays = dict(a=a, **(dict(b=b) if has_b else {}), w=w, z=z)
+    p = dict(zip(arrays, _addrs(which, dev, **arrays)))
+    pi = _info_addr(info, dev, f"{', '.join(arrays)}, info")
+    args = (batch, pd["n"], p["a"], pd["off_a"], pd["lda"]) + ((p["b"], pd["off_b"], pd["ldb"]) if has_b else ())
+    rc = _entry(lib, f"eigx_{which}_vbatch", dev)(*args, p["w"], pd["off_w"], p["z"], pd["off_z"], pd["ldz"], md, pi)
+    _finish(name, rc, (0, -5, -6, -7) if has_b else (0, -5, -6))
 
 
 def eigen_s_vbatch(batch, n, a, off_a, lda, w, off_w, z, off_z, ldz, mode="A", info=None):
@@ -648,44 +622,6 @@ def eigen_h_vbatch(batch, n, a, off_a, lda, w, off_w, z, off_z, ldz, mode="A", i
     _solve_vbatch("h", batch, n, a, off_a, lda, w, off_w, z, off_z, ldz, mode, info)
 
 
-def _solve_pencil_batch(which, n, batch, a, lda, b, ldb, w, z, ldz, mode, info, stride_a, stride_b, ldw, stride_z):
-    name = f"eigen_{which}_batch"
-    # the arguments are checked here, before the library is touched (status -2 = EIGX_ERR_BAD_ARG)
-    md = _char(mode, "A").upper()
-    try:
-        n, batch, lda, ldb = int(n), int(batch), int(lda), int(ldb)
-        ldw = n if ldw is None else int(ldw)
-        ldz = int(ldz) if md == b"A" else (0 if ldz is None else int(ldz))
-        stride_a = lda * n if stride_a is None else int(stride_a)
-        stride_b = ldb * n if stride_b is None else int(stride_b)
-        stride_z = ldz * n if stride_z is None else int(stride_z)
-        ok = n >= 1 and batch >= 0 and lda >= n and ldb >= n and ldw >= n and md in (b"A", b"N")
-        ok = ok and a is not None and b is not None and w is not None
-        ok = ok and (batch <= 1 or (stride_a >= lda * n and stride_b >= ldb * n))
-        if md == b"A":
-            ok = ok and z is not None and ldz >= n and (batch <= 1 or stride_z >= ldz * n)
-    except (TypeError, ValueError):
-        ok = False
-    if not ok:
-        _state["last_status"] = -2
-        print(f"Warning: {name}: invalid arguments (n={n}, batch={batch}, lda={lda}, ldb={ldb}, ldw={ldw}, ldz={ldz}, "
-              f"stride_a={stride_a}, stride_b={stride_b}, stride_z={stride_z}, mode={mode!r})", file=sys.stderr)
-        return
-    began = _begin(a)
-    if began is None:
-        return
-    lib, dev = began
-    if md != b"A":
-        z = None
-    for x, xname in ((a, "a"), (b, "b"), (w, "w"), (z, "z")):
-        if x is not None and not dev and not _is_torch(x) and x.ndim > 2 and not x.flags.f_contiguous:
-            raise ValueError(f"{xname}: Fortran (column-major) order required, as in the reference")
-    pa, pb, pw, pz = _addrs(which, dev, a=a, b=b, w=w, z=z)
-    pi = _info_addr(info, dev, "a, b, w, z, info")
-    rc = _entry(lib, f"eigx_{which}_batch", dev)(n, batch, pa, lda, stride_a, pb, ldb, stride_b, pw, ldw, pz, ldz, stride_z, md, pi)
-    _finish(name, rc, (0, -5, -6, -7))
-
-
 def eigen_gev_batch(n, batch, a, lda, b, ldb, w, z, ldz, mode="A", info=None, stride_a=None, stride_b=None, ldw=None, stride_z=None):
     """EXTENSION (not in the reference): ``batch`` symmetric-definite pencils ``A x = lambda B x`` of one size ``n`` in one call,
     one GPU.  ``a[lda, n, batch]`` and ``b[ldb, n, batch]`` (numpy, Fortran order, or GPU tensors with the same memory image:
@@ -697,7 +633,7 @@ def eigen_gev_batch(n, batch, a, lda, b, ldb, w, z, ldz, mode="A", info=None, st
     NaN, its ``z`` and ``b`` untouched), -7 (B not positive definite: ``w`` NaN, ``z`` untouched) or -6; ``last_status()`` is 0
     or the status of the first failed pencil.  For ``n <= 96`` one kernel launch solves the batch, one workgroup per pencil
     with both matrices in LDS; larger ``n`` runs ``KMATH_EIGEN_GEV_RANGE`` with ``il = 1, iu = n`` pencil by pencil."""
-    _solve_pencil_batch("gev", n, batch, a, lda, b, ldb, w, z, ldz, mode, info, stride_a, stride_b, ldw, stride_z)
+    _solve_batch("gev", n, batch, a, lda, w, z, ldz, mode, info, stride_a, ldw, stride_z, pencil=(b, ldb, stride_b))
 
 
 def eigen_hgev_batch(n, batch, a, lda, b, ldb, w, z, ldz, mode="A", info=None, stride_a=None, stride_b=None, ldw=None, stride_z=None):
@@ -711,7 +647,7 @@ def eigen_hgev_batch(n, batch, a, lda, b, ldb, w, z, ldz, mode="A", info=None, s
     ``last_status()`` as for ``eigen_gev_batch``; leading dimensions and strides count complex elements.  For ``n <= 64`` one
     kernel launch solves the batch, one workgroup per pencil with both matrices in LDS; larger ``n`` runs
     ``KMATH_EIGEN_HGEV_RANGE`` with ``il = 1, iu = n`` pencil by pencil."""
-    _solve_pencil_batch("hgev", n, batch, a, lda, b, ldb, w, z, ldz, mode, info, stride_a, stride_b, ldw, stride_z)
+    _solve_batch("hgev", n, batch, a, lda, w, z, ldz, mode, info, stride_a, ldw, stride_z, pencil=(b, ldb, stride_b))
 
 
 def eigen_gev_vbatch(batch, n, a, off_a, lda, b, off_b, ldb, w, off_w, z, off_z, ldz, mode="A", info=None):

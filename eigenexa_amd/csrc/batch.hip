@@ -8,10 +8,8 @@
 // No workgroup talks to another: no grid-wide barrier, no spin-wait, no atomics on the data.  Every sum is taken in an order
 // that depends on n alone, so a matrix's result does not depend on its position in the batch or on the batch size.
 // Matrices larger than the cutoff (eigx_tune key 21) go through solve_dev (eigen_s) one by one.
-// This file also holds the host side of all three batch families (eigx_h_batch: hbatch.hip, eigx_gev_batch: gbatch.hip): the
-// argument check, the device entry (batch_frame_dev: prologue, the loop above the cutoff, the launch and its first-failure
-// word, the timers), the host entry (batch_frame_host: staging in the pool, copy in, copy back) and copy_blocks.  A family
-// supplies its kernel launch by n-class and its full-size solve of one matrix; the kernels share batch_common.h.
+// Here: the kernel, the cutoff and the two functions the frame of the batch families asks for (batch_frame_dev / batch_frame_host,
+// batch_frame.hip): the launch by n-class and the full-size solve of one matrix.  The kernels of the families share batch_common.h.
 #include "eigx_context.h"
 #include "batch_common.h"
 #include "../../include/eigenexa_amd.h"
@@ -123,129 +121,6 @@ int set_batch_nmax(int v) {
   return old;
 }
 int get_batch_nmax() { return g_batch_nmax; }
-
-// ---- the frame of the three families (declared in eigx_context.h) ------------------------------------------------------------
-bool batch_status_per_matrix(int rc) {   // (solve_dev and herm_solve_dev never return EIGX_ERR_NOT_SPD: one set serves all)
-  return rc == EIGX_OK || rc == EIGX_ERR_NONFINITE || rc == EIGX_ERR_NOT_SPD || rc == EIGX_ERR_INTERNAL;
-}
-
-void copy_blocks(void* dst, int ldd, int64_t sd, const void* src, int lds, int64_t ss, int n, int b0, int nb, int esz, hipMemcpyKind kind) {
-  if (nb <= 0) return;
-  char* d = (char*)dst;
-  const char* s = (const char*)src;
-  const size_t e = (size_t)esz;
-  if (sd == (int64_t)ldd * n && ss == (int64_t)lds * n) {
-    EIGX_HIP_CHECK(hipMemcpy2D(d + e * b0 * sd, e * ldd, s + e * b0 * ss, e * lds, e * n, (size_t)n * nb, kind));
-    return;
-  }
-  for (int k = b0; k < b0 + nb; ++k) EIGX_HIP_CHECK(hipMemcpy2D(d + e * k * sd, e * ldd, s + e * k * ss, e * lds, e * n, (size_t)n, kind));
-}
-
-// what both entries require of their arguments (mode in upper case)
-static bool batch_args_ok(const BatchArgs& g) {
-  const int n = g.n, batch = g.batch;
-  if (n < 1 || batch < 0 || g.lda < n || g.ldw < n || (g.mode != 'A' && g.mode != 'N')) return false;
-  if (batch > 1 && g.stride_a < (int64_t)g.lda * n) return false;
-  if (g.has_b && (g.ldb < n || (batch > 1 && g.stride_b < (int64_t)g.ldb * n))) return false;
-  if (g.mode == 'A' && (g.ldz < n || (batch > 1 && g.stride_z < (int64_t)g.ldz * n))) return false;
-  if (batch > 0 && (!g.a || (g.has_b && !g.b) || !g.w || (g.mode == 'A' && !g.z))) return false;
-  return true;
-}
-// What both entries begin with.  Returns true to go on (g.mode in upper case, the device set), or false with the status to
-// return in rc: a refusal, or EIGX_OK for an empty batch.
-static bool batch_begin(Context& ctx, BatchArgs& g, int& rc) {
-  rc = EIGX_OK;
-  if (!ctx.initialized) {
-    rc = EIGX_ERR_NOT_INITIALIZED;
-    return false;
-  }
-  if (ctx.grid.nranks != 1) {
-    rc = refuse_several_ranks(ctx);
-    return false;
-  }
-  g.mode = upper_case(g.mode);
-  if (!batch_args_ok(g)) {
-    rc = EIGX_ERR_BAD_ARG;
-    return false;
-  }
-  if (g.batch == 0) return false;
-  EIGX_HIP_CHECK(hipSetDevice(ctx.device));
-  return true;
-}
-
-int batch_frame_dev(Context& ctx, BatchArgs g, int cutoff, BatchLaunch launch, BatchSolveOne solve_one) {
-  int rc;
-  if (!batch_begin(ctx, g, rc)) return rc;
-  EIGX_HIP_CHECK(hipStreamSynchronize(nullptr));   // the caller's default-stream work on the arguments (SolveFrame::begin)
-  const double t0 = now_s();
-  ctx.errinfo = 0;
-  hipStream_t st = ctx.stream;
-  if (g.n > cutoff) {
-    // above the cutoff: the full-size solver, matrix by matrix; the first failure is the call's status
-    for (int k = 0; k < g.batch; ++k) {
-      const int rk = solve_one(ctx, g, k);
-      if (!batch_status_per_matrix(rk)) return rk;   // nothing per matrix: out of memory, ...
-      if (g.info) EIGX_HIP_CHECK(hipMemcpy(g.info + k, &rk, sizeof(int), hipMemcpyHostToDevice));
-      if (rc == EIGX_OK) rc = rk;
-    }
-  } else {
-    unsigned long long* first = ctx.pool.get_t<unsigned long long>("batch.first", 1);
-    // memset 0xff of the first-failure word: all ones = "no matrix failed"; a failed one leaves (index << 8 | -code) by atomicMin
-    EIGX_HIP_CHECK(hipMemsetAsync(first, 0xff, sizeof(unsigned long long), st));
-    launch(g, st, first);
-    EIGX_HIP_CHECK(hipGetLastError());
-    unsigned long long f = 0;
-    EIGX_HIP_CHECK(hipMemcpyAsync(&f, first, sizeof(f), hipMemcpyDeviceToHost, st));
-    EIGX_HIP_CHECK(hipStreamSynchronize(st));
-    if (f != ~0ull) {                    // (index << 8 | -code) of the first matrix that failed
-      rc = -(int)(f & 0xff);
-      ctx.errinfo = -1;
-    }
-  }
-  for (int q = 0; q < 16; ++q) ctx.timers[q] = 0.0;
-  ctx.timers[0] = now_s() - t0;
-  return rc;
-}
-
-// Host arrays: a, b, z and w are staged in the pool buffers of the other host forms (host.a / host.b / host.z, or host.ha / host.hz
-// at 16 bytes per element, and host.w; leading dimension host_ld(n)), the per-matrix status words in batch.info.  info and w
-// come back for every matrix; z (mode 'A') and b (U, every mode) for those that succeeded: a failed matrix's stay untouched.
-int batch_frame_host(Context& ctx, BatchArgs g, int cutoff, BatchLaunch launch, BatchSolveOne solve_one) {
-  int rc;
-  if (!batch_begin(ctx, g, rc)) return rc;
-  const int n = g.n, batch = g.batch, esz = g.esz, ldd = host_ld(n);
-  const bool want_vec = g.mode == 'A', cplx = esz == 16;
-  const int64_t sd = (int64_t)ldd * n;
-  const size_t bytes = (size_t)esz * sd * batch;
-  BatchArgs dv = g;                      // the same call on the staged arrays
-  dv.a = (double*)ctx.pool.get(cplx ? "host.ha" : "host.a", bytes);
-  dv.b = g.has_b ? (double*)ctx.pool.get(cplx ? "host.hb" : "host.b", bytes) : nullptr;
-  dv.z = want_vec ? (double*)ctx.pool.get(cplx ? "host.hz" : "host.z", bytes) : nullptr;
-  dv.w = ctx.pool.get_t<double>("host.w", (size_t)n * batch);
-  dv.info = ctx.pool.get_t<int>("batch.info", (size_t)batch);
-  dv.lda = dv.ldb = dv.ldz = ldd;
-  dv.stride_a = dv.stride_b = dv.stride_z = sd;
-  dv.ldw = n;
-  const int64_t sa = batch > 1 ? g.stride_a : (int64_t)g.lda * n, sb = batch > 1 ? g.stride_b : (int64_t)g.ldb * n,
-                sz = batch > 1 ? g.stride_z : (int64_t)g.ldz * n;
-  copy_blocks(dv.a, ldd, sd, g.a, g.lda, sa, n, 0, batch, esz, hipMemcpyHostToDevice);
-  if (g.has_b) copy_blocks(dv.b, ldd, sd, g.b, g.ldb, sb, n, 0, batch, esz, hipMemcpyHostToDevice);
-  rc = batch_frame_dev(ctx, dv, cutoff, launch, solve_one);
-  if (!batch_status_per_matrix(rc)) return rc;
-  std::vector<int> ih((size_t)batch);
-  EIGX_HIP_CHECK(hipMemcpy(ih.data(), dv.info, (size_t)batch * sizeof(int), hipMemcpyDeviceToHost));
-  EIGX_HIP_CHECK(hipMemcpy2D(g.w, (size_t)g.ldw * 8, dv.w, (size_t)n * 8, (size_t)n * 8, (size_t)batch, hipMemcpyDeviceToHost));
-  // z and b come back in runs of matrices that succeeded (one copy_blocks per run): what the caller holds for a failed one stays
-  for (int k = 0; k < batch;) {
-    int k1 = k;
-    while (k1 < batch && ih[k1] == EIGX_OK) ++k1;
-    if (want_vec) copy_blocks(g.z, g.ldz, sz, dv.z, ldd, sd, n, k, k1 - k, esz, hipMemcpyDeviceToHost);
-    if (g.has_b) copy_blocks(g.b, g.ldb, sb, dv.b, ldd, sd, n, k, k1 - k, esz, hipMemcpyDeviceToHost);
-    k = k1 + 1;
-  }
-  if (g.info) std::copy(ih.begin(), ih.end(), g.info);
-  return rc;
-}
 
 }  // namespace eigx
 

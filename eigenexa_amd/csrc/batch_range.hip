@@ -528,30 +528,10 @@ bool brange_args_ok(const RangeBatchArgs& g) {
   if (batch > 0 && (!g.a || !g.w || (g.mode == 'A' && !g.z))) return false;
   return true;
 }
-// what both entries begin with (batch_begin of batch.hip): true to go on, or false with the status to return in rc
-bool brange_begin(Context& ctx, RangeBatchArgs& g, int& rc) {
-  rc = EIGX_OK;
-  if (!ctx.initialized) {
-    rc = EIGX_ERR_NOT_INITIALIZED;
-    return false;
-  }
-  if (ctx.grid.nranks != 1) {
-    rc = refuse_several_ranks(ctx);
-    return false;
-  }
-  g.mode = upper_case(g.mode);
-  if (!brange_args_ok(g)) {
-    rc = EIGX_ERR_BAD_ARG;
-    return false;
-  }
-  if (g.batch == 0) return false;
-  EIGX_HIP_CHECK(hipSetDevice(ctx.device));
-  return true;
-}
 
 int brange_frame_dev(Context& ctx, RangeBatchArgs g) {
   int rc;
-  if (!brange_begin(ctx, g, rc)) return rc;
+  if (!batch_entry_begin(ctx, g.mode, g.batch, [&] { return brange_args_ok(g); }, rc)) return rc;
   EIGX_HIP_CHECK(hipStreamSynchronize(nullptr));   // the caller's default-stream work on the arguments
   const double t0 = now_s();
   hipStream_t st = ctx.stream;
@@ -560,22 +540,21 @@ int brange_frame_dev(Context& ctx, RangeBatchArgs g) {
   g_last.redone = 0;
   if (n > get_batch_nmax()) {
     // route 3: the index-range solver of one large matrix (eigx_s_range_dev with the interface's default block sizes), matrix by
-    // matrix; the first failure is the call's status
+    // matrix; unlike the uniform frame this one sets errinfo to -1 after a failed matrix (the table of DESIGN section 8h)
     g_last.route = 3;
-    for (int k = 0; k < batch; ++k) {
-      const int rk = range_solve_dev(ctx, n, RangeWindow::index(g.il, g.iu), g.a + (size_t)k * g.stride_a, g.lda, g.w + (size_t)k * g.ldw,
-                                     g.mode == 'A' ? g.z + (size_t)k * g.stride_z : nullptr, g.ldz, 48, 128, g.mode, 1, false);
-      if (!batch_status_per_matrix(rk)) return rk;
-      if (g.info) EIGX_HIP_CHECK(hipMemcpy(g.info + k, &rk, sizeof(int), hipMemcpyHostToDevice));
-      if (rc == EIGX_OK) rc = rk;
-    }
+    rc = batch_loop_above_cutoff(batch, g.info, [&](int k) {
+      return range_solve_dev(ctx, n, RangeWindow::index(g.il, g.iu), g.a + (size_t)k * g.stride_a, g.lda, g.w + (size_t)k * g.ldw,
+                             g.mode == 'A' ? g.z + (size_t)k * g.stride_z : nullptr, g.ldz, 48, 128, g.mode, 1, false);
+    });
+    if (!batch_status_per_matrix(rc)) return rc;
     ctx.errinfo = rc == EIGX_OK ? 0 : -1;
   } else {
     const bool eligible = g.mode == 'N' || m <= window_width(n);
     const bool one = g_route_key == 2 ? false : eligible && (g_route_key == 1 || route1_measured_faster(n, g.mode, m));
     g_last.route = one ? 1 : 2;
-    unsigned long long* first = ctx.pool.get_t<unsigned long long>("brange.first", 1);
-    EIGX_HIP_CHECK(hipMemsetAsync(first, 0xff, sizeof(unsigned long long), st));   // all ones = "no matrix failed"
+    FirstFailure ff;                     // a word of its own: route 2's eigx_s_batch_dev arms batch.first while this one is live
+    ff.arm(ctx, "brange.first", st);
+    unsigned long long* first = ff.dev;
     if (one) {
       int* redo = ctx.pool.get_t<int>("brange.redo", (size_t)batch);
       brange_launch(g, st, first, redo);
@@ -597,61 +576,24 @@ int brange_frame_dev(Context& ctx, RangeBatchArgs g) {
       const int rr = brange_full_and_slice(ctx, g, 0, batch, first);
       if (rr != EIGX_OK) return rr;
     }
-    unsigned long long f = 0;
-    EIGX_HIP_CHECK(hipMemcpyAsync(&f, first, sizeof(f), hipMemcpyDeviceToHost, st));
-    EIGX_HIP_CHECK(hipStreamSynchronize(st));
     ctx.errinfo = 0;
-    if (f != ~0ull) {                    // (index << 8 | -code) of the first matrix that failed
-      rc = -(int)(f & 0xff);
-      ctx.errinfo = -1;
-    }
+    ff.finish(ctx, st, rc);
   }
-  for (int q = 0; q < 16; ++q) ctx.timers[q] = 0.0;
-  ctx.timers[0] = now_s() - t0;
+  batch_entry_end(ctx, t0);
   return rc;
 }
 
-// Host arrays: a, w and z are staged in pool buffers (leading dimension host_ld(n), z with m columns per matrix), the per-matrix
-// status words beside them.  info and w come back for every matrix, z (mode 'A') for runs of matrices that succeeded.
+// Host arrays: batch_stage_host (batch_frame.hip) with m columns of z and m entries of w per matrix, in pool buffers of this
+// entry's own (brange.h*: the names are part of the description of the entry in include/eigenexa_amd_batch_range.h).
 int brange_frame_host(Context& ctx, RangeBatchArgs g) {
   int rc;
-  if (!brange_begin(ctx, g, rc)) return rc;
-  const int n = g.n, batch = g.batch, m = g.m(), ldd = host_ld(n);
-  const bool want_vec = g.mode == 'A';
-  const int64_t sda = (int64_t)ldd * n, sdz = (int64_t)ldd * m;
-  RangeBatchArgs dv = g;
-  dv.a = ctx.pool.get_t<double>("brange.ha", (size_t)sda * batch);
-  dv.z = want_vec ? ctx.pool.get_t<double>("brange.hz", (size_t)sdz * batch) : nullptr;
-  dv.w = ctx.pool.get_t<double>("brange.hw", (size_t)m * batch);
-  dv.info = ctx.pool.get_t<int>("brange.hinfo", (size_t)batch);
-  dv.lda = dv.ldz = ldd;
-  dv.stride_a = sda;
-  dv.stride_z = sdz;
-  dv.ldw = m;
-  const int64_t sa = batch > 1 ? g.stride_a : (int64_t)g.lda * n, sz = batch > 1 ? g.stride_z : (int64_t)g.ldz * m;
-  copy_blocks(dv.a, ldd, sda, g.a, g.lda, sa, n, 0, batch, 8, hipMemcpyHostToDevice);
-  rc = brange_frame_dev(ctx, dv);
-  if (!batch_status_per_matrix(rc)) return rc;
-  std::vector<int> ih((size_t)batch);
-  EIGX_HIP_CHECK(hipMemcpy(ih.data(), dv.info, (size_t)batch * sizeof(int), hipMemcpyDeviceToHost));
-  EIGX_HIP_CHECK(hipMemcpy2D(g.w, (size_t)g.ldw * 8, dv.w, (size_t)m * 8, (size_t)m * 8, (size_t)batch, hipMemcpyDeviceToHost));
-  if (want_vec)
-    for (int k = 0; k < batch;) {
-      int k1 = k;
-      while (k1 < batch && ih[k1] == EIGX_OK) ++k1;
-      if (k1 > k) {
-        if (sz == (int64_t)g.ldz * m)    // evenly spaced columns on both sides: one copy for the run
-          EIGX_HIP_CHECK(hipMemcpy2D(g.z + (size_t)k * sz, (size_t)g.ldz * 8, dv.z + (size_t)k * sdz, (size_t)ldd * 8, (size_t)n * 8,
-                                     (size_t)m * (k1 - k), hipMemcpyDeviceToHost));
-        else
-          for (int q = k; q < k1; ++q)
-            EIGX_HIP_CHECK(hipMemcpy2D(g.z + (size_t)q * sz, (size_t)g.ldz * 8, dv.z + (size_t)q * sdz, (size_t)ldd * 8, (size_t)n * 8,
-                                       (size_t)m, hipMemcpyDeviceToHost));
-      }
-      k = k1 + 1;
-    }
-  if (g.info) std::copy(ih.begin(), ih.end(), g.info);
-  return rc;
+  if (!batch_entry_begin(ctx, g.mode, g.batch, [&] { return brange_args_ok(g); }, rc)) return rc;
+  const BatchArgs u{g.n, g.batch, g.a, g.lda, g.stride_a, nullptr, 0, 0, g.w, g.ldw, g.z, g.ldz, g.stride_z, g.mode, g.info, 8, false};
+  static const BatchStageNames names{"brange.ha", nullptr, "brange.hz", "brange.hw", "brange.hinfo"};
+  return batch_stage_host(ctx, u, g.m(), g.m(), names, [&](const BatchArgs& dv) {
+    return brange_frame_dev(ctx, RangeBatchArgs{g.n, g.batch, g.il, g.iu, dv.a, dv.lda, dv.stride_a, dv.w, dv.ldw, dv.z, dv.ldz,
+                                                dv.stride_z, g.mode, dv.info});
+  });
 }
 
 }  // namespace

@@ -316,7 +316,34 @@ struct SolveFrame {
 inline int host_ld(int nr) { return pad_ld(nr + 2); }
 void* host_to_dev(Context& ctx, const char* name, const void* h, int ld, int nr, int nc, int esz);
 void dev_to_host(void* h, int ld, const void* d, int ldd, int nr, int nc, int esz);
-// batch.hip: the frame of the batched small solvers (batch.hip, hbatch.hip, gbatch.hip, hgbatch.hip).  BatchArgs is a
+// batch_frame.hip: the host frame of the batched entries, uniform, ragged and windowed.  First the pieces every
+// frame is made of.
+// A status that belongs to one matrix of a batch (the others are solved all the same), not to the call: out of memory, ...
+bool batch_status_per_matrix(int rc);
+// What every entry, host or device form, begins with: not initialised -> its status; several ranks -> refuse_several_ranks; mode
+// to upper case; args_ok() (the family's predicate, which reads the mode in upper case) false -> EIGX_ERR_BAD_ARG; an empty batch
+// -> EIGX_OK; hipSetDevice.  Returns true to go on, or false with the status to return in rc.
+bool batch_entry_begin(Context& ctx, char& mode, int batch, const std::function<bool()>& args_ok, int& rc);
+// What every device form ends with: timers[0 .. 15] = 0, then timers[0] = the seconds since t0.
+void batch_entry_end(Context& ctx, double t0);
+// The first-failure word of a call: a pooled unsigned long long on the device, all ones = "nothing failed"; a matrix that fails
+// leaves (its index << 8 | -status) in it by atomicMin (report_failure, batch_common.h), so the lowest index wins.  arm: take the
+// word from the pool and set it on `st`; dev goes to the launches; merge adds a failure found on the host (the ragged frame's
+// blocks above the cutoff); finish reads the word back on `st` (not armed: nothing to read), drains `st` and, if anything
+// failed, sets rc to that status and ctx.errinfo to -1 -- otherwise it leaves both alone.
+// The pool name is a parameter because calls nest: route 2 of the windowed frame calls eigx_s_batch_dev, which arms batch.first
+// while the outer call's word (brange.first) is live.
+struct FirstFailure {
+  unsigned long long* dev = nullptr;
+  unsigned long long host = ~0ull;
+  void arm(Context& ctx, const char* name, hipStream_t st);
+  void merge(int k, int rc);
+  void finish(Context& ctx, hipStream_t st, int& rc);
+};
+// The loop above the cutoff of a uniform batch: solve_one(k) for every matrix, its status into info[k] (device; may be null).
+// Returns the first failure (or EIGX_OK), or at once a status that is not per matrix.  It does not touch ctx.errinfo.
+int batch_loop_above_cutoff(int batch, int* info, const std::function<int(int)>& solve_one);
+// The uniform frame (batch.hip, hbatch.hip, gbatch.hip, hgbatch.hip).  BatchArgs is a
 // call: the entry's arguments, b / ldb / stride_b for a family with has_b only, and esz = bytes per element of a, b and z (8, or
 // 16: interleaved complex, leading dimensions and strides in elements).  A family supplies its cutoff (n above it goes to the
 // full-size solver) and two functions: launch its kernel on `st` for the n-class of g.n (with_n_class; `first` is the launch's
@@ -344,15 +371,20 @@ void with_n_class(int n, F&& f) {
   if (TOP == 96 || n <= 96) return f(std::integral_constant<int, 96>());
   if constexpr (TOP == 128) f(std::integral_constant<int, 128>());
 }
-// a status that belongs to one matrix of a batch (the others are solved all the same), not to the call: out of memory, ...
-bool batch_status_per_matrix(int rc);
-// copy (kind: any direction) of the n x n blocks b0 .. b0 + nb - 1 of a strided batch of elements of esz bytes, block k at
+// copy (kind: any direction) of the nr x nc blocks b0 .. b0 + nb - 1 of a strided batch of elements of esz bytes, block k at
 // dst + k sd / src + k ss (in elements) with leading dimensions ldd / lds; one call where both sides are evenly spaced columns
-void copy_blocks(void* dst, int ldd, int64_t sd, const void* src, int lds, int64_t ss, int n, int b0, int nb, int esz, hipMemcpyKind kind);
+void copy_blocks(void* dst, int ldd, int64_t sd, const void* src, int lds, int64_t ss, int nr, int nc, int b0, int nb, int esz,
+                 hipMemcpyKind kind);
+// Host staging of a uniform batch (g: host arrays, mode in upper case; z has zcols columns and w has nw entries per matrix): a,
+// b, z, w and the status words in the pool buffers `names` with the leading dimension host_ld(n), a and b copied in, dev_form on
+// the staged arrays; info and w come back for every matrix, z and b for runs of consecutive matrices that succeeded.
+struct BatchStageNames { const char *a, *b, *z, *w, *info; };
+int batch_stage_host(Context& ctx, const BatchArgs& g, int zcols, int nw, const BatchStageNames& names,
+                     const std::function<int(const BatchArgs&)>& dev_form);
 // the device entry (device arrays; g.info may be null) and the host entry (host arrays) of a family
 int batch_frame_dev(Context& ctx, BatchArgs g, int cutoff, BatchLaunch launch, BatchSolveOne solve_one);
 int batch_frame_host(Context& ctx, BatchArgs g, int cutoff, BatchLaunch launch, BatchSolveOne solve_one);
-// vbatch.hip: the frame of the ragged batches (vbatch.hip: eigx_s_vbatch, hvbatch.hip: eigx_h_vbatch).  VbArgs is
+// The ragged frame (vbatch.hip: eigx_s_vbatch, hvbatch.hip: eigx_h_vbatch).  VbArgs is
 // a call: block k is a + off_a[k] (leading dimension lda[k]) of order n[k], its eigenvalues go to w + off_w[k], its
 // eigenvectors to z + off_z[k] (ldz[k]); the six descriptor arrays are host arrays of `batch` entries, offsets and leading
 // dimensions in elements of esz bytes (w: doubles).  VbDesc is what a workgroup reads of its block (k = the caller's index; its

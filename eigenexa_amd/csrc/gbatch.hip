@@ -219,7 +219,7 @@ using namespace eigx;
 
 extern "C" {
 
-// EXTENSION: `batch` symmetric-definite pencils of one size (one GPU); see batch_frame_host / batch_frame_dev (batch.hip)
+// EXTENSION: `batch` symmetric-definite pencils of one size (one GPU); see batch_frame_host / batch_frame_dev (batch_frame.hip)
 int eigx_gev_batch(int n, int batch, double* a, int lda, int64_t stride_a, double* b, int ldb, int64_t stride_b, double* w, int ldw,
                    double* z, int ldz, int64_t stride_z, char mode, int* info) {
   const BatchArgs g{n, batch, a, lda, stride_a, b, ldb, stride_b, w, ldw, z, ldz, stride_z, mode, info, 8, true};

@@ -183,7 +183,7 @@ using namespace eigx;
 
 extern "C" {
 
-// EXTENSION: `batch` symmetric-definite pencils of their own sizes (one GPU); see vbatch_frame_host / vbatch_frame_dev (vbatch.hip)
+// EXTENSION: `batch` symmetric-definite pencils of their own sizes (one GPU); see vbatch_frame_host / vbatch_frame_dev (batch_frame.hip)
 int eigx_gev_vbatch(int batch, const int* n, double* a, const int64_t* off_a, const int* lda, double* b, const int64_t* off_b,
                     const int* ldb, double* w, const int64_t* off_w, double* z, const int64_t* off_z, const int* ldz, char mode,
                     int* info) {

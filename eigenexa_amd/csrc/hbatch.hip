@@ -151,7 +151,7 @@ using namespace eigx;
 extern "C" {
 
 // EXTENSION: `batch` complex Hermitian eigenproblems of one size (one GPU; a, z interleaved complex; lda, ldz and the strides in
-// complex elements); see batch_frame_host / batch_frame_dev (batch.hip)
+// complex elements); see batch_frame_host / batch_frame_dev (batch_frame.hip)
 int eigx_h_batch(int n, int batch, double* a, int lda, int64_t stride_a, double* w, int ldw, double* z, int ldz, int64_t stride_z,
                  char mode, int* info) {
   const BatchArgs g{n, batch, a, lda, stride_a, nullptr, 0, 0, w, ldw, z, ldz, stride_z, mode, info, 16, false};

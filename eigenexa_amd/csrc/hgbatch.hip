@@ -232,7 +232,7 @@ using namespace eigx;
 extern "C" {
 
 // EXTENSION: `batch` Hermitian-definite pencils of one size (one GPU; a, b, z interleaved complex; lda, ldb, ldz and the strides
-// in complex elements); see batch_frame_host / batch_frame_dev (batch.hip)
+// in complex elements); see batch_frame_host / batch_frame_dev (batch_frame.hip)
 int eigx_hgev_batch(int n, int batch, double* a, int lda, int64_t stride_a, double* b, int ldb, int64_t stride_b, double* w, int ldw,
                     double* z, int ldz, int64_t stride_z, char mode, int* info) {
   const BatchArgs g{n, batch, a, lda, stride_a, b, ldb, stride_b, w, ldw, z, ldz, stride_z, mode, info, 16, true};

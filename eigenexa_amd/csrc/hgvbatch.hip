@@ -217,7 +217,7 @@ using namespace eigx;
 extern "C" {
 
 // EXTENSION: `batch` Hermitian-definite pencils of their own sizes (one GPU; a, b, z interleaved complex; offsets and leading
-// dimensions in complex elements); see vbatch_frame_host / vbatch_frame_dev (vbatch.hip)
+// dimensions in complex elements); see vbatch_frame_host / vbatch_frame_dev (batch_frame.hip)
 int eigx_hgev_vbatch(int batch, const int* n, double* a, const int64_t* off_a, const int* lda, double* b, const int64_t* off_b,
                      const int* ldb, double* w, const int64_t* off_w, double* z, const int64_t* off_z, const int* ldz, char mode,
                      int* info) {

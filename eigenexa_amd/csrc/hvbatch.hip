@@ -124,7 +124,7 @@ using namespace eigx;
 extern "C" {
 
 // EXTENSION: `batch` complex Hermitian eigenproblems of their own sizes (one GPU; a, z interleaved complex; offsets and leading
-// dimensions in complex elements); see vbatch_frame_host / vbatch_frame_dev (vbatch.hip)
+// dimensions in complex elements); see vbatch_frame_host / vbatch_frame_dev (batch_frame.hip)
 int eigx_h_vbatch(int batch, const int* n, double* a, const int64_t* off_a, const int* lda, double* w, const int64_t* off_w, double* z,
                   const int64_t* off_z, const int* ldz, char mode, int* info) {
   const VbArgs g{batch, n, a, off_a, lda, w, off_w, z, off_z, ldz, mode, info, 16};

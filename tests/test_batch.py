@@ -249,6 +249,46 @@ def test_failures_are_local(gpu_lib):
         _check_matrix(mats[k], w[k], Z[k], f"matrix {k} beside failed ones")
 
 
+def errinfo_case():
+    """three 5 x 5 matrices, a NaN in the upper triangle of the second (tests/test_vbatch.py uses them too)"""
+    from eigenexa_amd import layout
+
+    mats = [layout.random_symmetric(5, seed=40 + k) for k in range(3)]
+    mats[1][1, 3] = mats[1][3, 1] = np.nan
+    return mats
+
+
+def errinfo_after(lib):
+    err = C.c_int64(77)
+    assert lib.eigx_get_errinfo(C.byref(err)) == 0
+    return err.value
+
+
+# errinfo after a call in which one matrix failed, as the library before the shared host frame (csrc/batch_frame.hip) returned it
+# on a GPU: the kernel's first-failure word sets -1, the loop above the cutoff leaves the 0 the call began with (the table of
+# DESIGN section 8h)
+ERRINFO_AFTER_FAILURE = {"kernel": -1, "loop": 0}
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("route", ["kernel", "loop"])
+def test_errinfo_after_a_failed_matrix(gpu_lib, route):
+    """device form; route "loop": key 21 = 4, so that n = 5 goes matrix by matrix through eigx_s_dev"""
+    B = Batch(errinfo_case())
+    old = gpu_lib.eigx_tune(21, 4) if route == "loop" else None
+    try:
+        rc = B.run(gpu_lib)
+        err = errinfo_after(gpu_lib)
+    finally:
+        if old is not None:
+            assert gpu_lib.eigx_tune(21, old) == 4
+    w, Z, info = B.results()
+    print(f"eigx_s_batch_dev, {route}: status {rc}, info {info.tolist()}, errinfo {err}")
+    assert rc == NONFINITE and info.tolist() == [0, NONFINITE, 0]
+    assert np.isnan(w[1]).all() and np.isfinite(w[[0, 2]]).all()
+    assert err == ERRINFO_AFTER_FAILURE[route]
+
+
 # ------------------------------------------------------------------------------------------------ 5. position independence
 @pytest.mark.gpu
 def test_position_independence_and_reproducibility(gpu_lib):

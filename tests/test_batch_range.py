@@ -432,6 +432,40 @@ def test_host_and_device_forms_agree(gpu_lib):
 
 
 @pytest.mark.gpu
+def test_host_form_with_gapped_blocks_of_z_and_a_failed_matrix(gpu_lib):
+    """n = 5, il .. iu = 2 .. 4, three matrices, a NaN in the middle one, mode 'A'; z with ldz = n + 1 and stride_z = ldz m + 7 (the
+    layout of RBatch), so the m columns of a matrix come back by a copy of their own.  The block of the failed matrix, the padding
+    rows and the gaps keep what the caller passed; the other two blocks are those of the device form bit for bit."""
+    from eigenexa_amd import layout
+
+    n, nb, il, iu = 5, 3, 2, 4
+    m = iu - il + 1
+    mats = [layout.random_symmetric(n, seed=70 + k) for k in range(nb)]
+    mats[1][0, 3] = mats[1][3, 0] = np.nan
+    B = RBatch(mats, il, iu)
+    assert (B.ldz, B.stride_z) == (n + 1, (n + 1) * m + 7)
+    assert B.run(gpu_lib) == NONFINITE
+    wd, Zd, infod = B.results()
+    assert infod.tolist() == [0, NONFINITE, 0] and np.isfinite(Zd[[0, 2]]).all()
+    a = B.a_host.copy()
+    w, z = np.full(B.ldw * nb, GUARD), np.full(B.stride_z * nb, GUARD)
+    info = np.full(nb, 77, dtype=np.int32)
+    rc = gpu_lib.eigx_s_batch_range(n, nb, il, iu, a.ctypes.data, B.lda, B.stride_a, w.ctypes.data, B.ldw, z.ctypes.data, B.ldz,
+                                    B.stride_z, b"A", info.ctypes.data)
+    assert rc == NONFINITE and info.tolist() == [0, NONFINITE, 0]
+    zb = z.reshape(nb, B.stride_z)
+    assert (zb[1] == GUARD).all(), "z of the failed matrix was touched"
+    assert (zb[:, B.ldz * m:] == GUARD).all(), "the gaps between the eigenvector blocks were touched"
+    zz = zb[:, :B.ldz * m].reshape(nb, m, B.ldz)
+    assert (zz[:, :, n:] == GUARD).all(), "rows of z beyond n were touched"
+    wh = w.reshape(nb, B.ldw)
+    assert (wh[:, m:] == GUARD).all() and np.isnan(wh[1, :m]).all()
+    for k in (0, 2):
+        assert np.array_equal(wh[k, :m].view(np.int64), wd[k].view(np.int64)), k
+        assert np.array_equal(np.ascontiguousarray(zz[k, :, :n].T).view(np.int64), np.ascontiguousarray(Zd[k]).view(np.int64)), k
+
+
+@pytest.mark.gpu
 def test_arguments(gpu_lib):
     from eigenexa_amd import layout
 

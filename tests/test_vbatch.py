@@ -419,6 +419,32 @@ def test_above_the_cutoff(gpu_lib):
     check_above_cutoff(gpu_lib, S)
 
 
+# errinfo after a call in which one block failed, as the library before the shared host frame (csrc/batch_frame.hip) returned it on
+# a GPU: the ragged frame merges the failures of the blocks above the cutoff into the first-failure word, so both routes set -1
+# (the uniform entry leaves 0 above the cutoff: tests/test_batch.py and the table of DESIGN section 8h)
+ERRINFO_AFTER_FAILURE = {"kernel": -1, "loop": -1}
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("route", ["kernel", "loop"])
+def test_errinfo_after_a_failed_block(gpu_lib, route):
+    """device form, the three 5 x 5 matrices of tests/test_batch.py; route "loop": key 21 = 4, so that every block goes through
+    eigx_s_dev"""
+    R = Ragged(S, tb.errinfo_case())
+    old = gpu_lib.eigx_tune(21, 4) if route == "loop" else None
+    try:
+        rc = R.run(gpu_lib)
+        err = tb.errinfo_after(gpu_lib)
+    finally:
+        if old is not None:
+            assert gpu_lib.eigx_tune(21, old) == 4
+    ws, Zs, info = R.results()
+    print(f"eigx_s_vbatch_dev, {route}: status {rc}, info {info.tolist()}, errinfo {err}")
+    assert rc == NONFINITE and info.tolist() == [0, NONFINITE, 0]
+    assert np.isnan(ws[1]).all() and np.isfinite(ws[0]).all() and np.isfinite(ws[2]).all()
+    assert err == ERRINFO_AFTER_FAILURE[route]
+
+
 # ------------------------------------------------------------------------------------------------ 7. empty blocks
 def check_empty(lib, fam):
     dt = np.float64 if fam.cs == 1 else np.complex128

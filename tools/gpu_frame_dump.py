@@ -9,8 +9,9 @@ eigx_hgev_range_dev and their stages (Cholesky, triangular solves, reduction; ei
 the status, w, z and the arrays a / b as the call leaves them.  Then the real generalised solvers eigx_gev[_range][_dev],
 the value-window solves (m and il as well), the host forms of all four generalised solvers and their statuses (non-finite
 A or B, B not positive definite, a bad window, ldb < n) from sentinel-filled w and z.  An array above 8 MiB is stored as
-its SHA-256.  Last the batched small solvers eigx_s_batch, eigx_h_batch and eigx_gev_batch (batch_section below); --batch
-runs that section alone (well under a minute).
+its SHA-256.  Last the nine batched families -- the uniform eigx_{s,h,gev,hgev}_batch, the ragged eigx_{s,h,gev,hgev}_vbatch and
+the windowed eigx_s_batch_range, host and device forms (batch_section below); --batch runs that section alone (well under a
+minute).
 The library is deterministic, so two builds that compute the same leave directories that `cmp` finds equal:
     for f in A/*; do cmp $f B/$(basename $f); done
 Run each build in a fresh process.  --quick leaves out n >= 2048."""
@@ -46,15 +47,21 @@ def save(label, **arrays):
 
 
 def batch_section():
-    """eigx_{s,h,gev}_batch[_dev], modes A and N and mode A with info = NULL, at n = 1, 2, 17, 33, 64, 96 (s: 128 too) and, with
-    the cutoff key lowered to 32, at n = 40 through the full-size solvers (gev: odd and even leading dimensions).  A batch is the
-    families of the family's test file, the first of them scaled by 1e-200 and by 1e+200, one matrix with a NaN and (gev) one
-    pencil with an indefinite B.  Padded leading dimensions and strides, NaN outside the upper triangles, w / z / info prefilled;
-    recorded: the status and the whole buffers w, z, info and (gev) b as the call leaves them."""
+    """eigx_{s,h,gev,hgev}_batch[_dev], modes A and N and mode A with info = NULL, at n = 1, 2, 17, 33, 64 (s, h, gev: 96, s: 128
+    too) and, with the cutoff key lowered to 32, at n = 40 through the full-size solvers (gev: odd and even leading dimensions).
+    A batch is the families of the family's test file, the first of them scaled by 1e-200 and by 1e+200, one matrix with a NaN
+    and (gev, hgev) one pencil with an indefinite B.  Padded leading dimensions and strides, NaN outside the upper triangles,
+    w / z / info prefilled; recorded: the status, the whole buffers w, z, info and (gev, hgev) b as the call leaves them, errinfo
+    and the timers with entry 0 (the seconds of the call) set to zero.  Then the four ragged entries (ragged below) and
+    eigx_s_batch_range[_dev] (window below) at n = 17, 64, 100 with the windows (1, 1), (2, 5), (n - 3, n), each with key 26 = 1,
+    key 26 = 2 and keys 26 = 1, 27 = 101, and at n = 40 with key 21 = 32; of these also eigx_batch_range_info."""
     sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests"))
     import test_batch
     import test_gbatch
+    import test_gvbatch
     import test_hbatch
+    import test_hgbatch
+    import test_vbatch
 
     def image(mats, ld, stride, cplx):
         """upper triangles (complex: interleaved, Im of the diagonal NaN); NaN in the lower triangles, the padding and the gaps"""
@@ -68,8 +75,21 @@ def batch_section():
                 v[:, :n, 1] = np.where(upper & ~np.eye(n, dtype=bool), M.T.imag, np.nan)
         return buf
 
+    def frame_record(window=False):
+        """what the frame leaves beside the arrays: errinfo, the timers without the seconds of the call and, of the windowed
+        entry, (route, m, redone)"""
+        err, t = C.c_int64(0), (C.c_double * 16)()
+        lib.eigx_get_errinfo(C.byref(err))
+        lib.eigx_get_timers(t)
+        rec = dict(errinfo=np.int64(err.value), timers=np.array([0.0] + t[1:]))
+        if window:
+            r, m, d = C.c_int(-1), C.c_int(-1), C.c_int(-1)
+            lib.eigx_batch_range_info(C.byref(r), C.byref(m), C.byref(d))
+            rec["brinfo"] = np.array([r.value, m.value, d.value], dtype=np.int64)
+        return rec
+
     def one(fam, n, even, tag):
-        cplx, gev = fam == "h", fam == "gev"
+        cplx, gev = fam in ("h", "hgev"), fam in ("gev", "hgev")
         mats = (test_hbatch if cplx else test_batch)._families(n)
         bad = mats[0].copy()
         bad[0, n - 1] = bad[n - 1, 0] = np.nan
@@ -78,12 +98,12 @@ def batch_section():
         lda, ldb, ldz, ldw = (n + 4, n + 2, n + 2, n + 2) if even else (n + 3, n + 2, n + 1, n + 2)
         sa, sb, sz = lda * n + 5, ldb * n + 3, ldz * n + 7
         if gev:
-            ov = test_gbatch._overlaps(n)
+            ov = (test_hgbatch if cplx else test_gbatch)._overlaps(n)
             indef = ov[0].copy()
             indef[n // 2, n // 2] = -1.0
             mats, bs = mats + [mats[1]], [ov[k % len(ov)] for k in range(nb - 1)] + [indef]
         a0 = image(mats, lda, sa, cplx)
-        b0 = image(bs, ldb, sb, False) if gev else None
+        b0 = image(bs, ldb, sb, cplx) if gev else None
         c = 2 if cplx else 1
         for form in ("dev", "host"):
             fn = getattr(lib, f"eigx_{fam}_batch" + ("_dev" if form == "dev" else ""))
@@ -103,9 +123,10 @@ def batch_section():
                     torch.cuda.synchronize()
                     arrs = {k: v.cpu().numpy() for k, v in arrs.items()}
                 del arrs["a"]
-                save(f"{fam}batch_{form}_n{n}{tag}_{mode}{'' if with_info else '_noinfo'}", rc=np.int64(rc), **arrs)
+                save(f"{fam}batch_{form}_n{n}{tag}_{mode}{'' if with_info else '_noinfo'}", rc=np.int64(rc), **arrs, **frame_record())
 
-    for fam, key, sizes in (("s", 21, (1, 2, 17, 33, 64, 96, 128)), ("h", 22, (1, 2, 17, 33, 64, 96)), ("gev", 23, (1, 2, 17, 33, 64, 96))):
+    for fam, key, sizes in (("s", 21, (1, 2, 17, 33, 64, 96, 128)), ("h", 22, (1, 2, 17, 33, 64, 96)), ("gev", 23, (1, 2, 17, 33, 64, 96)),
+                            ("hgev", 24, (1, 2, 17, 33, 64))):
         for n in sizes:
             one(fam, n, False, "")
         cutoff = lib.eigx_tune(key, 32)
@@ -113,6 +134,87 @@ def batch_section():
         if fam == "gev":
             one(fam, 40, True, "_loop_evenld")
         lib.eigx_tune(key, cutoff)
+
+    def ragged(fam, pencil):
+        """One call per form and mode of a ragged entry, in the buffers of the family's test file (gaps in front of every block,
+        NaN outside the upper triangles, guards in w, z and info): orders 0, 1, 2, 17, 33, 64, `mid` and the largest the kernels
+        serve, with the cutoff key lowered to `mid` -- an order of the top class, so every class is launched and the largest block
+        alone goes through the full-size solver -- then a block with a NaN and (pencil families) one with an indefinite B."""
+        mid = {128: 100, 96: 80, 64: 40}[fam.top]
+        orders = [n for n in (0, 1, 2, 17, 33, 64) if n < mid] + [mid, fam.top]
+        dt = np.float64 if fam.cs == 1 else np.complex128
+
+        def pick(n, k):
+            """member k of the family's matrices of order n: (A,) or (A, B)"""
+            lists = fam.mixed(n) if pencil else (fam.families(n),)
+            return tuple(x[k % len(x)] for x in lists)
+
+        blocks = [pick(n, k) if n else (np.zeros((0, 0), dtype=dt),) * (1 + pencil) for k, n in enumerate(orders)]
+        bad = pick(17, 0)[0].copy()
+        bad[0, 16] = bad[16, 0] = np.nan
+        blocks.append((bad,) + pick(17, 0)[1:])
+        if pencil:
+            indef = pick(33, 1)[1].copy()
+            indef[16, 16] = -1.0
+            blocks.append((pick(33, 1)[0], indef))
+        lists = [list(x) for x in zip(*blocks)]
+        cutoff = lib.eigx_tune(fam.key, mid)
+        for form in ("dev", "host"):
+            for mode, with_info in (("A", True), ("N", True), ("A", False)):
+                R = (test_gvbatch.RaggedPencils if pencil else test_vbatch.Ragged)(fam, *lists, device=form == "dev")
+                rc = R.run(lib, mode=mode.encode(), info=with_info, z=mode == "A", host=form == "host")
+                if form == "dev":
+                    torch.cuda.synchronize()
+                img = R.images(host=form == "host")
+                arrs = dict(zip(("w", "z", "b", "info") if pencil else ("w", "z", "info"), img))
+                save(f"{fam.name}vbatch_{form}_{mode}{'' if with_info else '_noinfo'}", rc=np.int64(rc), **arrs, **frame_record())
+        lib.eigx_tune(fam.key, cutoff)
+
+    for fam, pencil in ((test_vbatch.S, False), (test_vbatch.H, False), (test_gvbatch.G, True), (test_gvbatch.HG, True)):
+        ragged(fam, pencil)
+
+    def window(n, il, iu, tag):
+        """eigx_s_batch_range[_dev], modes A and N, on the batch of one("s", ...): z with m columns per matrix"""
+        m = iu - il + 1
+        mats = test_batch._families(n)
+        bad = mats[0].copy()
+        bad[0, n - 1] = bad[n - 1, 0] = np.nan
+        mats = mats + [mats[0] * 1e-200, mats[0] * 1e200, bad]
+        nb = len(mats)
+        lda, ldz, ldw = n + 3, n + 1, m + 2
+        sa, sz = lda * n + 5, ldz * m + 7
+        a0 = image(mats, lda, sa, False)
+        for form in ("dev", "host"):
+            fn = getattr(lib, "eigx_s_batch_range" + ("_dev" if form == "dev" else ""))
+            for mode in "AN":
+                arrs = dict(a=a0.copy(), w=np.full(ldw * nb, SENT_B), z=np.full(sz * nb, SENT_B), info=np.full(nb, 77, dtype=np.int32))
+                if form == "dev":
+                    arrs = {k: torch.from_numpy(v).to(dev) for k, v in arrs.items()}
+                    ptr = {k: v.data_ptr() for k, v in arrs.items()}
+                else:
+                    ptr = {k: v.ctypes.data for k, v in arrs.items()}
+                rc = fn(n, nb, il, iu, ptr["a"], lda, sa, ptr["w"], ldw, ptr["z"] if mode == "A" else None, ldz, sz, mode.encode(),
+                        ptr["info"])
+                if form == "dev":
+                    torch.cuda.synchronize()
+                    arrs = {k: v.cpu().numpy() for k, v in arrs.items()}
+                del arrs["a"]
+                save(f"sbrange_{form}_n{n}_{il}_{iu}{tag}_{mode}", rc=np.int64(rc), **arrs, **frame_record(window=True))
+
+    for n in (17, 64, 100):
+        for il, iu in ((1, 1), (2, 5), (n - 3, n)):
+            for route in (1, 2):
+                old = lib.eigx_tune(26, route)
+                window(n, il, iu, f"_route{route}")
+                lib.eigx_tune(26, old)
+            old, accept = lib.eigx_tune(26, 1), lib.eigx_tune(27, 101)   # the window kernel refuses every matrix: all are redone
+            window(n, il, iu, "_refused")
+            lib.eigx_tune(26, old)
+            lib.eigx_tune(27, accept)
+    cutoff = lib.eigx_tune(21, 32)
+    for il, iu in ((1, 1), (2, 5), (37, 40)):
+        window(40, il, iu, "_loop")
+    lib.eigx_tune(21, cutoff)
 
 
 SENT_B = -7.25   # what w and z of the batch section start from
