@@ -179,7 +179,7 @@ VBATCH_SIGNATURES = {
     "eigx_vbatch_plan": (C.c_int, [_INT, _PTR, _INT, _INT, _PTR, _PTR]),
 }
 
-# The same for include/eigenexa_amd_gvbatch.h -- extension: ragged batches of pencils (csrc/gvbatch.hip, csrc/hgvbatch.hip,
+# The same for include/eigenexa_amd_gvbatch.h -- extension: ragged batches of pencils (csrc/gvbatch.hip, csrc/hgbatch.hip,
 # DESIGN 8m).  The eight descriptor arrays (n, off_a, lda, off_b, ldb, off_w, off_z, ldz) are host arrays in both forms.
 # batch, n, a, off_a, lda, b, off_b, ldb, w, off_w, z, off_z, ldz, mode, info
 _GVBATCH = [_INT, _PTR, _PTR, _PTR, _PTR, _PTR, _PTR, _PTR, _PTR, _PTR, _PTR, _PTR, _PTR, C.c_char, _PTR]

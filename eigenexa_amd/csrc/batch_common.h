@@ -77,8 +77,8 @@ __device__ inline void fail_matrix(int k, int code, bool row, int r, double* w, 
   if (threadIdx.x == 0) report_failure(first, info, k, code);
   __syncthreads();
 }
-// The same for a workgroup that serves one block of a ragged batch (gvbatch.hip, hgvbatch.hip) and ends with it: the block's
-// eigenvalues are at wk, k is its caller index; no barrier.
+// The same for a workgroup that serves one block and ends with it (gvbatch.hip; hgbatch.hip, whose kernel serves the uniform and
+// the ragged entry): the block's eigenvalues are at wk, k is its caller index; no barrier.
 __device__ inline void fail_block(int k, int code, bool row, int r, double* wk, int* info, unsigned long long* first) {
   if (row) wk[r] = std::numeric_limits<double>::quiet_NaN();
   if (threadIdx.x == 0) report_failure(first, info, k, code);

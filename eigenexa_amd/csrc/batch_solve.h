@@ -1,7 +1,7 @@
 // batch_solve.h -- the triangular substitutions of the one-workgroup-per-pencil kernels, one thread per column or row of the
 // matrix held in LDS, against the Cholesky factor U held in LDS beside it: solve_ut / solve_u for the real kernels
-// (gbatch.hip: gbatch_kernel, gvbatch.hip: gvbatch_kernel), zsolve_ut / zsolve_u on split planes for the complex ones
-// (hgbatch.hip: hgbatch_kernel, hgvbatch.hip: hgvbatch_kernel).  The uniform and the ragged kernel of a family call the same
+// (gbatch.hip: gbatch_kernel, gvbatch.hip: gvbatch_kernel), zsolve_ut / zsolve_u on split planes for the complex one
+// (hgbatch.hip: hgbatch_kernel, which serves both entries).  The uniform and the ragged entry of a family call the same
 // code, so a pencil's bits do not depend on the entry that solved it.
 #pragma once
 #include <hip/hip_runtime.h>

@@ -175,9 +175,9 @@ int get_hbatch_nmax();
 int set_gbatch_nmax(int v);
 // tuning hook (eigx_tune key 24, hgbatch.hip): largest n served by the batch kernel of eigx_hgev_batch, 0 .. EIGX_HGBATCH_NMAX
 int set_hgbatch_nmax(int v);
-// the current values of keys 23 and 24: the ragged pencil batches (gvbatch.hip, hgvbatch.hip) apply them block by block
+// the current value of key 23: the ragged pencil batch of gvbatch.hip applies it block by block (eigx_hgev_vbatch sits in
+// hgbatch.hip beside key 24)
 int get_gbatch_nmax();
-int get_hgbatch_nmax();
 // tuning hooks (eigx_tune keys 26 and 27, batch_range.hip): the route of eigx_s_batch_range (0 automatic, 1 the window kernel
 // wherever eligible, 2 the full solve and a slice) and the acceptance bound of the window kernel in percent, 0 .. 101
 int set_batch_range_route(int v);

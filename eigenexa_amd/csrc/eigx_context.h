@@ -400,7 +400,7 @@ struct VbArgs {
   double* z; const int64_t* off_z; const int* ldz;
   char mode; int* info;
   int esz;
-  // the pencil families (gvbatch.hip: eigx_gev_vbatch, hgvbatch.hip: eigx_hgev_vbatch) only: has_b, and
+  // the pencil families (gvbatch.hip: eigx_gev_vbatch, hgbatch.hip: eigx_hgev_vbatch) only: has_b, and
   // the second matrix of block k at b + off_b[k] with the leading dimension ldb[k], required in both modes
   bool has_b = false;
   double* b = nullptr; const int64_t* off_b = nullptr; const int* ldb = nullptr;
@@ -419,9 +419,8 @@ int vbatch_frame_dev(Context& ctx, VbArgs g, int cutoff, int top, VbLaunch launc
 int vbatch_frame_host(Context& ctx, VbArgs g, int cutoff, int top, VbLaunch launch, VbSolveOne solve_one);
 int vbatch_frame_dev(Context& ctx, VbArgs g, int cutoff, int top, VbPencilLaunch launch, VbSolveOne solve_one);
 int vbatch_frame_host(Context& ctx, VbArgs g, int cutoff, int top, VbPencilLaunch launch, VbSolveOne solve_one);
-// gbatch.hip, hgbatch.hip: pencil k of a uniform batch above the cutoff, through gev_range_dev / hgev_range_dev
+// gbatch.hip: pencil k of a uniform batch above the cutoff, through gev_range_dev (gvbatch.hip hands it its blocks)
 int gbatch_solve_one(Context& ctx, const BatchArgs& g, int k);
-int hgbatch_solve_one(Context& ctx, const BatchArgs& g, int k);
 // Host form of a solve on a local block of nr rows: a (nc columns), b (the same; b_h == nullptr: none), z (zcols columns,
 // allocated only) and w (nw entries) in the pool buffers host.a / host.b / host.z (esz 8) or host.ha / host.hb / host.hz
 // (esz 16, interleaved complex) and host.w, leading dimension ldd.  What comes back, and when, is each driver's contract:

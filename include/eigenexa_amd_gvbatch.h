@@ -42,7 +42,7 @@ extern "C" {
  * EIGX_ERR_INTERNAL (the QL iteration used up its 30 n iterations: w = NaN, z and b unspecified).  info may be NULL; in the _dev
  * forms it is a device int array of `batch` entries.  A failed block never disturbs the others; the call returns EIGX_OK or the
  * code of the failed block with the lowest caller index k.
- * Method (csrc/gvbatch.hip, csrc/hgvbatch.hip): the blocks with n[k] at or below the cutoff of the uniform
+ * Method (csrc/gvbatch.hip, csrc/hgbatch.hip): the blocks with n[k] at or below the cutoff of the uniform
  * entry (eigx_tune key 23 for eigx_gev_vbatch, at most 96; key 24 for eigx_hgev_vbatch, at most 64) are sorted by n-class (32,
  * 64, 96) on the host (eigx_vbatch_plan), one descriptor per block is uploaded in one copy, and one launch per non-empty class,
  * largest first, solves them with one workgroup per block, both matrices in LDS from load to store, by the arithmetic of

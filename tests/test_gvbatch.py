@@ -309,6 +309,94 @@ def test_bit_identity_with_the_uniform_entry(gpu_lib):
     check_bits(gpu_lib, G)
 
 
+# ------------------------------------------------------------------------------------------------ 2b. two entries, one result
+def _solo(lib, X, k, code):
+    """block k of X by eigx_*_batch_dev(n_k, 1, ...) with its own status word: the call returns `code`"""
+    n = int(X.n[k])
+    pa, pb, pw, pz = X.block_ptrs(k)
+    rc = X.fam.uniform(lib)(n, 1, pa, int(X.lda[k]), 0, pb, int(X.ldb[k]), 0, pw, n, pz, int(X.ldz[k]), 0, b"A", X.info.data_ptr() + 4 * k)
+    assert rc == code, (k, rc)
+
+
+def _check_good_and_failed(X, As, Bs, codes):
+    """the gates on the good blocks of X; w = NaN, the status and an untouched z for the failed ones"""
+    import scipy.linalg
+
+    failed = [k for k, c in enumerate(codes) if c]
+    ws, Zs, Us, info = X.results(untouched=failed)
+    assert info.tolist() == codes
+    for k, c in enumerate(codes):
+        if c:
+            assert np.isnan(ws[k]).all(), k
+        else:
+            X.fam.gates(As[k], Bs[k], ws[k], Zs[k], Us[k], f"{X.fam.name}: block {k} n={As[k].shape[0]}",
+                        wref=scipy.linalg.eigh(As[k], Bs[k], eigvals_only=True))
+
+
+def check_edges_with_failed_blocks(lib, fam):
+    """The uniform and the ragged entry promise the same bits, failures included (eigen_hgev: they are one kernel, csrc/hgbatch.hip).
+    One pencil at n = 1, 2 and on both sides of every n-class edge the
+    kernels reach, a block with a NaN in A and a block whose B is not positive definite, each between two good ones: w, z, b
+    and info of the ragged call against eigx_*_batch_dev(n_k, 1, ...) with info, bit for bit, whole buffers"""
+    sizes = [n for n in (1, 2, 32, 33, 64, 65, 96) if n <= fam.top]
+    pairs = [fam.random(n, 1, 200 + n) for n in sizes]
+    As, Bs = [p[0][0] for p in pairs], [p[1][0] for p in pairs]
+    nanA, goodB = (x[0] for x in fam.random(40, 1, 7))
+    nanA[3, 30] = nanA[30, 3] = np.nan
+    goodA, indefB = (x[0] for x in fam.random(20, 1, 8))
+    indefB[10, 10] = -1.0
+    As[3:3], Bs[3:3] = [nanA], [goodB]                              # between the blocks of n = 32 and n = 33
+    As[5:5], Bs[5:5] = [goodA], [indefB]                            # between the blocks of n = 33 and n = 64
+    codes = [0] * len(As)
+    codes[3], codes[5] = NONFINITE, NOT_SPD
+    R = RaggedPencils(fam, As, Bs)
+    assert R.run(lib) == NONFINITE                                  # the failed block with the lowest caller index
+    alone = RaggedPencils(fam, As, Bs)
+    for k in range(len(As)):
+        _solo(lib, alone, k, codes[k])
+    assert same_bits(R, alone), "a block differs from the uniform entry's solve of it"
+    for X in (R, alone):
+        _check_good_and_failed(X, As, Bs, codes)
+
+
+@pytest.mark.gpu
+def test_ragged_equals_uniform_at_the_class_edges_with_failed_blocks(gpu_lib):
+    check_edges_with_failed_blocks(gpu_lib, G)
+
+
+def check_uniform_failed_middle(lib, fam):
+    """The uniform entry, one n per class and both kinds of failure (a NaN in A, a B that is not positive definite): a batch of
+    three whose middle pencil fails leaves w, z, b and info of its neighbours as their solo calls (batch = 1) leave them, bit for
+    bit, and the failed pencil as its solo call leaves it.  (Three blocks of one order in the buffers of a ragged call are evenly
+    spaced: a uniform batch with those strides.)"""
+    for n in [n for n in (5, 33, 65) if n <= fam.top]:
+        for code in (NONFINITE, NOT_SPD):
+            As, Bs = fam.random(n, 3, 300 + n)
+            if code == NONFINITE:
+                As[1][0, n - 1] = As[1][n - 1, 0] = np.nan
+            else:
+                Bs[1][n // 2, n // 2] = -1.0
+            codes = [0, code, 0]
+            T, solo = RaggedPencils(fam, As, Bs), RaggedPencils(fam, As, Bs)
+            offs = (T.off_a, T.off_b, T.off_w, T.off_z)
+            steps = [int(v[1] - v[0]) for v in offs]
+            assert all(int(v[2] - v[1]) == s for v, s in zip(offs, steps))
+            pa, pb, pw, pz = T.block_ptrs(0)
+            rc = fam.uniform(lib)(n, 3, pa, int(T.lda[0]), steps[0], pb, int(T.ldb[0]), steps[1], pw, steps[2], pz, int(T.ldz[0]), steps[3],
+                                  b"A", T.info.data_ptr())
+            assert rc == code
+            for k in range(3):
+                _solo(lib, solo, k, codes[k])
+            assert same_bits(T, solo), f"n={n}, code {code}: a pencil beside a failed one differs from its solo result"
+            _check_good_and_failed(T, As, Bs, codes)
+            assert np.array_equal(T.images()[3], solo.images()[3])
+
+
+@pytest.mark.gpu
+def test_uniform_failed_pencil_leaves_its_neighbours(gpu_lib):
+    check_uniform_failed_middle(gpu_lib, G)
+
+
 # ------------------------------------------------------------------------------------------------ 3. many workgroups
 def check_many(lib, fam):
     """1500 pencils with n drawn from 1 .. 24 and three of n = 40 (two classes, more workgroups than the card holds): info all

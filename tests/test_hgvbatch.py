@@ -27,6 +27,19 @@ def test_bit_identity_with_the_uniform_entry(gpu_lib):
 
 
 @pytest.mark.gpu
+def test_ragged_equals_uniform_at_the_class_edges_with_failed_blocks(gpu_lib):
+    """n = 1, 2, 32, 33, 64, a NaN block and one with an indefinite B between good ones: w, both planes of z and b, and info"""
+    gv.check_edges_with_failed_blocks(gpu_lib, HG)
+
+
+@pytest.mark.gpu
+def test_uniform_failed_pencil_leaves_its_neighbours(gpu_lib):
+    """eigx_hgev_batch_dev on three pencils, the second failing (NaN in A; indefinite B), at n = 5, 33: the neighbours equal
+    their solo results"""
+    gv.check_uniform_failed_middle(gpu_lib, HG)
+
+
+@pytest.mark.gpu
 def test_more_workgroups_than_the_card_holds(gpu_lib):
     gv.check_many(gpu_lib, HG)
 

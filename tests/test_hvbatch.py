@@ -31,6 +31,18 @@ def test_bit_identity_with_the_uniform_entry(gpu_lib):
 
 
 @pytest.mark.gpu
+def test_ragged_equals_uniform_at_the_class_edges_with_a_failed_block(gpu_lib):
+    """n = 1, 2, 32, 33, 64, 65, 96 and a NaN block between two good ones: w, both planes of z and info, bit for bit"""
+    vb.check_edges_with_a_failed_block(gpu_lib, H)
+
+
+@pytest.mark.gpu
+def test_uniform_failed_matrix_leaves_its_neighbours(gpu_lib):
+    """eigx_h_batch_dev on three matrices, a NaN in the second, at n = 5, 33, 65: the neighbours equal their solo results"""
+    vb.check_uniform_failed_middle(gpu_lib, H)
+
+
+@pytest.mark.gpu
 def test_mode_n(gpu_lib):
     vb.check_mode_n(gpu_lib, H)
 

@@ -303,6 +303,70 @@ def test_bit_identity_with_the_uniform_entry(gpu_lib):
     check_bits(gpu_lib, S)
 
 
+# ------------------------------------------------------------------------------------------------ 3b. two entries, one result
+def check_edges_with_a_failed_block(lib, fam):
+    """The uniform and the ragged entry promise the same bits, failures included.  One block at n = 1, 2 and on both sides of every n-class edge the
+    kernels reach, and a NaN block between two good ones: w, z and info of the ragged call against eigx_*_batch_dev(n_k, 1, ...)
+    with info, bit for bit, whole buffers; the failed block has w = NaN, its status, and z untouched in both"""
+    sizes = [n for n in (1, 2, 32, 33, 64, 65, 96, 97, 128) if n <= fam.top]
+    mats = [fam.random(n, seed=200 + n) for n in sizes]
+    bad = fam.random(40, seed=7).copy()
+    bad[3, 30] = bad[30, 3] = np.nan
+    mats.insert(3, bad)                                             # between the blocks of n = 32 and n = 33
+    codes = [NONFINITE if k == 3 else 0 for k in range(len(mats))]
+    R = Ragged(fam, mats)
+    assert R.run(lib) == NONFINITE
+    alone = Ragged(fam, mats)
+    for k, M in enumerate(mats):
+        n = M.shape[0]
+        pa, pw, pz = alone.block_a(k)
+        rc = fam.uniform(lib)(n, 1, pa, int(alone.lda[k]), 0, pw, n, pz, int(alone.ldz[k]), 0, b"A", alone.info.data_ptr() + 4 * k)
+        assert rc == codes[k], k
+    assert same_bits(R, alone), "a block differs from the uniform entry's solve of it"
+    for X in (R, alone):
+        ws, Zs, info = X.results(untouched=[3])
+        assert info.tolist() == codes
+        assert np.isnan(ws[3]).all()
+        for k, M in enumerate(mats):
+            if k != 3:
+                fam.check_matrix(M, ws[k], Zs[k], f"block {k} n={M.shape[0]}")
+
+
+@pytest.mark.gpu
+def test_ragged_equals_uniform_at_the_class_edges_with_a_failed_block(gpu_lib):
+    check_edges_with_a_failed_block(gpu_lib, S)
+
+
+def check_uniform_failed_middle(lib, fam):
+    """The uniform entry, one n per class: a batch of three whose middle matrix holds a NaN leaves w, z and info of its
+    neighbours as their solo calls (batch = 1) leave them, bit for bit, and the failed matrix as its solo call leaves it.  (Three
+    blocks of one order in the buffers of a ragged call are evenly spaced: a uniform batch with those strides.)"""
+    for n in [n for n in (5, 33, 65, 97) if n <= fam.top]:
+        mats = [fam.random(n, seed=300 + n + k).copy() for k in range(3)]
+        mats[1][0, n - 1] = mats[1][n - 1, 0] = np.nan
+        T, solo = Ragged(fam, mats), Ragged(fam, mats)
+        lda, ldz = int(T.lda[0]), int(T.ldz[0])
+        steps = [int(v[1] - v[0]) for v in (T.off_a, T.off_w, T.off_z)]
+        assert all(int(v[2] - v[1]) == s for v, s in zip((T.off_a, T.off_w, T.off_z), steps))
+        pa, pw, pz = T.block_a(0)
+        assert fam.uniform(lib)(n, 3, pa, lda, steps[0], pw, steps[1], pz, ldz, steps[2], b"A", T.info.data_ptr()) == NONFINITE
+        for k in range(3):
+            pa, pw, pz = solo.block_a(k)
+            rc = fam.uniform(lib)(n, 1, pa, lda, 0, pw, n, pz, ldz, 0, b"A", solo.info.data_ptr() + 4 * k)
+            assert rc == (NONFINITE if k == 1 else 0)
+        assert same_bits(T, solo), f"n={n}: a matrix beside a failed one differs from its solo result"
+        ws, Zs, info = T.results(untouched=[1])
+        assert info.tolist() == [0, NONFINITE, 0] and np.array_equal(info, solo.results(untouched=[1])[2])
+        assert np.isnan(ws[1]).all()
+        for k in (0, 2):
+            fam.check_matrix(mats[k], ws[k], Zs[k], f"n={n}, matrix {k} beside the failed one")
+
+
+@pytest.mark.gpu
+def test_uniform_failed_matrix_leaves_its_neighbours(gpu_lib):
+    check_uniform_failed_middle(gpu_lib, S)
+
+
 # ------------------------------------------------------------------------------------------------ 4. mode 'N'
 def check_mode_n(lib, fam):
     mats = mixed_mats(fam)

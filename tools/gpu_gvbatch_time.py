@@ -1,5 +1,5 @@
 """Timing of the ragged batched generalised eigensolves (an extension: eigx_gev_vbatch_dev, eigx_hgev_vbatch_dev;
-csrc/gvbatch.hip, csrc/hgvbatch.hip) on one GPU, device API, against the routes a caller has without them.
+csrc/gvbatch.hip, csrc/hgbatch.hip) on one GPU, device API, against the routes a caller has without them.
 usage: gpu_gvbatch_time.py [--repeats R] [--loop L] [--gate G]
 Size distributions (pencils packed tightly, lda = ldb = ldz = n; A random symmetric / Hermitian, B random and diagonally
 dominant with the diagonal n):
