@@ -249,9 +249,14 @@ __global__ __launch_bounds__(2 * NMAX) void batch_range_kernel(int n, int batch,
     __syncthreads();
 
     // ---- 4. eigenvectors of T: inverse iteration, lane j on T - lam_j I ---------------------------------------------------------
-    if (tid == 0)                        // shifts closer than 10 eps ||T|| are moved apart
-      for (int j = 1; j < m; ++j)
-        if (lamv[j] - lamv[j - 1] < 10.0 * epsT) lamv[j] = lamv[j - 1] + 10.0 * epsT;
+    // shifts closer than 10 eps |lam_j| are moved apart (DSTEIN's rule).  The distance is relative to the shift, not to ||T||:
+    // 10 eps ||T|| per column added up to 150 eps ||T|| across a window of 16 near-zero eigenvalues of a graded matrix, past
+    // eigenvalues outside the window, and the window came back with the pairs of other indices
+    if (tid == 0)
+      for (int j = 1; j < m; ++j) {
+        const double sep = 10.0 * DBL_EPSILON * fabs(lamv[j]);
+        if (lamv[j] - lamv[j - 1] < sep) lamv[j] = lamv[j - 1] + sep;
+      }
     __syncthreads();
     double* ua = F;
     double* ub = F + NMAX * MW;

@@ -1,0 +1,336 @@
+"""Small dense matrices and pencils on which a one-workgroup-per-matrix eigensolver can go wrong (graded and glued input,
+multiplicities, near-identity, zero columns in the reduction, ill-conditioned B), extended-precision eigenvalue references for
+them, and column-wise / entry-wise error metrics in units of eps = 2^-52 (tests/test_batch_accuracy.py,
+tests/golden/make_batch_accuracy_bounds.py).
+
+References: real dense -> hard_band's Householder tridiagonalisation and bisection in longdouble; Hermitian -> the same on the
+real embedding [[Re, -Im], [Im, Re]] of order 2 n, every second eigenvalue; pencils -> C = L^-1 A L^-H with the Cholesky factor
+and the two triangular solves in mpmath at 50 digits (longdouble loses eps_LD cond(B) there), C rounded to longdouble, then the
+dense route.  References are computed in the process and cached: the B matrices go through LAPACK's QR and are not bit-
+reproducible across machines.
+
+A plain module: no fixtures, no pytest settings."""
+import functools
+import json
+import os
+
+import numpy as np
+
+import hard_band as hb
+from hard_band import BOUND_FACTOR, EPS, LD
+
+KINDS = ("s", "h", "gev", "hgev", "window")
+FAMILIES = ("random", "graded", "graded_rev", "glued_tri", "glued_rot", "half_integer", "identity_plus", "rank_one", "clement",
+            "blocks", "frank", "diagonal", "identity", "zero")
+# every kernel instance (n-classes 32, 64, 96, 128) from both sides of an edge, both parities (the halves split the columns at
+# (l + 2) / 2)
+SIZES = {"s": (5, 32, 33, 64, 65, 96, 97, 128), "h": (5, 32, 33, 64, 65, 96), "gev": (5, 33, 64, 96), "hgev": (5, 33, 65),
+         "window": (33, 96, 97, 128)}
+PENCIL_A = ("random", "glued_rot")
+PENCIL_C = (0, 1, 4, 8)                         # B = I (0) or Q diag(logspace(0, -c)) Q^H: cond_2(B) = 10^c
+BOUNDS_JSON = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "batch_accuracy_bounds.json")
+METRICS = ("E_w", "E_r", "E_o")
+PENCIL_METRICS = ("E_w", "E_r", "E_o", "E_f")
+
+
+def window_width(n):
+    """the widest window the window kernel serves in mode 'A' at this n"""
+    return 16 if n <= 96 else 4
+
+
+# ------------------------------------------------------------------------------------------------ matrices
+def _from_upper(M):
+    """the symmetric / Hermitian matrix that the upper triangle of M defines (of the diagonal the real parts): what a solver
+    that reads the upper triangle sees"""
+    U = np.triu(M, 1)
+    return np.ascontiguousarray(U + U.conj().T + np.diag(np.diag(M).real))
+
+
+def _rng(seed, n, k):
+    return np.random.default_rng([seed, n, k])
+
+
+def _normal(r, shape, cplx):
+    return r.standard_normal(shape) + (1j * r.standard_normal(shape) if cplx else 0.0)
+
+
+def _q(r, n, cplx):
+    return np.linalg.qr(_normal(r, (n, n), cplx))[0]
+
+
+def _sym(r, n, cplx):
+    S = _normal(r, (n, n), cplx)
+    return S + S.conj().T
+
+
+def _phased(r, T, cplx):
+    """D T D^H with unit phases D: a real matrix as a Hermitian one of the same spectrum"""
+    if not cplx:
+        return T
+    ph = np.exp(1j * r.uniform(0.0, 2.0 * np.pi, T.shape[0]))
+    return ph[:, None] * T * ph.conj()[None, :]
+
+
+def _glued(n):
+    """glued Wilkinson: blocks W21 (diagonal |i - 10|, off-diagonal 1) glued by 1e-10"""
+    i = np.arange(n)
+    e = np.ones(max(n - 1, 0))
+    e[20::21] = 1e-10
+    return np.diag(np.abs((i % 21) - 10.0)) + np.diag(e, 1) + np.diag(e, -1)
+
+
+def half_integer_spectrum(n, seed=0):
+    """the ascending diagonal of the half_integer family before rotation and perturbation: multiples of 1/2, most repeated"""
+    return np.sort(np.round(2 * _rng(seed, n, 5).standard_normal(n)) / 2)
+
+
+def matrix(family, n, cplx=False, seed=0):
+    """one matrix of the table, float64 or complex128, exactly symmetric / Hermitian with a real diagonal"""
+    k = FAMILIES.index(family)
+    r = _rng(seed, n, k)
+    i = np.arange(n)
+    g = 10.0 ** (-14.0 * i / max(n - 1, 1))
+    if family == "random":
+        M = _sym(r, n, cplx)
+    elif family in ("graded", "graded_rev"):      # graded by 1e-14 across rows and columns, the large entries at the top left
+        M = g[:, None] * _sym(_rng(seed, n, 1), n, cplx) * g[None, :]
+        M = M[::-1, ::-1] if family == "graded_rev" else M
+    elif family == "glued_tri":
+        M = _phased(r, _glued(n), cplx)
+    elif family == "glued_rot":
+        Q = _q(r, n, cplx)
+        M = Q @ _glued(n) @ Q.conj().T
+    elif family == "half_integer":                # multiplicities, split at the 1e-9 level
+        Q = _q(r, n, cplx)
+        M = (Q * half_integer_spectrum(n, seed)) @ Q.conj().T + 1e-9 * _sym(r, n, cplx)
+    elif family == "identity_plus":
+        M = np.eye(n) + 1e-15 * _sym(r, n, cplx)
+    elif family == "rank_one":                    # an (n - 1)-fold eigenvalue 1
+        v = _normal(r, n, cplx)
+        M = np.eye(n) + np.outer(v, v.conj())
+    elif family == "clement":
+        off = np.sqrt(i[1:] * (n - i[1:]).astype(np.float64))
+        M = _phased(r, np.diag(off, 1) + np.diag(off, -1), cplx)
+    elif family == "blocks":                      # block diagonal, blocks of 7 of scale 1 and 1e-8: zero columns in the reduction
+        M = np.zeros((n, n), dtype=np.complex128 if cplx else np.float64)
+        for b, s in enumerate(range(0, n, 7)):
+            t = min(s + 7, n)
+            M[s:t, s:t] = (1.0 if b % 2 == 0 else 1e-8) * _sym(r, t - s, cplx)
+    elif family == "frank":
+        M = _phased(r, np.minimum.outer(i + 1, i + 1).astype(np.float64), cplx)
+    elif family == "diagonal":
+        M = np.diag(r.standard_normal(n))
+    elif family == "identity":
+        M = np.eye(n)
+    elif family == "zero":
+        M = np.zeros((n, n))
+    else:
+        raise ValueError(family)
+    return _from_upper(np.asarray(M, dtype=np.complex128 if cplx else np.float64))
+
+
+def overlap(n, c, cplx=False, seed=0):
+    """B of a pencil: the identity (c = 0) or Q diag(logspace(0, -c, n)) Q^H"""
+    if c == 0:
+        return np.eye(n, dtype=np.complex128 if cplx else np.float64)
+    Q = _q(_rng(seed, n, 100 + c), n, cplx)
+    return _from_upper((Q * np.logspace(0.0, -float(c), n)) @ Q.conj().T)
+
+
+def windows(n):
+    """(il, iu, mode) of the window kind, 1-based: the lowest and the highest MW, (1, 1), (n, n), MW in the middle starting and
+    ending inside a cluster of the half_integer family, and one mode 'N' window of width n"""
+    mw = window_width(n)
+    d = half_integer_spectrum(n)
+    inside = [il for il in range(2, n - mw + 1) if d[il - 2] == d[il - 1] and d[il + mw - 2] == d[il + mw - 1]]
+    assert inside, n
+    il = min(inside, key=lambda q: abs(q - (n - mw) // 2))
+    return [(1, mw, "A"), (n - mw + 1, n, "A"), (1, 1, "A"), (n, n, "A"), (il, il + mw - 1, "A"), (1, n, "N")]
+
+
+def cases(kind):
+    """the case table of one kind: (n, family) for s and h, (n, family of A, c) for gev and hgev, (n, family, il, iu, mode) for
+    window.  Pencils at n = 96 come with c = 4 only (their references dominate the run time)."""
+    if kind in ("s", "h"):
+        return [(n, f) for n in SIZES[kind] for f in FAMILIES]
+    if kind in ("gev", "hgev"):
+        return [(n, f, c) for n in SIZES[kind] for f in PENCIL_A for c in ((4,) if n == 96 else PENCIL_C)]
+    if kind == "window":
+        return [(n, f, il, iu, mode) for n in SIZES[kind] for il, iu, mode in windows(n) for f in FAMILIES]
+    raise ValueError(kind)
+
+
+def case_id(kind, case):
+    if kind in ("s", "h"):
+        return f"{kind}-n{case[0]}-{case[1]}"
+    if kind in ("gev", "hgev"):
+        return f"{kind}-n{case[0]}-{case[1]}-c{case[2]}"
+    return f"window-n{case[0]}-{case[1]}-{case[2]}-{case[3]}-{case[4]}"
+
+
+# ------------------------------------------------------------------------------------------------ references
+def embed(A):
+    """the real symmetric [[Re, -Im], [Im, Re]] of order 2 n: every eigenvalue of the Hermitian A twice"""
+    return np.block([[A.real, -A.imag], [A.imag, A.real]])
+
+
+def reference_eigenvalues(A):
+    """ascending eigenvalues of the symmetric or Hermitian A (float64, longdouble or their complex types) in longdouble"""
+    A = np.asarray(A)
+    with np.errstate(over="ignore"):              # a Sturm pivot of 1e-4900 next to a double eigenvalue: e^2 / q = inf is meant
+        if np.iscomplexobj(A):
+            return np.sort(hb._bisect_tridiagonal(*hb._householder_tridiagonalise(embed(A))))[::2].copy()
+        return np.sort(hb._bisect_tridiagonal(*hb._householder_tridiagonalise(A)))
+
+
+def _to_ld(x):
+    """an mpmath real rounded to longdouble (two float64 pieces: 106 bits)"""
+    hi = float(x)
+    return LD(hi) + LD(float(x - hi))
+
+
+def reduced_pencil(A, B):
+    """C = L^-1 A L^-H, B = L L^H, in mpmath at 50 digits, rounded to longdouble (clongdouble for complex input)"""
+    import mpmath
+
+    n = A.shape[0]
+    cplx = np.iscomplexobj(A) or np.iscomplexobj(B)
+    with mpmath.workdps(50):
+        num = (lambda x: mpmath.mpc(x.real, x.imag)) if cplx else (lambda x: mpmath.mpf(float(x)))
+        conj = mpmath.conj if cplx else (lambda x: x)
+        zero = mpmath.mpf(0)
+        Lr = [[zero] * n for _ in range(n)]      # rows of L
+        for j in range(n):
+            s = mpmath.re(num(B[j, j])) - mpmath.fsum(abs(x) ** 2 for x in Lr[j][:j])
+            assert s > 0, "B is not positive definite"
+            Lr[j][j] = mpmath.sqrt(s)
+            cj = [conj(x) for x in Lr[j][:j]]
+            for i in range(j + 1, n):
+                Lr[i][j] = (num(B[i, j]) - mpmath.fdot(Lr[i][:j], cj)) / Lr[j][j]
+
+        def solve_columns(cols):
+            """L^-1 applied to every column"""
+            out = []
+            for x in cols:
+                y = []
+                for i in range(n):
+                    y.append((x[i] - mpmath.fdot(Lr[i][:i], y)) / Lr[i][i])
+                out.append(y)
+            return out
+
+        X = solve_columns([[num(A[i, j]) for i in range(n)] for j in range(n)])        # X[j][i] = (L^-1 A)(i, j)
+        # C = X L^-H = (L^-1 X^H)^H: the columns of X^H are the conjugated rows of X
+        Y = solve_columns([[conj(X[j][i]) for j in range(n)] for i in range(n)])       # Y[i][j] = conj(C(i, j))
+        C = np.zeros((n, n), dtype=np.clongdouble if cplx else LD)
+        for i in range(n):
+            for j in range(n):
+                v = conj(Y[i][j])
+                C[i, j] = _to_ld(mpmath.re(v)) + (1j * _to_ld(mpmath.im(v)) if cplx else 0)
+    return (C + C.conj().T) / 2
+
+
+class Case:
+    """one standard problem: A, its reference eigenvalues lam (longdouble, ascending, read-only) and |A|_2"""
+
+    def __init__(self, kind, n, family):
+        self.kind, self.n, self.family = kind, n, family
+        self.A = matrix(family, n, cplx=kind == "h")
+        self.A.setflags(write=False)
+        self.lam = reference_eigenvalues(self.A)
+        self.lam.setflags(write=False)
+        self.anorm = float(np.abs(self.lam).max())
+
+
+class Pencil:
+    """one pencil: A, B, the reference eigenvalues lam, |A|_2, |B|_2 and cond_2(B)"""
+
+    def __init__(self, kind, n, family, c):
+        cplx = kind == "hgev"
+        self.kind, self.n, self.family, self.c = kind, n, family, c
+        self.A = matrix(family, n, cplx=cplx)
+        self.B = overlap(n, c, cplx=cplx)
+        self.A.setflags(write=False)
+        self.B.setflags(write=False)
+        self.lam = reference_eigenvalues(reduced_pencil(self.A, self.B))
+        self.lam.setflags(write=False)
+        self.anorm = float(np.abs(np.linalg.eigvalsh(self.A)).max())
+        wb = np.linalg.eigvalsh(self.B)
+        self.bnorm, self.cond = float(wb[-1]), float(wb[-1] / wb[0])
+
+
+@functools.lru_cache(maxsize=None)
+def case(kind, n, family):
+    """the standard problem (kind s or h; the window kind uses s), computed once per process"""
+    return Case("s" if kind == "window" else kind, n, family)
+
+
+@functools.lru_cache(maxsize=None)
+def pencil(kind, n, family, c):
+    """the pencil (kind gev or hgev), its reference computed once per process"""
+    return Pencil(kind, n, family, c)
+
+
+# ------------------------------------------------------------------------------------------------ metrics
+def metrics(cs, w, Z, il=1):
+    """(E_w, E_r, E_o) of the columns il .. il + m - 1 of a standard problem, in eps: E_w = max |w_k - lambda_k| / (eps |A|_2),
+    E_r = max_j |A z_j - w_j z_j|_2 / (eps |A|_2), E_o = max |Z^H Z - I| / eps.  Z = None: E_w only (the others 0).  The zero
+    matrix: its w is held to 0 exactly by the caller; E_w and E_r are 0 here."""
+    w = np.asarray(w, dtype=np.float64)
+    m = len(w)
+    tn = cs.anorm if cs.anorm > 0 else 1.0
+    E_w = float(np.abs(w.astype(LD) - cs.lam[il - 1:il - 1 + m]).max()) / (EPS * tn)
+    if Z is None:
+        return E_w, 0.0, 0.0
+    if np.iscomplexobj(cs.A):
+        E_r, _ = hb.dense_metrics(embed(cs.A), w, np.vstack([Z.real, Z.imag]))
+        E_o = float(np.abs(Z.conj().T @ Z - np.eye(m)).max()) / EPS
+    else:
+        E_r, E_o = hb.dense_metrics(cs.A, w, np.asarray(Z, dtype=np.float64))
+    return E_w, E_r, E_o
+
+
+def pencil_metrics(pc, w, Z, U):
+    """(E_w, E_r, E_o, E_f) of a pencil in eps, products in longdouble: E_w = max_k |w_k - lambda_k| / (eps cond(B) max(|lambda_k|,
+    |A|_2 / |B|_2)), E_r = max_j |A z_j - w_j B z_j|_2 / (eps cond(B) (|A|_2 + |w_j| |B|_2) |z_j|_2), E_o = max |Z^H B Z - I| /
+    (eps cond(B)), E_f = max |U^H U - B| / (eps |B|_2) for the returned factor (U = None: 0)"""
+    cplx = np.iscomplexobj(pc.A)
+    T = np.clongdouble if cplx else LD
+    w = np.asarray(w, dtype=np.float64)
+    n = pc.n
+    ek = EPS * pc.cond
+    den = np.maximum(np.abs(pc.lam), LD(pc.anorm / pc.bnorm))
+    den = np.where(den > 0, den, LD(1))
+    E_w = float((np.abs(w.astype(LD) - pc.lam) / den).max()) / ek
+    Zl, Al, Bl = np.asarray(Z, dtype=T), np.asarray(pc.A, dtype=T), np.asarray(pc.B, dtype=T)
+    BZ = Bl @ Zl
+    R = Al @ Zl - BZ * w.astype(LD)[None, :]
+    rn = np.sqrt((np.abs(R) ** 2).sum(axis=0))
+    zn = np.sqrt((np.abs(Zl) ** 2).sum(axis=0))
+    scale = (LD(pc.anorm) + np.abs(w).astype(LD) * LD(pc.bnorm)) * zn
+    scale = np.where(scale > 0, scale, LD(1))
+    E_r = float((rn / scale).max()) / ek
+    E_o = float(np.abs(Zl.conj().T @ BZ - np.eye(n)).max()) / ek
+    E_f = 0.0
+    if U is not None:
+        Ul = np.asarray(U, dtype=T)
+        E_f = float(np.abs(Ul.conj().T @ Ul - Bl).max()) / (EPS * pc.bnorm)
+    return E_w, E_r, E_o, E_f
+
+
+# ------------------------------------------------------------------------------------------------ bounds
+@functools.lru_cache(maxsize=None)
+def _record():
+    return json.load(open(BOUNDS_JSON))
+
+
+def bounds(kind, c=None, family=None):
+    """the bounds in force, {metric: bound}: BOUND_FACTOR x LAPACK's worst value per (kind, metric), for pencils per cond group
+    c; the window kind uses those of s.  A family the record lists under "family_bounds" has its own (with the reason there)."""
+    rec = _record()
+    kind = "s" if kind == "window" else kind
+    worst = rec["worst"][kind] if c is None else rec["worst"][kind][f"c{c}"]
+    out = {k: BOUND_FACTOR * v for k, v in worst.items()}
+    own = rec.get("family_bounds", {}).get(f"{kind}-{family}")
+    if own:
+        out.update(own["bounds"])
+    return out
