@@ -159,8 +159,11 @@ void band_bisect_range_dev(Context& ctx, int n, int il, int iu, const double* d,
 void band_count_dev(Context& ctx, int n, const double* d, const double* e, int lde, int band, int npts, const double* x,
                     int* cnt);
 
-// The window of a range solve (range_solve_dev in solver.hip, gev_range_dev in gev.hip, hgev_range_dev in hgev.hip and their
-// host forms, herm_range_dev in herm.hip).  By index: eigenpairs
+// The range solves.  range.hip holds what every family shares: range_args_ok, refuse_several_ranks, range_info_reset,
+// resolve_value_window, range_window_stage and range_host_form.  The device drivers are range_solve_dev (solver.hip),
+// herm_range_dev (herm.hip), gev_range_dev (gev.hip) and hgev_range_dev (hgev.hip); band_eigvec_dev, range_info and the knobs
+// are subset.hip's.
+// The window of a range solve.  By index: eigenpairs
 // il .. iu (1-based, inclusive).  By value: those with vl <= lambda < vu, resolved into il .. iu by two Sturm counts after
 // the band reduction; at most mmax of them are returned, and *m_out / *il_out (host) receive their number and the index
 // of the first.  m() = the entries of w / columns of z the caller provides.
@@ -179,13 +182,27 @@ struct RangeWindow {
 // entries of w that a range call may write (NaN on a non-finite input), eigenvector columns it may ask room for
 inline int range_w_cap(const RangeWindow& W, char mode) { return (W.by_value && mode == 'C') ? 0 : W.m(); }
 inline int range_z_cap(int n, const RangeWindow& W, char mode) { const int c = range_w_cap(W, mode); return c < 1 ? 1 : (c < n ? c : n); }
-// solver.hip (see there): the argument check of every range entry, the refusal of a grid of several ranks
-// (EIGX_ERR_BAD_ARG), and the drivers of eigen_sx (band 2) / eigen_s (band 1) and of their range solve on device arrays
+// range.hip: the argument check of every range entry (mode in upper case), the refusal of a grid of several ranks
+// (EIGX_ERR_BAD_ARG), and what a device driver starts from: range_info() = path 0, m (by value: 0), no cond, no seconds
 bool range_args_ok(int n, const RangeWindow& W, const double* a, int lda, const double* w, const double* z, int ldz, char mode);
 int refuse_several_ranks(const Context& ctx);
+void range_info_reset(const RangeWindow& W);
 // value window -> index window right after a reduction to the band form (d, e) = sigma times the caller's matrix: W.il,
-// W.iu, *W.m_out, *W.il_out (range_solve_dev, herm_range_dev)
+// W.iu, *W.m_out, *W.il_out (range_window_stage)
 void resolve_value_window(Context& ctx, int n, const double* d, const double* e, int lde, int band, double sigma, RangeWindow& W);
+// The middle of range_solve_dev and herm_range_dev.  On entry the reduction is drained, F.t2 is set, (d, e, lde, band) is the
+// band form of sigma times the matrix and W, mode (upper case) have passed range_args_ok.  Resolves a value window (W.il, W.iu
+// from then on), computes w(1:m) and with mode 'A' the m band eigenvectors, keeps range_info, sets F.t3.  room(ncols) names n
+// rows x ncols columns for band eigenvectors: asked for m columns on path 1, for iu on paths 2 / 3, where the n eigenvalues of
+// the full D&C go to the pool buffer `wfull`.  Returns z / ld = the window's first column (paths 2 / 3: room + (il - 1) ld) and
+// f_mid, the flops of the stage for finish -- or ended with the status to return at once: EIGX_ERR_WINDOW and a negative status
+// of band_eigvec_dev (neither has gone through finish), a count-only or empty window (finished: EIGX_OK, w and z untouched).
+struct SolveFrame;
+struct RangeRoom { double* p; int ld; };
+struct RangeStaged { bool ended = false; int rc = 0; double* z = nullptr; int ld = 0; double f_mid = 0.0; };
+RangeStaged range_window_stage(SolveFrame& F, RangeWindow& W, char mode, const double* d, const double* e, int lde, int band,
+                               double* w, const char* wfull, const std::function<RangeRoom(int)>& room);
+// solver.hip (see there): the drivers of eigen_sx (band 2) / eigen_s (band 1) and of their range solve on device arrays
 int solve_dev(Context& ctx, int n, int nvec, double* a, int lda, double* w, double* z, int ldz, int mf, int mb, char mode, int band, int nb);
 int range_solve_dev(Context& ctx, int n, RangeWindow W, double* a, int lda, double* w, double* z, int ldz, int mf, int mb,
                     char mode, int band, bool fill_rest);
@@ -434,6 +451,13 @@ struct HostStage {
     dev_to_host(h, ld, d, ldd, nrows < 0 ? nr : nrows, ncols, esz);
   }
 };
+// range.hip: the host form of every range entry (esz 8 or 16; has_b: the pencil families, b / ldb checked and staged).  Not
+// initialised -> several ranks -> arguments; HostStage sized by range_w_cap / range_z_cap; dev_form on the staged arrays; w comes
+// back on EIGX_OK or EIGX_ERR_NONFINITE (the entries written), and on EIGX_OK the m columns of z (mode 'A') and what
+// rest_back copies: the statistics in a's first column, or b = U.
+int range_host_form(Context& ctx, int n, const RangeWindow& W, int esz, double* a, int lda, bool has_b, double* b, int ldb, double* w,
+                    double* z, int ldz, char mode, const std::function<int(const HostStage&)>& dev_form,
+                    const std::function<void(const HostStage&)>& rest_back);
 // gev.hip: the frame of the six generalised device drivers (gev.hip, hgev.hip).  A driver tests `initialized` and the number
 // of ranks itself, then: begin (EIGX_ERR_BAD_ARG, or device set, the caller's default stream drained, t[0] taken) -> mark
 // at the end of each of its first three stages -> finish (end of the last; timers[0] = total, [1 .. 4] = stages; EIGX_OK).

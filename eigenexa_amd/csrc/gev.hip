@@ -378,19 +378,10 @@ namespace {
 
 int gev_range_host(Context& ctx, int n, RangeWindow W, double* a, int lda, double* b, int ldb, double* w, double* z, int ldz,
                    char mode) {
-  if (!ctx.initialized) return EIGX_ERR_NOT_INITIALIZED;
-  if (ctx.grid.nranks != 1) return gev_range_dev(ctx, n, W, a, lda, b, ldb, w, z, ldz, mode);   // refuses
-  mode = upper_case(mode);
-  if (!range_args_ok(n, W, a, lda, w, z, ldz, mode) || !b || ldb < n) return EIGX_ERR_BAD_ARG;
-  const int wcap = range_w_cap(W, mode);
-  const HostStage S(ctx, 8, n, n, a, lda, b, ldb, mode == 'A' ? range_z_cap(n, W, mode) : 1, std::max(wcap, 1));
-  const int rc = gev_range_dev(ctx, n, W, S.a, S.ldd, S.b, S.ldd, S.w, S.z, S.ldd, mode);
-  const int m = (W.by_value && rc == EIGX_OK) ? (mode == 'C' ? 0 : *W.m_out) : wcap;   // entries that were written
-  if (rc == EIGX_OK || rc == EIGX_ERR_NONFINITE) S.w_back(w, m);
-  if (rc != EIGX_OK) return rc;   // (EIGX_ERR_WINDOW: a and b are as the caller passed them, ready for the retry by index)
-  S.back(b, ldb, S.b, n);         // U in the upper triangle; a is not returned
-  if (mode == 'A') S.back(z, ldz, S.z, m);   // (m = 0: nothing)
-  return EIGX_OK;
+  return range_host_form(
+      ctx, n, W, 8, a, lda, true, b, ldb, w, z, ldz, mode,
+      [&](const HostStage& S) { return gev_range_dev(ctx, n, W, S.a, S.ldd, S.b, S.ldd, S.w, S.z, S.ldd, mode); },
+      [&](const HostStage& S) { S.back(b, ldb, S.b, n); });   // U in the upper triangle; a is not returned
 }
 
 }  // namespace

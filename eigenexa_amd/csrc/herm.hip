@@ -1221,27 +1221,22 @@ int herm_solve_host(Context& ctx, int n, int nvec, double* a, int lda, double* w
   if (!ctx.initialized) return EIGX_ERR_NOT_INITIALIZED;
   const int nr = local_count(n, ctx.grid.Px, ctx.grid.px), nc = local_count(n, ctx.grid.Py, ctx.grid.py);
   if (n <= 0 || !a || !w || lda < nr) return EIGX_ERR_BAD_ARG;
-  EIGX_HIP_CHECK(hipSetDevice(ctx.device));
-  const int ldd = host_ld(nr);
-  double* ad = (double*)host_to_dev(ctx, "hh.a", a, lda, nr, nc, 16);
-  double* zd = (double*)host_to_dev(ctx, "hh.z", nullptr, 0, nr, nc, 16);
-  double* wd = ctx.pool.get_t<double>("hh.w", (size_t)n);
-  const int rc = herm_solve_dev(ctx, n, nvec, ad, ldd, wd, zd, ldd, mf, mb, mode);
-  EIGX_HIP_CHECK(hipMemcpy(w, wd, (size_t)n * 8, hipMemcpyDeviceToHost));
+  const HostStage S(ctx, 16, nr, nc, a, lda, nullptr, 0, nc, n);
+  const int rc = herm_solve_dev(ctx, n, nvec, S.a, S.ldd, S.w, S.z, S.ldd, mf, mb, mode);
+  S.w_back(w, n);
   if (rc != EIGX_OK) return rc;
   const SolveRequest rq = normalize_request(n, nvec, mode);
-  if (z && rq.want_vec) dev_to_host(z, ldz, zd, ldd, nr, local_count(rq.nvec, ctx.grid.Py, ctx.grid.py), 16);
-  dev_to_host(a, lda, ad, ldd, nc > 0 ? std::min(nr, 2) : 0, 1, 16);   // statistics only: a is destroyed
+  if (z && rq.want_vec) S.back(z, ldz, S.z, local_count(rq.nvec, ctx.grid.Py, ctx.grid.py));
+  S.back(a, lda, S.a, 1, nc > 0 ? std::min(nr, 2) : 0);   // statistics only: a is destroyed
   return EIGX_OK;
 }
 
 // ---- eigen_h range solve: eigenpairs il .. iu of the ascending spectrum, or those with vl <= lambda < vu (one GPU) ----------
 // EXTENSION, not in the reference: the Hermitian sibling of range_solve_dev (solver.hip) with band = 1.
-//   h_reduce_full (scaling, eigen_hrd, with mode 'A' the T factors) -> a value window resolved on (h.d, h.e) by two Sturm
-//   counts (resolve_value_window: the protocol of range_solve_dev word for word) -> multi-section on the index window ->
-//   band_eigvec_dev straight into the real plane Zr of m columns (path 1), or band_dc_dev with nvec = iu into planes of iu
-//   columns, of which the window is the pointer offset (il - 1) ldzp into both (path 3 by the size rule of key 17, path 2
-//   after a refusal by the acceptance test of key 19) -> Zi = 0 on the m columns -> phase B on the m columns -> z.
+//   h_reduce_full (scaling, eigen_hrd, with mode 'A' the T factors) -> range_window_stage on (h.d, h.e) (range.hip: the same
+//   code as range_solve_dev runs), its room the real plane Zr: m columns for band_eigvec_dev (path 1), or iu columns for
+//   band_dc_dev, of which the window is the pointer offset (il - 1) ldzp into both planes (path 3 by the size rule of key 17,
+//   path 2 after a refusal by the acceptance test of key 19) -> Zi = 0 on the m columns -> phase B on the m columns -> z.
 // Modes 'A', 'N' and, by value, 'C' (the count alone).  w(1:m), z(:, 1:m); a is destroyed and gets its two statistics.
 int herm_range_dev(Context& ctx, int n, RangeWindow W, double* a, int lda, double* w, double* z, int ldz, int mf, int mb,
                    char mode) {
@@ -1252,84 +1247,36 @@ int herm_range_dev(Context& ctx, int n, RangeWindow W, double* a, int lda, doubl
   F.a_user = a;
   const bool want_vec = mode == 'A';
   hipStream_t st = ctx.stream;
-  RangeInfo& info = range_info();
-  info.path = 0; info.m = W.by_value ? 0 : W.m(); info.cond = 0.0;
-  for (int q = 0; q < 4; ++q) info.t[q] = 0.0;
+  range_info_reset(W);
   HReduced R;
   if (const int rc = h_reduce_full(F, n, a, lda, w, range_w_cap(W, mode), std::min(std::min(mf <= 0 ? 48 : mf, HM), n), mb, want_vec, R)) {
     if (W.by_value) *W.m_out = 0;
     return rc;
   }
-  const double* d = R.H.d;
-  const double* e = R.H.e;
-  const int lde = R.lde;
-  const double t2 = F.t2;
 
-  if (W.by_value) {
-    resolve_value_window(ctx, n, d, e, lde, 1, F.sigma, W);
-    const int mv = *W.m_out;
-    info.m = mv;
-    if (mode != 'C' && mv > W.mmax) return EIGX_ERR_WINDOW;
-    if (mode == 'C' || mv == 0) {   // nothing to compute: the statistics of the reduction alone
-      F.t3 = now_s();
-      info.t[0] = F.t3 - t2;
-      return F.finish(w, 0, 0.0, 0, n);
-    }
-  }
-  const int il = W.il, iu = W.iu, m = iu - il + 1;
-
-  // ---- eigenvalues il .. iu, then their eigenvectors as the real plane Zr -------------------------------------------------
-  double* Zr = nullptr;
-  double* Zi = nullptr;
+  // ---- eigenvalues il .. iu, then their eigenvectors as the real plane Zr (range.hip).  Both planes in one buffer, the
+  // imaginary one H_PLANE_SKEW off, as h_tridiagonal_stage lays them out; the window lies at the same offset in both.
   const int ldzp = pad_ld(n + 2);
-  if (!want_vec) {
-    band_bisect_range_dev(ctx, n, il, iu, d, e, lde, 1, w);
-    info.path = 1;
-    info.t[0] = now_s() - t2;
-  } else {
-    // both planes in one buffer, the imaginary one H_PLANE_SKEW off, as h_tridiagonal_stage lays them out
-    auto planes = [&](int zcap) {
-      const size_t zplane = (size_t)ldzp * (zcap + 1) + H_PLANE_SKEW;
-      Zr = ctx.pool.get_t<double>("h.Zri", 2 * zplane);
-      Zi = Zr + zplane;
-    };
-    int path = range_takes_subset(n, m) ? 1 : 3;
-    if (path == 1) {
-      double* wsel = ctx.pool.get_t<double>("sub.wsel", (size_t)m);
-      band_bisect_range_dev(ctx, n, il, iu, d, e, lde, 1, wsel);
-      const double tb = now_s();
-      info.t[0] = tb - t2;
-      double cond = 0.0;
-      double ts[2] = {0.0, 0.0};
-      planes(m);
-      const int rc_ev = band_eigvec_dev(ctx, n, m, d, e, lde, 1, wsel, w, Zr, ldzp, &cond, ts);
-      if (rc_ev < 0) return rc_ev;
-      info.cond = cond; info.t[1] = ts[0]; info.t[2] = ts[1];
-      if (rc_ev > 0) path = 2;   // refused by the acceptance test
-    }
-    if (path != 1) {
-      // the full divide and conquer for the lowest iu pairs; the window is columns il .. iu of both planes where they lie
-      const double tf = now_s();
-      double* wn = ctx.pool.get_t<double>("h.wfull", (size_t)n);
-      planes(iu);
-      band_dc_dev(ctx, n, iu, d, e, lde, 1, wn, Zr, ldzp);
-      EIGX_HIP_CHECK(hipMemcpyAsync(w, wn + (il - 1), (size_t)m * 8, hipMemcpyDeviceToDevice, st));
-      Zr += (size_t)(il - 1) * ldzp;
-      Zi += (size_t)(il - 1) * ldzp;
-      EIGX_HIP_CHECK(hipStreamSynchronize(st));
-      info.t[2] += now_s() - tf;
-    }
-    info.path = path;
-    hipLaunchKernelGGL(fill_kernel, dim3(1024), dim3(256), 0, st, Zi, (size_t)ldzp * m, 0.0);
-  }
-  F.t3 = now_s();
+  double* Zr0 = nullptr;
+  double* Zi = nullptr;
+  const RangeStaged S = range_window_stage(F, W, mode, R.H.d, R.H.e, R.lde, 1, w, "h.wfull", [&](int zcap) {
+    const size_t zplane = (size_t)ldzp * (zcap + 1) + H_PLANE_SKEW;
+    Zr0 = ctx.pool.get_t<double>("h.Zri", 2 * zplane);
+    Zi = Zr0 + zplane;
+    return RangeRoom{Zr0, ldzp};
+  });
+  if (S.ended) return S.rc;
+  const int m = W.iu - W.il + 1;
 
   // ---- eigen_hrbakwyx on the m columns of the window ---------------------------------------------------------------------
-  if (want_vec && n > 1) h_back_transform(ctx, R, n, m, Zr, Zi, ldzp);
-  if (want_vec) zjoin(st, ZPlanes{Zr, Zi}, ldzp, n, m, false, z, ldz);
-  const double f_mid = want_vec ? (info.path == 1 ? 6.0 * (double)n * m * m : ctx.timers[11]) : 0.0;
-  int rc = F.finish(w, m, f_mid, want_vec ? m : 0, n);
-  info.t[3] = ctx.timers[3];
+  if (want_vec) {
+    Zi += S.z - Zr0;
+    hipLaunchKernelGGL(fill_kernel, dim3(1024), dim3(256), 0, st, Zi, (size_t)ldzp * m, 0.0);
+    if (n > 1) h_back_transform(ctx, R, n, m, S.z, Zi, ldzp);
+    zjoin(st, ZPlanes{S.z, Zi}, ldzp, n, m, false, z, ldz);
+  }
+  const int rc = F.finish(w, m, S.f_mid, want_vec ? m : 0, n);
+  range_info().t[3] = ctx.timers[3];
   if (rc == EIGX_OK) EIGX_HIP_CHECK(hipGetLastError());
   return rc;
 }
@@ -1338,19 +1285,10 @@ int herm_range_dev(Context& ctx, int n, RangeWindow W, double* a, int lda, doubl
 // non-finite input fills w(1:mmax) with NaN); a gets its a(1:2,1) statistics whenever the call returns EIGX_OK.
 int herm_range_host(Context& ctx, int n, RangeWindow W, double* a, int lda, double* w, double* z, int ldz, int mf, int mb,
                     char mode) {
-  if (!ctx.initialized) return EIGX_ERR_NOT_INITIALIZED;
-  if (ctx.grid.nranks != 1) return herm_range_dev(ctx, n, W, a, lda, w, z, ldz, mf, mb, mode);   // refuses
-  mode = upper_case(mode);
-  if (!range_args_ok(n, W, a, lda, w, z, ldz, mode)) return EIGX_ERR_BAD_ARG;
-  const int wcap = range_w_cap(W, mode);
-  const HostStage S(ctx, 16, n, n, a, lda, nullptr, 0, mode == 'A' ? range_z_cap(n, W, mode) : 1, std::max(wcap, 1));
-  const int rc = herm_range_dev(ctx, n, W, S.a, S.ldd, S.w, S.z, S.ldd, mf, mb, mode);
-  const int m = (W.by_value && rc == EIGX_OK) ? (mode == 'C' ? 0 : *W.m_out) : wcap;   // entries that were written
-  if (rc == EIGX_OK || rc == EIGX_ERR_NONFINITE) S.w_back(w, m);
-  if (rc != EIGX_OK) return rc;
-  if (mode == 'A') S.back(z, ldz, S.z, m);
-  S.back(a, lda, S.a, 1, std::min(n, 2));   // statistics only: a is destroyed
-  return EIGX_OK;
+  return range_host_form(
+      ctx, n, W, 16, a, lda, false, nullptr, 0, w, z, ldz, mode,
+      [&](const HostStage& S) { return herm_range_dev(ctx, n, W, S.a, S.ldd, S.w, S.z, S.ldd, mf, mb, mode); },
+      [&](const HostStage& S) { S.back(a, lda, S.a, 1, std::min(n, 2)); });   // statistics only: a is destroyed
 }
 
 }  // namespace eigx

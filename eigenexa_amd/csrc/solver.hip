@@ -259,74 +259,12 @@ int SolveFrame::finish(double* w, int nw, double f_mid, int bt_cols, int stat_ro
   return EIGX_OK;
 }
 
-namespace {
-
-__global__ void copy_vec_kernel(const double* __restrict__ src, double* __restrict__ dst, int n) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < n) dst[i] = src[i];
-}
-
-}  // namespace
-
-// ---- value window -> index window (EXTENSION) ------------------------------------------------------------------------------
-// The eigenvalues with vl <= lambda < vu of the matrix whose band form (d, e) is sigma times the caller's: il = count(sigma vl)
-// + 1, iu = count(sigma vu), count(x) = eigenvalues below x by band_count_dev.  The pentadiagonal count is not strictly
-// monotone in floating point: iu < il - 1 is an empty window like iu = il - 1.  An infinite bound needs no count.  One
-// launch, one 8-byte copy back, one stream synchronisation.
-void resolve_value_window(Context& ctx, int n, const double* d, const double* e, int lde, int band, double sigma,
-                          RangeWindow& W) {
-  const bool lo_inf = std::isinf(W.vl), hi_inf = std::isinf(W.vu);   // vl < vu: only vl = -Inf, vu = +Inf can be
-  int c[2] = {0, n};
-  if (!lo_inf || !hi_inf) {
-    hipStream_t st = ctx.stream;
-    double* xd = ctx.pool.get_t<double>("bis.vx", 2);
-    int* cd = ctx.pool.get_t<int>("bis.vcnt", 2);
-    const double x[2] = {sigma * W.vl, sigma * W.vu};
-    EIGX_HIP_CHECK(hipMemcpyAsync(xd, x, sizeof(x), hipMemcpyHostToDevice, st));
-    band_count_dev(ctx, n, d, e, lde, band, 2, xd, cd);
-    int h[2] = {0, n};
-    EIGX_HIP_CHECK(hipMemcpyAsync(h, cd, sizeof(h), hipMemcpyDeviceToHost, st));
-    EIGX_HIP_CHECK(hipStreamSynchronize(st));
-    if (!lo_inf) c[0] = h[0];
-    if (!hi_inf) c[1] = h[1];
-  }
-  W.il = c[0] + 1;
-  W.iu = std::max(c[1], c[0]);
-  *W.m_out = W.iu - W.il + 1;
-  *W.il_out = W.il;
-}
-
-// what both entry points of the range solves require of their arguments (mode in upper case).  By value: vl < vu (a NaN
-// fails it), room for at least one eigenpair unless only the count is asked for (mode 'C', value form only: w and z are
-// not used), and somewhere to put m and il.
-bool range_args_ok(int n, const RangeWindow& W, const double* a, int lda, const double* w, const double* z, int ldz, char mode) {
-  if (n <= 0 || !a || lda < n) return false;
-  if (W.by_value) {
-    if (!(W.vl < W.vu) || !W.m_out || !W.il_out || (mode != 'A' && mode != 'N' && mode != 'C')) return false;
-    if (mode == 'C') return true;
-    if (W.mmax < 1 || !w) return false;
-  } else {
-    if (W.il < 1 || W.iu > n || W.il > W.iu || (mode != 'A' && mode != 'N') || !w) return false;
-  }
-  return mode == 'N' || (z && ldz >= n);
-}
-int refuse_several_ranks(const Context& ctx) {
-  fprintf(stderr, "[eigx] index-range solves run on one GPU only (this grid has %d ranks)\n", ctx.grid.nranks);
-  return EIGX_ERR_BAD_ARG;
-}
-
 // ---- range solve: eigenpairs il .. iu (1-based, inclusive) of the ascending spectrum, one GPU ---------------------------
 // EXTENSION, not in the reference (whose nvec only trims the back-transformation, src/eigen_sx.F:200-240).
-//   scaling -> band reduction (as solve_dev) -> Sturm multi-section on the index window -> band_eigvec_dev (inverse
-//   iteration + CholQR2 + Rayleigh-Ritz, subset.hip) -> back-transformation of the m columns.
-// The subset path asks for no D&C workspace of the outer problem.  The full divide and conquer (nvec = iu, columns
-// il .. iu copied out) serves windows beyond the size rule (eigx_tune key 17; path 3) and results that the acceptance
-// test of band_eigvec_dev refused (path 2).  w(1:m), z(:, 1:m); fill_rest (the opt-in route of eigx_sx / eigx_s, il = 1):
-// w(m+1:n) is filled by bisection as well, so that w holds all n eigenvalues like the reference's.
-// A window by value (W.by_value) becomes an index window right after the reduction (resolve_value_window); what is sized
-// before that is sized by W.mmax.  *W.m_out, *W.il_out are set whenever the window was resolved: m = 0 returns EIGX_OK
-// and m > mmax EIGX_ERR_WINDOW, both without touching w or z and without an eigenvector stage; mode 'C' (value form
-// only) stops there in every case.  From then on a value call runs the code of the index call il .. iu.
+//   scaling -> band reduction (as solve_dev) -> range_window_stage (range.hip: the window, w(1:m), the band eigenvectors and
+//   the early exits of a window by value) -> back-transformation of the m columns.
+// w(1:m), z(:, 1:m); fill_rest (the opt-in route of eigx_sx / eigx_s, il = 1): w(m+1:n) is filled by bisection as well, so
+// that w holds all n eigenvalues like the reference's.  What is sized before a window by value is resolved is sized by W.mmax.
 int range_solve_dev(Context& ctx, int n, RangeWindow W, double* a, int lda, double* w, double* z, int ldz, int mf, int mb,
                     char mode, int band, bool fill_rest) {
   if (ctx.initialized && ctx.grid.nranks != 1) return refuse_several_ranks(ctx);
@@ -337,14 +275,10 @@ int range_solve_dev(Context& ctx, int n, RangeWindow W, double* a, int lda, doub
   if (mf <= 0) mf = 128;
   if (mb <= 0) mb = 128;
   hipStream_t st = ctx.stream;
-  RangeInfo& info = range_info();
-  info.path = 0; info.m = W.by_value ? 0 : W.m(); info.cond = 0.0;
-  for (int q = 0; q < 4; ++q) info.t[q] = 0.0;
-  const int wcap = range_w_cap(W, mode);
+  range_info_reset(W);
 
   if (const int rc = F.stage_inputs(a, lda, z, ldz, want_vec, W.by_value ? range_z_cap(n, W, mode) : W.m(), 1)) return rc;
-  double* wn = ctx.pool.get_t<double>("sub.wfull", (size_t)n);   // all n eigenvalues, where the full D&C serves the window
-  if (const int rc = F.scale(a, lda, w, fill_rest ? n : wcap)) {
+  if (const int rc = F.scale(a, lda, w, fill_rest ? n : range_w_cap(W, mode))) {
     if (W.by_value) *W.m_out = 0;
     return rc;
   }
@@ -356,61 +290,18 @@ int range_solve_dev(Context& ctx, int n, RangeWindow W, double* a, int lda, doub
   F.t1 = now_s();
   band_reduce_dev(ctx, n, a, lda, d, e, lde, mf, band);
   EIGX_HIP_CHECK(hipStreamSynchronize(st));
-  const double t2 = F.t2 = now_s();
+  F.t2 = now_s();
 
-  if (W.by_value) {
-    resolve_value_window(ctx, n, d, e, lde, band, F.sigma, W);
-    const int mv = *W.m_out;
-    info.m = mv;
-    if (mode != 'C' && mv > W.mmax) return EIGX_ERR_WINDOW;
-    if (mode == 'C' || mv == 0) {   // nothing to compute: the statistics of the reduction alone
-      F.t3 = now_s();
-      info.t[0] = F.t3 - t2;
-      return F.finish(w, 0, 0.0, 0, n);
-    }
-  }
-  const int il = W.il, iu = W.iu, m = iu - il + 1;
-  const int nw = fill_rest ? n : m;   // entries of w that belong to this call
-
-  // ---- eigenvalues il .. iu, then their eigenvectors -------------------------------------------------------------------
-  if (!want_vec) {
-    band_bisect_range_dev(ctx, n, il, iu, d, e, lde, band, w);
-    info.path = 1;
-    info.t[0] = now_s() - t2;
-  } else {
-    int path = range_takes_subset(n, m) ? 1 : 3;
-    if (path == 1) {
-      double* wsel = ctx.pool.get_t<double>("sub.wsel", (size_t)m);
-      band_bisect_range_dev(ctx, n, il, iu, d, e, lde, band, wsel);
-      const double tb = now_s();
-      info.t[0] = tb - t2;
-      double cond = 0.0;
-      double ts[2] = {0.0, 0.0};
-      const int rc_ev = band_eigvec_dev(ctx, n, m, d, e, lde, band, wsel, w, z, ldz, &cond, ts);
-      if (rc_ev < 0) return rc_ev;
-      info.cond = cond; info.t[1] = ts[0]; info.t[2] = ts[1];
-      if (rc_ev > 0) path = 2;   // refused by the acceptance test
-    }
-    if (path != 1) {
-      // the full divide and conquer for the lowest iu pairs; columns il .. iu are the answer
-      const double tf = now_s();
-      double* zf = z;
-      int ldzf = ldz;
-      if (il > 1) {
-        ldzf = pad_ld(n);
-        zf = ctx.pool.get_t<double>("sub.zfull", (size_t)ldzf * iu);
-      }
-      band_dc_dev(ctx, n, iu, d, e, lde, band, wn, zf, ldzf);
-      hipLaunchKernelGGL(copy_vec_kernel, dim3((m + 255) / 256), dim3(256), 0, st, (const double*)(wn + il - 1), w, m);
-      if (il > 1)
-        EIGX_HIP_CHECK(hipMemcpy2DAsync(z, (size_t)ldz * 8, zf + (size_t)(il - 1) * ldzf, (size_t)ldzf * 8, (size_t)n * 8, (size_t)m,
-                                        hipMemcpyDeviceToDevice, st));
-      EIGX_HIP_CHECK(hipStreamSynchronize(st));
-      info.t[2] += now_s() - tf;
-    }
-    info.path = path;
-  }
-  F.t3 = now_s();
+  // ---- eigenvalues il .. iu, then their band eigenvectors (range.hip): m columns go into z; the D&C's iu > m columns into
+  // sub.zfull, out of which the window is copied
+  const RangeStaged S = range_window_stage(F, W, mode, d, e, lde, band, w, "sub.wfull", [&](int ncols) {
+    if (ncols == W.iu - W.il + 1) return RangeRoom{z, ldz};
+    return RangeRoom{ctx.pool.get_t<double>("sub.zfull", (size_t)pad_ld(n) * ncols), pad_ld(n)};
+  });
+  if (S.ended) return S.rc;
+  const int iu = W.iu, m = iu - W.il + 1;
+  if (want_vec && S.z != z)
+    EIGX_HIP_CHECK(hipMemcpy2DAsync(z, (size_t)ldz * 8, S.z, (size_t)S.ld * 8, (size_t)n * 8, (size_t)m, hipMemcpyDeviceToDevice, st));
 
   // ---- back-transformation of the m columns (prepared here: the Rayleigh-Ritz solve used the bt.* buffers) -------------
   if (want_vec) {
@@ -418,9 +309,8 @@ int range_solve_dev(Context& ctx, int n, RangeWindow W, double* a, int lda, doub
     F.return_z(z, ldz, m);
   }
   if (fill_rest && iu < n) band_bisect_range_dev(ctx, n, iu + 1, n, d, e, lde, band, w + m);
-  const double f_mid = want_vec ? (info.path == 1 ? 6.0 * (double)n * m * m : ctx.timers[11]) : 0.0;
-  const int rc = F.finish(w, nw, f_mid, want_vec ? m : 0, n);
-  info.t[3] = ctx.timers[3];
+  const int rc = F.finish(w, fill_rest ? n : m, S.f_mid, want_vec ? m : 0, n);
+  range_info().t[3] = ctx.timers[3];
   return rc;
 }
 
@@ -428,19 +318,10 @@ int range_solve_dev(Context& ctx, int n, RangeWindow W, double* a, int lda, doub
 // w(1:mmax) with NaN); a gets its a(1:3,1) statistics whenever the call returns EIGX_OK.
 static int range_solve_host(Context& ctx, int n, RangeWindow W, double* a, int lda, double* w, double* z, int ldz, int mf, int mb,
                      char mode, int band) {
-  if (!ctx.initialized) return EIGX_ERR_NOT_INITIALIZED;
-  if (ctx.grid.nranks != 1) return range_solve_dev(ctx, n, W, a, lda, w, z, ldz, mf, mb, mode, band, false);   // refuses
-  mode = upper_case(mode);
-  if (!range_args_ok(n, W, a, lda, w, z, ldz, mode)) return EIGX_ERR_BAD_ARG;
-  const int wcap = range_w_cap(W, mode);
-  const HostStage S(ctx, 8, n, n, a, lda, nullptr, 0, mode == 'A' ? range_z_cap(n, W, mode) : 1, std::max(wcap, 1));
-  const int rc = range_solve_dev(ctx, n, W, S.a, S.ldd, S.w, S.z, S.ldd, mf, mb, mode, band, false);
-  const int m = (W.by_value && rc == EIGX_OK) ? (mode == 'C' ? 0 : *W.m_out) : wcap;   // entries that were written
-  if (rc == EIGX_OK || rc == EIGX_ERR_NONFINITE) S.w_back(w, m);
-  if (rc != EIGX_OK) return rc;
-  if (mode == 'A') S.back(z, ldz, S.z, m);
-  S.back(a, lda, S.a, 1, std::min(n, 3));
-  return EIGX_OK;
+  return range_host_form(
+      ctx, n, W, 8, a, lda, false, nullptr, 0, w, z, ldz, mode,
+      [&](const HostStage& S) { return range_solve_dev(ctx, n, W, S.a, S.ldd, S.w, S.z, S.ldd, mf, mb, mode, band, false); },
+      [&](const HostStage& S) { S.back(a, lda, S.a, 1, std::min(n, 3)); });
 }
 
 // nb = block size of the 2-D block-cyclic layout of a and z over the process grid (1 = the cyclic layout of the

@@ -1,5 +1,5 @@
 """Bit-for-bit record of what the whole-solve drivers return, for comparing two builds of the library.
-usage: [EIGX_LIB=other/libeigenexa_amd.so] gpu_frame_dump.py OUTDIR [--quick | --batch]
+usage: [EIGX_LIB=other/libeigenexa_amd.so] gpu_frame_dump.py OUTDIR [--quick | --batch | --range]
 
 Runs a fixed list of seeded calls of eigen_sx / eigen_s, the index-range solves and eigen_h (device and host entry
 points; every mode, panel widths, nvec < n, odd leading dimensions, scaled and non-finite inputs) and writes for each
@@ -11,7 +11,8 @@ the value-window solves (m and il as well), the host forms of all four generalis
 A or B, B not positive definite, a bad window, ldb < n) from sentinel-filled w and z.  An array above 8 MiB is stored as
 its SHA-256.  Last the nine batched families -- the uniform eigx_{s,h,gev,hgev}_batch, the ragged eigx_{s,h,gev,hgev}_vbatch and
 the windowed eigx_s_batch_range, host and device forms (batch_section below); --batch runs that section alone (well under a
-minute).
+minute).  --range runs range_section below alone instead (under a minute): every range entry of the five families, which the
+list above covers only in part; its .held files (bytes in the workspace pool) depend on the build, the others do not.
 The library is deterministic, so two builds that compute the same leave directories that `cmp` finds equal:
     for f in A/*; do cmp $f B/$(basename $f); done
 Run each build in a fresh process.  --quick leaves out n >= 2048."""
@@ -217,10 +218,132 @@ def batch_section():
     lib.eigx_tune(21, cutoff)
 
 
-SENT_B = -7.25   # what w and z of the batch section start from
+def range_section():
+    """The range solves of the five families (sx, s, h, gev, hgev), by index and by value, device and host forms, at n = 5, 65,
+    130 with a window that begins at the first eigenvalue and one that does not: mode A with key 17 = 100 and 0 (paths 1 and 3)
+    and with key 19 = 0 (the acceptance test refuses: path 2); modes N and, by value, C; by value also an empty window, one that
+    overflows mmax and infinite bounds; a NaN in A; A scaled by 1e+200 and 1e-200; and key 18 = 1 through eigx_sx_dev.
+    Recorded: the status, w, z, *m, *il, a (its seconds a(2,1) zeroed) and b as the call leaves them, eigx_range_info, errinfo, the
+    timers without their seconds (entries 0 .. 4), and, in a file of its own kind (.held), eigx_held_bytes()."""
+
+    def problem(fam, n):
+        cplx, pencil = fam in ("h", "hgev"), fam in ("gev", "hgev")
+        g = np.random.default_rng(5000 + n)
+        S = g.standard_normal((n, n)) + (1j * g.standard_normal((n, n)) if cplx else 0.0)
+        X = g.standard_normal((n, n)) + (1j * g.standard_normal((n, n)) if cplx else 0.0)
+        A = (S + S.conj().T) / 2
+        if not pencil:
+            return A, None, np.linalg.eigvalsh(A)
+        B = X @ X.conj().T / n + np.eye(n)
+        B = (B + B.conj().T) / 2
+        L = np.linalg.cholesky(B)
+        Cm = np.linalg.solve(L, np.linalg.solve(L, A).conj().T).conj().T
+        return A, B, np.linalg.eigvalsh((Cm + Cm.conj().T) / 2)
+
+    def image(M, ld, form):
+        if form == "host":
+            return np.asfortranarray(M.copy())
+        t = torch.zeros(M.shape[1], ld, dtype=torch.complex128 if np.iscomplexobj(M) else torch.float64, device=dev)
+        t[:, :M.shape[0]] = torch.from_numpy(np.ascontiguousarray(M.T)).to(dev)
+        return t
+
+    def one(label, fam, form, A, B, win, mode):
+        """win = (il, iu) or (vl, vu, mmax); w has two entries and z one column more than the call may write"""
+        n = A.shape[0]
+        by_value = len(win) == 3
+        cap = max(win[2] if by_value else win[1] - win[0] + 1, 0)
+        ld = n if form == "host" else n + (n & 1)
+        a, b = image(A, ld, form), None if B is None else image(B, ld, form)
+        if form == "host":
+            w, z = np.full(cap + 2, SENT_B), np.full((n, cap + 1), SENT_B, dtype=A.dtype, order="F")
+            ptr = lambda x: x.ctypes.data
+        else:
+            w = torch.full((cap + 2,), SENT_B, dtype=torch.float64, device=dev)
+            z = torch.full((cap + 1, ld), SENT_B, dtype=a.dtype, device=dev)
+            ptr = lambda x: x.data_ptr()
+        m, il = C.c_int(-77), C.c_int(-77)
+        fn = getattr(lib, f"eigx_{fam}_range" + ("_v" if by_value else "") + ("_dev" if form == "dev" else ""))
+        head = (n, float(win[0]), float(win[1]), win[2], C.byref(m), C.byref(il)) if by_value else (n, win[0], win[1])
+        mats = (ptr(a), ld) + (() if B is None else (ptr(b), ld))
+        rc = fn(*head, *mats, ptr(w), ptr(z), ld, *((0, 0) if B is None else ()), mode.encode())
+        if form == "dev":
+            torch.cuda.synchronize()
+            w, z, a = w.cpu().numpy(), z.cpu().numpy(), a.cpu().numpy().T.copy()
+            b = None if b is None else b.cpu().numpy()
+        if B is None and rc == 0 and n > 1:
+            a[1, 0] = 0.0   # the seconds of the call
+        finish(f"{fam}_{form}_n{n}_{label}", rc, w=w, z=z, a=a, m=np.int64(m.value), il=np.int64(il.value),
+               **({} if b is None else dict(b=b)))
+
+    def finish(label, rc, **arrays):
+        path, mm, cond = C.c_int(0), C.c_int(0), C.c_double(0.0)
+        lib.eigx_range_info(C.byref(path), C.byref(mm), C.byref(cond))
+        err, t = C.c_int64(0), (C.c_double * 16)()
+        lib.eigx_get_errinfo(C.byref(err))
+        lib.eigx_get_timers(t)
+        save(f"{label}_path{path.value}", rc=np.int64(rc), rinfo=np.array([path.value, mm.value, cond.value]), errinfo=np.int64(err.value),
+             timers=np.array([0.0] * 5 + t[5:]), held=np.int64(lib.eigx_held_bytes()), **arrays)
+
+    def mid(lam, k):
+        """between the eigenvalues k and k + 1 (1-based); k = 0: below all"""
+        return lam[0] - 1.0 if k == 0 else 0.5 * (lam[k - 1] + lam[k])
+
+    for n in (5, 65, 130):
+        wins = ((1, 3), (2, 4)) if n == 5 else ((1, 10), (n // 3, n // 3 + 9))
+        for fam in ("sx", "s", "h", "gev", "hgev"):
+            A, B, lam = problem(fam, n)
+            bad = A.copy()
+            bad[1, 3] = bad[3, 1] = np.nan
+            for form in ("dev", "host"):
+                for il, iu in wins:
+                    m = iu - il + 1
+                    vl, vu = mid(lam, il - 1), mid(lam, iu)
+                    for tag, k17, k19 in (("p1", 100, None), ("p3", 0, None), ("p2", 100, 0)):
+                        old17 = lib.eigx_tune(17, k17)
+                        old19 = lib.eigx_tune(19, k19) if k19 is not None else None
+                        one(f"{il}_{iu}_{tag}_A", fam, form, A, B, (il, iu), "A")
+                        one(f"v{il}_{iu}_{tag}_A", fam, form, A, B, (vl, vu, m + 1), "A")
+                        lib.eigx_tune(17, old17)
+                        if old19 is not None:
+                            lib.eigx_tune(19, old19)
+                    one(f"{il}_{iu}_N", fam, form, A, B, (il, iu), "N")
+                    one(f"v{il}_{iu}_N", fam, form, A, B, (vl, vu, m + 1), "N")
+                    one(f"v{il}_{iu}_C", fam, form, A, B, (vl, vu, 0), "C")
+                    one(f"v{il}_{iu}_small", fam, form, A, B, (vl, vu, m - 1), "A")
+                    one(f"{il}_{iu}_nan", fam, form, bad, B, (il, iu), "A")
+                    one(f"v{il}_{iu}_nan", fam, form, bad, B, (vl, vu, m + 1), "A")
+                    for tag, s in (("big", 1e200), ("tiny", 1e-200)):
+                        one(f"{il}_{iu}_{tag}", fam, form, A * s, B, (il, iu), "A")
+                        one(f"v{il}_{iu}_{tag}", fam, form, A * s, B, (vl * s, vu * s, m + 1), "A")
+                il = wins[1][0]
+                gap = lam[il - 1] - lam[il - 2]
+                one("v_empty", fam, form, A, B, (lam[il - 2] + 0.25 * gap, lam[il - 2] + 0.75 * gap, 4), "A")
+                one("v_all", fam, form, A, B, (-np.inf, np.inf, n), "A")
+                one("v_upper", fam, form, A, B, (mid(lam, n - 3), np.inf, 4), "A")
+        # the opt-in route of eigx_sx_dev: the lowest nvec pairs by the range path, w filled up by bisection
+        A = problem("sx", n)[0]
+        nvec = 3 if n == 5 else 10
+        old18 = lib.eigx_tune(18, 1)
+        a = image(A, n + (n & 1), "dev")
+        z = torch.full((nvec + 1, n + (n & 1)), SENT_B, dtype=torch.float64, device=dev)
+        w = torch.full((n + 2,), SENT_B, dtype=torch.float64, device=dev)
+        rc = lib.eigx_sx_dev(n, nvec, a.data_ptr(), n + (n & 1), w.data_ptr(), z.data_ptr(), n + (n & 1), 128, 128, b"A")
+        torch.cuda.synchronize()
+        lib.eigx_tune(18, old18)
+        a = a.cpu().numpy().T.copy()
+        a[1, 0] = 0.0
+        finish(f"sx_dev_n{n}_key18", rc, w=w.cpu().numpy(), z=z.cpu().numpy(), a=a)
+
+
+SENT_B = -7.25   # what w and z of the batch and range sections start from
 _sym = {}
 
 
+if "--range" in sys.argv[2:]:
+    range_section()
+    lib.eigx_free()
+    print(f"DUMPED {count[0]} calls into {out}", flush=True)
+    sys.exit(0)
 if "--batch" in sys.argv[2:]:
     batch_section()
     lib.eigx_free()
