@@ -200,6 +200,13 @@ BATCH_RANGE_SIGNATURES = {
     "eigx_batch_range_info": (C.c_int, [_c_int_p, _c_int_p, _c_int_p]),
 }
 
+# The same for include/eigenexa_amd_hbatch_range.h -- extension: the Hermitian sibling (csrc/hbatch_range.hip); a, z
+# interleaved complex, the argument kinds those of eigx_s_batch_range.  eigx_batch_range_info above reports these calls too.
+HBATCH_RANGE_SIGNATURES = {
+    "eigx_h_batch_range": (C.c_int, _BATCH_RANGE),
+    "eigx_h_batch_range_dev": (C.c_int, _BATCH_RANGE),
+}
+
 # The same for include/eigenexa_amd_gemm_lab.h, which eigenexa_amd.h does NOT include: a test interface to the GEMM dispatcher
 # (csrc/gemm_lab.hip) for tests/test_gemm_paths.py; nothing in the package calls it.  Strides are int64_t; the table of
 # eigx_dgemm_gather_table_dev is a host int64_t array.
@@ -230,7 +237,7 @@ def load():
         )
     lib = C.CDLL(LIB_PATH, mode=C.RTLD_GLOBAL)
     for name, (res, args) in {**SIGNATURES, **GBATCH_SIGNATURES, **HGBATCH_SIGNATURES, **VBATCH_SIGNATURES,
-                               **GVBATCH_SIGNATURES, **BATCH_RANGE_SIGNATURES}.items():
+                               **GVBATCH_SIGNATURES, **BATCH_RANGE_SIGNATURES, **HBATCH_RANGE_SIGNATURES}.items():
         fn = getattr(lib, name)  # AttributeError = header/library mismatch: fail loudly
         fn.restype = res
         fn.argtypes = args

@@ -447,7 +447,7 @@ def _info_addr(info, dev, names):
 
 
 def _solve_batch(which, n, batch, a, lda, w, z, ldz, mode, info, stride_a, ldw, stride_z, window=None, pencil=None):
-    """the uniform-batch wrappers; window = (il, iu) for eigen_s_batch_range (z has m = iu - il + 1 columns and w has m entries per
+    """the uniform-batch wrappers; window = (il, iu) for eigen_s_batch_range / eigen_h_batch_range (z has m = iu - il + 1 columns and w has m entries per
     matrix, otherwise n), pencil = (b, ldb, stride_b) for the generalised families"""
     name = f"eigen_{which}_batch" + ("_range" if window else "")
     has_b = pencil is not None
@@ -532,10 +532,24 @@ def eigen_s_batch_range(n, batch, il, iu, a, lda, w, z, ldz, mode="A", info=None
     _solve_batch("s", n, batch, a, lda, w, z, ldz, mode, info, stride_a, ldw, stride_z, window=(il, iu))
 
 
+def eigen_h_batch_range(n, batch, il, iu, a, lda, w, z, ldz, mode="A", info=None, stride_a=None, ldw=None, stride_z=None):
+    """EXTENSION (not in the reference): eigenpairs ``il .. iu`` (1-based, inclusive, the same window for every matrix) of
+    ``batch`` complex Hermitian matrices of one size ``n`` in one call, one GPU -- the complex sibling of
+    ``eigen_s_batch_range``.  ``a`` as for ``eigen_h_batch`` (complex128; leading dimensions and strides count complex
+    elements).  With ``m = iu - il + 1``: ``w[ldw, batch]`` (float64) receives ``w[:m, k]``, ascending; ``z[ldz, m, batch]``
+    (complex128) the orthonormal eigenvectors ``z[:n, :m, k]`` (mode 'A'; mode 'N': eigenvalues only, ``z`` may be None).
+    Defaults: ``stride_a = lda * n``, ``stride_z = ldz * m``, ``ldw = m``.  ``info`` and ``last_status()`` as for
+    ``eigen_s_batch``.  For ``n <= 96`` either a window kernel (Hermitian tridiagonalisation, then Sturm-count bisection,
+    inverse iteration and Rayleigh-Ritz on the real tridiagonal matrix, all in LDS; mode 'A' for ``m <= 16`` and ``n <= 64``)
+    or the kernel of ``eigen_h_batch`` with a slice solves the batch, by a measured rule (``eigx_tune`` key 26);
+    ``batch_range_info()`` tells which.  Larger ``n`` runs ``eigen_h_range`` matrix by matrix."""
+    _solve_batch("h", n, batch, a, lda, w, z, ldz, mode, info, stride_a, ldw, stride_z, window=(il, iu))
+
+
 def batch_range_info():
-    """What the last ``eigen_s_batch_range`` call did: ``route`` (1 the window kernel, 2 the full batch solve and a slice, 3
-    ``eigen_s_range`` matrix by matrix above the cutoff), ``m`` and ``redone`` (how many matrices the acceptance test of the
-    window kernel sent to route 2)."""
+    """What the last ``eigen_s_batch_range`` or ``eigen_h_batch_range`` call did: ``route`` (1 the window kernel, 2 the full
+    batch solve and a slice, 3 ``eigen_s_range`` / ``eigen_h_range`` matrix by matrix above the cutoff), ``m`` and ``redone``
+    (how many matrices the acceptance test of the window kernel sent to route 2)."""
     import collections
 
     lib = _lib.load()

@@ -472,7 +472,6 @@ struct RangeBatchArgs {
 
 int g_route_key = 0;       // key 26: 0 = automatic, 1 = route 1 wherever eligible, 2 = route 2 always
 int g_accept_key = 50;     // key 27: the acceptance bound in percent
-struct { int route = 0, m = 0, redone = 0; } g_last;
 
 // the widest window the class of n serves in mode 'A'
 int window_width(int n) { return n <= 96 ? 16 : 4; }
@@ -541,12 +540,11 @@ int brange_frame_dev(Context& ctx, RangeBatchArgs g) {
   const double t0 = now_s();
   hipStream_t st = ctx.stream;
   const int n = g.n, batch = g.batch, m = g.m();
-  g_last.m = m;
-  g_last.redone = 0;
+  int redone = 0;
   if (n > get_batch_nmax()) {
     // route 3: the index-range solver of one large matrix (eigx_s_range_dev with the interface's default block sizes), matrix by
     // matrix; unlike the uniform frame this one sets errinfo to -1 after a failed matrix (the table of DESIGN section 8h)
-    g_last.route = 3;
+    set_batch_range_last(3, m, 0);
     rc = batch_loop_above_cutoff(batch, g.info, [&](int k) {
       return range_solve_dev(ctx, n, RangeWindow::index(g.il, g.iu), g.a + (size_t)k * g.stride_a, g.lda, g.w + (size_t)k * g.ldw,
                              g.mode == 'A' ? g.z + (size_t)k * g.stride_z : nullptr, g.ldz, 48, 128, g.mode, 1, false);
@@ -556,7 +554,7 @@ int brange_frame_dev(Context& ctx, RangeBatchArgs g) {
   } else {
     const bool eligible = g.mode == 'N' || m <= window_width(n);
     const bool one = g_route_key == 2 ? false : eligible && (g_route_key == 1 || route1_measured_faster(n, g.mode, m));
-    g_last.route = one ? 1 : 2;
+    set_batch_range_last(one ? 1 : 2, m, 0);
     FirstFailure ff;                     // a word of its own: route 2's eigx_s_batch_dev arms batch.first while this one is live
     ff.arm(ctx, "brange.first", st);
     unsigned long long* first = ff.dev;
@@ -574,7 +572,7 @@ int brange_frame_dev(Context& ctx, RangeBatchArgs g) {
         while (k1 < batch && marks[k1]) ++k1;
         const int rr = brange_full_and_slice(ctx, g, k, k1 - k, first);
         if (rr != EIGX_OK) return rr;
-        g_last.redone += k1 - k;
+        set_batch_range_last(1, m, redone += k1 - k);
         k = k1;
       }
     } else {
@@ -602,6 +600,17 @@ int brange_frame_host(Context& ctx, RangeBatchArgs g) {
 }
 
 }  // namespace
+
+// what the last call of a windowed batched entry did (eigx_batch_range_info): written by this file's frame and by the Hermitian
+// family's (hbatch_range.hip) through set_batch_range_last
+static struct { int route = 0, m = 0, redone = 0; } g_last;
+void set_batch_range_last(int route, int m, int redone) {
+  g_last.route = route;
+  g_last.m = m;
+  g_last.redone = redone;
+}
+int get_batch_range_route() { return g_route_key; }
+int get_batch_range_accept() { return g_accept_key; }
 
 int set_batch_range_route(int v) {
   if (v < 0 || v > 2) return -1;

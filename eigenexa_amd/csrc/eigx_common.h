@@ -178,9 +178,14 @@ int set_hgbatch_nmax(int v);
 // the current value of key 23: the ragged pencil batch of gvbatch.hip applies it block by block (eigx_hgev_vbatch sits in
 // hgbatch.hip beside key 24)
 int get_gbatch_nmax();
-// tuning hooks (eigx_tune keys 26 and 27, batch_range.hip): the route of eigx_s_batch_range (0 automatic, 1 the window kernel
-// wherever eligible, 2 the full solve and a slice) and the acceptance bound of the window kernel in percent, 0 .. 101
+// tuning hooks (eigx_tune keys 26 and 27, batch_range.hip): the route of eigx_s_batch_range and eigx_h_batch_range (0 automatic, 1
+// the window kernel wherever eligible, 2 the full solve and a slice) and the acceptance bound of the window kernels in percent,
+// 0 .. 101; the current values for the Hermitian family (hbatch_range.hip)
 int set_batch_range_route(int v);
 int set_batch_range_accept(int v);
+int get_batch_range_route();
+int get_batch_range_accept();
+// the record behind eigx_batch_range_info (batch_range.hip): what the last call of a windowed batched entry of either family did
+void set_batch_range_last(int route, int m, int redone);
 
 }  // namespace eigx

@@ -37,6 +37,7 @@ module eigen_libs_mod
   public :: eigen_s_batch   ! EXTENSION: many small symmetric matrices in one call (one GPU)
   public :: eigen_s_batch_range   ! EXTENSION: eigenpairs il .. iu of many small symmetric matrices in one call (one GPU)
   public :: eigen_h_batch   ! EXTENSION: many small complex Hermitian matrices in one call (one GPU)
+  public :: eigen_h_batch_range   ! EXTENSION: eigenpairs il .. iu of many small complex Hermitian matrices in one call (one GPU)
   public :: eigen_s_vbatch  ! EXTENSION: many small symmetric matrices of differing sizes in one call (one GPU)
   public :: eigen_h_vbatch  ! EXTENSION: many small complex Hermitian matrices of differing sizes in one call (one GPU)
   public :: eigen_gev_vbatch  ! EXTENSION: many small symmetric-definite pencils of differing sizes in one call (one GPU)
@@ -158,6 +159,19 @@ module eigen_libs_mod
       integer(c_int64_t), value :: stride_a, stride_z
       real(c_double), intent(inout) :: a(*)
       real(c_double), intent(inout) :: w(*), z(*)
+      character(kind=c_char), value :: mode
+      integer(c_int), intent(out), optional :: info(*)
+    end function
+    ! EXTENSION (not in the reference): eigenpairs il .. iu of batch complex Hermitian matrices of one size, one GPU; leading
+    ! dimensions and strides in complex elements
+    integer(c_int) function eigx_h_batch_range(n, batch, il, iu, a, lda, stride_a, w, ldw, z, ldz, stride_z, mode, info) &
+        bind(C, name="eigx_h_batch_range")
+      import :: c_int, c_int64_t, c_double, c_double_complex, c_char
+      integer(c_int), value :: n, batch, il, iu, lda, ldw, ldz
+      integer(c_int64_t), value :: stride_a, stride_z
+      complex(c_double_complex), intent(inout) :: a(*)
+      real(c_double), intent(inout) :: w(*)
+      complex(c_double_complex), intent(inout) :: z(*)
       character(kind=c_char), value :: mode
       integer(c_int), intent(out), optional :: info(*)
     end function
@@ -848,6 +862,28 @@ contains
     rc = eigx_h_batch(n, batch, a, lda, int(lda, c_int64_t) * size(a, 2), w, size(w, 1), z, ldz, &
                       int(ldz, c_int64_t) * size(z, 2), md, info)
   end subroutine eigen_h_batch
+
+  !> eigen_h_batch_range(n, batch, il, iu, a, lda, w, z, ldz, mode, info) -- EXTENSION, not in the reference: eigenpairs
+  !> il .. iu (of the ascending spectrum, the same window for every matrix) of batch complex Hermitian matrices a(:, :, k) of
+  !> one size n on one GPU.  Upper triangles significant (of the diagonal the real parts), a destroyed; with m = iu - il + 1,
+  !> w(1:m, k) real and ascending and z(1:n, 1:m, k) orthonormal (w needs m rows, z m columns); modes 'A' and 'N' (z not
+  !> written).  info(k) = 0, or the status of matrix k (-5: NaN / Inf, w(1:m, k) = NaN); the other matrices are solved all the
+  !> same.  For n <= 96 one launch of a window kernel (bisection and inverse iteration in LDS) or of eigen_h_batch's kernel
+  !> with a slice, by a measured rule; larger n by eigen_h_range matrix by matrix.
+  subroutine eigen_h_batch_range(n, batch, il, iu, a, lda, w, z, ldz, mode, info)
+    integer, intent(in) :: n, batch, il, iu, lda, ldz
+    complex(8), intent(inout), contiguous :: a(:, :, :)
+    real(8), intent(inout), contiguous :: w(:, :)
+    complex(8), intent(inout), contiguous :: z(:, :, :)
+    character(*), intent(in), optional :: mode
+    integer, intent(out), optional :: info(*)
+    integer :: rc
+    character(kind=c_char) :: md
+    md = 'A'
+    if (present(mode)) md = mode(1:1)
+    rc = eigx_h_batch_range(n, batch, il, iu, a, lda, int(lda, c_int64_t) * size(a, 2), w, size(w, 1), z, ldz, &
+                            int(ldz, c_int64_t) * size(z, 2), md, info)
+  end subroutine eigen_h_batch_range
 
   !> eigen_s_vbatch(batch, n, a, ia, lda, w, iw, z, iz, ldz, mode, info) -- EXTENSION, not in the reference: the eigenpairs of batch
   !> symmetric matrices of differing orders n(k) on one GPU, held in the flat arrays a, w and z: block k starts at a(ia(k)),
