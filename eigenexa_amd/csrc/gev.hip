@@ -19,13 +19,36 @@ __global__ void symmetrize_kernel(double* __restrict__ a, int lda, int n) {
     a[(size_t)j * lda + i] = a[(size_t)i * lda + j];
 }
 
-// b(:, j) = z(:, j) * w(j)^(-1/2)   (diag_mult, src/KMATH_EIGEN_GEV_misc.F:49-104)
-__global__ void scale_cols_rsqrt_kernel(const double* __restrict__ z, int ldz, const double* __restrict__ w,
-                                        double* __restrict__ b, int ldb, int n) {
-  const int j = blockIdx.y;
-  const double s = 1.0 / sqrt(w[j]);
+// b(:, j) = z(:, k) * w(k)^(-1/2), k = n - 1 - j   (diag_mult, src/KMATH_EIGEN_GEV_misc.F:49-104, the columns in DESCENDING
+// order of w).  A' = b^T A b is graded by w^(-1/2): in this order its large entries stand at the bottom right, where the
+// reduction of eigen_s starts (it works from the last column up), and the small eigenvalues of A' come out to their own
+// scale.  In ascending order they came out to eps |A'|: at cond(B) = 1e4 a hundred times the residual.
+__global__ void scale_cols_rsqrt_reversed_kernel(const double* __restrict__ z, int ldz, const double* __restrict__ w,
+                                                 double* __restrict__ b, int ldb, int n) {
+  const int j = blockIdx.y, k = n - 1 - j;
+  const double s = 1.0 / sqrt(w[k]);
   for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x)
-    b[(size_t)j * ldb + i] = z[(size_t)j * ldz + i] * s;
+    b[(size_t)j * ldb + i] = z[(size_t)k * ldz + i] * s;
+}
+
+// columns j and n - 1 - j of b change places (grid.y = n / 2)
+__global__ void reverse_cols_kernel(double* __restrict__ b, int ldb, int n) {
+  const int j = blockIdx.y, k = n - 1 - j;
+  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
+    const double t = b[(size_t)j * ldb + i];
+    b[(size_t)j * ldb + i] = b[(size_t)k * ldb + i];
+    b[(size_t)k * ldb + i] = t;
+  }
+}
+
+// rows i and n - 1 - i of a change places in every column (grid.y = n)
+__global__ void reverse_rows_kernel(double* __restrict__ a, int lda, int n) {
+  double* col = a + (size_t)blockIdx.y * lda;
+  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n / 2; i += gridDim.x * blockDim.x) {
+    const double t = col[i];
+    col[i] = col[n - 1 - i];
+    col[n - 1 - i] = t;
+  }
 }
 
 // ---- multi-rank KMATH_EIGEN_GEV on the 2-D cyclic blocks -------------------------------------------------------------
@@ -235,7 +258,9 @@ static int dist_gemm_nn(Context& ctx, int n, const double* A, int lda, const dou
 // Same sequence as KMATH_EIGEN_GEV_1 (src/KMATH_EIGEN_GEV_1.F:57-139): eigen_s(B, 'X') -> B^(-1/2) := Z_B W_B^(-1/2);
 // A' = B^(-1/2)^T A B^(-1/2) by two GEMMs; eigen_s(A', 'X') -> w, Y; Z = B^(-1/2) Y (B-orthonormal).  On entry only
 // the upper triangles of a and b are significant; a, b are destroyed (a holds Y, b holds B^(-1/2) on exit, as in
-// the reference).  One GPU; all three products run on the fp64 MFMA GEMM.
+// the reference).  One GPU; all three products run on the fp64 MFMA GEMM, and between the two solves the columns of
+// B^(-1/2) stand in descending order of w (scale_cols_rsqrt_reversed_kernel says why); the several-rank path keeps the
+// ascending order.
 // Several ranks: the same sequence on the 2-D cyclic blocks, nothing gathered -- two distributed eigen_s solves, the
 // symmetrisation of A and the transposed factor by dist_transpose, three SUMMA products with local MFMA GEMMs
 // (round 4; the first version gathered A and B on every rank).
@@ -288,7 +313,7 @@ int gev_dev(Context& ctx, int n, double* a, int lda, double* b, int ldb, double*
   if (rc != EIGX_OK) return rc;
   F.mark();
   if (!b_is_positive_definite(ctx, w)) return EIGX_ERR_NOT_SPD;
-  hipLaunchKernelGGL(scale_cols_rsqrt_kernel, dim3(8, n), dim3(256), 0, st, z, ldz, w, b, ldb, n);
+  hipLaunchKernelGGL(scale_cols_rsqrt_reversed_kernel, dim3(8, n), dim3(256), 0, st, z, ldz, w, b, ldb, n);
   const int ldc = pad_ld(n);
   double* c = ctx.pool.get_t<double>("gev.c", (size_t)ldc * n);
   dgemm_dev(st, 'N', 'N', n, n, n, 1.0, a, lda, b, ldb, 0.0, c, ldc);          // C  = A B^(-1/2)
@@ -299,6 +324,10 @@ int gev_dev(Context& ctx, int n, double* a, int lda, double* b, int ldb, double*
   if (rc != EIGX_OK) return rc;
   F.mark();
   dgemm_dev(st, 'N', 'N', n, n, n, 1.0, b, ldb, a, lda, 0.0, z, ldz);          // Z = B^(-1/2) Y
+  if (n > 1) {   // on exit b and a are what the reference leaves: B^(-1/2) with its columns in ascending order of w, and its Y
+    hipLaunchKernelGGL(reverse_cols_kernel, dim3(8, n / 2), dim3(256), 0, st, b, ldb, n);
+    hipLaunchKernelGGL(reverse_rows_kernel, dim3(8, n), dim3(256), 0, st, a, lda, n);
+  }
   EIGX_HIP_CHECK(hipStreamSynchronize(st));
   return F.finish();
 }

@@ -9,6 +9,10 @@ and the two triangular solves in mpmath at 50 digits (longdouble loses eps_LD co
 dense route.  References are computed in the process and cached: the B matrices go through LAPACK's QR and are not bit-
 reproducible across machines.
 
+The second half serves the dense generalised solvers (tests/test_dense_pencil_accuracy.py,
+tests/golden/make_dense_pencil_bounds.py): longdouble substitution and reduction with a given float64 factor as the stage
+references, E_f / E_t / E_c, the case table of the whole solves, an exactly scaled copy of a pencil, and their bounds.
+
 A plain module: no fixtures, no pytest settings."""
 import functools
 import json
@@ -31,6 +35,13 @@ PENCIL_C = (0, 1, 4, 8)                         # B = I (0) or Q diag(logspace(0
 BOUNDS_JSON = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "batch_accuracy_bounds.json")
 METRICS = ("E_w", "E_r", "E_o")
 PENCIL_METRICS = ("E_w", "E_r", "E_o", "E_f")
+# the dense Cholesky-route and spectral-route solvers (tests/test_dense_pencil_accuracy.py): sizes of the stage cases and of the
+# whole solves, and the record of what LAPACK reaches on them
+DENSE_BOUNDS_JSON = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "dense_pencil_bounds.json")
+STAGE_SIZES = (1, 2, 63, 64, 65, 130, 200, 330)
+STAGE_NRHS = 7                                  # the widest nrhs of the solve stage besides n
+DENSE_SIZES = (65, 130)
+STAGES = {"chol": ("E_f",), "trsm": ("E_t",), "reduce": ("E_c",)}
 
 
 def window_width(n):
@@ -289,18 +300,20 @@ def metrics(cs, w, Z, il=1):
     return E_w, E_r, E_o
 
 
-def pencil_metrics(pc, w, Z, U):
-    """(E_w, E_r, E_o, E_f) of a pencil in eps, products in longdouble: E_w = max_k |w_k - lambda_k| / (eps cond(B) max(|lambda_k|,
-    |A|_2 / |B|_2)), E_r = max_j |A z_j - w_j B z_j|_2 / (eps cond(B) (|A|_2 + |w_j| |B|_2) |z_j|_2), E_o = max |Z^H B Z - I| /
-    (eps cond(B)), E_f = max |U^H U - B| / (eps |B|_2) for the returned factor (U = None: 0)"""
+def pencil_metrics(pc, w, Z, U, il=1):
+    """(E_w, E_r, E_o, E_f) of the columns il .. il + m - 1 of a pencil in eps, products in longdouble: E_w = max_k |w_k -
+    lambda_k| / (eps cond(B) max(|lambda_k|, |A|_2 / |B|_2)), E_r = max_j |A z_j - w_j B z_j|_2 / (eps cond(B) (|A|_2 + |w_j|
+    |B|_2) |z_j|_2), E_o = max |Z^H B Z - I| / (eps cond(B)), E_f = max |U^H U - B| / (eps |B|_2) for the returned factor (U =
+    None: 0)"""
     cplx = np.iscomplexobj(pc.A)
     T = np.clongdouble if cplx else LD
     w = np.asarray(w, dtype=np.float64)
-    n = pc.n
+    m = len(w)
+    lam = pc.lam[il - 1:il - 1 + m]
     ek = EPS * pc.cond
-    den = np.maximum(np.abs(pc.lam), LD(pc.anorm / pc.bnorm))
+    den = np.maximum(np.abs(lam), LD(pc.anorm / pc.bnorm))
     den = np.where(den > 0, den, LD(1))
-    E_w = float((np.abs(w.astype(LD) - pc.lam) / den).max()) / ek
+    E_w = float((np.abs(w.astype(LD) - lam) / den).max()) / ek
     Zl, Al, Bl = np.asarray(Z, dtype=T), np.asarray(pc.A, dtype=T), np.asarray(pc.B, dtype=T)
     BZ = Bl @ Zl
     R = Al @ Zl - BZ * w.astype(LD)[None, :]
@@ -309,7 +322,7 @@ def pencil_metrics(pc, w, Z, U):
     scale = (LD(pc.anorm) + np.abs(w).astype(LD) * LD(pc.bnorm)) * zn
     scale = np.where(scale > 0, scale, LD(1))
     E_r = float((rn / scale).max()) / ek
-    E_o = float(np.abs(Zl.conj().T @ BZ - np.eye(n)).max()) / ek
+    E_o = float(np.abs(Zl.conj().T @ BZ - np.eye(m)).max()) / ek
     E_f = 0.0
     if U is not None:
         Ul = np.asarray(U, dtype=T)
@@ -334,3 +347,187 @@ def bounds(kind, c=None, family=None):
     if own:
         out.update(own["bounds"])
     return out
+
+
+# ------------------------------------------------------------------------------------------------ dense pencils: stages
+def nan_lower(M, diag=True):
+    """M with NaN in the strict lower triangle and, for a complex M (unless diag is False), in Im of the diagonal: what a
+    routine that reads the upper triangle only must not notice"""
+    M = np.array(M)
+    lower = np.tril(np.ones(M.shape, dtype=bool), -1)
+    if np.iscomplexobj(M):
+        M[lower] = np.nan + 1j * np.nan
+        if diag:
+            M.imag[np.diag_indices(M.shape[0])] = np.nan
+    else:
+        M[lower] = np.nan
+    return M
+
+
+def upper_of(M):
+    """the upper triangular matrix a routine has left in the upper triangle of M (the strict lower triangle as zero)"""
+    return np.triu(np.nan_to_num(np.asarray(M), nan=0.0))
+
+
+def solve_upper_ld(U, R, trans):
+    """op(U)^-1 R for the upper triangular U by substitution in longdouble / clongdouble: trans 'N' -> U, anything else ->
+    U^H.  All right-hand sides advance together, one row of U per step."""
+    cplx = np.iscomplexobj(U) or np.iscomplexobj(R)
+    T = np.clongdouble if cplx else LD
+    Ul, X = np.asarray(U, dtype=T), np.array(R, dtype=T)
+    n = Ul.shape[0]
+    if trans == "N":
+        for i in range(n - 1, -1, -1):
+            X[i] = (X[i] - Ul[i, i + 1:] @ X[i + 1:]) / Ul[i, i]
+    else:
+        L = Ul.conj().T
+        for i in range(n):
+            X[i] = (X[i] - L[i, :i] @ X[:i]) / L[i, i]
+    return X
+
+
+def reduce_ld(A, U):
+    """U^-H A U^-1 by two substitutions in longdouble with the float64 U as it is"""
+    X = solve_upper_ld(U, A, "C")                             # U^-H A
+    return solve_upper_ld(U, X.conj().T, "C").conj().T        # (U^-H (U^-H A)^H)^H
+
+
+class Stage:
+    """what the stage tests of one (kind, n, c) share: B = overlap(n, c), its float64 factor U from LAPACK (B = U^H U: the solve
+    and reduction stages are judged independently of the project's factorisation), |B|_2, |U^-1|_2^2, max(n, STAGE_NRHS) seeded
+    normal right-hand sides R (so that every nrhs the tests pass has that many columns behind it) and op(U)^-1 R for both ops
+    in longdouble.  Read-only."""
+
+    def __init__(self, kind, n, c):
+        import scipy.linalg
+
+        cplx = kind == "hgev"
+        self.kind, self.n, self.c = kind, n, c
+        self.B = overlap(n, c, cplx=cplx)
+        self.U = np.triu(scipy.linalg.cholesky(self.B))
+        sv = np.linalg.svd(self.U, compute_uv=False)
+        self.bnorm, self.uinv2 = float(np.linalg.eigvalsh(self.B)[-1]), float(sv[-1] ** -2.0)
+        self.R = _normal(_rng(1, n, 200 + c), (n, n), cplx)
+        if n < STAGE_NRHS:                         # the first n columns stay what they were: LAPACK's record is taken on those
+            self.R = np.hstack([self.R, _normal(_rng(1, n, 300 + c), (n, STAGE_NRHS - n), cplx)])
+        self.X = {"N": solve_upper_ld(self.U, self.R, "N"), "C": solve_upper_ld(self.U, self.R, "C")}
+        for M in (self.B, self.U, self.R, self.X["N"], self.X["C"]):
+            M.setflags(write=False)
+
+
+class Reduction:
+    """A = matrix(family, n), U of stage(kind, n, c), |A|_2 and C_ref = U^-H A U^-1 in longdouble.  Read-only."""
+
+    def __init__(self, kind, n, family, c):
+        self.st = stage(kind, n, c)
+        self.A = matrix(family, n, cplx=kind == "hgev")
+        self.anorm = float(np.abs(np.linalg.eigvalsh(self.A)).max())
+        self.C = reduce_ld(self.A, self.st.U)
+        self.A.setflags(write=False)
+        self.C.setflags(write=False)
+
+
+@functools.lru_cache(maxsize=None)
+def stage(kind, n, c):
+    return Stage(kind, n, c)
+
+
+@functools.lru_cache(maxsize=None)
+def reduction(kind, n, family, c):
+    return Reduction(kind, n, family, c)
+
+
+def factor_error(B, U, bnorm):
+    """E_f = max |U^H U - B| / (eps |B|_2), the product in longdouble"""
+    T = np.clongdouble if np.iscomplexobj(B) else LD
+    Ul = np.asarray(U, dtype=T)
+    return float(np.abs(Ul.conj().T @ Ul - np.asarray(B, dtype=T)).max()) / (EPS * bnorm)
+
+
+def solve_error(X, Xref):
+    """E_t = max_j |x_j - xref_j|_2 / (eps |xref_j|_2), column by column"""
+    T = Xref.dtype
+    d = np.sqrt((np.abs(np.asarray(X, dtype=T) - Xref) ** 2).sum(axis=0))
+    r = np.sqrt((np.abs(Xref) ** 2).sum(axis=0))
+    return float((d / np.where(r > 0, r, LD(1))).max()) / EPS
+
+
+def solve_residual(U, X, R, trans):
+    """max_j |op(U) x_j - r_j|_2 / (eps |U|_2 |x_j|_2) in longdouble: reported, not bounded (substitution's is ten times smaller
+    than a correct block inversion's for op = U^H)"""
+    T = np.clongdouble if np.iscomplexobj(U) or np.iscomplexobj(X) else LD
+    Ul, Xl = np.asarray(U, dtype=T), np.asarray(X, dtype=T)
+    D = (Ul if trans == "N" else Ul.conj().T) @ Xl - np.asarray(R, dtype=T)
+    d = np.sqrt((np.abs(D) ** 2).sum(axis=0))
+    x = np.sqrt((np.abs(Xl) ** 2).sum(axis=0))
+    return float((d / np.where(x > 0, x, LD(1))).max()) / (EPS * float(np.linalg.norm(U, 2)))
+
+
+def reduction_error(rd, Cu):
+    """E_c = max over the upper triangle of |C - C_ref| / (eps |U^-1|_2^2 |A|_2); of a complex C's diagonal the real part"""
+    C = np.array(Cu)
+    if np.iscomplexobj(C):
+        C[np.diag_indices(rd.st.n)] = C.real.diagonal()
+    up = np.triu_indices(rd.st.n)
+    scale = rd.st.uinv2 * (rd.anorm if rd.anorm > 0 else 1.0)
+    return float(np.abs(np.asarray(C, dtype=rd.C.dtype)[up] - rd.C[up]).max()) / (EPS * scale)
+
+
+# ------------------------------------------------------------------------------------------------ dense pencils: whole solves
+def dense_cases(kind):
+    """(n, family of A, c) of the whole solves: every pencil at n = 65; at n = 130 every real one and, of the complex ones,
+    (glued_rot, 8) alone (their references take 10 s each)"""
+    out = [(65, f, c) for f in PENCIL_A for c in PENCIL_C]
+    if kind == "gev":
+        return out + [(130, f, c) for f in PENCIL_A for c in PENCIL_C]
+    return out + [(130, "glued_rot", 8)]
+
+
+class ScaledPencil:
+    """the pencil (A 2^ka, B 2^kb) of pc: the scaling and with it the reference (lam 2^(ka - kb)) are exact, cond(B) is that of
+    pc, and every metric of pencil_metrics is invariant"""
+
+    def __init__(self, pc, ka, kb):
+        self.kind, self.n, self.family, self.c, self.cond = pc.kind, pc.n, pc.family, pc.c, pc.cond
+        sc = (lambda M, k: np.ldexp(M.real, k) + 1j * np.ldexp(M.imag, k)) if np.iscomplexobj(pc.A) else np.ldexp
+        self.A, self.B = sc(pc.A, ka), sc(pc.B, kb)
+        self.lam = pc.lam * LD(2) ** (ka - kb)
+        self.anorm, self.bnorm = float(np.ldexp(pc.anorm, ka)), float(np.ldexp(pc.bnorm, kb))
+        for M in (self.A, self.B, self.lam):
+            M.setflags(write=False)
+
+
+def windows_dense(n):
+    """(il, iu) of the range solvers' cases, 1-based: everything, the lowest 8, the highest 8, 8 in the middle"""
+    mid = (n - 8) // 2 + 1
+    return [(1, n), (1, 8), (n - 7, n), (mid, mid + 7)]
+
+
+def basis_error(pc, F):
+    """max |F^H B F - I| / (eps cond(B)) for the B-orthonormal basis the spectral route returns, products in longdouble"""
+    T = np.clongdouble if np.iscomplexobj(pc.A) else LD
+    Fl = np.asarray(F, dtype=T)
+    return float(np.abs(Fl.conj().T @ (np.asarray(pc.B, dtype=T) @ Fl) - np.eye(pc.n)).max()) / (EPS * pc.cond)
+
+
+@functools.lru_cache(maxsize=None)
+def _dense_record():
+    return json.load(open(DENSE_BOUNDS_JSON))
+
+
+def dense_bounds(kind, c, route=None):
+    """the bounds of the whole solves, {metric: bound}: BOUND_FACTOR x what LAPACK's gv / gvd and potrf reach at worst on
+    dense_cases(kind) in the cond group c.  A route ("cholesky", "spectral") the record lists under "family_bounds" as
+    kind-route has bounds of its own there, per cond group, with the reason."""
+    rec = _dense_record()
+    out = {k: BOUND_FACTOR * v for k, v in rec["worst"][kind]["whole"][f"c{c}"].items()}
+    own = rec.get("family_bounds", {}).get(f"{kind}-{route}")
+    if own:
+        out.update(own["bounds"].get(f"c{c}", {}))
+    return out
+
+
+def stage_bounds(kind, what):
+    """the bounds of one stage (chol, trsm, reduce), {metric: bound}: BOUND_FACTOR x LAPACK's worst value (potrf, trtrs, sygst /
+    hegst) over STAGE_SIZES and PENCIL_C"""
+    return {k: BOUND_FACTOR * v for k, v in _dense_record()["worst"][kind][what].items()}
