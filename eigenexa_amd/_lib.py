@@ -207,6 +207,16 @@ HBATCH_RANGE_SIGNATURES = {
     "eigx_h_batch_range_dev": (C.c_int, _BATCH_RANGE),
 }
 
+# The same for include/eigenexa_amd_gbatch_range.h -- extension: the pencil sibling (csrc/gbatch_range.hip); b comes
+# back as U.  eigx_batch_range_info above reports these calls too.
+# n, batch, il, iu, a, lda, stride_a, b, ldb, stride_b, w, ldw, z, ldz, stride_z, mode, info
+_GEV_BATCH_RANGE = [_INT, _INT, _INT, _INT, _PTR, _INT, C.c_int64, _PTR, _INT, C.c_int64, _PTR, _INT, _PTR, _INT, C.c_int64,
+                    C.c_char, _PTR]
+GBATCH_RANGE_SIGNATURES = {
+    "eigx_gev_batch_range": (C.c_int, _GEV_BATCH_RANGE),
+    "eigx_gev_batch_range_dev": (C.c_int, _GEV_BATCH_RANGE),
+}
+
 # The same for include/eigenexa_amd_gemm_lab.h, which eigenexa_amd.h does NOT include: a test interface to the GEMM dispatcher
 # (csrc/gemm_lab.hip) for tests/test_gemm_paths.py; nothing in the package calls it.  Strides are int64_t; the table of
 # eigx_dgemm_gather_table_dev is a host int64_t array.
@@ -237,7 +247,8 @@ def load():
         )
     lib = C.CDLL(LIB_PATH, mode=C.RTLD_GLOBAL)
     for name, (res, args) in {**SIGNATURES, **GBATCH_SIGNATURES, **HGBATCH_SIGNATURES, **VBATCH_SIGNATURES,
-                               **GVBATCH_SIGNATURES, **BATCH_RANGE_SIGNATURES, **HBATCH_RANGE_SIGNATURES}.items():
+                               **GVBATCH_SIGNATURES, **BATCH_RANGE_SIGNATURES, **HBATCH_RANGE_SIGNATURES,
+                               **GBATCH_RANGE_SIGNATURES}.items():
         fn = getattr(lib, name)  # AttributeError = header/library mismatch: fail loudly
         fn.restype = res
         fn.argtypes = args

@@ -180,7 +180,7 @@ int set_hgbatch_nmax(int v);
 int get_gbatch_nmax();
 // tuning hooks (eigx_tune keys 26 and 27, batch_range.hip): the route of eigx_s_batch_range and eigx_h_batch_range (0 automatic, 1
 // the window kernel wherever eligible, 2 the full solve and a slice) and the acceptance bound of the window kernels in percent,
-// 0 .. 101; the current values for the Hermitian family (hbatch_range.hip)
+// 0 .. 101; the current values for the Hermitian family (hbatch_range.hip) and the pencils (gbatch_range.hip)
 int set_batch_range_route(int v);
 int set_batch_range_accept(int v);
 int get_batch_range_route();

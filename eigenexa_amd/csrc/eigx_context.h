@@ -438,6 +438,8 @@ int vbatch_frame_dev(Context& ctx, VbArgs g, int cutoff, int top, VbPencilLaunch
 int vbatch_frame_host(Context& ctx, VbArgs g, int cutoff, int top, VbPencilLaunch launch, VbSolveOne solve_one);
 // gbatch.hip: pencil k of a uniform batch above the cutoff, through gev_range_dev (gvbatch.hip hands it its blocks)
 int gbatch_solve_one(Context& ctx, const BatchArgs& g, int k);
+// the same for eigenpairs il .. iu (gbatch_range.hip): w(1:m) at g.w + k g.ldw, z(1:n, 1:m) at block k of g.z
+int gbatch_solve_window(Context& ctx, const BatchArgs& g, int k, int il, int iu);
 // Host form of a solve on a local block of nr rows: a (nc columns), b (the same; b_h == nullptr: none), z (zcols columns,
 // allocated only) and w (nw entries) in the pool buffers host.a / host.b / host.z (esz 8) or host.ha / host.hb / host.hz
 // (esz 16, interleaved complex) and host.w, leading dimension ldd.  What comes back, and when, is each driver's contract:

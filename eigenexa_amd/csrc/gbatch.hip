@@ -180,30 +180,34 @@ void gbatch_launch(const BatchArgs& g, hipStream_t st, unsigned long long* first
 // Above the cutoff: gev_range_dev with il = 1, iu = n.  It wants even leading dimensions: a pencil with an odd lda, ldb or ldz is
 // staged through the pool buffers gbatch.a / gbatch.b / gbatch.z, and U and z are copied out where it succeeded.  The frame
 // calls this once per pencil, so the three buffers are looked up by name per pencil (the same size every time: only the first
-// lookup of a call can allocate).  (Also what eigx_gev_vbatch does with a block above the cutoff: gvbatch.hip.)
-int gbatch_solve_one(Context& ctx, const BatchArgs& g, int k) {
-  const int n = g.n;
+// lookup of a call can allocate).  (Also what eigx_gev_vbatch does with a block above the cutoff: gvbatch.hip.)  With a window
+// il .. iu (gbatch_solve_window: eigx_gev_batch_range above the cutoff, gbatch_range.hip) w and z hold m = iu - il + 1 entries
+// and columns.
+int gbatch_solve_window(Context& ctx, const BatchArgs& g, int k, int il, int iu) {
+  const int n = g.n, m = iu - il + 1;
   const bool want_vec = g.mode == 'A';
   double* ak = g.block(g.a, g.stride_a, k);
   double* bk = g.block(g.b, g.stride_b, k);
   double* wk = g.w + (size_t)k * g.ldw;
   double* zk = want_vec ? g.block(g.z, g.stride_z, k) : nullptr;
   const bool stage = ((g.lda | g.ldb) & 1) || (want_vec && (g.ldz & 1));
-  if (!stage) return gev_range_dev(ctx, n, RangeWindow::index(1, n), ak, g.lda, bk, g.ldb, wk, zk, g.ldz, g.mode);
+  if (!stage) return gev_range_dev(ctx, n, RangeWindow::index(il, iu), ak, g.lda, bk, g.ldb, wk, zk, g.ldz, g.mode);
   const int lds = pad_ld(n);
   const size_t col = (size_t)n * 8;
   double* as = ctx.pool.get_t<double>("gbatch.a", (size_t)lds * n);
   double* bs = ctx.pool.get_t<double>("gbatch.b", (size_t)lds * n);
-  double* zs = want_vec ? ctx.pool.get_t<double>("gbatch.z", (size_t)lds * n) : nullptr;
+  double* zs = want_vec ? ctx.pool.get_t<double>("gbatch.z", (size_t)lds * m) : nullptr;
   EIGX_HIP_CHECK(hipMemcpy2D(as, (size_t)lds * 8, ak, (size_t)g.lda * 8, col, (size_t)n, hipMemcpyDeviceToDevice));
   EIGX_HIP_CHECK(hipMemcpy2D(bs, (size_t)lds * 8, bk, (size_t)g.ldb * 8, col, (size_t)n, hipMemcpyDeviceToDevice));
-  const int rk = gev_range_dev(ctx, n, RangeWindow::index(1, n), as, lds, bs, lds, wk, zs, lds, g.mode);
+  const int rk = gev_range_dev(ctx, n, RangeWindow::index(il, iu), as, lds, bs, lds, wk, zs, lds, g.mode);
   if (rk == EIGX_OK) {
     EIGX_HIP_CHECK(hipMemcpy2D(bk, (size_t)g.ldb * 8, bs, (size_t)lds * 8, col, (size_t)n, hipMemcpyDeviceToDevice));
-    if (want_vec) EIGX_HIP_CHECK(hipMemcpy2D(zk, (size_t)g.ldz * 8, zs, (size_t)lds * 8, col, (size_t)n, hipMemcpyDeviceToDevice));
+    if (want_vec) EIGX_HIP_CHECK(hipMemcpy2D(zk, (size_t)g.ldz * 8, zs, (size_t)lds * 8, col, (size_t)m, hipMemcpyDeviceToDevice));
   }
   return rk;
 }
+
+int gbatch_solve_one(Context& ctx, const BatchArgs& g, int k) { return gbatch_solve_window(ctx, g, k, 1, g.n); }
 
 int set_gbatch_nmax(int v) {
   if (v < 0 || v > EIGX_GBATCH_NMAX) return -1;
