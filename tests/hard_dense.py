@@ -13,6 +13,10 @@ The second half serves the dense generalised solvers (tests/test_dense_pencil_ac
 tests/golden/make_dense_pencil_bounds.py): longdouble substitution and reduction with a given float64 factor as the stage
 references, E_f / E_t / E_c, the case table of the whole solves, an exactly scaled copy of a pencil, and their bounds.
 
+The last part serves the dense standard drivers and their stages (tests/test_dense_driver_accuracy.py,
+tests/golden/make_dense_driver_bounds.py): the case table with its panel widths, E_s / E_q of a reduction with its Q formed, the
+back-transformation reflector by reflector in longdouble (E_b), an exactly scaled copy of a standard problem, and their bounds.
+
 A plain module: no fixtures, no pytest settings."""
 import functools
 import json
@@ -188,7 +192,9 @@ def embed(A):
 def reference_eigenvalues(A):
     """ascending eigenvalues of the symmetric or Hermitian A (float64, longdouble or their complex types) in longdouble"""
     A = np.asarray(A)
-    with np.errstate(over="ignore"):              # a Sturm pivot of 1e-4900 next to a double eigenvalue: e^2 / q = inf is meant
+    if not A.any():                               # the zero matrix: what the bisection returns after 9 s at n = 330
+        return np.zeros(A.shape[0], dtype=LD)
+    with np.errstate(over="ignore"):             # a Sturm pivot of 1e-4900 next to a double eigenvalue: e^2 / q = inf is meant
         if np.iscomplexobj(A):
             return np.sort(hb._bisect_tridiagonal(*hb._householder_tridiagonalise(embed(A))))[::2].copy()
         return np.sort(hb._bisect_tridiagonal(*hb._householder_tridiagonalise(A)))
@@ -531,3 +537,129 @@ def stage_bounds(kind, what):
     """the bounds of one stage (chol, trsm, reduce), {metric: bound}: BOUND_FACTOR x LAPACK's worst value (potrf, trtrs, sygst /
     hegst) over STAGE_SIZES and PENCIL_C"""
     return {k: BOUND_FACTOR * v for k, v in _dense_record()["worst"][kind][what].items()}
+
+
+# ------------------------------------------------------------------------------------------------ dense standard drivers
+# eigx_sx / eigx_s / eigx_h and their stages eigx_band_reduce_dev / eigx_trbak_dev (tests/test_dense_driver_accuracy.py,
+# tests/golden/make_dense_driver_bounds.py)
+DRIVER_BOUNDS_JSON = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "dense_driver_bounds.json")
+# (n, m_forward, m_backward, q), q = eigx_tune key 2 (super-block factor of the back-transformation): the smallest sizes with
+# more than one panel, a partial last panel and a partial last back-transformation block; (330, 32, 128, 2) has one super-block
+# of 256 reflectors and a head range of 72 (band 1) / 71 (band 2), (517, 64, 128, 4) one super-block of 512
+DRIVER_TABLE = ((5, 4, 8, 0), (65, 16, 16, 0), (130, 48, 48, 0), (330, 128, 128, 0), (330, 32, 128, 2), (517, 64, 128, 4))
+DRIVER_LARGE_FAMILIES = ("random", "graded", "glued_rot", "blocks")         # the families at n = 517
+DRIVER_H_TABLE = ((5, 4, 8, 0), (17, 4, 8, 0), (65, 16, 16, 0), (130, 48, 48, 0), (200, 48, 48, 0))
+DRIVER_STAGES = {"reduce": ("E_s", "E_q"), "trbak": ("E_b",), "whole": METRICS}
+BACK_INPUTS = ("identity", "normal", "scaled")
+# reflector norms over 14 decades (graded both ways), trivial reflectors (glued_tri, diagonal) and whole trivial blocks (blocks)
+BACK_FAMILIES = ("graded", "graded_rev", "blocks", "diagonal", "glued_tri", "random")
+
+
+def driver_table(kind):
+    return DRIVER_H_TABLE if kind == "h" else DRIVER_TABLE
+
+
+def driver_families(n):
+    return DRIVER_LARGE_FAMILIES if n > 330 else FAMILIES
+
+
+def driver_cases(kind, max_n=None):
+    """the case table of the dense drivers, kind s or h: (n, m_forward, m_backward, q, family)"""
+    return [row + (f,) for row in driver_table(kind) if max_n is None or row[0] <= max_n for f in driver_families(row[0])]
+
+
+def driver_problems(kind):
+    """(n, family) of the table without repetition: what LAPACK's record is taken on (it has no panel widths)"""
+    return sorted({(c[0], c[4]) for c in driver_cases(kind)}, key=lambda c: (c[0], FAMILIES.index(c[1])))
+
+
+def driver_case_id(kind, c):
+    return f"{kind}-n{c[0]}-mf{c[1]}-mb{c[2]}-q{c[3]}-{c[4]}"
+
+
+def similarity_metrics(A, Q, T=None, anorm=None):
+    """(E_s, E_q) of a reduction A -> T = Q^H A Q in eps, products in longdouble / clongdouble: E_s = max |Q^H A Q - T| /
+    (eps |A|_2) over all entries, E_q = max |Q^H Q - I| / eps.  anorm = |A|_2 (Case.anorm; LAPACK's if None), 1 for the zero
+    matrix.  T = None (a driver that does not return (d, e)): T is the real part of the tridiagonal part of Q^H A Q itself, so
+    that E_s measures what lies outside the band and the imaginary part inside it."""
+    cplx = np.iscomplexobj(A) or np.iscomplexobj(Q)
+    Tt = np.clongdouble if cplx else LD
+    if anorm is None:
+        anorm = float(np.abs(np.linalg.eigvalsh(A)).max())
+    anorm = anorm if anorm > 0 else 1.0
+    Ql = np.asarray(Q, dtype=Tt)
+    S = Ql.conj().T @ (np.asarray(A, dtype=Tt) @ Ql)
+    n = S.shape[0]
+    if T is None:
+        i, j = np.indices((n, n))
+        T = np.where(np.abs(i - j) <= 1, S.real, LD(0))
+    E_s = float(np.abs(S - np.asarray(T, dtype=Tt)).max()) / (EPS * anorm)
+    E_q = float(np.abs(Ql.conj().T @ Ql - np.eye(n)).max()) / EPS
+    return E_s, E_q
+
+
+def apply_reflectors_ld(refl, e, band, Z):
+    """the back-transformation H_(n-1) ... H_band Z reflector by reflector in longdouble, from the stored form of the band
+    reduction: H_i = I - u u^T / beta_i with the un-normalised u = refl[0:L, i], L = i - band + 1, and beta_i = -u_(L-1)
+    e[band-1, i] (a zero beta is the identity), as orc_trbak of oracle/eigx_oracle.c recovers it.  Returns Z_ref (longdouble);
+    E_b = solve_error(Z, Z_ref) = max_j |z_j - zref_j|_2 / (eps |zref_j|_2)."""
+    R = np.asarray(refl, dtype=LD)
+    el = np.asarray(e, dtype=LD).reshape(band, -1)
+    X = np.array(Z, dtype=LD)
+    for i in range(band, R.shape[0]):
+        L = i - band + 1
+        beta = -R[L - 1, i] * el[band - 1, i]
+        if beta == 0:
+            continue
+        u = R[:L, i]
+        X[:L] -= np.outer(u, (u @ X[:L]) / beta)
+    return X
+
+
+def back_input(n, which, cplx=False):
+    """seeded Z of the back-transformation tests: the identity, normal random, normal random with the columns scaled by
+    logspace(0, -14)"""
+    if which == "identity":
+        return np.eye(n, dtype=np.complex128 if cplx else np.float64)
+    Z = _normal(_rng(2, n, 400), (n, n), cplx)
+    if which == "scaled":
+        Z = Z * np.logspace(0.0, -14.0, n)[None, :]
+    elif which != "normal":
+        raise ValueError(which)
+    return Z
+
+
+class ScaledDense:
+    """the standard problem A 2^k of a Case: the scaling and with it the reference (lam 2^k) are exact, and every metric of
+    metrics and similarity_metrics is invariant"""
+
+    def __init__(self, cs, k):
+        self.kind, self.n, self.family, self.k = cs.kind, cs.n, cs.family, k
+        self.A = (np.ldexp(cs.A.real, k) + 1j * np.ldexp(cs.A.imag, k)) if np.iscomplexobj(cs.A) else np.ldexp(cs.A, k)
+        self.lam = cs.lam * LD(2) ** k
+        self.anorm = float(np.ldexp(cs.anorm, k))
+        self.A.setflags(write=False)
+        self.lam.setflags(write=False)
+
+
+@functools.lru_cache(maxsize=None)
+def _driver_record():
+    return json.load(open(DRIVER_BOUNDS_JSON))
+
+
+def driver_stage_bounds(kind, what, family=None):
+    """the bounds of one stage of the dense drivers (reduce: E_s, E_q; trbak: E_b; whole: E_w, E_r, E_o), {metric: bound}:
+    BOUND_FACTOR x LAPACK's worst value over the table (sytrd / hetrd with Q formed, ormqr / unmqr, syevd / heevd).  A family
+    the record lists under "family_bounds" as kind-family has bounds of its own there, per stage, with the reason and the
+    measured value."""
+    rec = _driver_record()
+    out = {k: BOUND_FACTOR * v for k, v in rec["worst"][kind][what].items()}
+    own = rec.get("family_bounds", {}).get(f"{kind}-{family}")
+    if own:
+        out.update(own["bounds"].get(what, {}))
+    return out
+
+
+def driver_bounds(kind, family=None):
+    """the bounds of the whole solves of eigx_sx / eigx_s (kind s) and eigx_h (kind h)"""
+    return driver_stage_bounds(kind, "whole", family)
