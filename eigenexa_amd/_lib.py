@@ -217,6 +217,13 @@ GBATCH_RANGE_SIGNATURES = {
     "eigx_gev_batch_range_dev": (C.c_int, _GEV_BATCH_RANGE),
 }
 
+# The same for include/eigenexa_amd_hgbatch_range.h -- extension: the complex pencil sibling (csrc/hgbatch_range.hip); a, b,
+# z interleaved complex, b comes back as U.  The argument kinds are those of eigx_gev_batch_range.
+HGBATCH_RANGE_SIGNATURES = {
+    "eigx_hgev_batch_range": (C.c_int, _GEV_BATCH_RANGE),
+    "eigx_hgev_batch_range_dev": (C.c_int, _GEV_BATCH_RANGE),
+}
+
 # The same for include/eigenexa_amd_gemm_lab.h, which eigenexa_amd.h does NOT include: a test interface to the GEMM dispatcher
 # (csrc/gemm_lab.hip) for tests/test_gemm_paths.py; nothing in the package calls it.  Strides are int64_t; the table of
 # eigx_dgemm_gather_table_dev is a host int64_t array.
@@ -248,7 +255,7 @@ def load():
     lib = C.CDLL(LIB_PATH, mode=C.RTLD_GLOBAL)
     for name, (res, args) in {**SIGNATURES, **GBATCH_SIGNATURES, **HGBATCH_SIGNATURES, **VBATCH_SIGNATURES,
                                **GVBATCH_SIGNATURES, **BATCH_RANGE_SIGNATURES, **HBATCH_RANGE_SIGNATURES,
-                               **GBATCH_RANGE_SIGNATURES}.items():
+                               **GBATCH_RANGE_SIGNATURES, **HGBATCH_RANGE_SIGNATURES}.items():
         fn = getattr(lib, name)  # AttributeError = header/library mismatch: fail loudly
         fn.restype = res
         fn.argtypes = args

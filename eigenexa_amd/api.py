@@ -447,7 +447,7 @@ def _info_addr(info, dev, names):
 
 
 def _solve_batch(which, n, batch, a, lda, w, z, ldz, mode, info, stride_a, ldw, stride_z, window=None, pencil=None):
-    """the uniform-batch wrappers; window = (il, iu) for eigen_s_batch_range / eigen_h_batch_range / eigen_gev_batch_range (z has m = iu - il + 1 columns and w has m entries per
+    """the uniform-batch wrappers; window = (il, iu) for eigen_s_batch_range / eigen_h_batch_range / eigen_gev_batch_range / eigen_hgev_batch_range (z has m = iu - il + 1 columns and w has m entries per
     matrix, otherwise n), pencil = (b, ldb, stride_b) for the generalised families"""
     name = f"eigen_{which}_batch" + ("_range" if window else "")
     has_b = pencil is not None
@@ -563,11 +563,30 @@ def eigen_gev_batch_range(n, batch, il, iu, a, lda, b, ldb, w, z, ldz, mode="A",
     _solve_batch("gev", n, batch, a, lda, w, z, ldz, mode, info, stride_a, ldw, stride_z, window=(il, iu), pencil=(b, ldb, stride_b))
 
 
+def eigen_hgev_batch_range(n, batch, il, iu, a, lda, b, ldb, w, z, ldz, mode="A", info=None, stride_a=None, stride_b=None, ldw=None,
+                           stride_z=None):
+    """EXTENSION (not in the reference): eigenpairs ``il .. iu`` (1-based, inclusive, the same window for every pencil) of
+    ``batch`` Hermitian-definite pencils ``A x = lambda B x`` of one size ``n`` in one call, one GPU -- the complex sibling of
+    ``eigen_gev_batch_range``.  ``a`` and ``b`` as for ``eigen_hgev_batch`` (complex128; leading dimensions and strides count
+    complex elements): upper triangles significant (of the diagonals the real parts), ``a`` destroyed, ``b`` returns ``U`` with
+    ``B = U^H U`` and a real positive diagonal in its upper triangle for every pencil that succeeded (bit for bit the ``U`` of
+    ``eigen_hgev_batch``; a failed pencil keeps its ``b``).  With ``m = iu - il + 1``: ``w[ldw, batch]`` (float64) receives
+    ``w[:m, k]``, ascending; ``z[ldz, m, batch]`` (complex128) the eigenvectors ``z[:n, :m, k]`` with ``z^H B z = I`` (mode 'A';
+    mode 'N': eigenvalues only, ``z`` may be None).  Defaults: ``stride_a = lda * n``, ``stride_b = ldb * n``,
+    ``stride_z = ldz * m``, ``ldw = m``.  ``info`` and ``last_status()`` as for ``eigen_hgev_batch`` (0, -5, -6 or -7 per
+    pencil).  For ``n <= 64`` either a window kernel (complex Cholesky, ``C = U^-H A U^-1``, Hermitian tridiagonalisation,
+    Sturm-count bisection, inverse iteration, Rayleigh-Ritz and ``Z = U^-1 V`` in LDS; mode 'A' for ``m <= 16`` at ``n <= 32``
+    and for ``m <= 8`` at ``33 <= n <= 64``, mode 'N' for any ``m``) or the kernel of ``eigen_hgev_batch`` with a slice solves
+    the batch, by a measured rule (``eigx_tune`` key 26); ``batch_range_info()`` tells which.  Larger ``n`` runs
+    ``KMATH_EIGEN_HGEV_RANGE`` pencil by pencil."""
+    _solve_batch("hgev", n, batch, a, lda, w, z, ldz, mode, info, stride_a, ldw, stride_z, window=(il, iu), pencil=(b, ldb, stride_b))
+
+
 def batch_range_info():
-    """What the last ``eigen_s_batch_range``, ``eigen_h_batch_range`` or ``eigen_gev_batch_range`` call did: ``route`` (1 the
-    window kernel, 2 the full batch solve and a slice, 3 ``eigen_s_range`` / ``eigen_h_range`` / ``eigen_gev_range`` matrix by
-    matrix above the cutoff), ``m`` and ``redone`` (how many matrices the acceptance test of the window kernel sent to route
-    2)."""
+    """What the last ``eigen_s_batch_range``, ``eigen_h_batch_range``, ``eigen_gev_batch_range`` or ``eigen_hgev_batch_range``
+    call did: ``route`` (1 the window kernel, 2 the full batch solve and a slice, 3 ``eigen_s_range`` / ``eigen_h_range`` /
+    ``eigen_gev_range`` / ``KMATH_EIGEN_HGEV_RANGE`` matrix by matrix above the cutoff), ``m`` and ``redone`` (how many matrices
+    the acceptance test of the window kernel sent to route 2)."""
     import collections
 
     lib = _lib.load()

@@ -374,7 +374,7 @@ int eigx_tune(int key, int value) {
   if (key == 23) return set_gbatch_nmax(value);   // the same for eigx_gev_batch (gbatch.hip)
   if (key == 24) return set_hgbatch_nmax(value);  // the same for eigx_hgev_batch (hgbatch.hip)
   if (key == 25) return set_gemm_latec_kmax(value);  // largest K of the one-GPU trailing update's late-C path, 0 = never (gemm_f64.hip)
-  if (key == 26) return set_batch_range_route(value);   // eigx_s_batch_range, eigx_h_batch_range, eigx_gev_batch_range: 0 automatic, 1 window kernel where eligible, 2 full solve + slice
+  if (key == 26) return set_batch_range_route(value);   // eigx_s_batch_range, eigx_h_batch_range, eigx_gev_batch_range, eigx_hgev_batch_range: 0 automatic, 1 window kernel where eligible, 2 full solve + slice
   if (key == 27) return set_batch_range_accept(value);  // its acceptance bound in percent, 0 .. 101 (101 refuses every matrix) (batch_range.hip)
   return -1;
 }

@@ -1,7 +1,7 @@
 // batch_frame.hip -- the host frame of the batched entries: uniform (eigx_s_batch: batch.hip, eigx_h_batch:
 // hbatch.hip, eigx_gev_batch: gbatch.hip, eigx_hgev_batch: hgbatch.hip), ragged (eigx_s_vbatch: vbatch.hip, eigx_h_vbatch:
 // hvbatch.hip, eigx_gev_vbatch: gvbatch.hip, eigx_hgev_vbatch: hgbatch.hip) and windowed (eigx_s_batch_range: batch_range.hip,
-// eigx_h_batch_range: hbatch_range.hip, eigx_gev_batch_range: gbatch_range.hip).
+// eigx_h_batch_range: hbatch_range.hip, eigx_gev_batch_range: gbatch_range.hip, eigx_hgev_batch_range: hgbatch_range.hip).
 // Host code only, no kernel:
 //   the pieces every frame is made of: the prologue (batch_entry_begin), the first-failure word (FirstFailure), the loop above
 //   the cutoff of a uniform batch (batch_loop_above_cutoff), the epilogue (batch_entry_end), the host staging of a uniform batch

@@ -269,6 +269,7 @@ int set_hgbatch_nmax(int v) {
   g_hgbatch_nmax = v;
   return old;
 }
+int get_hgbatch_nmax() { return g_hgbatch_nmax; }
 
 }  // namespace eigx
 

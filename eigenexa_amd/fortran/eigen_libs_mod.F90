@@ -45,6 +45,7 @@ module eigen_libs_mod
   public :: eigen_gev_batch   ! EXTENSION: many small symmetric-definite pencils in one call (one GPU)
   public :: eigen_hgev_batch   ! EXTENSION: many small Hermitian-definite pencils in one call (one GPU)
   public :: eigen_gev_batch_range   ! EXTENSION: eigenpairs il .. iu of many small symmetric-definite pencils in one call (one GPU)
+  public :: eigen_hgev_batch_range   ! EXTENSION: eigenpairs il .. iu of many small Hermitian-definite pencils in one call (one GPU)
 
   interface
     integer(c_int) function eigx_init(device) bind(C, name="eigx_init")
@@ -272,6 +273,19 @@ module eigen_libs_mod
         bind(C, name="eigx_hgev_batch")
       import :: c_int, c_int64_t, c_double, c_double_complex, c_char
       integer(c_int), value :: n, batch, lda, ldb, ldw, ldz
+      integer(c_int64_t), value :: stride_a, stride_b, stride_z
+      complex(c_double_complex), intent(inout) :: a(*), b(*)
+      real(c_double), intent(inout) :: w(*)
+      complex(c_double_complex), intent(inout) :: z(*)
+      character(kind=c_char), value :: mode
+      integer(c_int), intent(out), optional :: info(*)
+    end function
+    ! EXTENSION (not in the reference): eigenpairs il .. iu of batch Hermitian-definite pencils of one size, one GPU; leading
+    ! dimensions and strides in complex elements; info may be absent (NULL)
+    integer(c_int) function eigx_hgev_batch_range(n, batch, il, iu, a, lda, stride_a, b, ldb, stride_b, w, ldw, z, ldz, stride_z, &
+                                                  mode, info) bind(C, name="eigx_hgev_batch_range")
+      import :: c_int, c_int64_t, c_double, c_double_complex, c_char
+      integer(c_int), value :: n, batch, il, iu, lda, ldb, ldw, ldz
       integer(c_int64_t), value :: stride_a, stride_b, stride_z
       complex(c_double_complex), intent(inout) :: a(*), b(*)
       real(c_double), intent(inout) :: w(*)
@@ -1075,6 +1089,30 @@ contains
     rc = eigx_hgev_batch(n, batch, a, lda, int(lda, c_int64_t) * size(a, 2), b, ldb, int(ldb, c_int64_t) * size(b, 2), &
                          w, size(w, 1), z, ldz, int(ldz, c_int64_t) * size(z, 2), md, info)
   end subroutine eigen_hgev_batch
+
+  !> eigen_hgev_batch_range(n, batch, il, iu, a, lda, b, ldb, w, z, ldz, mode, info) -- EXTENSION, not in the reference:
+  !> eigenpairs il .. iu (of the ascending spectrum, the same window for every pencil) of batch Hermitian-definite pencils
+  !> a(:, :, k) x = lambda b(:, :, k) x of one size n on one GPU.  Upper triangles significant (of the diagonals the real parts), a
+  !> destroyed, b(:, :, k) returns U with B = U^H U and a real positive diagonal in its upper triangle (the U of eigen_hgev_batch,
+  !> bit for bit); with m = iu - il + 1, w(1:m, k) real and ascending and z(1:n, 1:m, k) with z^H B z = I (w needs m rows, z m
+  !> columns); modes 'A' and 'N' (z not written).  info(k) = 0, or the status of pencil k (-5: NaN / Inf, -7: B not positive
+  !> definite; w(1:m, k) = NaN, b(:, :, k) as passed); the other pencils are solved all the same.  For n <= 64 one launch of a
+  !> window kernel (bisection and inverse iteration in LDS; mode 'A' for m <= 16 at n <= 32 and m <= 8 above) or of
+  !> eigen_hgev_batch's kernel with a slice, by a measured rule; larger n by KMATH_EIGEN_HGEV_RANGE pencil by pencil.
+  subroutine eigen_hgev_batch_range(n, batch, il, iu, a, lda, b, ldb, w, z, ldz, mode, info)
+    integer, intent(in) :: n, batch, il, iu, lda, ldb, ldz
+    complex(8), intent(inout), contiguous :: a(:, :, :), b(:, :, :)
+    real(8), intent(inout), contiguous :: w(:, :)
+    complex(8), intent(inout), contiguous :: z(:, :, :)
+    character(*), intent(in), optional :: mode
+    integer, intent(out), optional :: info(*)
+    integer :: rc
+    character(kind=c_char) :: md
+    md = 'A'
+    if (present(mode)) md = mode(1:1)
+    rc = eigx_hgev_batch_range(n, batch, il, iu, a, lda, int(lda, c_int64_t) * size(a, 2), b, ldb, &
+                               int(ldb, c_int64_t) * size(b, 2), w, size(w, 1), z, ldz, int(ldz, c_int64_t) * size(z, 2), md, info)
+  end subroutine eigen_hgev_batch_range
 
   !> eigen_sx_range_v(n, vl, vu, mmax, m, il, a, lda, w, z, ldz, m_forward, m_backward, mode) -- EXTENSION, not in the
   !> reference (LAPACK's range = 'V'): the eigenpairs with vl <= lambda < vu by the pentadiagonal route on one GPU.  On

@@ -335,6 +335,9 @@ int eigx_h_batch_dev(int n, int batch, double* a_dev, int lda, int64_t stride_a,
 /* Windowed batches of pencils, eigx_gev_batch_range[_dev]: eigenpairs il .. iu of every symmetric-definite pencil of a batch --
  * EXTENSION: declared and documented in eigenexa_amd_gbatch_range.h. */
 #include "eigenexa_amd_gbatch_range.h"
+/* Windowed batches of complex pencils, eigx_hgev_batch_range[_dev]: eigenpairs il .. iu of every Hermitian-definite pencil of a
+ * batch -- EXTENSION: declared and documented in eigenexa_amd_hgbatch_range.h. */
+#include "eigenexa_amd_hgbatch_range.h"
 
 /* ScaLAPACK interop without a redistribution step.  The reference asks block-cyclic callers to
  * convert with pdgemr2d into its cyclic layout first (manual 3.4; benchmark/ev_test.f:68-84 does the reverse for the
@@ -605,8 +608,10 @@ int eigx_profile_read_kinds(double* out, int nkinds);
  * update reads its C tile under the last MFMAs instead of before the first (0 .. 511, default 256: the measurements of
  * DESIGN sections 3 and 5; 0 = never, for A/B; other values are refused; the update is rounded as C - sum below it and as
  * -((-C) + sum) above).  key 26 = the route of eigx_s_batch_range below the cutoff of key 21, of
- * eigx_h_batch_range below that of key 22 and of eigx_gev_batch_range below that of key 23: 0 = automatic (default: the
- * measured table of DESIGN section 8n, for the Hermitian family that of section 8o, for the pencils that of section 8p), 1 = the window kernel wherever it is eligible (mode 'N', or a window no wider than
+ * eigx_h_batch_range below that of key 22, of eigx_gev_batch_range below that of key 23 and of eigx_hgev_batch_range below that
+ * of key 24: 0 = automatic (default: the
+ * measured table of DESIGN section 8n, for the Hermitian family that of section 8o, for the pencils that of section 8p, for the
+ * complex pencils that of section 8q), 1 = the window kernel wherever it is eligible (mode 'N', or a window no wider than
  * its n-class serves), 2 = always the full batch solve and a slice; other values are refused.  key 27 = the acceptance bound
  * of the window kernel in percent (0 .. 101, default 50: every vector keeps half its norm in the second Gram-Schmidt pass;
  * 101 refuses every matrix, so that a test reaches the redo at a small size, like key 19; other values are refused).  Returns

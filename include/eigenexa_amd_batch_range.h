@@ -48,8 +48,8 @@ int eigx_s_batch_range(int n, int batch, int il, int iu, double* a, int lda, int
 int eigx_s_batch_range_dev(int n, int batch, int il, int iu, double* a_dev, int lda, int64_t stride_a, double* w_dev, int ldw,
                            double* z_dev, int ldz, int64_t stride_z, char mode, int* info_dev);
 /* What the last call of a windowed batched entry did -- the two above, their Hermitian siblings eigx_h_batch_range[_dev]
- * (eigenexa_amd_hbatch_range.h) or their pencil siblings eigx_gev_batch_range[_dev] (eigenexa_amd_gbatch_range.h), whichever
- * ran last: *route = 1, 2 or 3 as listed (1 also when some matrices went to the redo),
+ * (eigenexa_amd_hbatch_range.h) or their pencil siblings eigx_gev_batch_range[_dev] (eigenexa_amd_gbatch_range.h) and
+ * eigx_hgev_batch_range[_dev] (eigenexa_amd_hgbatch_range.h), whichever ran last: *route = 1, 2 or 3 as listed (1 also when some matrices went to the redo),
  * *m = iu - il + 1, *redone = the number of matrices the acceptance test of route 1 sent to route 2.  Any pointer may be NULL.
  * Returns EIGX_OK. */
 int eigx_batch_range_info(int* route, int* m, int* redone);
