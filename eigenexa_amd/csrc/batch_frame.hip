@@ -2,15 +2,17 @@
 // hbatch.hip, eigx_gev_batch: gbatch.hip, eigx_hgev_batch: hgbatch.hip), ragged (eigx_s_vbatch: vbatch.hip, eigx_h_vbatch:
 // hvbatch.hip, eigx_gev_vbatch: gvbatch.hip, eigx_hgev_vbatch: hgbatch.hip) and windowed (eigx_s_batch_range: batch_range.hip,
 // eigx_h_batch_range: hbatch_range.hip, eigx_gev_batch_range: gbatch_range.hip, eigx_hgev_batch_range: hgbatch_range.hip).
-// Host code only, no kernel:
+// Host code, and the one kernel that belongs to a frame and not to a family (batch_range_gather):
 //   the pieces every frame is made of: the prologue (batch_entry_begin), the first-failure word (FirstFailure), the loop above
 //   the cutoff of a uniform batch (batch_loop_above_cutoff), the epilogue (batch_entry_end), the host staging of a uniform batch
 //   (batch_stage_host over copy_blocks);
-//   the uniform frame (batch_frame_dev / batch_frame_host) and the ragged frame (vbatch_frame_dev / vbatch_frame_host with the
-//   schedule vbatch_plan) whole.  The windowed frame is route logic and stays beside its kernels; it calls the pieces.
-// A family supplies its kernel launch by n-class and its full-size solve of one matrix; what errinfo is after a failed matrix
-// differs between the frames and is tabulated in DESIGN section 8h.
+//   the uniform frame (batch_frame_dev / batch_frame_host), the windowed frame (brange_frame_dev / brange_frame_host with
+//   eigx_tune keys 26 and 27 and the record of eigx_batch_range_info) and the ragged frame (vbatch_frame_dev / vbatch_frame_host
+//   with the schedule vbatch_plan) whole.
+// A family supplies its kernel launch by n-class and its full-size solve of one matrix (a windowed family: its WindowFamily record);
+// what errinfo is after a failed matrix differs between the frames and is tabulated in DESIGN section 8h.
 #include "eigx_context.h"
+#include "batch_common.h"
 #include "../../include/eigenexa_amd.h"
 #include <algorithm>
 #include <cstdlib>
@@ -168,6 +170,166 @@ int batch_frame_host(Context& ctx, BatchArgs g, int cutoff, BatchLaunch launch, 
       cplx{"host.ha", "host.hb", "host.hz", "host.w", "batch.info"};
   return batch_stage_host(ctx, g, g.n, g.n, g.esz == 16 ? cplx : real,
                           [&](const BatchArgs& dv) { return batch_frame_dev(ctx, dv, cutoff, launch, solve_one); });
+}
+
+// ---- the windowed frame ---------------------------------------------------------------------------------------------------------
+namespace {
+
+int g_route_key = 0;       // key 26: 0 = automatic, 1 = route 1 wherever eligible, 2 = route 2 always
+int g_accept_key = 50;     // key 27: the acceptance bound in percent
+
+// what the last call of a windowed batched entry did (eigx_batch_range_info)
+struct { int route = 0, m = 0, redone = 0; } g_last;
+void set_batch_range_last(int route, int m, int redone) {
+  g_last.route = route;
+  g_last.m = m;
+  g_last.redone = redone;
+}
+
+// Route 2's second step: the window of the full solves of matrices kb .. kb + gridDim.x - 1 (rw(n, .), rz(n, n, .), rinfo: what
+// the family's full_solve left in the workspace) -> the caller's w(1:m, k), z(1:n, 1:m, k), info[k] and the first-failure word.
+// C doubles per element of z (2: interleaved complex, a column is 2 n doubles).  A failed matrix: w(1:m, k) = NaN, z(:, :, k)
+// untouched.
+template <int C>
+__global__ __launch_bounds__(256) void batch_range_gather(int n, int kb, int k0, int m, const double* __restrict__ rw,
+                                                          const double* __restrict__ rz, const int* __restrict__ rinfo,
+                                                          double* __restrict__ w, int ldw, double* __restrict__ z, int ldz,
+                                                          int64_t stride_z, int want_vec, int* __restrict__ info,
+                                                          unsigned long long* __restrict__ first) {
+  const int kl = blockIdx.x, k = kb + kl, tid = threadIdx.x;
+  const int code = rinfo[kl];
+  double* wk = w + (size_t)k * ldw;
+  if (code != 0) {
+    for (int j = tid; j < m; j += 256) wk[j] = std::numeric_limits<double>::quiet_NaN();
+    if (tid == 0) report_failure(first, info, k, code);
+    return;
+  }
+  for (int j = tid; j < m; j += 256) wk[j] = rw[(size_t)kl * n + k0 + j];
+  if (want_vec) {
+    // (one address; the real instance adds the two offsets one after the other, as the kernel it replaces did: the sum in
+    // brackets compiles to other instructions there, profiles/brange_one_frame.log)
+    const double* src = C == 1 ? rz + (size_t)kl * n * n + (size_t)k0 * n : rz + C * ((size_t)kl * n * n + (size_t)k0 * n);
+    double* zk = z + C * (size_t)k * stride_z;
+    for (int idx = tid; idx < C * n * m; idx += 256) zk[idx % (C * n) + C * (size_t)(idx / (C * n)) * ldz] = src[idx];
+  }
+  if (tid == 0 && info) info[k] = 0;
+}
+
+// Route 2 on matrices kb .. kb + cnt - 1: the family's full solve (on the caller's a, and b where there is one: U lands in b
+// directly) with w and z in the workspace, chunk by chunk (at most 256 MiB of workspace), and the gather.  Returns EIGX_OK or a
+// status that does not belong to one matrix.
+int brange_full_and_slice(Context& ctx, const BatchArgs& g, int il, int iu, const WindowFamily& fam, int kb, int cnt,
+                          unsigned long long* first) {
+  const int n = g.n, m = iu - il + 1;
+  const bool want_vec = g.mode == 'A';
+  const size_t cs = (size_t)g.esz / 8;   // doubles per element of z
+  const size_t per = 8 * ((size_t)n + (want_vec ? cs * n * n : 0));
+  const int chunk = (int)std::max<size_t>(1, std::min<size_t>((size_t)cnt, ((size_t)256 << 20) / per));
+  BatchArgs c = g;                       // the full solve of a chunk: the caller's a and b, the workspace's w, z and info
+  c.w = ctx.pool.get_t<double>(fam.rw, (size_t)n * chunk);
+  c.z = want_vec ? ctx.pool.get_t<double>(fam.rz, cs * n * n * chunk) : nullptr;
+  c.info = ctx.pool.get_t<int>(fam.rinfo, (size_t)chunk);
+  c.ldw = c.ldz = n;
+  c.stride_z = (int64_t)n * n;
+  for (int c0 = 0; c0 < cnt; c0 += chunk) {
+    const int nc = std::min(chunk, cnt - c0), kc = kb + c0;
+    c.batch = nc;
+    c.a = g.block(g.a, g.stride_a, kc);
+    if (g.has_b) c.b = g.block(g.b, g.stride_b, kc);
+    const int rc = fam.full_solve(c);
+    if (!batch_status_per_matrix(rc)) return rc;
+    const auto gather = g.esz == 16 ? batch_range_gather<2> : batch_range_gather<1>;
+    hipLaunchKernelGGL(gather, dim3((unsigned)nc), dim3(256), 0, ctx.stream, n, kc, il - 1, m, (const double*)c.w, (const double*)c.z,
+                       (const int*)c.info, g.w, g.ldw, g.z, g.ldz, g.stride_z, (int)want_vec, g.info, first);
+    EIGX_HIP_CHECK(hipGetLastError());
+    EIGX_HIP_CHECK(hipStreamSynchronize(ctx.stream));   // the next chunk overwrites the workspace
+  }
+  return EIGX_OK;
+}
+
+// what the entries require of their arguments (mode in upper case)
+bool brange_args_ok(const BatchArgs& g, int il, int iu) {
+  const int n = g.n, batch = g.batch, m = iu - il + 1;
+  if (n < 1 || batch < 0 || il < 1 || iu > n || il > iu || g.lda < n || g.ldw < m || (g.mode != 'A' && g.mode != 'N')) return false;
+  if (batch > 1 && g.stride_a < (int64_t)g.lda * n) return false;
+  if (g.has_b && (g.ldb < n || (batch > 1 && g.stride_b < (int64_t)g.ldb * n))) return false;
+  if (g.mode == 'A' && (g.ldz < n || (batch > 1 && g.stride_z < (int64_t)g.ldz * m))) return false;
+  if (batch > 0 && (!g.a || (g.has_b && !g.b) || !g.w || (g.mode == 'A' && !g.z))) return false;
+  return true;
+}
+
+}  // namespace
+
+int brange_frame_dev(Context& ctx, BatchArgs g, int il, int iu, const WindowFamily& fam) {
+  int rc;
+  if (!batch_entry_begin(ctx, g.mode, g.batch, [&] { return brange_args_ok(g, il, iu); }, rc)) return rc;
+  EIGX_HIP_CHECK(hipStreamSynchronize(nullptr));   // the caller's default-stream work on the arguments
+  const double t0 = now_s();
+  hipStream_t st = ctx.stream;
+  const int n = g.n, batch = g.batch, m = iu - il + 1;
+  int redone = 0;
+  if (n > fam.cutoff()) {
+    // route 3: the family's index-range solver of one large matrix, matrix by matrix; unlike the uniform frame this one sets
+    // errinfo to -1 after a failed matrix (the table of DESIGN section 8h)
+    set_batch_range_last(3, m, 0);
+    rc = batch_loop_above_cutoff(batch, g.info, [&](int k) { return fam.solve_window(ctx, g, k, il, iu); });
+    if (!batch_status_per_matrix(rc)) return rc;
+    ctx.errinfo = rc == EIGX_OK ? 0 : -1;
+  } else {
+    const bool eligible = g.mode == 'N' || m <= fam.window_width(n);
+    const bool one = g_route_key == 2 ? false : eligible && (g_route_key == 1 || fam.route1_measured_faster(n, g.mode, m));
+    set_batch_range_last(one ? 1 : 2, m, 0);
+    FirstFailure ff;                     // a word of its own: route 2's full solve arms batch.first while this one is live
+    ff.arm(ctx, fam.first, st);
+    unsigned long long* first = ff.dev;
+    if (one) {
+      int* redo = ctx.pool.get_t<int>(fam.redo, (size_t)batch);
+      fam.launch(g, il - 1, m, g_accept_key / 100.0, st, first, redo);
+      EIGX_HIP_CHECK(hipGetLastError());
+      std::vector<int> marks((size_t)batch);
+      EIGX_HIP_CHECK(hipMemcpyAsync(marks.data(), redo, (size_t)batch * sizeof(int), hipMemcpyDeviceToHost, st));
+      EIGX_HIP_CHECK(hipStreamSynchronize(st));
+      // the redo: route 2 on every run of consecutive marked matrices (route 1 left their b as it was passed: B, not U)
+      for (int k = 0; k < batch;) {
+        if (!marks[k]) { ++k; continue; }
+        int k1 = k;
+        while (k1 < batch && marks[k1]) ++k1;
+        const int rr = brange_full_and_slice(ctx, g, il, iu, fam, k, k1 - k, first);
+        if (rr != EIGX_OK) return rr;
+        set_batch_range_last(1, m, redone += k1 - k);
+        k = k1;
+      }
+    } else {
+      const int rr = brange_full_and_slice(ctx, g, il, iu, fam, 0, batch, first);
+      if (rr != EIGX_OK) return rr;
+    }
+    ctx.errinfo = 0;
+    ff.finish(ctx, st, rc);
+  }
+  batch_entry_end(ctx, t0);
+  return rc;
+}
+
+// Host arrays: batch_stage_host with m columns of z and m entries of w per matrix, in pool buffers of the entry's own (fam.host:
+// the names are part of the description of each entry in its public header).  b comes back (as U) for the pencils that succeeded.
+int brange_frame_host(Context& ctx, BatchArgs g, int il, int iu, const WindowFamily& fam) {
+  int rc;
+  if (!batch_entry_begin(ctx, g.mode, g.batch, [&] { return brange_args_ok(g, il, iu); }, rc)) return rc;
+  const int m = iu - il + 1;
+  return batch_stage_host(ctx, g, m, m, fam.host, [&](const BatchArgs& dv) { return brange_frame_dev(ctx, dv, il, iu, fam); });
+}
+
+int set_batch_range_route(int v) {
+  if (v < 0 || v > 2) return -1;
+  const int old = g_route_key;
+  g_route_key = v;
+  return old;
+}
+int set_batch_range_accept(int v) {
+  if (v < 0 || v > 101) return -1;
+  const int old = g_accept_key;
+  g_accept_key = v;
+  return old;
 }
 
 // ---- the ragged frame -----------------------------------------------------------------------------------------------------------
@@ -385,3 +547,15 @@ int vbatch_frame_host(Context& ctx, VbArgs g, int cutoff, int top, VbPencilLaunc
 }
 
 }  // namespace eigx
+
+extern "C" {
+
+// EXTENSION: what the last call of a windowed batched entry (of any of the four families) did
+int eigx_batch_range_info(int* route, int* m, int* redone) {
+  if (route) *route = eigx::g_last.route;
+  if (m) *m = eigx::g_last.m;
+  if (redone) *redone = eigx::g_last.redone;
+  return EIGX_OK;
+}
+
+}  // extern "C"

@@ -12,106 +12,20 @@
 // the acceptance test refuses leaves a mark and is solved again by route 2: eigx_s_batch_dev into pooled workspace and a gather
 // of the window (bit for bit the slice of that entry's result).  n above the cutoff of eigx_s_batch (eigx_tune key 21) goes
 // through range_solve_dev matrix by matrix (route 3).  Which of routes 1 and 2 a call takes: eigx_tune key 26.
+// This file holds the window kernel, the measured-route table and the family's WindowFamily record; the routes, the redo and the
+// gather are the windowed frame's (batch_frame.hip), the reduction is sym_tridiag (batch_tridiag.h), sturm_count and start_entry
+// are batch_window.h's.  The window stage itself stays written out in the kernel's body: see the head of batch_window.h.
 #include "eigx_context.h"
 #include "batch_common.h"
+#include "batch_tridiag.h"
+#include "batch_window.h"
 #include "../../include/eigenexa_amd.h"
-#include <algorithm>
 #include <cfloat>
-#include <vector>
 
 #pragma clang fp contract(off)
 
 namespace eigx {
 namespace {
-
-// Phase 2 of sym_tridiag_ql (batch_common.h) alone: the full symmetric matrix of order n in A(LD, NMAX) -> (d, e), e[i] coupling
-// i - 1 and i, e[0] = 0; the reflector of step i stays in A(0 .. i-1, i), its h in hv[i] (0: no reflector).  The loop is that
-// function's first loop word for word: calling this from there would move the code of the existing kernels (see the head of
-// batch_common.h).  Every thread of the workgroup makes the call; the results are behind a barrier.
-template <int NMAX>
-__device__ __forceinline__ void sym_tridiag(int n, double* A, double* d, double* e, double* hv, double* u, double* q, double* pt,
-                                            double (*red)[4]) {
-  constexpr int NT = 2 * NMAX, LD = NMAX + 1;
-  const int tid = threadIdx.x, r = tid % NMAX, hh = tid / NMAX;
-  const bool row = hh == 0 && r < n;
-  for (int i = n - 1; i >= 1; --i) {
-    const int l = i - 1;
-    double* rd = red[2 * (i & 1)];     // by parity: a step that leaves early has no closing barrier
-    if (l == 0) {
-      if (tid == 0) { e[1] = A[LD]; hv[1] = 0.0; }
-      continue;
-    }
-    const double x = (hh == 0 && r <= l) ? A[r + i * LD] : 0.0;
-    const double f = A[l + i * LD];    // (read before the barrier: thread l overwrites it below)
-    double h = block_sum<NT>(x * x, rd);
-    if (h == 0.0) {                    // nothing to annihilate (uniform)
-      if (tid == 0) { e[i] = f; hv[i] = 0.0; }
-      continue;
-    }
-    const double g = f >= 0.0 ? -sqrt(h) : sqrt(h);
-    h -= f * g;
-    if (hh == 0 && r <= l) {
-      const double ur = r == l ? f - g : x;
-      u[r] = ur;
-      A[r + i * LD] = ur;
-    }
-    if (tid == 0) { e[i] = g; hv[i] = h; }
-    __syncthreads();
-    const int mid = (l + 2) / 2, k0 = hh ? mid : 0, k1 = hh ? l + 1 : mid;
-    if (r <= l) {
-      double acc = 0.0;
-#pragma unroll 4
-      for (int t = 0; t < mid; ++t) {
-        const int c = k0 + t;
-        const double uc = u[c];
-        acc = fma(A[r + c * LD], c < k1 ? uc : 0.0, acc);
-      }
-      pt[hh * NMAX + r] = acc;
-    }
-    __syncthreads();
-    double qr = 0.0, ur = 0.0;
-    if (hh == 0 && r <= l) { ur = u[r]; qr = (pt[r] + pt[NMAX + r]) / h; }
-    const double hk = block_sum<NT>(qr * ur, rd + 4) / (h + h);
-    if (hh == 0 && r <= l) q[r] = qr - hk * ur;
-    __syncthreads();
-    if (r <= l) {
-      ur = u[r];
-      qr = q[r];
-#pragma unroll 4
-      for (int t = 0; t < mid; ++t) {
-        const int c = k0 + t;
-        const double ac = A[r + c * LD], qc = q[c], uc = u[c];
-        A[r + c * LD] = c < k1 ? ac - (ur * qc + qr * uc) : ac;
-      }
-    }
-    __syncthreads();
-  }
-  if (row) d[r] = A[r + r * LD];
-  if (tid == 0) { e[0] = 0.0; hv[0] = 0.0; }
-  __syncthreads();
-}
-
-// the number of eigenvalues of the tridiagonal (d, e2 = e^2) below x; a pivot smaller than pivmin counts as -pivmin (DLAEBZ)
-__device__ inline int sturm_count(int n, const double* d, const double* e2, double x, double pivmin) {
-  double p = d[0] - x;
-  if (fabs(p) < pivmin) p = -pivmin;
-  int c = p < 0.0 ? 1 : 0;
-  for (int i = 1; i < n; ++i) {
-    p = d[i] - x - e2[i] / p;
-    if (fabs(p) < pivmin) p = -pivmin;
-    c += p < 0.0 ? 1 : 0;
-  }
-  return c;
-}
-
-// entry i of the start vector of window column j, in [-0.5, 0.5): a hash of (i, j) alone
-__device__ inline double start_entry(int i, int j) {
-  unsigned h = (unsigned)i * 2654435761u ^ ((unsigned)j * 40503u + 0x9e3779b9u);
-  h ^= h >> 15; h *= 0x2c1b3c6du;
-  h ^= h >> 12; h *= 0x297a2d39u;
-  h ^= h >> 15;
-  return (double)(h >> 8) * (1.0 / 16777216.0) - 0.5;
-}
 
 // One workgroup of 2 NMAX threads per matrix, thread (r, hh) = (row, half) as in batch_kernel.  MW: the widest window of mode 'A'.
 // F: the four factor arrays of the inverse iteration, entry (i, j) at [i MW + j] (lane-fastest); later T Y, the projected
@@ -435,44 +349,6 @@ __global__ __launch_bounds__(2 * NMAX) void batch_range_kernel(int n, int batch,
   }
 }
 
-// Route 2's second step: the window of the full solves of matrices kb .. kb + gridDim.x - 1 (rw(n, .), rz(n, n, .), rinfo: what
-// eigx_s_batch_dev left in the workspace) -> the caller's w(1:m, k), z(1:n, 1:m, k), info[k] and the first-failure word.  A
-// failed matrix: w(1:m, k) = NaN, z(:, :, k) untouched.
-__global__ __launch_bounds__(256) void batch_range_gather(int n, int kb, int k0, int m, const double* __restrict__ rw,
-                                                          const double* __restrict__ rz, const int* __restrict__ rinfo,
-                                                          double* __restrict__ w, int ldw, double* __restrict__ z, int ldz,
-                                                          int64_t stride_z, int want_vec, int* __restrict__ info,
-                                                          unsigned long long* __restrict__ first) {
-  const int kl = blockIdx.x, k = kb + kl, tid = threadIdx.x;
-  const int code = rinfo[kl];
-  double* wk = w + (size_t)k * ldw;
-  if (code != 0) {
-    for (int j = tid; j < m; j += 256) wk[j] = std::numeric_limits<double>::quiet_NaN();
-    if (tid == 0) report_failure(first, info, k, code);
-    return;
-  }
-  for (int j = tid; j < m; j += 256) wk[j] = rw[(size_t)kl * n + k0 + j];
-  if (want_vec) {
-    const double* src = rz + (size_t)kl * n * n + (size_t)k0 * n;
-    double* zk = z + (size_t)k * stride_z;
-    for (int idx = tid; idx < n * m; idx += 256) zk[idx % n + (size_t)(idx / n) * ldz] = src[idx];
-  }
-  if (tid == 0 && info) info[k] = 0;
-}
-
-// a call: the arguments of the entries (device or host arrays)
-struct RangeBatchArgs {
-  int n, batch, il, iu;
-  double* a; int lda; int64_t stride_a;
-  double* w; int ldw;
-  double* z; int ldz; int64_t stride_z;
-  char mode; int* info;
-  int m() const { return iu - il + 1; }
-};
-
-int g_route_key = 0;       // key 26: 0 = automatic, 1 = route 1 wherever eligible, 2 = route 2 always
-int g_accept_key = 50;     // key 27: the acceptance bound in percent
-
 // the widest window the class of n serves in mode 'A'
 int window_width(int n) { return n <= 96 ? 16 : 4; }
 
@@ -491,140 +367,32 @@ bool route1_measured_faster(int n, char mode, int m) {
   return true;
 }
 
-void brange_launch(const RangeBatchArgs& g, hipStream_t st, unsigned long long* first, int* redo) {
+void brange_launch(const BatchArgs& g, int k0, int m, double accept, hipStream_t st, unsigned long long* first, int* redo) {
   with_n_class<EIGX_BATCH_NMAX>(g.n, [&](auto nmax) {
     constexpr int NMAX = decltype(nmax)::value;
     constexpr int MW = NMAX <= 96 ? 16 : 4;
-    hipLaunchKernelGGL((batch_range_kernel<NMAX, MW>), dim3((unsigned)g.batch), dim3(2 * NMAX), 0, st, g.n, g.batch, g.il - 1, g.m(),
-                       (const double*)g.a, g.lda, g.stride_a, g.w, g.ldw, g.z, g.ldz, g.stride_z, (int)(g.mode == 'A'),
-                       g_accept_key / 100.0, g.info, first, redo);
+    hipLaunchKernelGGL((batch_range_kernel<NMAX, MW>), dim3((unsigned)g.batch), dim3(2 * NMAX), 0, st, g.n, g.batch, k0, m,
+                       (const double*)g.a, g.lda, g.stride_a, g.w, g.ldw, g.z, g.ldz, g.stride_z, (int)(g.mode == 'A'), accept, g.info,
+                       first, redo);
   });
 }
 
-// Route 2 on matrices kb .. kb + cnt - 1: eigx_s_batch_dev into the workspace, chunk by chunk (at most 256 MiB of workspace), and
-// the gather.  Returns EIGX_OK or a status that does not belong to one matrix.
-int brange_full_and_slice(Context& ctx, const RangeBatchArgs& g, int kb, int cnt, unsigned long long* first) {
-  const int n = g.n;
-  const bool want_vec = g.mode == 'A';
-  const size_t per = 8 * ((size_t)n + (want_vec ? (size_t)n * n : 0));
-  const int chunk = (int)std::max<size_t>(1, std::min<size_t>((size_t)cnt, ((size_t)256 << 20) / per));
-  double* rw = ctx.pool.get_t<double>("batch.rw", (size_t)n * chunk);
-  double* rz = want_vec ? ctx.pool.get_t<double>("batch.rz", (size_t)n * n * chunk) : nullptr;
-  int* rinfo = ctx.pool.get_t<int>("batch.rinfo", (size_t)chunk);
-  for (int c0 = 0; c0 < cnt; c0 += chunk) {
-    const int nc = std::min(chunk, cnt - c0), kc = kb + c0;
-    const int rc = eigx_s_batch_dev(n, nc, g.a + (size_t)kc * g.stride_a, g.lda, g.stride_a, rw, n, rz, n, (int64_t)n * n, g.mode, rinfo);
-    if (!batch_status_per_matrix(rc)) return rc;
-    hipLaunchKernelGGL(batch_range_gather, dim3((unsigned)nc), dim3(256), 0, ctx.stream, n, kc, g.il - 1, g.m(), (const double*)rw,
-                       (const double*)rz, (const int*)rinfo, g.w, g.ldw, g.z, g.ldz, g.stride_z, (int)want_vec, g.info, first);
-    EIGX_HIP_CHECK(hipGetLastError());
-    EIGX_HIP_CHECK(hipStreamSynchronize(ctx.stream));   // the next chunk overwrites the workspace
-  }
-  return EIGX_OK;
+int brange_full_solve(const BatchArgs& c) {
+  return eigx_s_batch_dev(c.n, c.batch, c.a, c.lda, c.stride_a, c.w, c.ldw, c.z, c.ldz, c.stride_z, c.mode, c.info);
 }
 
-bool brange_args_ok(const RangeBatchArgs& g) {
-  const int n = g.n, batch = g.batch;
-  if (n < 1 || batch < 0 || g.il < 1 || g.iu > n || g.il > g.iu || g.lda < n || g.ldw < g.m() || (g.mode != 'A' && g.mode != 'N'))
-    return false;
-  if (batch > 1 && g.stride_a < (int64_t)g.lda * n) return false;
-  if (g.mode == 'A' && (g.ldz < n || (batch > 1 && g.stride_z < (int64_t)g.ldz * g.m()))) return false;
-  if (batch > 0 && (!g.a || !g.w || (g.mode == 'A' && !g.z))) return false;
-  return true;
+// route 3: eigx_s_range_dev with the interface's default block sizes on matrix k
+int brange_solve_window(Context& ctx, const BatchArgs& g, int k, int il, int iu) {
+  return range_solve_dev(ctx, g.n, RangeWindow::index(il, iu), g.block(g.a, g.stride_a, k), g.lda, g.w + (size_t)k * g.ldw,
+                         g.mode == 'A' ? g.block(g.z, g.stride_z, k) : nullptr, g.ldz, 48, 128, g.mode, 1, false);
 }
 
-int brange_frame_dev(Context& ctx, RangeBatchArgs g) {
-  int rc;
-  if (!batch_entry_begin(ctx, g.mode, g.batch, [&] { return brange_args_ok(g); }, rc)) return rc;
-  EIGX_HIP_CHECK(hipStreamSynchronize(nullptr));   // the caller's default-stream work on the arguments
-  const double t0 = now_s();
-  hipStream_t st = ctx.stream;
-  const int n = g.n, batch = g.batch, m = g.m();
-  int redone = 0;
-  if (n > get_batch_nmax()) {
-    // route 3: the index-range solver of one large matrix (eigx_s_range_dev with the interface's default block sizes), matrix by
-    // matrix; unlike the uniform frame this one sets errinfo to -1 after a failed matrix (the table of DESIGN section 8h)
-    set_batch_range_last(3, m, 0);
-    rc = batch_loop_above_cutoff(batch, g.info, [&](int k) {
-      return range_solve_dev(ctx, n, RangeWindow::index(g.il, g.iu), g.a + (size_t)k * g.stride_a, g.lda, g.w + (size_t)k * g.ldw,
-                             g.mode == 'A' ? g.z + (size_t)k * g.stride_z : nullptr, g.ldz, 48, 128, g.mode, 1, false);
-    });
-    if (!batch_status_per_matrix(rc)) return rc;
-    ctx.errinfo = rc == EIGX_OK ? 0 : -1;
-  } else {
-    const bool eligible = g.mode == 'N' || m <= window_width(n);
-    const bool one = g_route_key == 2 ? false : eligible && (g_route_key == 1 || route1_measured_faster(n, g.mode, m));
-    set_batch_range_last(one ? 1 : 2, m, 0);
-    FirstFailure ff;                     // a word of its own: route 2's eigx_s_batch_dev arms batch.first while this one is live
-    ff.arm(ctx, "brange.first", st);
-    unsigned long long* first = ff.dev;
-    if (one) {
-      int* redo = ctx.pool.get_t<int>("brange.redo", (size_t)batch);
-      brange_launch(g, st, first, redo);
-      EIGX_HIP_CHECK(hipGetLastError());
-      std::vector<int> marks((size_t)batch);
-      EIGX_HIP_CHECK(hipMemcpyAsync(marks.data(), redo, (size_t)batch * sizeof(int), hipMemcpyDeviceToHost, st));
-      EIGX_HIP_CHECK(hipStreamSynchronize(st));
-      // the redo: route 2 on every run of consecutive marked matrices
-      for (int k = 0; k < batch;) {
-        if (!marks[k]) { ++k; continue; }
-        int k1 = k;
-        while (k1 < batch && marks[k1]) ++k1;
-        const int rr = brange_full_and_slice(ctx, g, k, k1 - k, first);
-        if (rr != EIGX_OK) return rr;
-        set_batch_range_last(1, m, redone += k1 - k);
-        k = k1;
-      }
-    } else {
-      const int rr = brange_full_and_slice(ctx, g, 0, batch, first);
-      if (rr != EIGX_OK) return rr;
-    }
-    ctx.errinfo = 0;
-    ff.finish(ctx, st, rc);
-  }
-  batch_entry_end(ctx, t0);
-  return rc;
-}
-
-// Host arrays: batch_stage_host (batch_frame.hip) with m columns of z and m entries of w per matrix, in pool buffers of this
-// entry's own (brange.h*: the names are part of the description of the entry in include/eigenexa_amd_batch_range.h).
-int brange_frame_host(Context& ctx, RangeBatchArgs g) {
-  int rc;
-  if (!batch_entry_begin(ctx, g.mode, g.batch, [&] { return brange_args_ok(g); }, rc)) return rc;
-  const BatchArgs u{g.n, g.batch, g.a, g.lda, g.stride_a, nullptr, 0, 0, g.w, g.ldw, g.z, g.ldz, g.stride_z, g.mode, g.info, 8, false};
-  static const BatchStageNames names{"brange.ha", nullptr, "brange.hz", "brange.hw", "brange.hinfo"};
-  return batch_stage_host(ctx, u, g.m(), g.m(), names, [&](const BatchArgs& dv) {
-    return brange_frame_dev(ctx, RangeBatchArgs{g.n, g.batch, g.il, g.iu, dv.a, dv.lda, dv.stride_a, dv.w, dv.ldw, dv.z, dv.ldz,
-                                                dv.stride_z, g.mode, dv.info});
-  });
-}
+// (the pool names are part of the description of the entry in include/eigenexa_amd_batch_range.h)
+const WindowFamily brange_family{get_batch_nmax, window_width, route1_measured_faster, brange_launch, brange_full_solve,
+                                 brange_solve_window, "brange.first", "brange.redo", "batch.rw", "batch.rz", "batch.rinfo",
+                                 {"brange.ha", nullptr, "brange.hz", "brange.hw", "brange.hinfo"}};
 
 }  // namespace
-
-// what the last call of a windowed batched entry did (eigx_batch_range_info): written by this file's frame and by the Hermitian
-// family's (hbatch_range.hip) through set_batch_range_last
-static struct { int route = 0, m = 0, redone = 0; } g_last;
-void set_batch_range_last(int route, int m, int redone) {
-  g_last.route = route;
-  g_last.m = m;
-  g_last.redone = redone;
-}
-int get_batch_range_route() { return g_route_key; }
-int get_batch_range_accept() { return g_accept_key; }
-
-int set_batch_range_route(int v) {
-  if (v < 0 || v > 2) return -1;
-  const int old = g_route_key;
-  g_route_key = v;
-  return old;
-}
-int set_batch_range_accept(int v) {
-  if (v < 0 || v > 101) return -1;
-  const int old = g_accept_key;
-  g_accept_key = v;
-  return old;
-}
-
 }  // namespace eigx
 
 using namespace eigx;
@@ -632,21 +400,16 @@ using namespace eigx;
 extern "C" {
 
 // EXTENSION: eigenpairs il .. iu of `batch` symmetric matrices of one size (one GPU); see brange_frame_host / brange_frame_dev
+// (batch_frame.hip)
 int eigx_s_batch_range(int n, int batch, int il, int iu, double* a, int lda, int64_t stride_a, double* w, int ldw, double* z, int ldz,
                        int64_t stride_z, char mode, int* info) {
-  const RangeBatchArgs g{n, batch, il, iu, a, lda, stride_a, w, ldw, z, ldz, stride_z, mode, info};
-  return eigx_guard(g_ctx, [&] { return brange_frame_host(g_ctx, g); });
+  const BatchArgs g{n, batch, a, lda, stride_a, nullptr, 0, 0, w, ldw, z, ldz, stride_z, mode, info, 8, false};
+  return eigx_guard(g_ctx, [&] { return brange_frame_host(g_ctx, g, il, iu, brange_family); });
 }
 int eigx_s_batch_range_dev(int n, int batch, int il, int iu, double* a_dev, int lda, int64_t stride_a, double* w_dev, int ldw,
                            double* z_dev, int ldz, int64_t stride_z, char mode, int* info_dev) {
-  const RangeBatchArgs g{n, batch, il, iu, a_dev, lda, stride_a, w_dev, ldw, z_dev, ldz, stride_z, mode, info_dev};
-  return eigx_guard(g_ctx, [&] { return brange_frame_dev(g_ctx, g); });
-}
-int eigx_batch_range_info(int* route, int* m, int* redone) {
-  if (route) *route = g_last.route;
-  if (m) *m = g_last.m;
-  if (redone) *redone = g_last.redone;
-  return EIGX_OK;
+  const BatchArgs g{n, batch, a_dev, lda, stride_a, nullptr, 0, 0, w_dev, ldw, z_dev, ldz, stride_z, mode, info_dev, 8, false};
+  return eigx_guard(g_ctx, [&] { return brange_frame_dev(g_ctx, g, il, iu, brange_family); });
 }
 
 }  // extern "C"

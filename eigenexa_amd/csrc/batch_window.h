@@ -1,10 +1,11 @@
 // batch_window.h -- the real tridiagonal window stage of a windowed one-workgroup-per-matrix kernel as device functions:
 // eigenpairs k0 .. k0 + m - 1 of the real symmetric tridiagonal matrix (d, e) of order n held in LDS, without a QL sweep of the
-// whole matrix (DESIGN sections 8n and 8o).  hbatch_range.hip (hbatch_range_kernel, complex Hermitian, whose reduction ends in a
-// real (d, e)) calls them.  They are steps 3 to 6 of batch_range_kernel (batch_range.hip, real symmetric), which keeps those steps
-// written out in its body: with the calls in their place that kernel compiled to other instructions (24 854 lines of ISA for
-// 20 992, a spilled scalar register), and the existing entry is not to change (section 8o; an entry on section 8h's list of what
-// stays written more than once).  One rule differs from that body: a pivot below ptiny counts as zero in the inverse iteration.
+// whole matrix (DESIGN sections 8n and 8o).  hbatch_range_kernel, gbatch_range_kernel and hgbatch_range_kernel, whose reductions
+// end in a real (d, e), call them.  They are steps 3 to 6 of batch_range_kernel (batch_range.hip, real symmetric), which keeps those
+// steps written out in its body and takes only sturm_count and start_entry from here: with the calls in their place that kernel
+// compiled to other instructions (24 854 lines of ISA for 20 992, a spilled scalar register), and the existing entry is not to
+// change (section 8o; an entry on section 8h's list of what stays written more than once).  One rule differs from that body: a
+// pivot below ptiny counts as zero in the inverse iteration.
 //   window_bounds        Gershgorin bounds, the pivot floor and the scale of the shifts
 //   window_multisection  Sturm-count multi-section: a group of lanes per eigenvalue
 //   window_inverse_iteration  one lane per vector on a tridiagonal LU with partial pivoting held in LDS

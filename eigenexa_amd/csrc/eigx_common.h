@@ -180,15 +180,10 @@ int set_hgbatch_nmax(int v);
 int get_gbatch_nmax();
 // the current value of key 24: the cutoff between the kernel routes and route 3 of eigx_hgev_batch_range (hgbatch_range.hip)
 int get_hgbatch_nmax();
-// tuning hooks (eigx_tune keys 26 and 27, batch_range.hip): the route of eigx_s_batch_range and eigx_h_batch_range (0 automatic, 1
-// the window kernel wherever eligible, 2 the full solve and a slice) and the acceptance bound of the window kernels in percent,
-// 0 .. 101; the current values for the Hermitian family (hbatch_range.hip), the pencils (gbatch_range.hip) and the complex pencils
-// (hgbatch_range.hip, whose cutoff is key 24)
+// tuning hooks (eigx_tune keys 26 and 27, the windowed frame of batch_frame.hip): the route of the four windowed batched entries
+// (0 automatic, 1 the window kernel wherever eligible, 2 the full solve and a slice) and the acceptance bound of the window kernels
+// in percent, 0 .. 101
 int set_batch_range_route(int v);
 int set_batch_range_accept(int v);
-int get_batch_range_route();
-int get_batch_range_accept();
-// the record behind eigx_batch_range_info (batch_range.hip): what the last call of a windowed batched entry of either family did
-void set_batch_range_last(int route, int m, int redone);
 
 }  // namespace eigx

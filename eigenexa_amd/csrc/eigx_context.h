@@ -401,6 +401,25 @@ int batch_stage_host(Context& ctx, const BatchArgs& g, int zcols, int nw, const 
 // the device entry (device arrays; g.info may be null) and the host entry (host arrays) of a family
 int batch_frame_dev(Context& ctx, BatchArgs g, int cutoff, BatchLaunch launch, BatchSolveOne solve_one);
 int batch_frame_host(Context& ctx, BatchArgs g, int cutoff, BatchLaunch launch, BatchSolveOne solve_one);
+// The windowed frame (batch_range.hip, hbatch_range.hip, gbatch_range.hip, hgbatch_range.hip; DESIGN sections 8n to 8q): eigenpairs
+// il .. iu of every matrix of a BatchArgs call, w with m = iu - il + 1 entries and z with m columns per matrix.  Route 1 is the
+// family's window kernel with a redo of the matrices it refused, route 2 the family's full batched solve into pooled workspace and
+// a gather of the window, route 3 (n above the cutoff) the range solver of one matrix at a time; eigx_tune keys 26 and 27 and the
+// record behind eigx_batch_range_info live with the frame.  A family is this record:
+struct WindowFamily {
+  int (*cutoff)();                                        // n above it: route 3 (the cutoff key of the family's uniform entry)
+  int (*window_width)(int n);                             // the widest window route 1 serves at n in mode 'A' (0: mode 'N' only)
+  bool (*route1_measured_faster)(int n, char mode, int m);   // key 26 = 0: the family's measured table
+  // route 1: the window kernel on the whole call for the n-class of g.n; k0 = il - 1, accept = key 27 / 100, redo[k] = 1 marks a
+  // matrix that was refused and of which nothing was written
+  void (*launch)(const BatchArgs& g, int k0, int m, double accept, hipStream_t st, unsigned long long* first, int* redo);
+  int (*full_solve)(const BatchArgs& c);                  // route 2: the family's eigx_*_batch_dev on a chunk (c.w, c.z, c.info: workspace)
+  int (*solve_window)(Context& ctx, const BatchArgs& g, int k, int il, int iu);   // route 3: matrix k (its status; mode upper case)
+  const char *first, *redo, *rw, *rz, *rinfo;             // pool names: the first-failure word, the marks, route 2's workspace
+  BatchStageNames host;                                   // pool names of the host form
+};
+int brange_frame_dev(Context& ctx, BatchArgs g, int il, int iu, const WindowFamily& fam);
+int brange_frame_host(Context& ctx, BatchArgs g, int il, int iu, const WindowFamily& fam);
 // The ragged frame (vbatch.hip: eigx_s_vbatch, hvbatch.hip: eigx_h_vbatch).  VbArgs is
 // a call: block k is a + off_a[k] (leading dimension lda[k]) of order n[k], its eigenvalues go to w + off_w[k], its
 // eigenvectors to z + off_z[k] (ldz[k]); the six descriptor arrays are host arrays of `batch` entries, offsets and leading
@@ -438,7 +457,7 @@ int vbatch_frame_dev(Context& ctx, VbArgs g, int cutoff, int top, VbPencilLaunch
 int vbatch_frame_host(Context& ctx, VbArgs g, int cutoff, int top, VbPencilLaunch launch, VbSolveOne solve_one);
 // gbatch.hip: pencil k of a uniform batch above the cutoff, through gev_range_dev (gvbatch.hip hands it its blocks)
 int gbatch_solve_one(Context& ctx, const BatchArgs& g, int k);
-// the same for eigenpairs il .. iu (gbatch_range.hip): w(1:m) at g.w + k g.ldw, z(1:n, 1:m) at block k of g.z
+// the same for eigenpairs il .. iu (route 3 of eigx_gev_batch_range): w(1:m) at g.w + k g.ldw, z(1:n, 1:m) at block k of g.z
 int gbatch_solve_window(Context& ctx, const BatchArgs& g, int k, int il, int iu);
 // Host form of a solve on a local block of nr rows: a (nc columns), b (the same; b_h == nullptr: none), z (zcols columns,
 // allocated only) and w (nw entries) in the pool buffers host.a / host.b / host.z (esz 8) or host.ha / host.hb / host.hz

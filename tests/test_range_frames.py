@@ -15,7 +15,9 @@ copies of A and B, and what it left is compared exactly with the sentinel and th
 Then per family: the value call and the index call of the window it returned give bit-identical w and z; one device call at
 n = 65 with il > 1 and eigx_tune key 17 = 0, which cuts the window out of the full divide and conquer (path 3); and all twenty
 entries return EIGX_ERR_NOT_INITIALIZED before they look at any argument (a fresh process: this file run as a script).
-Nothing here depends on how the drivers are written: the file passes unchanged against the library before range.hip."""
+Nothing here depends on how the drivers are written: the file passes unchanged against the library before range.hip.
+Last the windowed batched entries eigx_{s,h,gev,hgev}_batch_range_dev (csrc/batch_frame.hip: one frame for the four families):
+what each of the three routes leaves after a batch with one failed matrix."""
 import ctypes as C
 import functools
 import os
@@ -243,6 +245,74 @@ def test_window_cut_out_of_the_full_divide_and_conquer(gpu_lib, fam):
     print(f"  eigx_{fam}_range_dev n={n} {il}..{iu} path 3: residual {res:.2f} (768), orthogonality {orth:.2f} (8) n eps")
     assert res < 768 and orth < 8
     assert np.abs(wm - lam[il - 1:iu]).max() < 1e-12 * n * max(1.0, np.abs(lam).max())
+
+
+BATCH_CUTOFF_KEY = {"s": 21, "h": 22, "gev": 23, "hgev": 24}
+NOT_TOUCHED = -7.25
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("route", [1, 2, 3])
+@pytest.mark.parametrize("fam", ["s", "h", "gev", "hgev"])
+def test_windowed_batch_frame_after_a_failed_matrix(gpu_lib, fam, route):
+    """What the one windowed frame of the four batched families (csrc/batch_frame.hip: brange_frame_dev) leaves after a batch in
+    which one matrix fails, on each of its three routes: eigx_<fam>_batch_range_dev on three matrices / pencils of order 5, the
+    second with a NaN in A, window (2, 4), mode 'A'.  Route 1 (eigx_tune key 26 = 1: the window kernel), route 2 (key 26 = 2: the
+    full batched solve and a gather), route 3 (the family's cutoff key lowered to 4: the range solver matrix by matrix).  The
+    expected values are those of the four separate frames this one replaced, read off that library: the four families and the
+    three routes agree in every one of them (errinfo = -1 on route 3 too, unlike the uniform batched frame: DESIGN section 8h)."""
+    import torch
+
+    n, nb, il, iu, ld = 5, 3, 2, 4, 6
+    m = iu - il + 1
+    dev = torch.device("cuda:0")
+    A, B, _ = _problem(fam, n)
+    cplx, pencil = np.iscomplexobj(A), B is not None
+    dt = torch.complex128 if cplx else torch.float64
+
+    def stack(M, nan_in_second):
+        t = torch.zeros(nb, n, ld, dtype=dt, device=dev)          # t[k, j, i] = M_k(i, j)
+        for k in range(nb):
+            Mk = np.array(M) * (1.0 + 0.25 * k)
+            if nan_in_second and k == 1:
+                Mk[1, 3] = Mk[3, 1] = np.nan
+            t[k, :, :n] = torch.from_numpy(np.ascontiguousarray(Mk.T)).to(dev)
+        return t
+
+    a = stack(A, True)
+    b = stack(B, False) if pencil else None
+    b_in = b.clone() if pencil else None
+    w = torch.full((nb, m + 1), NOT_TOUCHED, dtype=torch.float64, device=dev)
+    z = torch.full((nb, m, ld), NOT_TOUCHED, dtype=dt, device=dev)
+    info = torch.full((nb,), 77, dtype=torch.int32, device=dev)
+    key = BATCH_CUTOFF_KEY[fam] if route == 3 else 26
+    old = gpu_lib.eigx_tune(key, 4 if route == 3 else route)
+    assert old >= 0                               # the key took the value
+    try:
+        pens = (b.data_ptr(), ld, n * ld) if pencil else ()
+        rc = getattr(gpu_lib, f"eigx_{fam}_batch_range_dev")(n, nb, il, iu, a.data_ptr(), ld, n * ld, *pens, w.data_ptr(), m + 1,
+                                                            z.data_ptr(), ld, m * ld, b"A", info.data_ptr())
+        torch.cuda.synchronize()
+        err, r, mm, redone = C.c_int64(77), C.c_int(-1), C.c_int(-1), C.c_int(-1)
+        gpu_lib.eigx_get_errinfo(C.byref(err))
+        gpu_lib.eigx_batch_range_info(C.byref(r), C.byref(mm), C.byref(redone))
+    finally:
+        gpu_lib.eigx_tune(key, old)
+    wh, zh, ih = w.cpu().numpy(), z.cpu().numpy(), info.cpu().numpy()
+    print(f"  eigx_{fam}_batch_range_dev route {route}: rc {rc}, info {ih.tolist()}, errinfo {err.value}, "
+          f"range_info {(r.value, mm.value, redone.value)}, w[1] {wh[1].tolist()}, z[1] untouched {bool((zh[1] == NOT_TOUCHED).all())}")
+    assert rc == NONFINITE
+    assert ih.tolist() == [OK, NONFINITE, OK]
+    assert err.value == -1
+    assert (r.value, mm.value, redone.value) == (route, m, 0)
+    assert np.isnan(wh[1, :m]).all() and wh[1, m] == NOT_TOUCHED
+    assert (zh[1] == NOT_TOUCHED).all()
+    for k in (0, 2):                              # the others are solved all the same
+        assert np.isfinite(wh[k, :m]).all() and (np.diff(wh[k, :m]) >= 0).all() and wh[k, m] == NOT_TOUCHED
+        assert np.isfinite(zh[k, :, :n]).all() and (zh[k, :, n:] == NOT_TOUCHED).all()
+    if pencil:
+        assert torch.equal(b[1], b_in[1])
+        assert not torch.equal(b[0], b_in[0])     # (U has taken B's place where the pencil was solved)
 
 
 def _uninitialised():

@@ -9,9 +9,9 @@ eigx_hgev_range_dev and their stages (Cholesky, triangular solves, reduction; ei
 the status, w, z and the arrays a / b as the call leaves them.  Then the real generalised solvers eigx_gev[_range][_dev],
 the value-window solves (m and il as well), the host forms of all four generalised solvers and their statuses (non-finite
 A or B, B not positive definite, a bad window, ldb < n) from sentinel-filled w and z.  An array above 8 MiB is stored as
-its SHA-256.  Last the nine batched families -- the uniform eigx_{s,h,gev,hgev}_batch, the ragged eigx_{s,h,gev,hgev}_vbatch and
-the windowed eigx_s_batch_range, host and device forms (batch_section below); --batch runs that section alone (well under a
-minute).  --range runs range_section below alone instead (under a minute): every range entry of the five families, which the
+its SHA-256.  Last the twelve batched families -- the uniform eigx_{s,h,gev,hgev}_batch, the ragged eigx_{s,h,gev,hgev}_vbatch
+and the windowed eigx_{s,h,gev,hgev}_batch_range, host and device forms (batch_section below); --batch runs that section alone
+(about a minute).  --range runs range_section below alone instead (under a minute): every range entry of the five families, which the
 list above covers only in part; its .held files (bytes in the workspace pool) depend on the build, the others do not.
 The library is deterministic, so two builds that compute the same leave directories that `cmp` finds equal:
     for f in A/*; do cmp $f B/$(basename $f); done
@@ -53,9 +53,11 @@ def batch_section():
     A batch is the families of the family's test file, the first of them scaled by 1e-200 and by 1e+200, one matrix with a NaN
     and (gev, hgev) one pencil with an indefinite B.  Padded leading dimensions and strides, NaN outside the upper triangles,
     w / z / info prefilled; recorded: the status, the whole buffers w, z, info and (gev, hgev) b as the call leaves them, errinfo
-    and the timers with entry 0 (the seconds of the call) set to zero.  Then the four ragged entries (ragged below) and
-    eigx_s_batch_range[_dev] (window below) at n = 17, 64, 100 with the windows (1, 1), (2, 5), (n - 3, n), each with key 26 = 1,
-    key 26 = 2 and keys 26 = 1, 27 = 101, and at n = 40 with key 21 = 32; of these also eigx_batch_range_info."""
+    and the timers with entry 0 (the seconds of the call) set to zero.  Then the four ragged entries (ragged below) and the four
+    windowed entries eigx_{s,h,gev,hgev}_batch_range[_dev] (window below) at one n below each class edge of the family's window
+    kernel (s: 17, 64, 80, 100; h, gev: 17, 64, 80; hgev: 17, 64) with the windows (1, 1), (2, 5), (n - 3, n), each with key 26 = 1,
+    key 26 = 2 and keys 26 = 1, 27 = 101, and at n = 40 with the family's cutoff key (21 to 24) lowered to 32; of these also b
+    (gev, hgev) and eigx_batch_range_info."""
     sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests"))
     import test_batch
     import test_gbatch
@@ -174,48 +176,59 @@ def batch_section():
     for fam, pencil in ((test_vbatch.S, False), (test_vbatch.H, False), (test_gvbatch.G, True), (test_gvbatch.HG, True)):
         ragged(fam, pencil)
 
-    def window(n, il, iu, tag):
-        """eigx_s_batch_range[_dev], modes A and N, on the batch of one("s", ...): z with m columns per matrix"""
-        m = iu - il + 1
-        mats = test_batch._families(n)
+    def window(fam, n, il, iu, tag):
+        """eigx_{fam}_batch_range[_dev], modes A and N, on the batch of one(fam, ...) (a NaN matrix; gev, hgev: an indefinite B
+        too): z with m columns per matrix"""
+        cplx, gev = fam in ("h", "hgev"), fam in ("gev", "hgev")
+        m, c = iu - il + 1, 2 if cplx else 1
+        mats = (test_hbatch if cplx else test_batch)._families(n)
         bad = mats[0].copy()
         bad[0, n - 1] = bad[n - 1, 0] = np.nan
         mats = mats + [mats[0] * 1e-200, mats[0] * 1e200, bad]
-        nb = len(mats)
-        lda, ldz, ldw = n + 3, n + 1, m + 2
-        sa, sz = lda * n + 5, ldz * m + 7
-        a0 = image(mats, lda, sa, False)
+        nb = len(mats) + gev
+        lda, ldb, ldz, ldw = n + 3, n + 2, n + 1, m + 2
+        sa, sb, sz = lda * n + 5, ldb * n + 3, ldz * m + 7
+        if gev:
+            ov = (test_hgbatch if cplx else test_gbatch)._overlaps(n)
+            indef = ov[0].copy()
+            indef[n // 2, n // 2] = -1.0
+            mats, bs = mats + [mats[1]], [ov[k % len(ov)] for k in range(nb - 1)] + [indef]
+        a0 = image(mats, lda, sa, cplx)
+        b0 = image(bs, ldb, sb, cplx) if gev else None
         for form in ("dev", "host"):
-            fn = getattr(lib, "eigx_s_batch_range" + ("_dev" if form == "dev" else ""))
+            fn = getattr(lib, f"eigx_{fam}_batch_range" + ("_dev" if form == "dev" else ""))
             for mode in "AN":
-                arrs = dict(a=a0.copy(), w=np.full(ldw * nb, SENT_B), z=np.full(sz * nb, SENT_B), info=np.full(nb, 77, dtype=np.int32))
+                arrs = dict(a=a0.copy(), w=np.full(ldw * nb, SENT_B), z=np.full(c * sz * nb, SENT_B), info=np.full(nb, 77, dtype=np.int32),
+                            **(dict(b=b0.copy()) if gev else {}))
                 if form == "dev":
                     arrs = {k: torch.from_numpy(v).to(dev) for k, v in arrs.items()}
                     ptr = {k: v.data_ptr() for k, v in arrs.items()}
                 else:
                     ptr = {k: v.ctypes.data for k, v in arrs.items()}
-                rc = fn(n, nb, il, iu, ptr["a"], lda, sa, ptr["w"], ldw, ptr["z"] if mode == "A" else None, ldz, sz, mode.encode(),
-                        ptr["info"])
+                rc = fn(n, nb, il, iu, ptr["a"], lda, sa, *((ptr["b"], ldb, sb) if gev else ()), ptr["w"], ldw,
+                        ptr["z"] if mode == "A" else None, ldz, sz, mode.encode(), ptr["info"])
                 if form == "dev":
                     torch.cuda.synchronize()
                     arrs = {k: v.cpu().numpy() for k, v in arrs.items()}
                 del arrs["a"]
-                save(f"sbrange_{form}_n{n}_{il}_{iu}{tag}_{mode}", rc=np.int64(rc), **arrs, **frame_record(window=True))
+                save(f"{fam}brange_{form}_n{n}_{il}_{iu}{tag}_{mode}", rc=np.int64(rc), **arrs, **frame_record(window=True))
 
-    for n in (17, 64, 100):
-        for il, iu in ((1, 1), (2, 5), (n - 3, n)):
-            for route in (1, 2):
-                old = lib.eigx_tune(26, route)
-                window(n, il, iu, f"_route{route}")
+    # per family: an order below each class edge of its window kernel, then n = 40 above the cutoff key lowered to 32
+    for fam, key, sizes in (("s", 21, (17, 64, 80, 100)), ("h", 22, (17, 64, 80)), ("gev", 23, (17, 64, 80)), ("hgev", 24, (17, 64))):
+        for n in sizes:
+            for il, iu in ((1, 1), (2, 5), (n - 3, n)):
+                for route in (1, 2):
+                    old = lib.eigx_tune(26, route)
+                    window(fam, n, il, iu, f"_route{route}")
+                    lib.eigx_tune(26, old)
+                old, accept = lib.eigx_tune(26, 1), lib.eigx_tune(27, 101)   # the window kernel refuses every matrix: all are redone
+                window(fam, n, il, iu, "_refused")
                 lib.eigx_tune(26, old)
-            old, accept = lib.eigx_tune(26, 1), lib.eigx_tune(27, 101)   # the window kernel refuses every matrix: all are redone
-            window(n, il, iu, "_refused")
-            lib.eigx_tune(26, old)
-            lib.eigx_tune(27, accept)
-    cutoff = lib.eigx_tune(21, 32)
-    for il, iu in ((1, 1), (2, 5), (37, 40)):
-        window(40, il, iu, "_loop")
-    lib.eigx_tune(21, cutoff)
+                lib.eigx_tune(27, accept)
+        cutoff = lib.eigx_tune(key, 32)
+        for il, iu in ((1, 1), (2, 5), (37, 40)):
+            window(fam, 40, il, iu, "_loop")
+        lib.eigx_tune(key, cutoff)
 
 
 def range_section():
